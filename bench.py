@@ -5,9 +5,16 @@ fused env step on device), GAE, then `epochs` passes of minibatch updates over t
 exactly the per-iteration body of the reference's PPO.train (reference rl/algos/ppo.py:459-566).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full          # + isolated-launch calibration and the CPU baseline
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Nothing here reads /root/reference.
+A plain run sets up, warms up, times --steps iterations and prints the headline line (the roofline block comes from HIP events
+recorded inside the timed iterations, nothing extra is run for it).  --full adds what takes runs of its own: the whole-batch
+control-step kernel timed in isolation after the timed region (`roofline.step_kernel_isolated`) and the CPU baseline
+(`cpu_baseline`, unless --no-cpu-baseline).  --dump-outputs DIR writes what the last timed iteration computed (see dump_outputs).
+
+Prints ONE JSON line (rank 0).  Nothing here reads files outside the repository.
 """
 import argparse
 import json
@@ -114,6 +121,29 @@ def run_cpu_baseline(env_name, target_seconds=15.0):
                        f"sampling only, no PPO update; {busy:.1f}s busy / {wall:.1f}s wall")
 
 
+DUMP_SAMPLE_ROWS = 65536     # rows of the [T * N] sample tensors written by --dump-outputs (fixed seed, sorted)
+
+
+def dump_outputs(out_dir, batch, kernels):
+    """Write what the caller of PPO.iterate receives from the last timed iteration -- its rollout batch (time-major [T * N] samples)
+    and the network parameters the update left behind -- as float32 .npy files under out_dir.  The sample tensors are cut to
+    DUMP_SAMPLE_ROWS rows drawn with a fixed seed, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = batch.states.shape[0]
+    rows = np.arange(n) if n <= DUMP_SAMPLE_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(batch.states.device)
+    arrays = dict(sample_rows=rows)
+    for name in ("states", "actions", "rewards", "values", "returns", "dones"):
+        arrays[name] = getattr(batch, name).index_select(0, idx)
+    arrays["ep_lens"], arrays["ep_rewards"] = batch.ep_lens, batch.ep_rewards
+    arrays["theta"] = kernels.theta
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -124,7 +154,12 @@ def main():
     ap.add_argument("--traj-len", type=int, default=400, help="control steps per env per iteration (max_traj_len)")
     ap.add_argument("--minibatch-size", type=int, default=32768, help="per-GPU minibatch rows")
     ap.add_argument("--epochs", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: the isolated-launch calibration of the control-step "
+                         "kernel and the CPU baseline (off by default: a plain run times the steps and prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed iteration's rollout batch (a seeded sample of its rows) and updated parameters as DIR/<name>.npy")
     ap.add_argument("--no-mirror", action="store_true")
     ap.add_argument("--infer-fp16", action="store_true", help="rollout inference with fp16 operands; update stays f32")
     ap.add_argument("--fp16", action="store_true", help="BASELINE config 5: fp16 actor / critic (inference and every GEMM of the update with fp16 operands, f32 accumulation / master weights / Adam)")
@@ -256,20 +291,23 @@ def main():
     t0 = time.time()
     sample_t = opt_t = 0.0
     iter_s = []
+    batch = None
     for i in range(args.steps):
-        _, st, ot = algo.iterate(args.warmup + i)
+        batch, st, ot = algo.iterate(args.warmup + i)
         sample_t += st
         opt_t += ot
         iter_s.append(st + ot)
     barrier()
     elapsed = time.time() - t0
+    timing["on"] = False
+    if args.dump_outputs and rank == 0 and batch is not None:
+        dump_outputs(args.dump_outputs, batch, algo.kernels)
     faults = env.pop_fault_stats() if hasattr(env, "pop_fault_stats") else (0, 0)
     reruns = env.pop_rerun_count() if hasattr(env, "pop_rerun_count") else 0
-    # calibration of the dominant kernel outside the timed region (rank 0): whole-batch launches, one at a time, nothing
+    # --full: calibration of the dominant kernel outside the timed region (rank 0): whole-batch launches, one at a time, nothing
     # else on the GPU -- the duration rocprofv3 --kernel-trace reports for an isolated launch
     isolated_ms = None
-    timing["on"] = False
-    if rank == 0 and hasattr(env, "step_range"):
+    if args.full and rank == 0 and hasattr(env, "step_range"):
         ro = algo.rollout
         evs = []
         for t in range(min(20, ro.T)):
@@ -316,12 +354,13 @@ def main():
             step_kernel_isolated=dict(kernel=spec.step_kernel_name, avg_launch_ms=isolated_ms, envs_per_launch=N,
                                       algorithmic_fp64_tflops=iso_tf, algorithmic_fp64_frac=None if iso_tf is None else iso_tf / FP64_VALU_PEAK_TFLOPS,
                                       note="one control step of the whole batch as ONE launch of the launch-per-step kernel, median of 20 issued one at a "
-                                           "time after the timed region (HIP events on the launch stream)"),
+                                           "time after the timed region (HIP events on the launch stream); measured with --full only"),
             algorithmic_flops_per_launch=flops_per_env_step * N, algorithmic_bytes_per_launch=bytes_per_env_step * N,
             algorithmic_flops_per_env_step=flops_per_env_step, algorithmic_bytes_per_env_step=bytes_per_env_step,
             avg_launch_ms=isolated_ms if isolated_ms is not None else avg_step_ms, envs_per_launch=N if isolated_ms is not None else NL,
-            launch_note="median of 20 whole-batch control-step launches issued one at a time after the timed region, HIP events on the "
-                        "launch stream (no overlap): the duration rocprofv3 --kernel-trace reports for an isolated dispatch",
+            launch_note=("median of 20 whole-batch control-step launches issued one at a time after the timed region, HIP events on the "
+                         "launch stream (no overlap): the duration rocprofv3 --kernel-trace reports for an isolated dispatch")
+                        if isolated_ms is not None else "mean span of the control-step launches of the timed region (HIP events on their streams)",
             rollout_mode=mode,
             overlapped=(None if resident else dict(avg_launch_ms=avg_step_ms, launches=len(step_ms), envs_per_launch=NL, concurrent_launches=groups,
                             fp64_tflops=overlapped_tf, fp64_frac=overlapped_tf / FP64_VALU_PEAK_TFLOPS,
@@ -404,7 +443,7 @@ def main():
                                         allreduce_ms_per_iter=float(np.sum(ar)) / K if ar else None,
                                         note="rank 0, timed iterations: one sum-all-reduce of the flat gradient per optimiser step (events on the update's stream, "
                                              "so a call's span includes waiting for the slowest rank's minibatch); envs are sharded by global env id, no other data-path collective")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = run_cpu_baseline(env_name)
         print(json.dumps(out))
     if use_dist:

@@ -8,21 +8,21 @@ OUT=/root/repo/gpurun_out/profiles_raw
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B=/root/repo/bench.py
-timeout 300 python $B --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu.json
-timeout 200 python $B --steps 5 --warmup 2 --no-cpu-baseline --task-hook walking 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu_task_plugin.json
-timeout 200 python $B --env h1 --num-envs 8192 --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_h1_8192_1gpu.json
-timeout 100 python $B --env cartpole --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_cartpole_1gpu.json
-timeout 200 python $B --env jvrc_step --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_jvrc_step_1gpu.json
-timeout 200 python $B --env h1_walk --num-envs 8192 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_h1_walk_8192_1gpu.json
-timeout 200 python $B --env h1 --num-envs 8192 --fp16 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_h1_8192_fp16_1gpu.json
-LHW_ROLLOUT_MODE=steps timeout 200 python $B --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu_launch_per_step.json
+timeout 300 python $B --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu.json
+timeout 200 python $B --full --steps 5 --warmup 2 --no-cpu-baseline --task-hook walking 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu_task_plugin.json
+timeout 200 python $B --full --env h1 --num-envs 8192 --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_h1_8192_1gpu.json
+timeout 100 python $B --full --env cartpole --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_cartpole_1gpu.json
+timeout 200 python $B --full --env jvrc_step --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_jvrc_step_1gpu.json
+timeout 200 python $B --full --env h1_walk --num-envs 8192 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_h1_walk_8192_1gpu.json
+timeout 200 python $B --full --env h1 --num-envs 8192 --fp16 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_h1_8192_fp16_1gpu.json
+LHW_ROLLOUT_MODE=steps timeout 200 python $B --full --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_jvrc_walk_1gpu_launch_per_step.json
 # per-kernel durations of the default bench command (the rollout kernel's average must agree with the bench line's HIP events)
-rm -rf /tmp/kt; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $B --no-cpu-baseline > $OUT/kt.log 2>&1
+rm -rf /tmp/kt; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $B --full --no-cpu-baseline > $OUT/kt.log 2>&1
 cp /tmp/kt/*/*kernel_stats.csv $OUT/jvrc_walk_kernel_stats.csv
 grep '^{' $OUT/kt.log | tail -1 > $OUT/bench_jvrc_walk_under_rocprof.json
 for E in h1 jvrc_step h1_walk; do
   NE=4096; [ $E != jvrc_step ] && NE=8192
-  rm -rf /tmp/kt; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $B --env $E --num-envs $NE --steps 2 --warmup 1 --no-cpu-baseline > /tmp/kt.log 2>&1
+  rm -rf /tmp/kt; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $B --env $E --num-envs $NE --steps 2 --warmup 1 --full --no-cpu-baseline > /tmp/kt.log 2>&1
   cp /tmp/kt/*/*kernel_stats.csv $OUT/${E}_kernel_stats.csv
 done
 timeout 120 python /root/repo/scripts/jvrc_phase_profile.py 4096 > $OUT/jvrc_walk_phase_cycles.txt 2>/dev/null

@@ -3,7 +3,7 @@
 TAG=${1:-q}; OUT=/root/repo/gpurun_out/$TAG; mkdir -p $OUT
 cd /root/repo
 timeout 400 python -m pytest tests -m gpu -x -q ${PYTEST_K:+-k "$PYTEST_K"} > $OUT/pytest.txt 2>&1; tail -3 $OUT/pytest.txt
-timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench.json
+timeout 300 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench.json
 timeout 120 python scripts/jvrc_phase_profile.py 4096 > $OUT/phase.txt 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pm

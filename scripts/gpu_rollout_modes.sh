@@ -6,13 +6,13 @@ cd /root/repo
 timeout 900 python -m pytest tests/test_rollout_resident_gpu.py tests/test_iteration_gpu.py -m gpu -x -q > $OUT/pytest.txt 2>&1; tail -5 $OUT/pytest.txt
 for i in 1 2; do
   for MODE in steps resident; do
-    LHW_ROLLOUT_MODE=$MODE timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>$OUT/bench_${MODE}_$i.err | tail -1 > $OUT/bench_jvrc_walk_${MODE}_$i.json
+    LHW_ROLLOUT_MODE=$MODE timeout 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline 2>$OUT/bench_${MODE}_$i.err | tail -1 > $OUT/bench_jvrc_walk_${MODE}_$i.json
   done
 done
 for E in h1 h1_walk jvrc_step; do
   NE=8192; [ $E = jvrc_step ] && NE=4096
   for MODE in steps resident; do
-    LHW_ROLLOUT_MODE=$MODE timeout 300 python bench.py --env $E --num-envs $NE --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_${E}_${MODE}.json
+    LHW_ROLLOUT_MODE=$MODE timeout 300 python bench.py --env $E --num-envs $NE --steps 2 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_${E}_${MODE}.json
   done
 done
 python - <<PY

@@ -224,8 +224,9 @@ def main():
     run_env("h1_a", H1Env, seed=5, T=260, act_dim=10, act_std=0.223, out=out, extra=jvrc_extra if False else None)
     run_env("h1_b", H1Env, seed=17, T=200, act_dim=10, act_std=0.05, out=out)
     run_env("h1_walk_a", H1WalkEnv, seed=7, T=220, act_dim=10, act_std=0.15, out=out)
-    np.savez_compressed(os.path.join(OUT, "refenv.npz"), **out)
-    print("wrote", os.path.join(OUT, "refenv.npz"))
+    for part in ("jvrc", "h1"):          # two files: each stays under the 1 MiB limit of a committed file
+        np.savez_compressed(os.path.join(OUT, f"refenv_{part}.npz"), **{k: v for k, v in out.items() if k.startswith(part)})
+        print("wrote", os.path.join(OUT, f"refenv_{part}.npz"))
     gen_rollout_worker(os.path.join(OUT, "rollout_worker.npz"))
 
 

@@ -1,6 +1,8 @@
-"""Checkpoint files are loadable by the REFERENCE's own classes and vice versa.  CPU."""
+"""Checkpoint files are loadable by the REFERENCE's own classes and vice versa.  CPU.
+
+The reference's side is pinned by tests/golden/checkpoints/ (tests/golden/gen_checkpoints.py): what its classes computed after
+unpickling our files, the attribute names those objects carried, and files its classes wrote."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -10,7 +12,7 @@ import torch
 from learninghumanoidwalking_amd import checkpoint as ck
 from learninghumanoidwalking_amd.ppo_kernels import reference_init
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "checkpoints")
 NAMES = ["w1", "b1", "w2", "b2", "w3", "b3"]
 
 
@@ -26,7 +28,7 @@ def test_roundtrip_without_reference_on_path(tmp_path):
     om, osd = torch.randn(37), torch.rand(37) + 0.5
     a, c = tmp_path / "actor_7.pt", tmp_path / "critic_7.pt"
     ck.save_reference_checkpoint(t, om, osd, False, a, c)
-    assert "rl.policies.actor" not in sys.modules or os.path.isdir(REF)   # stand-in modules are removed again
+    assert "rl.policies.actor" not in sys.modules   # stand-in modules are removed again
     t2, om2, os2 = ck.load_reference_checkpoint(a, c)
     for k in t:
         assert torch.equal(t[k].float(), t2[k]), k
@@ -35,46 +37,44 @@ def test_roundtrip_without_reference_on_path(tmp_path):
     assert b"rl.policies.actor" in raw and b"Gaussian_FF_Actor" in raw    # pickled under the reference's class path
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rl")), reason="reference checkout not present")
+def _unpickled(path):
+    """our file as the reference's torch.load sees it: the object graph under the reference's class paths"""
+    with ck.reference_classes():
+        return torch.load(path, weights_only=False, map_location="cpu")
+
+
+def _attr_names(m):
+    """the names gen_checkpoints.py recorded from the reference's unpickled objects (attributes, submodules, parameters, buffers)"""
+    return sorted(k for k in vars(m) if not k.startswith("_") and k != "training") + sorted(m._modules) + sorted(m._parameters) + sorted(m._buffers)
+
+
 def test_reference_classes_load_our_files_and_compute_the_same(tmp_path):
+    """Our files carry what the reference's Gaussian_FF_Actor / FF_V read (the attribute names its unpickled objects had), and
+    what those classes computed from our files (tests/golden/checkpoints/ff.npz) equals the oracle's forward."""
     from oracle import ppo_oracle as po
+    g = np.load(os.path.join(GOLDEN, "ff.npz"))
     t = _tensors()
-    om, osd = torch.randn(37) * 0.1, torch.rand(37) + 0.5
+    om, osd, obs = torch.from_numpy(g["obs_mean"]), torch.from_numpy(g["obs_std"]), torch.from_numpy(g["obs"])
     a, c = tmp_path / "actor_0.pt", tmp_path / "critic_0.pt"
     ck.save_reference_checkpoint(t, om, osd, True, a, c)
-    obs = torch.randn(5, 37)
-    torch.save(obs, tmp_path / "obs.pt")
-    code = (
-        "import sys, torch; sys.path.insert(0, %r)\n"
-        "from rl.policies.actor import Gaussian_FF_Actor; from rl.policies.critic import FF_V\n"
-        "p = torch.load(%r, weights_only=False); v = torch.load(%r, weights_only=False)\n"
-        "assert type(p) is Gaussian_FF_Actor and type(v) is FF_V, (type(p), type(v))\n"
-        "obs = torch.load(%r)\n"
-        "torch.save((p(obs, deterministic=True).detach(), v(obs).detach(), p.distribution(obs).stddev.detach()), %r)\n"
-        % (REF, str(a), str(c), str(tmp_path / "obs.pt"), str(tmp_path / "out.pt")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-1500:]
-    mu, val, sd = torch.load(tmp_path / "out.pt")
+    p, v = _unpickled(a), _unpickled(c)
+    assert (type(p).__module__, type(p).__name__, type(v).__module__, type(v).__name__) == ("rl.policies.actor", "Gaussian_FF_Actor", "rl.policies.critic", "FF_V")
+    assert _attr_names(p) == g["actor_names"].tolist() and _attr_names(v) == g["critic_names"].tolist()
+    with torch.no_grad():      # the stand-ins' forward passes are the reference's (checkpoint.py)
+        np.testing.assert_allclose(p(obs, deterministic=True).numpy(), g["mu"], rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(v(obs).numpy(), g["val"], rtol=1e-5, atol=1e-6)
     xn = (obs - om) / osd
-    np.testing.assert_allclose(mu.numpy(), po.mlp(xn, *[t[f"a_{n}"] for n in NAMES]).numpy(), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(val.numpy(), po.mlp(xn, *[t[f"c_{n}"] for n in NAMES]).numpy(), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(sd.numpy(), np.full((5, 12), 0.223, dtype=np.float32), rtol=1e-6)
+    np.testing.assert_allclose(g["mu"], po.mlp(xn, *[t[f"a_{n}"] for n in NAMES]).numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(g["val"], po.mlp(xn, *[t[f"c_{n}"] for n in NAMES]).numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(g["sd"], np.full((5, 12), 0.223, dtype=np.float32), rtol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rl")), reason="reference checkout not present")
-def test_we_load_files_written_by_the_reference(tmp_path):
-    code = (
-        "import sys, torch; sys.path.insert(0, %r)\n"
-        "from rl.policies.actor import Gaussian_FF_Actor; from rl.policies.critic import FF_V\n"
-        "torch.manual_seed(5); p = Gaussian_FF_Actor(37, 12, init_std=0.2, learn_std=False); v = FF_V(37)\n"
-        "p.obs_mean = torch.zeros(37); p.obs_std = torch.ones(37); v.obs_mean = p.obs_mean; v.obs_std = p.obs_std\n"
-        "torch.save(p, %r); torch.save(v, %r)\n" % (REF, str(tmp_path / "actor_3.pt"), str(tmp_path / "critic_3.pt")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-1500:]
-    t, om, osd = ck.load_reference_checkpoint(tmp_path / "actor_3.pt", tmp_path / "critic_3.pt")
+def test_we_load_files_written_by_the_reference():
+    t, om, osd = ck.load_reference_checkpoint(os.path.join(GOLDEN, "ref_actor_3.pt"), os.path.join(GOLDEN, "ref_critic_3.pt"))
     ref = reference_init(37, 12, 256, 0.2, generator_seed=5)   # same torch seed -> same constructor draws
     for k in ref:
         assert torch.equal(ref[k].float(), t[k]), k
+    assert torch.equal(om, torch.zeros(37)) and torch.equal(osd, torch.ones(37))
 
 
 # ----------------------------------------------------------------------------- recurrent (LSTM) checkpoints
@@ -96,38 +96,26 @@ def test_recurrent_roundtrip_without_reference_on_path(tmp_path):
     assert b"rl.policies.actor" in raw and b"Gaussian_LSTM_Actor" in raw
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rl")), reason="reference checkout not present")
 def test_reference_lstm_classes_load_our_files_and_we_load_theirs(tmp_path):
-    """Gaussian_LSTM_Actor / LSTM_V of the reference unpickle our files and produce the oracle's sequence outputs; files
-    written by the reference load back, and the same torch seed reproduces the reference's constructor draws."""
+    """Gaussian_LSTM_Actor / LSTM_V of the reference unpickle our files and produce the oracle's sequence outputs
+    (tests/golden/checkpoints/lstm.npz); files written by the reference load back, and the same torch seed reproduces the
+    reference's constructor draws."""
     from oracle import ppo_oracle as po
+    g = np.load(os.path.join(GOLDEN, "lstm.npz"))
     t = _lstm_tensors()
-    om, osd = torch.randn(37) * 0.1, torch.rand(37) + 0.5
+    om, osd, obs = torch.from_numpy(g["obs_mean"]), torch.from_numpy(g["obs_std"]), torch.from_numpy(g["obs"])   # obs [T, B, D]
     a, c = tmp_path / "actor_0.pt", tmp_path / "critic_0.pt"
     ck.save_recurrent_checkpoint(t, om, osd, False, a, c)
-    obs = torch.randn(6, 3, 37)           # [T, B, D]: a batch of trajectories
-    torch.save(obs, tmp_path / "obs.pt")
-    code = (
-        "import sys, torch; sys.path.insert(0, %r)\n"
-        "from rl.policies.actor import Gaussian_LSTM_Actor; from rl.policies.critic import LSTM_V\n"
-        "p = torch.load(%r, weights_only=False); v = torch.load(%r, weights_only=False)\n"
-        "assert type(p) is Gaussian_LSTM_Actor and type(v) is LSTM_V, (type(p), type(v))\n"
-        "obs = torch.load(%r)\n"
-        "torch.save((p(obs, deterministic=True).detach(), v(obs).detach()), %r)\n"
-        "torch.manual_seed(9); q = Gaussian_LSTM_Actor(37, 12, layers=(32, 32), init_std=0.2); w = LSTM_V(37, layers=(32, 32))\n"
-        "q.obs_mean = torch.zeros(37); q.obs_std = torch.ones(37); w.obs_mean = q.obs_mean; w.obs_std = q.obs_std\n"
-        "torch.save(q, %r); torch.save(w, %r)\n"
-        % (REF, str(a), str(c), str(tmp_path / "obs.pt"), str(tmp_path / "out.pt"), str(tmp_path / "actor_9.pt"), str(tmp_path / "critic_9.pt")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-1500:]
-    mu, val = torch.load(tmp_path / "out.pt")
+    p, v = _unpickled(a), _unpickled(c)
+    assert (type(p).__module__, type(p).__name__, type(v).__module__, type(v).__name__) == ("rl.policies.actor", "Gaussian_LSTM_Actor", "rl.policies.critic", "LSTM_V")
+    assert _attr_names(p) == g["actor_names"].tolist() and _attr_names(v) == g["critic_names"].tolist()
     names = ["wih1", "whh1", "bih1", "bhh1", "wih2", "whh2", "bih2", "bhh2", "wout", "bout"]
     reset = torch.zeros(6, 3, dtype=torch.bool)
     reset[0] = True
     xn = (obs - om) / osd
-    np.testing.assert_allclose(mu.numpy(), po.lstm_net(xn, reset, [t[f"a_{n}"] for n in names]).numpy(), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(val.numpy(), po.lstm_net(xn, reset, [t[f"c_{n}"] for n in names]).numpy(), rtol=1e-5, atol=1e-6)
-    t9, _, _, hidden = ck.load_recurrent_checkpoint(tmp_path / "actor_9.pt", tmp_path / "critic_9.pt")
+    np.testing.assert_allclose(g["mu"], po.lstm_net(xn, reset, [t[f"a_{n}"] for n in names]).numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(g["val"], po.lstm_net(xn, reset, [t[f"c_{n}"] for n in names]).numpy(), rtol=1e-5, atol=1e-6)
+    t9, _, _, hidden = ck.load_recurrent_checkpoint(os.path.join(GOLDEN, "ref_lstm_actor_9.pt"), os.path.join(GOLDEN, "ref_lstm_critic_9.pt"))
     ref = _lstm_tensors(seed=9)
     assert hidden == 32
     for k in ref:

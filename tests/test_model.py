@@ -8,7 +8,7 @@ from learninghumanoidwalking_amd import mjcf, model
 from learninghumanoidwalking_amd.envs.cartpole import CARTPOLE_XML
 from learninghumanoidwalking_amd.envs.jvrc_walk import JVRC_STANDIN_XML, LEG_JOINTS
 
-REF_CARTPOLE = "/root/reference/envs/cartpole/cartpole.xml"
+REF_CARTPOLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files", "cartpole.xml")   # the reference's file, unchanged
 
 
 def test_cartpole_known_facts():
@@ -28,7 +28,6 @@ def test_cartpole_known_facts():
     np.testing.assert_allclose(m.meaninertia, np.trace(M) / 2)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CARTPOLE), reason="reference checkout not present")
 def test_own_cartpole_asset_equals_reference_xml():
     """The repo's cartpole.xml is a re-authored file; the reference's XML must compile to the same dynamics."""
     a = mjcf.compile_file(CARTPOLE_XML, 0.005)

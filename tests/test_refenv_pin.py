@@ -1,5 +1,5 @@
 """The oracle envs (oracle/env_{jvrc_walk,h1,h1_walk}.py -- the checkers the HIP kernels are held to) against the reference's
-OWN environment code, executed: tests/golden/refenv.npz was produced by running the reference's JvrcWalkEnv / H1Env / H1WalkEnv
+OWN environment code, executed: tests/golden/refenv_{jvrc,h1}.npz were produced by running the reference's JvrcWalkEnv / H1Env / H1WalkEnv
 (BaseHumanoidEnv.step / reset_model / get_obs, RobotBase, RobotInterface, WalkingTask / StandingTask, tasks/rewards.py,
 tasks/observations.py, domain_randomization.py) unchanged, on a stand-in `mujoco` module served by the oracle physics
 (tests/golden/gen_refenv.py, tests/golden/_fake_mujoco.py).  Here the oracle env replays the same action tape; its random draws
@@ -12,7 +12,8 @@ import os
 import numpy as np
 import pytest
 
-G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refenv.npz"))
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+G = {k: v for part in ("jvrc", "h1") for k, v in np.load(os.path.join(_GOLDEN, f"refenv_{part}.npz")).items()}   # one fixture, two files
 
 
 class TapeReader:

@@ -1,6 +1,6 @@
 """"YAML configs and footstep plans drop in unchanged" (BASELINE.json north_star): every Spec is built from the REFERENCE's own
-envs/*/configs/*.yaml and utils/footstep_plans.txt, and the resulting env is reset and stepped -- on the host-side SIMT
-emulator, so this runs in the CPU suite.  Skipped where /root/reference is absent (the GPU box)."""
+envs/*/configs/*.yaml and utils/footstep_plans.txt (copied unchanged into tests/golden/reference_files/), and the resulting env is
+reset and stepped -- on the host-side SIMT emulator, so this runs in the CPU suite."""
 import os
 
 import numpy as np
@@ -8,8 +8,7 @@ import pytest
 
 from tests import emu
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "envs")), reason="reference checkout not present")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files")
 
 
 def _cases():
@@ -17,11 +16,11 @@ def _cases():
     from learninghumanoidwalking_amd.envs.h1_walk import H1WalkSpec
     from learninghumanoidwalking_amd.envs.jvrc_step import JvrcStepSpec
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
-    jv = os.path.join(REF, "envs", "jvrc", "configs", "base.yaml")
+    jv = os.path.join(REF, "jvrc_base.yaml")
     return [("jvrc_walk", lambda: JvrcWalkSpec(yaml_path=jv)),
-            ("jvrc_step", lambda: JvrcStepSpec(yaml_path=jv, plans_path=os.path.join(REF, "utils", "footstep_plans.txt"))),
-            ("h1", lambda: H1Spec(yaml_path=os.path.join(REF, "envs", "h1", "configs", "base.yaml"))),
-            ("h1_walk", lambda: H1WalkSpec(yaml_path=os.path.join(REF, "envs", "h1", "configs", "walk.yaml")))]
+            ("jvrc_step", lambda: JvrcStepSpec(yaml_path=jv, plans_path=os.path.join(REF, "footstep_plans.txt"))),
+            ("h1", lambda: H1Spec(yaml_path=os.path.join(REF, "h1_base.yaml"))),
+            ("h1_walk", lambda: H1WalkSpec(yaml_path=os.path.join(REF, "h1_walk.yaml")))]
 
 
 @pytest.mark.parametrize("name", ["jvrc_walk", "jvrc_step", "h1", "h1_walk"])

@@ -4,8 +4,6 @@ inputs after every control step and the policy is trained on ITS reward / termin
 in, training must reproduce the fused path (rewards 1e-6, weights 3e-6); with one weight changed in the plugged task, the rewards
 must change.  Reference: robots/robot_base.py:88-96 (task.step / calc_reward / done per control step), tasks/base_task.py:41-70,
 tasks/walking_task.py:85-147."""
-import importlib.util
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,7 +11,6 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-REF_REWARDS = "/root/reference/tasks/rewards.py"
 
 
 def _args(N, T):
@@ -24,13 +21,7 @@ def _args(N, T):
 
 
 def _rewards_module():
-    """the reference's tasks/rewards.py by file path where the reference checkout exists (build container); on the GPU box the
-    restatement that tests/test_specs.py pins to that module, behind the same function names"""
-    if os.path.exists(REF_REWARDS):
-        spec = importlib.util.spec_from_file_location("ref_rewards_hook", REF_REWARDS)
-        rw = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(rw)
-        return rw
+    """the restatement of the reference's tasks/rewards.py that tests/test_specs.py pins to that module, behind the same function names"""
     from tests.test_task_inputs import reward_functions
     return reward_functions()[0]
 

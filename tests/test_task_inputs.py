@@ -1,23 +1,13 @@
 """The batched sim-facade seam (include/lhw.h: lhw_env_enable_task_inputs / lhw_env_get_task_inputs): the kernel exports what
 the reference's tasks read through RobotInterface for the control step it just rewarded; recomputing the ten walking reward
-terms OUTSIDE the kernel from that export -- with the reference's own tasks/rewards.py, loaded by file path, when /root/reference
-is present (build container), else with the restatement pinned to it (oracle/env_jvrc_walk.py, tests/test_specs.py) -- must give
-the kernel's fused `rew_terms`.  This is the slow-path BaseTask hook of INTEGRATION.md, exercised: it ties the fused reward to
-reference code directly.  Runs on the SIMT emulator here; tests/test_task_inputs_gpu.py is the GPU twin."""
-import importlib.util
-import os
-
+terms OUTSIDE the kernel from that export -- with the restatement of the reference's tasks/rewards.py that is pinned to it
+(oracle/env_jvrc_walk.py, tests/test_specs.py, tests/golden/rewards.npz) -- must give the kernel's fused `rew_terms`.  This is the
+slow-path BaseTask hook of INTEGRATION.md, exercised.  Runs on the SIMT emulator here; tests/test_task_inputs_gpu.py is the GPU twin."""
 import numpy as np
 
-REF_REWARDS = "/root/reference/tasks/rewards.py"
-
-
 def reward_functions():
-    if os.path.exists(REF_REWARDS):
-        spec = importlib.util.spec_from_file_location("ref_rewards_seam", REF_REWARDS)
-        rw = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(rw)
-        return rw, True
+    """-> (module-like object with the reference's tasks/rewards.py function names, False): the oracle's restatement, which
+    tests/test_specs.py pins to the reference module's outputs (tests/golden/rewards.npz)"""
     from oracle import env_jvrc_walk as o
 
     class RW:      # same call signatures as the reference module
