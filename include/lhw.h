@@ -22,6 +22,10 @@
  *                       (envs/common/mujoco_env.py:118-127); parity hooks
  *   lhw_env_set_iteration <- RolloutWorker.sync_state's env.robot.iteration_count = itr
  *                       (rl/workers/rollout_worker.py:95)
+ *   lhw_env_*task_inputs, lhw_env_*step_task_inputs
+ *                    <- what RobotBase.step hands the exchangeable task once per control step
+ *                       (robots/robot_base.py:88-96: task.step / calc_reward / done reading RobotInterface);
+ *                       the second record adds what SteppingTask reads besides (tasks/stepping_task.py:66-123, 209-262)
  *   lhw_gae          <- PPOBuffer.finish_path over every trajectory of the batch
  *                       (rl/storage/rollout_storage.py:53-85)
  *   lhw_mlp_*, lhw_ppo_* <- Gaussian_FF_Actor / FF_V forward and PPO.update_actor_critic
@@ -245,6 +249,37 @@ int lhw_env_enable_task_inputs(LhwEnv* env, int enable);
 int lhw_env_get_task_inputs(LhwEnv* env, double* out_host);
 /* The same records on the device (valid until the env is destroyed or the export disabled); NULL while disabled. */
 int lhw_env_task_inputs_device(LhwEnv* env, double** out_dev);
+/* The stepping task's second record (jvrc_step only): what SteppingTask.step / calc_reward / done (tasks/stepping_task.py:66-123,
+ * 209-262) read besides the LhwTaskInput fields -- the foot force sites, the footstep targets and the target state machine, the root
+ * quaternion -- as the fused kernel saw them for the LAST control step, after task.step() (update_target_steps included).  A stepping
+ * task plugged in from outside the kernel reads this record next to the LhwTaskInput one (task_hook.py: VectorSteppingTask).  The
+ * target state machine that feeds the observation stays in the kernel; the record carries its state. */
+enum LhwStepTaskInput {
+  LHW_STIN_RSITE_XPOS = 0,    /* 3: get_object_xpos_by_name("rf_force", OBJ_SITE) -- r_foot_pos (stepping_task.py:218), the stale site frame */
+  LHW_STIN_LSITE_XPOS = 3,    /* 3: "lf_force" -- l_foot_pos (:217) */
+  LHW_STIN_TARGET1 = 6,       /* 4: sequence[t1] x, y, z, theta (:67, :81, :225) after update_target_steps (:201-207) */
+  LHW_STIN_TARGET2 = 10,      /* 4: sequence[t2] (:73) */
+  LHW_STIN_REACHED = 14,      /* target_reached (:70, :230-234) */
+  LHW_STIN_FRAMES = 15,       /* target_reached_frames (:231) */
+  LHW_STIN_T1 = 16,           /* t1, t2 (:201-207) */
+  LHW_STIN_T2 = 17,
+  LHW_STIN_NSEQ = 18,         /* len(sequence) */
+  LHW_STIN_GOAL = 19,         /* 8: update_goal_steps (:184-199): goal x[2] y[2] z[2] theta[2] in the root frame, observation order (jvrc_step.py:66-77) */
+  LHW_STIN_ROOT_XQUAT = 27,   /* 4: get_object_xquat_by_name(root, OBJ_BODY) (:82), w x y z -- calc_body_orient_reward's root_quat */
+  LHW_STEP_TASK_INPUT_DIM = 32   /* (31: reserved, written as 0) */
+};
+/* Arms (enable = 1: allocates [N][LHW_STEP_TASK_INPUT_DIM] float64, released with the env) or stops (0) the export; the launch-per-step
+ * path writes it on every control step from then on.  LHW_ERR_UNSUPPORTED on an env of another task. */
+int lhw_env_enable_step_task_inputs(LhwEnv* env, int enable);
+/* HOST pointer [N][LHW_STEP_TASK_INPUT_DIM] float64, synchronous; after lhw_env_enable_step_task_inputs(env, 1). */
+int lhw_env_get_step_task_inputs(LhwEnv* env, double* out_host);
+/* The same records on the device (valid until the env is destroyed or the export disabled); NULL while disabled. */
+int lhw_env_step_task_inputs_device(LhwEnv* env, double** out_dev);
+/* lhw_env_rollout_task_inputs that also exports the stepping record of EVERY control step: stin_dev [T][N][LHW_STEP_TASK_INPUT_DIM]
+ * float64 (jvrc_step only, LHW_ERR_UNSUPPORTED otherwise).  Everything else as lhw_env_rollout_task_inputs. */
+int lhw_env_rollout_step_task_inputs(LhwEnv* env, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev,
+                                     float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev,
+                                     double* tin_dev, double* stin_dev, void* stream);
 /* Actuated-joint fields of the LAST forward pass, as the reference's RobotInterface getters return them after env.step
  * (envs/common/robot_interface.py:163-185: get_act_joint_positions / _velocities / _torques = actuator_length / gear,
  * actuator_velocity / gear, actuator_force * gear).  HOST pointers [N][nu] float64, synchronous; humanoid tasks only. */

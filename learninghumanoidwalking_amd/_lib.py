@@ -47,6 +47,17 @@ TASK_INPUT_FIELDS = dict(grf_r=(0, 1), grf_l=(1, 1), contact_z=(2, 1), foot_cont
                          act_tau=(111, 12), prev_torque=(123, 12), prev_action=(135, 12), action=(147, 12), root_xmat=(160, 9))
 
 
+# include/lhw.h: enum LhwStepTaskInput (the stepping task's second record; offsets into one env's record, length)
+STEP_TASK_INPUT_DIM = 32
+STEP_TASK_INPUT_FIELDS = dict(rsite_xpos=(0, 3), lsite_xpos=(3, 3), target1=(6, 4), target2=(10, 4), reached=(14, 1), frames=(15, 1), t1=(16, 1),
+                              t2=(17, 1), nseq=(18, 1), goal=(19, 8), root_xquat=(27, 4))
+
+
+def split_step_task_inputs(rec):
+    """[N][STEP_TASK_INPUT_DIM] records -> dict of named arrays."""
+    return {k: (rec[:, o] if n == 1 else rec[:, o:o + n]) for k, (o, n) in STEP_TASK_INPUT_FIELDS.items()}
+
+
 def split_task_inputs(rec, nq, nv, nu):
     """[N][TASK_INPUT_DIM] records -> dict of named arrays (vectors cut to the model's nq / nv / nu)."""
     cut = dict(qpos=nq, qvel=nv, qacc=nv, act_pos=nu, act_vel=nu, act_tau=nu, prev_torque=nu, prev_action=nu, action=nu)
@@ -178,6 +189,9 @@ def declare(L):
     sig("lhw_env_enable_task_inputs", [vp, i32])
     sig("lhw_env_get_task_inputs", [vp, vp])
     sig("lhw_env_task_inputs_device", [vp, ctypes.POINTER(vp)])
+    sig("lhw_env_enable_step_task_inputs", [vp, i32])
+    sig("lhw_env_get_step_task_inputs", [vp, vp])
+    sig("lhw_env_step_task_inputs_device", [vp, ctypes.POINTER(vp)])
     sig("lhw_env_debug_wave_cycles", [vp, vp])
     sig("lhw_debug_gemm", [i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp])
     sig("lhw_debug_mlp_strip_forward", [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp])
@@ -194,6 +208,7 @@ def declare(L):
     sig("lhw_env_rollout", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_last_rollout_queued", [vp])
     sig("lhw_env_rollout_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_env_rollout_step_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_rollout_policy", [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(LhwRolloutPolicy)])
     sig("lhw_debug_policy_step", [ctypes.POINTER(LhwRolloutPolicy), vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp])
     return L

@@ -183,14 +183,17 @@ class BatchedEnv:
                                               _ptr(done), _ptr(self.rew_terms), _stream_ptr(self.device)))
 
     def rollout(self, policy, T: int, obs: torch.Tensor, act: torch.Tensor, logp: torch.Tensor, term_obs: torch.Tensor, rew: torch.Tensor,
-                done: torch.Tensor, first: int = 0, count: int | None = None, task_inputs: torch.Tensor | None = None) -> bool:
+                done: torch.Tensor, first: int = 0, count: int | None = None, task_inputs: torch.Tensor | None = None,
+                step_task_inputs: torch.Tensor | None = None) -> bool:
         """The resident rollout (lhw_env_rollout): T control steps of envs [first, first + count) in ONE launch on the current
         stream, the actor (`policy`: PpoKernels.rollout_policy()) evaluated inside the stepper's wavefronts -- the body of
         RolloutWorker.sample's loop (reference rl/workers/rollout_worker.py:142-181) with no wavefront waiting for another env.
         Buffers are time-major over the full batch: obs [T + 1, N, D] (slice 0 in), act [T, N, A], logp / rew / done [T, N],
         term_obs [T, N, D].  `task_inputs` [T, N, TASK_INPUT_DIM] float64 (optional): the sim-facade record of EVERY control step
-        (lhw_env_rollout_task_inputs), for reward-only task plug-ins.  Returns False (nothing launched) where the library has no
-        resident kernel for this env / policy; a HIP failure raises."""
+        (lhw_env_rollout_task_inputs), for reward-only task plug-ins; `step_task_inputs` [T, N, STEP_TASK_INPUT_DIM] float64 (stepping
+        task only, together with `task_inputs`): the stepping task's second record of every control step as well
+        (lhw_env_rollout_step_task_inputs).  Returns False (nothing launched) where the library has no resident kernel for this env /
+        policy; a HIP failure raises."""
         N = self.n_envs
         if self.history_len > 1 or policy is None or not hasattr(self._L, "lhw_env_rollout"):
             return False
@@ -200,9 +203,16 @@ class BatchedEnv:
             assert x.is_cuda and x.is_contiguous()
         args = (self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), _ptr(obs),
                 _ptr(act), _ptr(logp), _ptr(term_obs), _ptr(rew), _ptr(done), _ptr(self.rew_terms))
+        if step_task_inputs is not None:
+            assert task_inputs is not None, "the stepping record is exported together with the LhwTaskInput one"
+            assert step_task_inputs.shape == (T, N, _lib.STEP_TASK_INPUT_DIM) and step_task_inputs.dtype == torch.float64
+            assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
         if task_inputs is not None:
             assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
-            rc = self._L.lhw_env_rollout_task_inputs(*args, _ptr(task_inputs), _stream_ptr(self.device))
+            if step_task_inputs is not None:
+                rc = self._L.lhw_env_rollout_step_task_inputs(*args, _ptr(task_inputs), _ptr(step_task_inputs), _stream_ptr(self.device))
+            else:
+                rc = self._L.lhw_env_rollout_task_inputs(*args, _ptr(task_inputs), _stream_ptr(self.device))
         else:
             rc = self._L.lhw_env_rollout(*args, _stream_ptr(self.device))
         if rc == -4:      # LHW_ERR_UNSUPPORTED: the caller keeps the launch-per-step pipeline (anything else -- LHW_ERR_HIP ... -- raises)
@@ -260,6 +270,17 @@ class BatchedEnv:
         rec = np.zeros((self.n_envs, _lib.TASK_INPUT_DIM))
         _lib.check(self._L.lhw_env_get_task_inputs(self._h, rec.ctypes.data))
         return _lib.split_task_inputs(rec, self.nq, self.nv, self.act_dim)
+
+    def enable_step_task_inputs(self, enable: bool = True):
+        """Arm / disarm the stepping task's second record (include/lhw.h: LhwStepTaskInput; jvrc_step only): foot force sites,
+        footstep targets, the target state machine and the root quaternion of every control step from the next one on."""
+        _lib.check(self._L.lhw_env_enable_step_task_inputs(self._h, int(bool(enable))))
+
+    def get_step_task_inputs(self) -> dict:
+        """Named float64 arrays of the last control step's stepping record (host copy, synchronous)."""
+        rec = np.zeros((self.n_envs, _lib.STEP_TASK_INPUT_DIM))
+        _lib.check(self._L.lhw_env_get_step_task_inputs(self._h, rec.ctypes.data))
+        return _lib.split_step_task_inputs(rec)
 
     def wave_cycles(self):
         """Per-env shader-clock cycles of the last control-step launch (diagnostic; the first call only arms the recording)."""

@@ -226,11 +226,12 @@ extern "C" int lhw_env_step_range(LhwEnv* e, int32_t first, int32_t count, const
 }
 
 static int env_rollout_impl(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
-                            float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, double* tin_dev, void* stream) {
+                            float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, double* tin_dev, double* stin_dev,
+                            void* stream) {
   if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
   if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout: wave-per-env (humanoid) steppers only");
   HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_rollout(e->hum, first, count, T, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, (hipStream_t)stream);
+  const int rc = humanoid_rollout(e->hum, first, count, T, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, (hipStream_t)stream);
   if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
   if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
   if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout: needs a float32 actor obs %d -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's resident kernel",
@@ -240,13 +241,20 @@ static int env_rollout_impl(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t f
 }
 extern "C" int lhw_env_rollout(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, void* stream) {
-  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, nullptr, stream);
+  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, nullptr, nullptr, stream);
 }
 extern "C" int lhw_env_rollout_task_inputs(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                            float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, double* tin_dev,
                                            void* stream) {
   if (!tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_task_inputs: null task-input buffer");
-  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stream);
+  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, nullptr, stream);
+}
+extern "C" int lhw_env_rollout_step_task_inputs(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev,
+                                                float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev,
+                                                float* rew_terms_dev, double* tin_dev, double* stin_dev, void* stream) {
+  if (!e || e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_step_task_inputs: stepping-task envs only");
+  if (!tin_dev || !stin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_step_task_inputs: null task-input buffer");
+  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
 }
 
 extern "C" int lhw_env_last_rollout_queued(LhwEnv* e) {
@@ -346,6 +354,24 @@ extern "C" int lhw_env_get_task_inputs(LhwEnv* e, double* out_host) {
 extern "C" int lhw_env_task_inputs_device(LhwEnv* e, double** out_dev) {
   if (!e || !e->hum || !out_dev) return lhw_fail(LHW_ERR_ARG, "null argument / not a humanoid task");
   return humanoid_task_inputs(e->hum, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "task input buffer") : LHW_OK;
+}
+extern "C" int lhw_env_enable_step_task_inputs(LhwEnv* e, int enable) {
+  if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "the stepping task-input record exists for the stepping task only");
+  HIPCHK(hipSetDevice(e->device));
+  if (humanoid_step_task_inputs(e->hum, enable ? 1 : 0, nullptr, nullptr)) return lhw_fail(LHW_ERR_HIP, "stepping task input buffer");
+  return LHW_OK;
+}
+extern "C" int lhw_env_get_step_task_inputs(LhwEnv* e, double* out_host) {
+  if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP || !out_host) return lhw_fail(LHW_ERR_ARG, "null argument / not a stepping-task env");
+  HIPCHK(hipSetDevice(e->device));
+  const int rc = humanoid_step_task_inputs(e->hum, -1, out_host, nullptr);
+  if (rc == -2) return lhw_fail(LHW_ERR_ARG, "lhw_env_get_step_task_inputs: call lhw_env_enable_step_task_inputs(env, 1) first");
+  if (rc) return lhw_fail(LHW_ERR_HIP, "stepping task input copy");
+  return LHW_OK;
+}
+extern "C" int lhw_env_step_task_inputs_device(LhwEnv* e, double** out_dev) {
+  if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP || !out_dev) return lhw_fail(LHW_ERR_ARG, "null argument / not a stepping-task env");
+  return humanoid_step_task_inputs(e->hum, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "stepping task input buffer") : LHW_OK;
 }
 extern "C" int lhw_env_get_actuator_state(LhwEnv* e, double* pos_host, double* vel_host, double* torque_host) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");

@@ -556,7 +556,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
   if (rec) h->dev_allocs.push_back(rec);
   if (irec) h->dev_allocs.push_back(irec);
   if (eps) h->dev_allocs.push_back(eps);
-  h->st.rec = (double*)rec; h->st.irec = (int*)irec; h->st.ep_stats = (double*)eps; h->st.prof = nullptr; h->st.wave_cyc = nullptr; h->st.tin = nullptr;
+  h->st.rec = (double*)rec; h->st.irec = (int*)irec; h->st.ep_stats = (double*)eps; h->st.prof = nullptr; h->st.wave_cyc = nullptr; h->st.tin = nullptr; h->st.stin = nullptr;
   if (!ok) { humanoid_destroy(h); return lhw_fail(LHW_ERR_HIP, "humanoid_create: device allocation failed or bad body ids"); }
   *obs_dim = stepping ? 39 : (walk ? 37 : (h1walk ? 43 : 35)); *act_dim = nu; *n_terms = ((walk && !stepping) || h1walk) ? 10 : 6;
   p.reset_template = -1;
@@ -675,6 +675,26 @@ int humanoid_task_inputs(HumanoidEnv* h, int enable, double* out_host, double** 
     if (!h->st.tin) return -2;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpy(out_host, h->st.tin, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  }
+  return 0;
+}
+// the stepping task's second record (LhwStepTaskInput), the same way
+int humanoid_step_task_inputs(HumanoidEnv* h, int enable, double* out_host, double** out_dev) {
+  const size_t n = (size_t)h->p.n_envs * LHW_STEP_TASK_INPUT_DIM;
+  if (enable == 1 && !h->st.stin) {
+    void* d = nullptr;
+    if (lhw_malloc(&d, n * sizeof(double)) != hipSuccess) return -1;
+    (void)hipMemset(d, 0, n * sizeof(double));
+    h->dev_allocs.push_back(d);
+    h->st.stin = (double*)d;
+  } else if (enable == 0) {
+    h->st.stin = nullptr;   // (the buffer is released with the env)
+  }
+  if (out_dev) *out_dev = h->st.stin;
+  if (out_host) {
+    if (!h->st.stin) return -2;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(out_host, h->st.stin, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   }
   return 0;
 }

@@ -298,6 +298,8 @@ struct HState {
   long long* wave_cyc;  // optional [N] shader-clock cycles the env's group spent in the last control-step launch (NULL = off)
   double* bigd;    // stepping task: [N][BW_DOUBLES] / [N][BW_INTS] workspace of the many-contact path (NULL for the other tasks)
   int* bigi;
+  double* stin;    // stepping task, optional [N][LHW_STEP_TASK_INPUT_DIM]: the second task-input record (lhw_env_enable_step_task_inputs); its
+                   // slice of a control step sits at lz.tin_off / LHW_TASK_INPUT_DIM * LHW_STEP_TASK_INPUT_DIM (the records are exported together)
 };
 // Analysis builds (-DLHW_FINEPROF=<phase slot>): the phase of that slot is split further, FINE_MARK(phase, i) accumulating the
 // clock of env 0 into g_fine[i] (read back through lhw_env_profile in place of the phase table).  Compiled out of the product.
@@ -3707,6 +3709,19 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
           if (lane < m.nu) {
             ti[LHW_TIN_ACT_POS + lane] = S.sq[lane]; ti[LHW_TIN_ACT_VEL + lane] = S.sv[lane]; ti[LHW_TIN_ACT_TAU + lane] = cur_tq;
             ti[LHW_TIN_PREV_TORQUE + lane] = prevtq; ti[LHW_TIN_PREV_ACTION + lane] = prevact; ti[LHW_TIN_ACTION + lane] = target;
+          }
+        }
+        if constexpr (TASK == TASK_STEP) {
+          if (st.stin) {   // the stepping task's second record (include/lhw.h: LhwStepTaskInput): what SteppingTask reads besides
+            double* si = st.stin + lz.tin_off / LHW_TASK_INPUT_DIM * LHW_STEP_TASK_INPUT_DIM + (size_t)env * LHW_STEP_TASK_INPUT_DIM;
+            if (lane < 6) si[LHW_STIN_RSITE_XPOS + lane] = S.spos[3 + lane];   // tracked points 1 (rf_force), 2 (lf_force): stale site frames
+            if (lane < 8) si[LHW_STIN_TARGET1 + lane] = ter[T_SEQ + 6 * (lane < 4 ? t1 : t2) + (lane & 3)];   // x y z theta of both targets
+            if (lane < 4) si[LHW_STIN_ROOT_XQUAT + lane] = S.rootquat[lane];
+            if (lane == 0) {
+              si[LHW_STIN_REACHED] = reached; si[LHW_STIN_FRAMES] = frames; si[LHW_STIN_T1] = t1; si[LHW_STIN_T2] = t2; si[LHW_STIN_NSEQ] = nseq;
+              for (int k = 0; k < 8; k++) si[LHW_STIN_GOAL + k] = goal[k];
+              si[LHW_STEP_TASK_INPUT_DIM - 1] = 0.0;
+            }
           }
         }
         // failure detection: a non-finite state ends the episode (counted in ep_stats[4]); outputs are sanitised so one

@@ -57,7 +57,8 @@ struct HRollout {
   // in the order (chunk 0 of every group, chunk 1 of every group, ...), queue[1 + group] counts the group's finished chunks.
   unsigned* queue;
   int chunk;
-  long long tin_step;    // doubles per control step of the task-input export (n_total * LHW_TASK_INPUT_DIM), 0: the per-launch record (or none)
+  long long tin_step;    // doubles per control step of the task-input export (n_total * LHW_TASK_INPUT_DIM), 0: the per-launch record (or none);
+                         // the stepping task's second record (HState::stin) follows it at LHW_STEP_TASK_INPUT_DIM doubles per env
   LhwRolloutPolicy pol;
 };
 
@@ -333,7 +334,7 @@ void humanoid_rollout_launch_step(bool queued, dim3 grid, hipStream_t s, const H
 int humanoid_last_rollout_queued(const HumanoidEnv* h) { return h->last_rollout_queued; }
 
 int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, hipStream_t s) {
+                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
   if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
   const int obs_dim = h->p.task == TASK_STEP ? 39 : (h->p.task == TASK_WALK ? 37 : (h->p.task == TASK_H1WALK ? 43 : 35));
   if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
@@ -347,6 +348,12 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
   ro.tin_step = tin_all ? (long long)h->p.n_envs * LHW_TASK_INPUT_DIM : 0;
   HState st = h->st;
   if (tin_all) st.tin = tin_all;   // [T][n_envs][LHW_TASK_INPUT_DIM]: every control step's record instead of the last one's
+  if (stin_all) {                  // [T][n_envs][LHW_STEP_TASK_INPUT_DIM] (stepping task, exported together with tin_all: its slice offset follows tin_off)
+    if (!tin_all || h->p.task != TASK_STEP) return -1;
+    st.stin = stin_all;
+  } else if (tin_all) {
+    st.stin = nullptr;             // (an armed per-launch stepping record is [n_envs] long: not written at the time slices of tin_all)
+  }
   const HLaunch lz{first, count, 0, h->iteration, 0};
   if (!h->fast && h->p.task != TASK_STEP) return -3;   // a walking / standing model that does not fit the two-envs-per-wave layout (or LHW_ONE_ENV_PER_WAVE): launch-per-step only
   // Stepping task with more env groups than wave slots: the resident waves share a job queue of `chunk`-step pieces instead of a

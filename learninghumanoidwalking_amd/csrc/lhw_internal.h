@@ -41,7 +41,7 @@ int humanoid_step_range(HumanoidEnv* h, int first, int count, const float* act, 
                         float* rew_terms, hipStream_t s);
 int humanoid_last_rollout_queued(const HumanoidEnv* h);
 int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, hipStream_t s);   // lhw_humanoid_rollout.hip; -1 bad range, -2 / -3 unsupported, -4 HIP error
+                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // lhw_humanoid_rollout.hip; -1 bad range, -2 / -3 unsupported, -4 HIP error
 void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t s);
 void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, hipStream_t s);
 double* humanoid_ep_stats(HumanoidEnv* h);
@@ -50,6 +50,7 @@ int humanoid_occupancy();
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
 int humanoid_task_inputs(HumanoidEnv* h, int enable /* -1: leave */, double* out_host, double** out_dev);
+int humanoid_step_task_inputs(HumanoidEnv* h, int enable /* -1: leave */, double* out_host, double** out_dev);   // stepping task only
 int humanoid_actuator_state(HumanoidEnv* h, double* pos, double* vel, double* tq);
 int humanoid_step_record(HumanoidEnv* h, double* seq, double* floor_z, int32_t* istate);
 

@@ -41,6 +41,7 @@ class H1Spec:
     yaml_path: str = H1_BASE_YAML
     xml_path: str = H1_STANDIN_XML
     name: str = "h1"
+    task_code = TASK_H1_STAND      # the kernels' task (a class attribute, not a field): which fused task a plugged-in VectorTask replaces
     obs_dim: int = 35
     act_dim: int = 10
     step_kernel_name: str = "humanoid_kernel<0, 2, 32>"     # rocprof name of the control-step kernel (MODE 0, TASK_STAND)

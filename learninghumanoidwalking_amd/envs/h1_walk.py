@@ -26,6 +26,7 @@ MIRROR_ACTS = [-5, -6, 7, 8, 9, -0.1, -1, 2, 3, 4]   # h1_walk.py:113
 class H1WalkSpec(H1Spec):
     yaml_path: str = H1_WALK_YAML
     name: str = "h1_walk"
+    task_code = TASK_H1_WALK      # the kernels' task (a class attribute, not a field): which fused task a plugged-in VectorTask replaces
     obs_dim: int = 43
     step_kernel_name: str = "humanoid_kernel<0, 4, 32>"
 

@@ -63,6 +63,7 @@ class JvrcWalkSpec:
     yaml_path: str = JVRC_BASE_YAML
     xml_path: str = JVRC_STANDIN_XML
     name: str = "jvrc_walk"
+    task_code = TASK_JVRC_WALK      # the kernels' task (a class attribute, not a field): which fused task a plugged-in VectorTask replaces
     obs_dim: int = 37
     act_dim: int = 12
     step_kernel_name: str = "humanoid_kernel<0, 1, 32>"     # rocprof name of the control-step kernel (MODE 0, TASK_WALK)

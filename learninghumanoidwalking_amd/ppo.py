@@ -20,7 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib, dist_utils
+from .batched_env import TASK_JVRC_STEP
 from .ppo_kernels import PpoKernels, reference_init
+from .task_hook import reward_only_on
 
 
 @dataclass
@@ -116,8 +118,9 @@ class Rollout:
         if task is not None and getattr(env, "history_len", 1) > 1:
             # (the hooked paths write the reset observation / history rows themselves and know nothing of the env-side history deque)
             raise NotImplementedError("a plugged-in task with obs_history_len > 1 is not supported")
-        self.reward_only = bool(task is not None and getattr(task, "reward_only", False))
-        self._tin_all = None
+        # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
+        self.reward_only = reward_only_on(task, env.task)
+        self._tin_all = self._stin_all = None
         N, D, A, dev = env.n_envs, env.obs_dim, env.act_dim, env.device
         self.N = N
         self.obs = torch.zeros(T + 1, N, D, dtype=torch.float32, device=dev)
@@ -258,16 +261,18 @@ class Rollout:
         self._ep_ret = torch.where(none, self._ep_ret + cc[-1], tail)
         self._traj_len = torch.where(none, self._traj_len.to(torch.int64) + T, (T - 1) - fin).to(torch.int32)
 
-    def _evaluate_reward_batch(self, rec):
-        """The plugged task's reward for [M, TASK_INPUT_DIM] records (non-finite -> 0: the kernel ended that episode itself)."""
+    def _evaluate_reward_batch(self, rec, srec=None):
+        """The plugged task's reward for [M, TASK_INPUT_DIM] records (and, stepping env, the [M, STEP_TASK_INPUT_DIM] ones of the same
+        rows; non-finite -> 0: the kernel ended that episode itself)."""
         from .task_hook import TaskInputs
         env = self.env
-        rew, _ = self.task.evaluate(TaskInputs(rec, env.nq, env.nv, env.act_dim))
+        rew, _ = self.task.evaluate(TaskInputs(rec, env.nq, env.nv, env.act_dim, srec))
         return torch.where(torch.isfinite(rew), rew, torch.zeros_like(rew)).float()
 
     def _collect_resident_hooked(self, deterministic) -> bool:
         """Reward-only task plug-ins at the resident rollout's speed: one lhw_env_rollout_task_inputs launch (fused termination,
-        truncation and resets; the sim-facade record of every control step exported, [T][N][160] float64), then ONE evaluation of
+        truncation and resets; the sim-facade record of every control step exported, [T][N][176] float64 -- 2.3 GB at 4096 envs x
+        T = 400 -- and on the stepping env the stepping record as well, [T][N][32] float64, another 420 MB), then ONE evaluation of
         the task over the whole batch -- RobotBase.step's `task.calc_reward` (robots/robot_base.py:88-96) moved behind the rollout,
         which it may be because a reward does not feed back into the simulation."""
         env, k, T = self.env, self.k, self.T
@@ -282,14 +287,18 @@ class Rollout:
         self._pol_keep = pol
         if self._tin_all is None:
             self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-        if not env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done, task_inputs=self._tin_all):
+        if self._stin_all is None and env.task == TASK_JVRC_STEP:
+            self._stin_all = _lib.empty(T, self.N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+        if not env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done, task_inputs=self._tin_all,
+                           step_task_inputs=self._stin_all):
             return False
         self.counter += T
         rec = self._tin_all.reshape(T * self.N, -1)
+        srec = self._stin_all.reshape(T * self.N, -1) if self._stin_all is not None else None
         rew = self.rew.reshape(-1)
         chunk = max(self.N, (1 << 19) // self.N * self.N)      # whole time slices, about half a million rows per evaluation
         for a in range(0, rec.shape[0], chunk):
-            rew[a:a + chunk] = self._evaluate_reward_batch(rec[a:a + chunk])
+            rew[a:a + chunk] = self._evaluate_reward_batch(rec[a:a + chunk], srec[a:a + chunk] if srec is not None else None)
         self._episode_stats_from_buffers()
         return True
 
@@ -305,7 +314,7 @@ class Rollout:
             k.forward(self.obs[t], seed=self.seed, env_id_base=self.env_base, counter=self.counter, deterministic=deterministic,
                       want_value=False, want_mu=False, act=self.act[t], logp=self.logp[t])
             env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self.tob_all[t], rew_out=self._scratch_rew, done_out=self.done[t])
-            self.rew[t].copy_(self._evaluate_reward_batch(ti.rec))
+            self.rew[t].copy_(self._evaluate_reward_batch(ti.rec, ti.srec))
             self.counter += 1
         self._episode_stats_from_buffers()
 
@@ -551,7 +560,8 @@ class PPO:
         self.task = task(spec, self.device) if task is not None else None
         # A task that decides terminations itself is consulted after every control step and the env never ends an episode by itself:
         # the rollout truncates and resets (Rollout._collect_hooked).  A reward-only task leaves all that to the kernel.
-        own_done = self.task is not None and not getattr(self.task, "reward_only", False)
+        # (reward_only counts only where the task declares this env's fused termination as its own: task_hook.reward_only_on)
+        own_done = self.task is not None and not reward_only_on(self.task, getattr(spec, "task_code", None))
         self.env = spec.make_batched(self.n_proc, seed=env_seed, device=self.device, max_traj_len=0 if own_done else self.max_traj_len,
                                      env_id_base=dist_utils.shard_env_ids(self.n_proc, self.rank))
         self.env.env_id_base = dist_utils.shard_env_ids(self.n_proc, self.rank)

@@ -11,8 +11,10 @@ every control step and train on ITS reward and termination instead of the fused 
         def evaluate(self, ti):            # ti: TaskInputs (named float64 device tensors, [N] or [N, k])
             return reward, done            # float tensor [N], bool tensor [N]
 
-Two tasks ship: ``VectorWalkingTask`` -- WalkingTask.calc_reward / done (tasks/walking_task.py:85-147,184-192) on torch tensors,
-term weights adjustable -- and ``PerEnvRewards`` -- the slow path proper: it calls the functions of a ``tasks/rewards.py`` MODULE
+Four tasks ship: ``VectorWalkingTask`` -- WalkingTask.calc_reward / done (tasks/walking_task.py:85-147,184-192) on torch tensors,
+term weights adjustable --, ``VectorStandingTask`` (tasks/standing_task.py), ``VectorSteppingTask`` -- SteppingTask.calc_reward / done
+(tasks/stepping_task.py:66-123,249-262), which also reads the stepping env's second record (include/lhw.h: LhwStepTaskInput: foot
+force sites, footstep targets, target state, root quaternion) -- and ``PerEnvRewards`` -- the slow path proper: it calls the functions of a ``tasks/rewards.py`` MODULE
 (the reference's own file, or an edited copy) env by env on the host, unchanged.  The task's state machine that feeds the
 OBSERVATION (gait phase, walk mode, mode_ref) stays in the kernel; the record carries it (``phase``, ``mode``, ``mode_ref``).
 With a task plugged in, the env never resets itself (it is created with ``max_traj_len = 0``): the rollout truncates and resets on
@@ -26,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .batched_env import TASK_H1_STAND, TASK_H1_WALK, TASK_JVRC_STEP, TASK_JVRC_WALK
 
 
 class _DevArray:
@@ -38,28 +41,40 @@ class _DevArray:
 class TaskInputs:
     """Named views of the [N, LHW_TASK_INPUT_DIM] float64 record the last control step exported (include/lhw.h: enum LhwTaskInput):
     grf_r grf_l contact_z foot_contact self_collision phase mode mode_ref rfoot_vel lfoot_vel root_vel_local root_xpos head_xpos
-    rfoot_xpos lfoot_xpos qpos qvel qacc act_pos act_vel act_tau prev_torque prev_action action root_xmat."""
+    rfoot_xpos lfoot_xpos qpos qvel qacc act_pos act_vel act_tau prev_torque prev_action action root_xmat.
+    With the stepping env's second record `srec` [N, LHW_STEP_TASK_INPUT_DIM] (enum LhwStepTaskInput) also: rsite_xpos lsite_xpos
+    target1 target2 reached frames t1 t2 nseq goal root_xquat."""
 
-    def __init__(self, rec: torch.Tensor, nq: int, nv: int, nu: int):
-        self.rec, self.n_envs = rec, rec.shape[0]
+    def __init__(self, rec: torch.Tensor, nq: int, nv: int, nu: int, srec: torch.Tensor | None = None):
+        self.rec, self.srec, self.n_envs = rec, srec, rec.shape[0]
         self._cut = dict(qpos=nq, qvel=nv, qacc=nv, act_pos=nu, act_vel=nu, act_tau=nu, prev_torque=nu, prev_action=nu, action=nu)
 
     def __getattr__(self, name):
         f = _lib.TASK_INPUT_FIELDS.get(name)
+        if f is not None:
+            o, n = f
+            n = self._cut.get(name, n)
+            return self.rec[:, o] if n == 1 else self.rec[:, o:o + n]
+        f = _lib.STEP_TASK_INPUT_FIELDS.get(name)
         if f is None:
             raise AttributeError(name)
+        srec = self.__dict__.get("srec")
+        if srec is None:
+            raise AttributeError(f"'{name}' is a field of the stepping task's record (LhwStepTaskInput), which only the jvrc_step env exports")
         o, n = f
-        n = self._cut.get(name, n)
-        return self.rec[:, o] if n == 1 else self.rec[:, o:o + n]
+        return srec[:, o] if n == 1 else srec[:, o:o + n]
 
     def numpy(self) -> dict:
-        """host copy, as BatchedEnv.get_task_inputs() returns it"""
-        return _lib.split_task_inputs(self.rec.cpu().numpy(), self._cut["qpos"], self._cut["qvel"], self._cut["action"])
+        """host copy, as BatchedEnv.get_task_inputs() (and, for a stepping env, get_step_task_inputs()) return it"""
+        out = _lib.split_task_inputs(self.rec.cpu().numpy(), self._cut["qpos"], self._cut["qvel"], self._cut["action"])
+        if self.srec is not None:
+            out.update(_lib.split_step_task_inputs(self.srec.cpu().numpy()))
+        return out
 
 
 def device_task_inputs(env) -> TaskInputs:
-    """The env's task-input record as device tensors (no copy; arms the export on first use).  The view stays valid until the env
-    is destroyed; its contents are those of the env's last control step on the stream that ran it."""
+    """The env's task-input record(s) as device tensors (no copy; arms the export on first use -- on a stepping env both records).
+    The view stays valid until the env is destroyed; its contents are those of the env's last control step on the stream that ran it."""
     view = getattr(env, "_task_inputs_view", None)
     if view is None:
         env.enable_task_inputs(True)
@@ -68,8 +83,25 @@ def device_task_inputs(env) -> TaskInputs:
         if not p.value:
             raise _lib.LhwError(-4, "this env exports no task inputs (humanoid tasks only)")
         rec = torch.as_tensor(_DevArray(p.value, (env.n_envs, _lib.TASK_INPUT_DIM)), device=env.device)
-        view = env._task_inputs_view = TaskInputs(rec, env.nq, env.nv, env.act_dim)
+        srec = None
+        if env.task == TASK_JVRC_STEP:
+            env.enable_step_task_inputs(True)
+            q = ctypes.c_void_p()
+            _lib.check(env._L.lhw_env_step_task_inputs_device(env._h, ctypes.byref(q)))
+            srec = torch.as_tensor(_DevArray(q.value, (env.n_envs, _lib.STEP_TASK_INPUT_DIM)), device=env.device)
+        view = env._task_inputs_view = TaskInputs(rec, env.nq, env.nv, env.act_dim, srec)
     return view
+
+
+def reward_only_on(task, env_task) -> bool:
+    """Whether a plugged-in task runs as a reward-only plug-in on an env of kernel task `env_task` (batched_env.TASK_*): the kernel
+    then keeps its own termination, so the task's `reward_only = True` is honoured only where its `done()` IS that env's fused
+    termination.  A task names the envs for which that holds in `fused_tasks`; a task without that declaration (a user's) is taken at
+    its word.  PPO (the env's max_traj_len) and Rollout (which collection path) both decide with this predicate."""
+    if task is None or not getattr(task, "reward_only", False):
+        return False
+    fused = getattr(task, "fused_tasks", None)
+    return fused is None or env_task in fused
 
 
 class VectorTask:
@@ -79,8 +111,11 @@ class VectorTask:
     case: an edited tasks/rewards.py, other term weights).  The rollout then stays resident (one launch per rollout, the kernel's
     own termination / truncation / resets), exports the record of every control step, and `evaluate` is called ONCE over the whole
     [T * N] batch after the launch; the `done` it returns is ignored (Rollout._collect_resident_hooked).  With False (default)
-    the task is consulted after every control step and decides terminations itself (Rollout._collect_hooked)."""
+    the task is consulted after every control step and decides terminations itself (Rollout._collect_hooked).  `fused_tasks` (optional)
+    names the envs (batched_env.TASK_*) whose fused termination `done` equals; on any other env the task is consulted step by step
+    whatever `reward_only` says (reward_only_on)."""
     reward_only = False
+    fused_tasks = None
 
     def evaluate(self, ti: TaskInputs):
         """-> (reward [N] float tensor, done [N] bool tensor); called once per control step, after the env step"""
@@ -95,6 +130,7 @@ class VectorWalkingTask(VectorTask):
     inputs, vectorised over the batch in float64 torch.  `weights` overrides the reference's term weights by name."""
 
     reward_only = True      # done() below IS the fused WalkingTask.done: the resident rollout may keep the kernel's own flags
+    fused_tasks = (TASK_JVRC_WALK, TASK_H1_WALK)      # (z < 0.6 || z > 1.4 || self collision: control_step's walking-task branch)
     TERMS = ("foot_frc_score", "foot_vel_score", "root_accel", "height_error", "com_vel_error", "yaw_vel_error", "upper_body_reward",
              "posture_error", "torque_penalty", "action_penalty")
     WEIGHTS = dict(foot_frc_score=0.225, foot_vel_score=0.225, root_accel=0.050, height_error=0.050, com_vel_error=0.150,
@@ -160,6 +196,7 @@ class VectorStandingTask(VectorTask):
     plug-in (`head_xpos` of that env is the torso link, `root_xmat` the pelvis frame).  `weights` overrides term weights by name."""
 
     reward_only = True
+    fused_tasks = (TASK_H1_STAND,)
     TERMS = ("com_vel_error", "yaw_vel_error", "height", "upperbody", "joint_torque_reward", "posture")
     WEIGHTS = dict(com_vel_error=0.3, yaw_vel_error=0.3, height=0.1, upperbody=0.1, joint_torque_reward=0.1, posture=0.1)
 
@@ -190,6 +227,67 @@ class VectorStandingTask(VectorTask):
         reward = sum(self.last_terms[k] for k in self.TERMS)
         z = ti.qpos[:, 2]
         done = (z < self.zlim[0]) | (z > self.zlim[1]) | (ti.self_collision != 0)     # standing_task.py:111-131
+        return reward, done
+
+
+class VectorSteppingTask(VectorTask):
+    """SteppingTask.calc_reward + done (reference tasks/stepping_task.py:66-123, 249-262; tasks/rewards.py) on the exported inputs of a
+    jvrc_step env -- both records: LhwTaskInput (forces, contacts, foot velocities, root / head positions, phase, mode) and
+    LhwStepTaskInput (force sites, the targets sequence[t1] / sequence[t2] after update_target_steps, target_reached, root quaternion)
+    -- vectorised over the batch in float64 torch.  `weights` overrides the reference's term weights by name; `min_root_height` is
+    done()'s bound on the root height above the lower foot site (another value than 0.6 makes the task decide terminations itself)."""
+
+    reward_only = True
+    fused_tasks = (TASK_JVRC_STEP,)
+    TERMS = ("foot_frc_score", "foot_vel_score", "orient_cost", "height_error", "step_reward", "upper_body_reward")
+    WEIGHTS = dict(foot_frc_score=0.150, foot_vel_score=0.150, orient_cost=0.050, height_error=0.050, step_reward=0.450, upper_body_reward=0.050)
+    CURVED, STANDING, BACKWARD, LATERAL, FORWARD = 0, 1, 2, 3, 4      # the kernels' walk modes (envs/jvrc_step.py: WALK_*)
+
+    def __init__(self, spec, device, weights: dict | None = None, min_root_height: float = 0.6):
+        if float(min_root_height) != 0.6:
+            self.reward_only = False      # another termination rule than the fused one: consulted step by step
+        self.w = dict(self.WEIGHTS, **(weights or {}))
+        unknown = set(self.w) - set(self.TERMS)
+        if unknown:
+            raise KeyError(f"unknown reward terms {sorted(unknown)}")
+        self.lut = torch.as_tensor(np.asarray(spec.clock_lut(), dtype=np.float64), device=device)     # [4][period]: r_frc r_vel l_frc l_vel
+        self.mass = float(spec.model().body_mass.sum())         # get_robot_mass(): the static boxes included (envs/jvrc_step.py)
+        self.goal_height = float(spec.goal_height)
+        self.min_root_height = float(min_root_height)
+        self.last_terms = None
+
+    def evaluate(self, ti: TaskInputs):
+        ph = ti.phase.long()
+        standing = ti.mode.long() == self.STANDING
+        one = torch.ones_like(ti.grf_r)
+        zero = torch.zeros_like(one)
+        r_frc = torch.where(standing, one, self.lut[0][ph]); r_vel = torch.where(standing, -one, self.lut[1][ph])
+        l_frc = torch.where(standing, one, self.lut[2][ph]); l_vel = torch.where(standing, -one, self.lut[3][ph])
+        clock = VectorWalkingTask._clock
+        t = {}
+        t["foot_frc_score"] = clock(ti.grf_l, ti.grf_r, l_frc, r_frc, self.mass * 9.8 * 0.5)
+        t["foot_vel_score"] = clock(ti.lfoot_vel.norm(dim=1), ti.rfoot_vel.norm(dim=1), l_vel, r_vel, 0.2)
+        # calc_body_orient_reward(root_quat, euler2quat(0, 0, theta of sequence[t1])): the target quaternion is (cos th/2, 0, 0, sin th/2)
+        th, q = ti.target1[:, 3], ti.root_xquat
+        inner = torch.cos(th / 2) * q[:, 0] + torch.sin(th / 2) * q[:, 3]
+        t["orient_cost"] = torch.exp(-10 * (1 - inner * inner))
+        cz = torch.where(ti.foot_contact != 0, ti.contact_z, zero)
+        herr = (ti.root_xpos[:, 2] - cz - self.goal_height).abs()
+        herr = torch.where(herr < 0.01, zero, herr)           # calc_height_reward with the stepping task's goal speed, 0
+        t["height_error"] = torch.exp(-40 * herr * herr)
+        # step_reward (stepping_task.py:66-77): a foot site on the current target, progress of the root towards the targets' midpoint
+        tp = ti.target1[:, 0:3]
+        dist = torch.minimum((ti.lsite_xpos - tp).norm(dim=1), (ti.rsite_xpos - tp).norm(dim=1))
+        hit = torch.where(ti.reached != 0, torch.exp(-dist / 0.25), zero)
+        mid = (ti.target1[:, 0:2] + ti.target2[:, 0:2]) / 2
+        progress = torch.exp(-(ti.root_xpos[:, 0:2] - mid).norm(dim=1) / 2)
+        t["step_reward"] = 0.8 * hit + 0.2 * progress
+        hn = (ti.head_xpos[:, 0:2] - ti.root_xpos[:, 0:2]).norm(dim=1)
+        t["upper_body_reward"] = torch.exp(-10 * (hn * hn))
+        self.last_terms = {k: self.w[k] * t[k] for k in self.TERMS}
+        reward = sum(self.last_terms[k] for k in self.TERMS)
+        foot_z = torch.minimum(ti.lsite_xpos[:, 2], ti.rsite_xpos[:, 2])
+        done = (ti.root_xpos[:, 2] - foot_z < self.min_root_height) | (ti.self_collision != 0)     # stepping_task.py:249-262
         return reward, done
 
 
