@@ -437,9 +437,13 @@ int lhw_ppo_grad(LhwPpo* ppo, const float* theta, float* grad, const float* xn, 
 /* dual clip_grad_norm_ + Adam; zeroes grad */
 int lhw_ppo_apply(LhwPpo* ppo, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
                   void* stream);
+/* test hook: synchronises the device and copies to the host the two squared gradient norms (actor group, critic group; the gradient
+ * times grad_scale, before clipping) that the last lhw_ppo_apply / lhw_ppo_step clipped with */
+int lhw_ppo_debug_grad_sqnorms(LhwPpo* ppo, float* out2_host);
 /* lhw_ppo_grad followed by lhw_ppo_apply as ONE launch: the optimiser step of rl/algos/ppo.py:387-396 (zero_grad, backward, two
- * clip_grad_norm_, two Adam steps) captured once as a hipGraph per (buffers, minibatch size) and replayed, the minibatch's index pointer
- * and Adam's bias corrections patched into the graph's kernel nodes.  Bitwise the result of the two calls.  Single process only: with data
+ * clip_grad_norm_, two Adam steps) captured once as a hipGraph per (buffers, minibatch size, grad_scale) and replayed, the minibatch's
+ * index pointer and Adam's bias corrections patched into the graph's kernel nodes (a new grad_scale recaptures).  Bitwise the result of
+ * the two calls.  Single process only: with data
  * parallelism the gradient all-reduce belongs between lhw_ppo_grad and lhw_ppo_apply. */
 int lhw_ppo_step(LhwPpo* ppo, float* theta, float* grad, float* adam_m, float* adam_v, const float* xn, const float* xm, const float* act,
                  const float* old_logp, const float* adv, const float* ret, const int32_t* idx, int32_t B, float* stats_dev, int64_t step,
@@ -470,6 +474,8 @@ int lhw_rnn_grad(LhwRnn* rnn, const float* theta, float* grad, int32_t T, int32_
                  const int32_t* cols, int32_t B, float* stats_dev, void* stream);
 int lhw_rnn_apply(LhwRnn* rnn, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
                   void* stream);
+/* lhw_ppo_debug_grad_sqnorms for the recurrent handle (the norms of the last lhw_rnn_apply) */
+int lhw_rnn_debug_grad_sqnorms(LhwRnn* rnn, float* out2_host);
 /* xn (and xm) for the recurrent path: same as lhw_ppo_normalize but on an LhwRnn handle */
 int lhw_rnn_normalize(LhwRnn* rnn, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
                       float* xm, void* stream);

@@ -204,6 +204,8 @@ def declare(L):
     sig("lhw_env_step_range", [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_set_imitation", [vp, vp, vp, ctypes.c_float, i64])
     sig("lhw_ppo_step", [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, ctypes.c_float, vp])
+    sig("lhw_ppo_debug_grad_sqnorms", [vp, ctypes.POINTER(ctypes.c_float)])
+    sig("lhw_rnn_debug_grad_sqnorms", [vp, ctypes.POINTER(ctypes.c_float)])
     sig("lhw_env_debug_step_record", [vp, vp, vp, vp])
     sig("lhw_env_rollout", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_last_rollout_queued", [vp])

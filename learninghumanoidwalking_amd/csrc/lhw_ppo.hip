@@ -719,14 +719,16 @@ struct LhwPpo {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int two_streams = 1;
-  // lhw_ppo_step: one optimiser step (lhw_ppo_grad + lhw_ppo_apply) captured once as a hipGraph and replayed; the two things that change
-  // from step to step -- the minibatch's index pointer (gather_kernel) and Adam's bias corrections (adam2_kernel) -- are patched into
-  // the executable graph's kernel nodes before each launch
+  // lhw_ppo_step: one optimiser step (lhw_ppo_grad + lhw_ppo_apply) captured once per (buffers, minibatch size, grad_scale) as a hipGraph
+  // and replayed; the two things that change from step to step -- the minibatch's index pointer (gather_kernel) and Adam's bias
+  // corrections (adam2_kernel) -- are patched into the executable graph's kernel nodes before each launch.  grad_scale is part of the key
+  // (its bits): sumsq2_kernel's node keeps the scale it was captured with, so a new scale recaptures instead of clipping with a stale norm
   hipGraph_t step_graph = nullptr;
   hipGraphExec_t step_exec = nullptr;
   hipGraphNode_t node_gather = nullptr, node_adam = nullptr;
-  const void* step_key[14] = {nullptr};
+  const void* step_key[12] = {nullptr};
   int step_key_b = 0, step_key_half = 0;
+  uint32_t step_key_gs = 0;
 };
 
 #define HIPCHK(x)                                                                                   \
@@ -1696,13 +1698,25 @@ extern "C" int lhw_ppo_apply(LhwPpo* p, float* theta, float* grad, float* adam_m
   return LHW_OK;
 }
 
+// Test hook: waits for the device, then copies the two squared gradient norms (actor group, critic group; after grad_scale, before
+// clipping) that the last lhw_ppo_apply / lhw_ppo_step wrote into stats[8..9] to the host
+extern "C" int lhw_ppo_debug_grad_sqnorms(LhwPpo* p, float* out2_host) {
+  if (!p || !out2_host) return lhw_fail(LHW_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out2_host, p->stats + 8, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  return LHW_OK;
+}
+
 // One optimiser step as ONE graph launch (round 6).  lhw_ppo_grad + lhw_ppo_apply are some forty launches on two streams, a dozen of
 // them small (gather, loss, ordered reductions, transposes, clip, Adam: 5-20 us of work each behind a launch gap of the same order);
-// captured once per (buffers, minibatch size) as a hipGraph they replay with one host call and the runtime's graph scheduling between the
-// nodes.  Same kernels, same order, same arithmetic: bitwise the weights of the two-call path (tests/test_ppo_gpu.py).  What changes from
-// step to step is patched into the executable graph: the minibatch's index pointer (gather_kernel's first argument) and Adam's bias
-// corrections (adam2_kernel's last two).  Single process only -- with data parallelism the gradient all-reduce sits between the two halves
-// (the Python layer then keeps lhw_ppo_grad / all-reduce / lhw_ppo_apply).  LHW_PPO_GRAPH=0 turns it off (the two calls, eagerly).
+// captured once per (buffers, minibatch size, grad_scale) as a hipGraph they replay with one host call and the runtime's graph scheduling
+// between the nodes.  Same kernels, same order, same arithmetic: bitwise the weights of the two-call path (tests/test_iteration_gpu.py,
+// tests/test_optimizer_gpu.py).  What changes from step to step is patched into the executable graph: the minibatch's index pointer
+// (gather_kernel's first argument) and Adam's bias corrections (adam2_kernel's last two).  A different grad_scale recaptures: it is also
+// an argument of sumsq2_kernel, whose node is not patched.  Single process only -- with data parallelism the gradient all-reduce sits
+// between the two halves (the Python layer then keeps lhw_ppo_grad / all-reduce / lhw_ppo_apply).  LHW_PPO_GRAPH=0 turns it off (the two
+// calls, eagerly).
 static bool ppo_graph_on() {
   static const bool on = !(getenv("LHW_PPO_GRAPH") && atoi(getenv("LHW_PPO_GRAPH")) == 0);
   return on;
@@ -1718,9 +1732,9 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
     return rc ? rc : lhw_ppo_apply(p, theta, grad, adam_m, adam_v, step, grad_scale, stream);
   }
   HIPCHK(hipSetDevice(p->device));
-  const void* key[14] = {theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream, nullptr, nullptr};
-  float gs_key; memcpy(&gs_key, &grad_scale, sizeof gs_key);
-  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half;
+  const void* key[12] = {theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream};
+  uint32_t gs_key; memcpy(&gs_key, &grad_scale, sizeof gs_key);
+  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_gs == gs_key;
   for (int i = 0; same && i < 12; i++) same = p->step_key[i] == key[i];
   const size_t na = p->learn_std ? p->off_std + p->A : p->off_std;
   const float bc1 = 1.f - powf(p->beta1, (float)step), bc2s = sqrtf(1.f - powf(p->beta2, (float)step));
@@ -1751,7 +1765,7 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
     if (!p->node_gather || !p->node_adam) return lhw_fail(LHW_ERR_HIP, "lhw_ppo_step: gather / Adam nodes not found in the captured graph (%zu nodes)", nn);
     HIPCHK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
     for (int i = 0; i < 12; i++) p->step_key[i] = key[i];
-    p->step_key_b = B; p->step_key_half = p->update_half;
+    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_gs = gs_key;
   }
   // patch the two nodes: the kernels' full argument lists, as lhw_ppo_grad / clip_and_adam pass them
   {
@@ -2192,6 +2206,15 @@ extern "C" int lhw_rnn_apply(LhwRnn* p, float* theta, float* grad, float* adam_m
                 p->lr, p->beta1, p->beta2, p->adam_eps, s);
   if (!p->learn_std) HIPCHK(hipMemsetAsync(grad + p->off_std, 0, sizeof(float) * pad4(p->A), s));
   HIPCHK(hipGetLastError());
+  return LHW_OK;
+}
+
+// lhw_ppo_debug_grad_sqnorms on an LhwRnn handle (the norms of the last lhw_rnn_apply)
+extern "C" int lhw_rnn_debug_grad_sqnorms(LhwRnn* p, float* out2_host) {
+  if (!p || !out2_host) return lhw_fail(LHW_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out2_host, p->stats + 8, 2 * sizeof(float), hipMemcpyDeviceToHost));
   return LHW_OK;
 }
 

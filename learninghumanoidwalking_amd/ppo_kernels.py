@@ -44,6 +44,7 @@ def _setup(L):
     L.lhw_standardize.argtypes = [vp, i64, vp, ctypes.c_double, vp]
     L.lhw_ppo_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
     L.lhw_ppo_apply.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp]
+    L.lhw_ppo_debug_grad_sqnorms.argtypes = [vp, ctypes.POINTER(f32)]
     L.lhw_ppo_set_inference_dtype.argtypes = [vp, ctypes.c_int]
     L.lhw_ppo_set_update_dtype.argtypes = [vp, ctypes.c_int]
     L.lhw_ppo_forward_at.argtypes = [vp, vp, vp, i64, vp, vp, u64, u32, u32, ctypes.c_int, i64, vp, vp, vp, vp, vp]
@@ -242,17 +243,24 @@ class PpoKernels:
         _lib.check(self._L.lhw_ppo_grad(self._h, _p(self.theta), _p(self.grad), _p(xn), _p(xm), _p(act), _p(old_logp),
                                         _p(adv), _p(ret), _p(idx), B, _p(self.stats), self._stream()))
 
-    def step_minibatch(self, xn, xm, act, old_logp, adv, ret, idx):
+    def step_minibatch(self, xn, xm, act, old_logp, adv, ret, idx, grad_scale=1.0):
         """grad_minibatch + apply as ONE hipGraph launch (lhw_ppo_step: single process, no imitation term).  Must run on a torch stream
         other than the default one (a legacy default stream cannot be captured: the library then makes the two calls eagerly)."""
         self.adam_step += 1
         _lib.check(self._L.lhw_ppo_step(self._h, _p(self.theta), _p(self.grad), _p(self.adam_m), _p(self.adam_v), _p(xn), _p(xm), _p(act),
-                                        _p(old_logp), _p(adv), _p(ret), _p(idx), idx.numel(), _p(self.stats), self.adam_step, 1.0, self._stream()))
+                                        _p(old_logp), _p(adv), _p(ret), _p(idx), idx.numel(), _p(self.stats), self.adam_step,
+                                        float(grad_scale), self._stream()))
 
     def apply(self, grad_scale=1.0):
         self.adam_step += 1
         _lib.check(self._L.lhw_ppo_apply(self._h, _p(self.theta), _p(self.grad), _p(self.adam_m), _p(self.adam_v),
                                          self.adam_step, float(grad_scale), self._stream()))
+
+    def debug_grad_sqnorms(self):
+        """(actor, critic) squared gradient norms the last apply / step_minibatch clipped with (synchronises the device)."""
+        out = (ctypes.c_float * 2)()
+        _lib.check(self._L.lhw_ppo_debug_grad_sqnorms(self._h, out))
+        return float(out[0]), float(out[1])
 
 
 def reference_init(obs_dim, act_dim, hidden=256, init_std=0.223, generator_seed=None):

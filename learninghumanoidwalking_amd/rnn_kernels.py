@@ -26,6 +26,7 @@ def _setup_rnn(L):
     L.lhw_rnn_forward.argtypes = [vp, vp, vp, i64, vp, vp, vp, u64, u32, u32, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
     L.lhw_rnn_grad.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
     L.lhw_rnn_apply.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp]
+    L.lhw_rnn_debug_grad_sqnorms.argtypes = [vp, ctypes.POINTER(f32)]
     L.lhw_rnn_normalize.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     _SETUP_RNN = True
 
@@ -188,6 +189,12 @@ class RnnKernels:
         self.adam_step += 1
         _lib.check(self._L.lhw_rnn_apply(self._h, _p(self.theta), _p(self.grad), _p(self.adam_m), _p(self.adam_v), self.adam_step,
                                          float(grad_scale), self._stream()))
+
+    def debug_grad_sqnorms(self):
+        """(actor, critic) squared gradient norms the last apply clipped with (synchronises the device)."""
+        out = (ctypes.c_float * 2)()
+        _lib.check(self._L.lhw_rnn_debug_grad_sqnorms(self._h, out))
+        return float(out[0]), float(out[1])
 
 
 def reference_init_lstm(obs_dim, act_dim, hidden=256, init_std=0.2, generator_seed=None):
