@@ -33,6 +33,16 @@ class LhwEnvConfig(ctypes.Structure):
     ]
 
 
+class LhwPpoConfig(ctypes.Structure):      # include/lhw.h: hyper-parameters and shapes of a PPO / LSTM handle
+    _fields_ = [
+        ("device", ctypes.c_int32), ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
+        ("learn_std", ctypes.c_int32), ("max_rows", ctypes.c_int32), ("lr", ctypes.c_float), ("eps", ctypes.c_float),
+        ("clip", ctypes.c_float), ("entropy_coeff", ctypes.c_float), ("mirror_coeff", ctypes.c_float),
+        ("max_grad_norm", ctypes.c_float), ("mirror_obs_src", ctypes.c_void_p), ("mirror_obs_sign", ctypes.c_void_p),
+        ("mirror_act_src", ctypes.c_void_p), ("mirror_act_sign", ctypes.c_void_p),
+    ]
+
+
 class LhwRolloutPolicy(ctypes.Structure):      # include/lhw.h: the frozen actor as lhw_env_rollout reads it
     _fields_ = [(n, ctypes.c_void_p) for n in ("w1t", "b1", "w2t", "b2", "w3t", "b3", "stdv", "obs_mean", "obs_std")] + [
         (n, ctypes.c_int32) for n in ("obs_dim", "obs_pad", "act_dim", "act_pad", "hidden", "deterministic", "fp16_operands")] + [
@@ -160,7 +170,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def declare(L):
     """Attach the argument types of include/lhw.h's entry points to a loaded library (entry points the library
     does not export are skipped: the emulated test build has no PPO kernels)."""
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    vp, i32, i64, u32, u64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
 
     def sig(name, argtypes=None, restype=None):
         f = getattr(L, name, None)
@@ -202,17 +212,42 @@ def declare(L):
     sig("lhw_debug_wgrad_skinny", [i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_phase_cycles", [vp, ctypes.c_int, vp])
     sig("lhw_env_step_range", [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
-    sig("lhw_ppo_set_imitation", [vp, vp, vp, ctypes.c_float, i64])
-    sig("lhw_ppo_step", [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, ctypes.c_float, vp])
-    sig("lhw_ppo_debug_grad_sqnorms", [vp, ctypes.POINTER(ctypes.c_float)])
-    sig("lhw_rnn_debug_grad_sqnorms", [vp, ctypes.POINTER(ctypes.c_float)])
+    sig("lhw_ppo_create", [ctypes.POINTER(LhwPpoConfig), ctypes.POINTER(vp)])
+    sig("lhw_ppo_destroy", [vp])
+    sig("lhw_ppo_param_count", [vp], i64)
+    sig("lhw_ppo_layout", [vp, ctypes.POINTER(i64)])
+    sig("lhw_ppo_normalize", [vp, vp, i64, vp, vp, vp, vp, vp])
+    sig("lhw_ppo_forward", [vp, vp, vp, i64, vp, vp, u64, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp])
+    sig("lhw_ppo_forward_at", [vp, vp, vp, i64, vp, vp, u64, u32, u32, ctypes.c_int, i64, vp, vp, vp, vp, vp])
+    sig("lhw_ppo_begin_rollout", [vp, vp, vp])
+    sig("lhw_ppo_end_rollout", [vp])
+    sig("lhw_ppo_set_inference_dtype", [vp, ctypes.c_int])
+    sig("lhw_ppo_set_update_dtype", [vp, ctypes.c_int])
+    sig("lhw_ppo_set_imitation", [vp, vp, vp, f32, i64])
+    sig("lhw_ppo_grad", [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp])
+    sig("lhw_ppo_apply", [vp, vp, vp, vp, vp, i64, f32, vp])
+    sig("lhw_ppo_step", [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, f32, vp])
+    sig("lhw_ppo_debug_grad_sqnorms", [vp, ctypes.POINTER(f32)])
+    sig("lhw_gae", [i32, i32, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp])
+    sig("lhw_moments", [vp, i64, vp, vp])
+    sig("lhw_scale_shift", [vp, i64, f32, f32, vp])
+    sig("lhw_standardize", [vp, i64, vp, ctypes.c_double, vp])
+    sig("lhw_rnn_create", [ctypes.POINTER(LhwPpoConfig), i32, i32, i32, ctypes.POINTER(vp)])
+    sig("lhw_rnn_destroy", [vp])
+    sig("lhw_rnn_param_count", [vp], i64)
+    sig("lhw_rnn_layout", [vp, ctypes.POINTER(i64)])
+    sig("lhw_rnn_normalize", [vp, vp, i64, vp, vp, vp, vp, vp])
+    sig("lhw_rnn_forward", [vp, vp, vp, i64, vp, vp, vp, u64, u32, u32, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp])
+    sig("lhw_rnn_grad", [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp])
+    sig("lhw_rnn_apply", [vp, vp, vp, vp, vp, i64, f32, vp])
+    sig("lhw_rnn_debug_grad_sqnorms", [vp, ctypes.POINTER(f32)])
     sig("lhw_env_debug_step_record", [vp, vp, vp, vp])
     sig("lhw_env_rollout", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_last_rollout_queued", [vp])
     sig("lhw_env_rollout_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_rollout_step_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig("lhw_ppo_rollout_policy", [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(LhwRolloutPolicy)])
-    sig("lhw_debug_policy_step", [ctypes.POINTER(LhwRolloutPolicy), vp, i32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp])
+    sig("lhw_ppo_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutPolicy)])
+    sig("lhw_debug_policy_step", [ctypes.POINTER(LhwRolloutPolicy), vp, i32, u32, u32, vp, vp, vp, vp])
     return L
 
 

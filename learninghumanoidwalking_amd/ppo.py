@@ -53,7 +53,7 @@ class BatchData:
 
 class _AdamView:
     """`actor_optimizer` / `critic_optimizer` of the reference (torch.optim.Adam over the two networks, ppo.py:128-129) as a
-    read-only view: one fused Adam kernel updates the flat parameter vector, its moments live in PpoKernels.adam_m / adam_v."""
+    read-only view: one fused Adam kernel updates the flat parameter vector, its moments live in the kernels' adam_m / adam_v."""
 
     def __init__(self, kernels, names, lr, eps):
         self._k, self._names = kernels, names
@@ -62,10 +62,8 @@ class _AdamView:
 
     def state_dict(self):
         k = self._k
-        key = getattr(k, "_adam_view_specs", None)      # (recurrent kernels: _view takes the tensor's spec)
-        view = (lambda flat, n: k._view(flat, key[n])) if key else k._view
-        state = {n: dict(step=int(k.adam_step), exp_avg=view(k.adam_m, n).detach().cpu().clone(),
-                         exp_avg_sq=view(k.adam_v, n).detach().cpu().clone()) for n in self._names}
+        state = {n: dict(step=int(k.adam_step), exp_avg=k._view(k.adam_m, n).detach().cpu().clone(),
+                         exp_avg_sq=k._view(k.adam_v, n).detach().cpu().clone()) for n in self._names}
         return dict(state=state, param_groups=[dict(self.defaults, params=list(self._names))])
 
     def zero_grad(self):      # gradients are zeroed by the apply kernel after every optimiser step
@@ -102,38 +100,60 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
-class Rollout:
-    """Time-major rollout storage + collection loop for one GPU (N envs x T steps per iteration).
+class _RolloutStorage:
+    """Time-major rollout storage of one GPU (N envs x T steps per iteration) and the episode carry-over every policy kind shares.
 
     Semantics of RolloutWorker.sample (reference rl/workers/rollout_worker.py:97-199) for every env:
     exactly T transitions per call, episodes carried over between calls, truncation at max_traj_len,
     bootstrap (not done) * V(s') at episode ends and V(s_T) where the buffer fills mid-episode.
     """
 
-    def __init__(self, env, kernels: PpoKernels, T: int, seed: int = 0, task=None, max_traj_len: int | None = None):
+    def __init__(self, env, kernels, T: int, seed: int = 0):
         self.env, self.k, self.T, self.seed = env, kernels, int(T), int(seed)
-        # task: a task_hook.VectorTask evaluated OUTSIDE the kernels after every control step; its reward / termination replace
-        # the fused ones and the rollout, not the env, truncates at max_traj_len and resets (see _collect_hooked)
-        self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
-        if task is not None and getattr(env, "history_len", 1) > 1:
-            # (the hooked paths write the reset observation / history rows themselves and know nothing of the env-side history deque)
-            raise NotImplementedError("a plugged-in task with obs_history_len > 1 is not supported")
-        # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
-        self.reward_only = reward_only_on(task, env.task)
-        self._tin_all = self._stin_all = None
         N, D, A, dev = env.n_envs, env.obs_dim, env.act_dim, env.device
         self.N = N
         self.obs = torch.zeros(T + 1, N, D, dtype=torch.float32, device=dev)
         self.act = torch.zeros(T, N, A, dtype=torch.float32, device=dev)
-        self.mu = torch.zeros(N, A, dtype=torch.float32, device=dev)
         self.logp = torch.zeros(T, N, dtype=torch.float32, device=dev)
         self.val = torch.zeros(T, N, dtype=torch.float32, device=dev)
         self.rew = torch.zeros(T, N, dtype=torch.float32, device=dev)
         self.done = torch.zeros(T, N, dtype=torch.uint8, device=dev)
         self.vterm = torch.zeros(T, N, dtype=torch.float32, device=dev)
         self.vfinal = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.tob = torch.zeros(N, D, dtype=torch.float32, device=dev)
-        self.tob_all = None      # [T][N][D] terminal observations of the feed-forward path (allocated on first use)
+        self.counter = 0
+        self.started = False
+        self.env_base = getattr(env, "env_id_base", 0)      # (a host-only stand-in env may have none)
+
+    def _start(self):
+        """The envs are reset once, before the first rollout; afterwards a rollout starts from the last observation of the previous one."""
+        if not self.started:
+            self.obs[0].copy_(self.env.reset())
+            self.started = True
+        else:
+            self.obs[0].copy_(self.obs[self.T])
+
+    def pop_episode_stats(self):
+        """(sum of finished-episode returns, sum of their lengths, their number) since the last call: the env's own counters."""
+        return self.env.pop_episode_stats()
+
+
+class Rollout(_RolloutStorage):
+    """Feed-forward policies: the resident rollout where the library has it, else one policy and one env launch per control step.
+
+    `task`: a task_hook.VectorTask evaluated OUTSIDE the kernels.  A reward-only task keeps the env's fused termination, truncation
+    and resets and only replaces the reward; any other task decides terminations itself after every control step, and the rollout,
+    not the env, truncates at max_traj_len and resets."""
+
+    def __init__(self, env, kernels: PpoKernels, T: int, seed: int = 0, task=None, max_traj_len: int | None = None):
+        super().__init__(env, kernels, T, seed)
+        self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
+        if task is not None and env.history_len > 1:
+            # (the hooked paths write the reset observation / history rows themselves and know nothing of the env-side history deque)
+            raise NotImplementedError("a plugged-in task with obs_history_len > 1 is not supported")
+        # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
+        self.reward_only = reward_only_on(task, env.task)
+        N, D, dev = self.N, env.obs_dim, env.device
+        self.tob_all = torch.zeros(T, N, D, dtype=torch.float32, device=dev)      # [T][N][D] terminal observations
         # Number of independent env groups pipelined on separate streams (wave-per-env steppers; LHW_ROLLOUT_GROUPS overrides).
         # Two groups: one group's policy launch and the tail of its control-step kernel -- a launch ends with its slowest wave,
         # the chip draining meanwhile -- hide behind the other group's kernel.  Measured on the round-4 kernels
@@ -141,46 +161,159 @@ class Rollout:
         # (rollout 0.608 -> 0.538 s), h1 @ 4096 +11 %, jvrc_walk @ 2048 / 1024 +4 / +3 %; three or four groups lose badly
         # (jvrc_walk @ 4096: 1.07 s).  (An earlier round had measured one group ahead at 4096 envs, 2.07 vs 1.99 M, on a
         # slower control step and an unfused policy step.)  Small batches keep one group: their launches are latency-bound.
-        auto = "1"
-        if hasattr(env, "step_range") and env.task != 0:
-            auto = "2" if N >= 1024 else "1"
-        want = int(os.environ.get("LHW_ROLLOUT_GROUPS", auto))
+        # Only the plain launch-per-step path uses the groups; with a task plugged in the batch is one group on the current stream.
+        want = int(os.environ.get("LHW_ROLLOUT_GROUPS", "2" if N >= 1024 else "1"))
         self.groups = max(1, min(want, N)) if env.task != 0 else 1
-        self.streams = None
-        self.counter = 0
-        self.started = False
-        self.env_base = getattr(env, "env_id_base", 0)
+        self.streams = None      # (created by the first grouped rollout)
+        # plug-in state: episodes carried between rollouts, finished-episode statistics, and the rows the env step writes its own
+        # reward (and, hooked, flags) to where the task's replace them
+        self._traj_len = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._ep_ret = torch.zeros(N, dtype=torch.float64, device=dev)
+        self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # sum of returns, sum of lengths, episodes
+        self._scratch_rew = torch.zeros(N, dtype=torch.float32, device=dev)
+        self._scratch_done = torch.zeros(N, dtype=torch.uint8, device=dev)
+        # the resident rollout's record of every control step for a reward-only task, [T][N][176] float64 -- 2.3 GB at 4096 envs x
+        # T = 400 -- and on the stepping env its stepping record, [T][N][32]: allocated by the first resident rollout that needs them
+        self._tin_all = self._stin_all = None
+        self._rare_path_warm = False
 
     def collect(self, deterministic=False):
-        env, k, T = self.env, self.k, self.T
-        if getattr(k, "recurrent", False):
-            return self._collect_recurrent(deterministic)
-        if not self.started:
-            self.obs[0].copy_(env.reset())
-            self.started = True
-        else:
-            self.obs[0].copy_(self.obs[T])
+        self._start()
         # Only the actor sits on the step-to-step dependency chain.  The critic's weights do not change during a rollout
         # and it is feed-forward, so V(s_t), V(terminal obs) and V(s_T) are evaluated afterwards in large batches instead
         # of two extra 3-GEMM passes per control step (same values, ~2000 fewer kernel launches per iteration).
-        if self.tob_all is None:
-            self.tob_all = torch.zeros(T, self.N, self.obs.shape[2], dtype=torch.float32, device=self.obs.device)
-        k.begin_rollout()      # theta is frozen for the whole rollout (policy steps and the batched critic passes behind them)
+        self.k.begin_rollout()      # theta is frozen for the whole rollout (policy steps and the batched critic passes behind them)
         try:
-            if not getattr(self, "_rare_path_warm", False):
+            if not self._rare_path_warm:
                 self._warm_rare_path()
-            self._collect_steps(deterministic)
+            self._collect(deterministic)
+            self._critic_values()
         finally:
-            k.end_rollout()
+            self.k.end_rollout()
+
+    def _collect(self, deterministic):
+        """Fills obs / act / logp / tob_all / rew / done and sets last_mode: which path collected the rollout (tests, bench line)."""
+        T = self.T
+        hooked = self.task is not None and not self.reward_only
+        if not hooked and self._collect_resident(deterministic, task_inputs=self.reward_only):
+            self.last_mode = "resident"
+            if self.reward_only:
+                self._evaluate_recorded_rewards()
+        elif self.task is None:
+            self.last_mode = "steps"
+            self._collect_steps(deterministic, self.rew, self.done)
+        else:
+            from .task_hook import device_task_inputs
+            self.last_mode = "hooked"
+            ti = device_task_inputs(self.env)      # (arms the export before the first control step)
+            if self.reward_only:      # the kernel's own flags and resets, the task's reward per control step, no host round trip
+                self._collect_steps(deterministic, [self._scratch_rew] * T, self.done,
+                                    lambda t: self.rew[t].copy_(self._evaluate_reward_batch(ti.rec, ti.srec)))
+            else:
+                self._collect_steps(deterministic, [self._scratch_rew] * T, [self._scratch_done] * T, lambda t: self._task_step(t, ti))
+        if self.reward_only:
+            self._episode_stats_from_buffers()
+
+    def _collect_resident(self, deterministic, task_inputs=False) -> bool:
+        """All T control steps in one launch, the actor evaluated inside the stepper's wavefronts (BatchedEnv.rollout): bitwise the
+        values of the launch-per-step loop (float32 inference; with fp16 inference float32-rounding-close), without its per-control-step
+        barrier across the envs.  `task_inputs`: the launch also exports the task-input record(s) of every control step
+        (lhw_env_rollout_task_inputs), for a reward-only task evaluated behind it -- RobotBase.step's `task.calc_reward`
+        (robots/robot_base.py:88-96) moved behind the rollout, which it may be because a reward does not feed back into the simulation.
+        LHW_ROLLOUT_MODE = auto (default: resident wherever the library has the kernel) | resident (declining raises) | steps.
+        Returns False where the launch-per-step pipeline is to run instead."""
+        # Measured, same box, interleaved (profiles/r05_rollout_modes.txt, final kernels): resident over launch-per-step with two groups --
+        # jvrc_walk @ 4096 +25 % env-steps/s (rollout 0.524 -> 0.397 s), jvrc_step @ 4096 +26 %, h1_walk @ 8192 +9 %, h1 @ 8192 +2 %
+        # (twice as many wavefronts as the chip holds and a narrow spread of wave times: there two whole-chip launches in flight
+        # already backfill each other's tails).
+        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
+        if mode not in ("auto", "resident"):
+            return False
+        env, T = self.env, self.T
+        pol = self.k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
+        if pol is None:
+            why = "the kernels have no in-wave policy step for this actor"
+        elif env.env_id_base != self.env_base:
+            # (the in-wave policy step keys its noise by the env's own global ids; the per-step calls pass self.env_base + row)
+            why = "the env's env_id_base is not the rollout's"
+        else:
+            if task_inputs and self._tin_all is None:
+                self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+                if env.task == TASK_JVRC_STEP:
+                    self._stin_all = _lib.empty(T, self.N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+            if env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done,
+                           task_inputs=self._tin_all if task_inputs else None, step_task_inputs=self._stin_all if task_inputs else None):
+                self.counter += T
+                return True
+            why = "the library has no resident rollout kernel for this env / policy"
+        if mode == "resident":
+            raise _lib.LhwError(-4, f"LHW_ROLLOUT_MODE=resident, but {why}")
+        return False
+
+    def _collect_steps(self, deterministic, rew, done, after_step=None):
+        """Launch per control step: the actor, then the env step writing its reward and flags to rew[t] / done[t], then
+        `after_step(t)`.  Without a task the batch advances as `groups` env groups, each on its own HIP stream."""
+        env, k, T = self.env, self.k, self.T
+        G = self.groups if self.task is None else 1
+        bounds = [(g * self.N // G, (g + 1) * self.N // G) for g in range(G)]
+        streams = [None]      # (one group: the current stream)
+        if G > 1:
+            # Environments are independent, so the batch is advanced as G groups on their own HIP streams: a group's policy
+            # forward waits only for that group's control-step kernel.  Without the batch-wide barrier per control step the
+            # tail of one group's kernel (waves that drew more contacts / Newton iterations / a reset) overlaps the other
+            # group's work: 3.8 -> 2.9 ms per control step of 4096 envs with two groups.  Every value is unchanged (the RNG is
+            # keyed by global env id and step counter, not by launch order).
+            main = torch.cuda.current_stream(self.obs.device)
+            if self.streams is None:
+                self.streams = [torch.cuda.Stream(device=self.obs.device) for _ in range(G)]
+            streams = self.streams
+            for s in streams:
+                s.wait_stream(main)
+        for t in range(T):
+            for s, (a, b) in zip(streams, bounds):
+                with torch.cuda.stream(s):
+                    k.forward(self.obs[t, a:b], seed=self.seed, env_id_base=self.env_base + a, counter=self.counter,
+                              deterministic=deterministic, want_value=False, want_mu=False, ws_row=a, act=self.act[t, a:b],
+                              logp=self.logp[t, a:b])
+                    if G > 1:
+                        env.step_range(a, b - a, self.act[t], self.obs[t + 1], self.tob_all[t], rew[t], done[t])
+                    else:
+                        env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self.tob_all[t], rew_out=rew[t], done_out=done[t])
+            if after_step is not None:
+                after_step(t)
+            self.counter += 1
+        if G > 1:
+            for s in streams:
+                main.wait_stream(s)
+
+    def _critic_values(self):
+        T, N = self.T, self.N
+        self._batched_values(self.obs[:T].reshape(T * N, -1), self.val.reshape(-1))
+        # V(terminal observation) is only read where a trajectory was TRUNCATED (max_traj_len) without terminating: the bootstrap
+        # of rl/workers/rollout_worker.py:163-190 (lhw_gae: `(f & 1) ? 0 : vterm`).  That is about one row per env and rollout --
+        # 0.25 % of the T x N terminal observations at T = max_traj_len = 400 -- so only those rows go through the critic
+        # (50 fewer 32768-row passes per iteration at 4096 envs); everywhere else vterm is 0 and unread.
+        need = ((self.done & 2) != 0) & ((self.done & 1) == 0)
+        idx = torch.nonzero(need.reshape(-1)).reshape(-1)
+        self.vterm.zero_()
+        if idx.numel():
+            vals = _lib.empty(idx.numel(), dtype=torch.float32, device=self.obs.device)
+            self._batched_values(self.tob_all.reshape(T * N, -1).index_select(0, idx), vals)
+            self.vterm.reshape(-1).index_copy_(0, idx, vals)
+        self.k.forward(self.obs[T], want_actor=False, value=self.vfinal)
+
+    def _batched_values(self, obs_flat, out_flat):
+        chunk = int(self.k.max_rows)
+        for a in range(0, obs_flat.shape[0], chunk):
+            b = min(a + chunk, obs_flat.shape[0])
+            self.k.forward(obs_flat[a:b], want_actor=False, value=out_flat[a:b])
 
     def _warm_rare_path(self):
-        """Runs the truncated-trajectory branch of _collect_steps once on eight dummy rows.  An untrained policy falls long before
+        """Runs the truncated-trajectory branch of _critic_values once on eight dummy rows.  An untrained policy falls long before
         max_traj_len, so that branch is first taken some ten iterations into a run -- and the first call of its torch ops
         (index_select, index_copy_) loads their code objects: 0.1-0.2 s in the middle of that iteration (bench.py's iter_s showed
         it at iteration 10 of every run).  A process start-up cost, paid here before the first rollout instead."""
         self._rare_path_warm = True
-        if self.obs.device.type != "cuda" or self.tob_all is None:
-            return
         T = self.T
         need = torch.zeros(T * self.N, dtype=torch.bool, device=self.obs.device)
         need[:8] = True
@@ -190,59 +323,54 @@ class Rollout:
         self.vterm.reshape(-1).index_copy_(0, idx, vals)
         self.vterm.zero_()
 
-    def _collect_hooked(self, deterministic):
-        """Launch-per-step rollout with the TASK outside the kernels (task_hook.py): after each control step the env's exported
-        task inputs go to `self.task.evaluate`, whose reward and termination are stored; truncation at max_traj_len, the episode
-        statistics and the resets (`lhw_env_reset(mask)`: the reset code and random draws of the in-kernel auto-reset) are done
-        here -- RobotBase.step + the episode handling of RolloutWorker.sample (robots/robot_base.py:88-96,
-        rl/workers/rollout_worker.py:150-181) with an exchangeable task."""
-        from .task_hook import device_task_inputs
-        env, k, T, dev = self.env, self.k, self.T, self.obs.device
-        ti = device_task_inputs(env)
-        if not hasattr(self, "_traj_len"):
-            self._traj_len = torch.zeros(self.N, dtype=torch.int32, device=dev)
-            self._ep_ret = torch.zeros(self.N, dtype=torch.float64, device=dev)
-            self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # sum of returns, sum of lengths, episodes
-            self._scratch_rew = torch.zeros(self.N, dtype=torch.float32, device=dev)
-            self._scratch_done = torch.zeros(self.N, dtype=torch.uint8, device=dev)
-        for t in range(T):
-            k.forward(self.obs[t], seed=self.seed, env_id_base=self.env_base, counter=self.counter, deterministic=deterministic,
-                      want_value=False, want_mu=False, act=self.act[t], logp=self.logp[t])
-            env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self.tob_all[t], rew_out=self._scratch_rew, done_out=self._scratch_done)
-            rew, term = self.task.evaluate(ti)
-            # a diverged env (the kernel has sanitised its state, the record is exported before that): the episode ends -- whatever
-            # the plugged task's reward looks at
-            bad = ~torch.isfinite(rew) | ~torch.isfinite(ti.qpos).all(1) | ~torch.isfinite(ti.qvel).all(1) | ~torch.isfinite(ti.qacc).all(1)
-            rew = torch.where(bad, torch.zeros_like(rew), rew)
-            term = term.bool() | bad
-            self.rew[t].copy_(rew)
-            self._traj_len += 1
-            self._ep_ret += rew.double()
-            trunc = self._traj_len >= self.max_traj_len
-            self.done[t].copy_(term.to(torch.uint8) | (trunc.to(torch.uint8) << 1))
-            ended = term | trunc
-            # (no host round trip per control step: the statistics are masked sums and the reset launch takes the mask as it is --
-            # an all-zero mask is a launch whose waves return at once)
-            self._stats += torch.stack([(self._ep_ret * ended).sum(), (self._traj_len * ended).sum().double(), ended.sum().double()])
-            self.task.reset(ended)
-            env.reset(ended.to(torch.uint8), obs_out=self.obs[t + 1])      # rows of the other envs are left untouched
-            self._traj_len.masked_fill_(ended, 0)
-            self._ep_ret.masked_fill_(ended, 0)
-            self.counter += 1
-        self.last_mode = "hooked"
+    # ---- task plug-ins (task_hook.py)
+    def _task_step(self, t, ti):
+        """After control step t with a task that decides terminations itself: the env's exported task inputs `ti` go to
+        `self.task.evaluate`, whose reward and termination are stored; truncation at max_traj_len, the episode statistics and the
+        resets (`lhw_env_reset(mask)`: the reset code and random draws of the in-kernel auto-reset) are done here -- RobotBase.step +
+        the episode handling of RolloutWorker.sample (robots/robot_base.py:88-96, rl/workers/rollout_worker.py:150-181) with an
+        exchangeable task."""
+        rew, term = self.task.evaluate(ti)
+        # a diverged env (the kernel has sanitised its state, the record is exported before that): the episode ends -- whatever
+        # the plugged task's reward looks at
+        bad = ~torch.isfinite(rew) | ~torch.isfinite(ti.qpos).all(1) | ~torch.isfinite(ti.qvel).all(1) | ~torch.isfinite(ti.qacc).all(1)
+        rew = torch.where(bad, torch.zeros_like(rew), rew)
+        term = term.bool() | bad
+        self.rew[t].copy_(rew)
+        self._traj_len += 1
+        self._ep_ret += rew.double()
+        trunc = self._traj_len >= self.max_traj_len
+        self.done[t].copy_(term.to(torch.uint8) | (trunc.to(torch.uint8) << 1))
+        ended = term | trunc
+        # (no host round trip per control step: the statistics are masked sums and the reset launch takes the mask as it is --
+        # an all-zero mask is a launch whose waves return at once)
+        self._stats += torch.stack([(self._ep_ret * ended).sum(), (self._traj_len * ended).sum().double(), ended.sum().double()])
+        self.task.reset(ended)
+        self.env.reset(ended.to(torch.uint8), obs_out=self.obs[t + 1])      # rows of the other envs are left untouched
+        self._traj_len.masked_fill_(ended, 0)
+        self._ep_ret.masked_fill_(ended, 0)
 
-    # ---- reward-only plug-ins: the kernel keeps its own termination / truncation / resets, the task supplies the reward
-    def _hook_state(self):
-        dev = self.obs.device
-        if not hasattr(self, "_traj_len"):
-            self._traj_len = torch.zeros(self.N, dtype=torch.int32, device=dev)
-            self._ep_ret = torch.zeros(self.N, dtype=torch.float64, device=dev)
-            self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # sum of returns, sum of lengths, episodes
+    def _evaluate_reward_batch(self, rec, srec=None):
+        """The plugged task's reward for [M, TASK_INPUT_DIM] records (and, stepping env, the [M, STEP_TASK_INPUT_DIM] ones of the same
+        rows; non-finite -> 0: the kernel ended that episode itself)."""
+        from .task_hook import TaskInputs
+        env = self.env
+        rew, _ = self.task.evaluate(TaskInputs(rec, env.nq, env.nv, env.act_dim, srec))
+        return torch.where(torch.isfinite(rew), rew, torch.zeros_like(rew)).float()
+
+    def _evaluate_recorded_rewards(self):
+        """A reward-only task over the records the resident rollout exported: ONE evaluation per half a million rows."""
+        T, N = self.T, self.N
+        rec = self._tin_all.reshape(T * N, -1)
+        srec = self._stin_all.reshape(T * N, -1) if self._stin_all is not None else None
+        rew = self.rew.reshape(-1)
+        chunk = max(N, (1 << 19) // N * N)      # whole time slices, about half a million rows per evaluation
+        for a in range(0, rec.shape[0], chunk):
+            rew[a:a + chunk] = self._evaluate_reward_batch(rec[a:a + chunk], srec[a:a + chunk] if srec is not None else None)
 
     def _episode_stats_from_buffers(self):
         """Finished-episode returns / lengths of this rollout from self.rew (the plugged task's rewards) and self.done (the kernel's
         flags), vectorised over [T, N]; episodes carried in from / out to the neighbouring rollouts through _ep_ret / _traj_len."""
-        self._hook_state()
         T, N, dev = self.T, self.N, self.obs.device
         ended = self.done != 0
         cc = torch.cumsum(self.rew.double(), dim=0)
@@ -261,178 +389,34 @@ class Rollout:
         self._ep_ret = torch.where(none, self._ep_ret + cc[-1], tail)
         self._traj_len = torch.where(none, self._traj_len.to(torch.int64) + T, (T - 1) - fin).to(torch.int32)
 
-    def _evaluate_reward_batch(self, rec, srec=None):
-        """The plugged task's reward for [M, TASK_INPUT_DIM] records (and, stepping env, the [M, STEP_TASK_INPUT_DIM] ones of the same
-        rows; non-finite -> 0: the kernel ended that episode itself)."""
-        from .task_hook import TaskInputs
-        env = self.env
-        rew, _ = self.task.evaluate(TaskInputs(rec, env.nq, env.nv, env.act_dim, srec))
-        return torch.where(torch.isfinite(rew), rew, torch.zeros_like(rew)).float()
-
-    def _collect_resident_hooked(self, deterministic) -> bool:
-        """Reward-only task plug-ins at the resident rollout's speed: one lhw_env_rollout_task_inputs launch (fused termination,
-        truncation and resets; the sim-facade record of every control step exported, [T][N][176] float64 -- 2.3 GB at 4096 envs x
-        T = 400 -- and on the stepping env the stepping record as well, [T][N][32] float64, another 420 MB), then ONE evaluation of
-        the task over the whole batch -- RobotBase.step's `task.calc_reward` (robots/robot_base.py:88-96) moved behind the rollout,
-        which it may be because a reward does not feed back into the simulation."""
-        env, k, T = self.env, self.k, self.T
-        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
-        if mode not in ("auto", "resident") or not hasattr(env, "rollout") or not hasattr(k, "rollout_policy"):
-            return False
-        if not hasattr(env._L, "lhw_env_rollout_task_inputs") or getattr(env, "env_id_base", 0) != self.env_base:
-            return False
-        pol = k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
-        if pol is None:
-            return False
-        self._pol_keep = pol
-        if self._tin_all is None:
-            self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-        if self._stin_all is None and env.task == TASK_JVRC_STEP:
-            self._stin_all = _lib.empty(T, self.N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-        if not env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done, task_inputs=self._tin_all,
-                           step_task_inputs=self._stin_all):
-            return False
-        self.counter += T
-        rec = self._tin_all.reshape(T * self.N, -1)
-        srec = self._stin_all.reshape(T * self.N, -1) if self._stin_all is not None else None
-        rew = self.rew.reshape(-1)
-        chunk = max(self.N, (1 << 19) // self.N * self.N)      # whole time slices, about half a million rows per evaluation
-        for a in range(0, rec.shape[0], chunk):
-            rew[a:a + chunk] = self._evaluate_reward_batch(rec[a:a + chunk], srec[a:a + chunk] if srec is not None else None)
-        self._episode_stats_from_buffers()
-        return True
-
-    def _collect_reward_only_steps(self, deterministic):
-        """The same plug-in on the launch-per-step pipeline (LHW_ROLLOUT_MODE=steps, or no resident kernel for this env / policy):
-        the kernel's own flags and resets, the task's reward per control step, no host round trip."""
-        from .task_hook import device_task_inputs
-        env, k, T = self.env, self.k, self.T
-        ti = device_task_inputs(env)
-        if not hasattr(self, "_scratch_rew"):
-            self._scratch_rew = torch.zeros(self.N, dtype=torch.float32, device=self.obs.device)
-        for t in range(T):
-            k.forward(self.obs[t], seed=self.seed, env_id_base=self.env_base, counter=self.counter, deterministic=deterministic,
-                      want_value=False, want_mu=False, act=self.act[t], logp=self.logp[t])
-            env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self.tob_all[t], rew_out=self._scratch_rew, done_out=self.done[t])
-            self.rew[t].copy_(self._evaluate_reward_batch(ti.rec, ti.srec))
-            self.counter += 1
-        self._episode_stats_from_buffers()
-
     def pop_episode_stats(self):
         """(sum of finished-episode returns, sum of their lengths, their number) since the last call -- the env's own counters, or,
         with a task plugged in, the rollout's (returns in the plugged task's reward)."""
         if self.task is None:
             return self.env.pop_episode_stats()
-        if not hasattr(self, "_stats"):
-            return 0.0, 0.0, 0
         s = self._stats.cpu().numpy()
         self._stats.zero_()
         return float(s[0]), float(s[1]), int(s[2])
 
-    def _collect_resident(self, deterministic) -> bool:
-        """All T control steps in one launch per rollout group, the actor evaluated inside the stepper's wavefronts
-        (BatchedEnv.rollout): bitwise the values of the launch-per-step loop below (float32 inference; with fp16 inference float32-rounding-close),
-        without its per-control-step barrier across
-        the envs of a group.  LHW_ROLLOUT_MODE = auto (default) | resident | steps (the launch-per-step pipeline)."""
+
+class RecurrentRollout(_RolloutStorage):
+    """LSTM policies.  As in the reference's worker (rollout_worker.py:130-190: `current_state` / hidden state are only
+    initialised when they are None), episodes AND the LSTM hidden / cell state are carried from one batch to the next:
+    the envs are reset once, before the first batch; afterwards a batch starts from the last observation of the previous
+    one with the hidden state the previous batch left, zeroed only for envs whose episode ended on its last step.  The
+    hidden state advances with every policy / critic call; terminal and final values are evaluated without advancing it.
+    (The update, like the reference's, restarts every stored trajectory -- here every env column -- from a zero state.)"""
+
+    def __init__(self, env, kernels, T: int, seed: int = 0):
+        super().__init__(env, kernels, T, seed)
+        N, D, A, dev = self.N, env.obs_dim, env.act_dim, env.device
+        self.mu = torch.zeros(N, A, dtype=torch.float32, device=dev)
+        self.tob = torch.zeros(N, D, dtype=torch.float32, device=dev)
+        self._rec_reset = torch.ones(N, dtype=torch.uint8, device=dev)      # every env starts from a zero state
+
+    def collect(self, deterministic=False):
         env, k, T = self.env, self.k, self.T
-        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
-        if mode not in ("auto", "resident") or not hasattr(env, "rollout") or not hasattr(k, "rollout_policy"):
-            return False
-        # Measured, same box, interleaved (profiles/r05_rollout_modes.txt, final kernels): resident over launch-per-step with two groups --
-        # jvrc_walk @ 4096 +25 % env-steps/s (rollout 0.524 -> 0.397 s), jvrc_step @ 4096 +26 %, h1_walk @ 8192 +9 %, h1 @ 8192 +2 %
-        # (twice as many wavefronts as the chip holds and a narrow spread of wave times: there two whole-chip launches in flight
-        # already backfill each other's tails).  So `auto` is resident wherever the library has the kernel.
-        pol = k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
-        if pol is None:
-            return False
-        self._pol_keep = pol      # (passed by value at the launch; kept for the debugger's sake)
-        # (the in-wave policy step keys its noise by the env's own global ids; the per-step calls below pass self.env_base + row)
-        if getattr(env, "env_id_base", 0) != self.env_base:
-            return False
-        if not env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done):
-            if mode == "resident":
-                raise _lib.LhwError(-4, "LHW_ROLLOUT_MODE=resident, but the library has no resident rollout kernel for this env / policy")
-            return False
-        self.counter += T
-        return True
-
-    def _collect_steps(self, deterministic):
-        env, k, T = self.env, self.k, self.T
-        G = self.groups
-        self.last_mode = "steps"      # which path collected the last rollout (tests, bench line)
-        if self.task is not None and self.reward_only:
-            if self._collect_resident_hooked(deterministic):
-                self.last_mode = "resident"
-            else:
-                self._collect_reward_only_steps(deterministic)
-                self.last_mode = "hooked"
-        elif self.task is not None:
-            self._collect_hooked(deterministic)
-        elif self._collect_resident(deterministic):
-            self.last_mode = "resident"
-        elif G <= 1:
-            for t in range(T):
-                k.forward(self.obs[t], seed=self.seed, env_id_base=self.env_base, counter=self.counter,
-                          deterministic=deterministic, want_value=False, want_mu=False, act=self.act[t], logp=self.logp[t])
-                env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self.tob_all[t], rew_out=self.rew[t], done_out=self.done[t])
-                self.counter += 1
-        else:
-            # Environments are independent, so the batch is advanced as G groups on their own HIP streams: a group's policy
-            # forward waits only for that group's control-step kernel.  Without the batch-wide barrier per control step the
-            # tail of one group's kernel (waves that drew more contacts / Newton iterations / a reset) overlaps the other
-            # group's work: 3.8 -> 2.9 ms per control step of 4096 envs with two groups.  Every value is unchanged (the RNG is
-            # keyed by global env id and step counter, not by launch order).
-            main = torch.cuda.current_stream(self.obs.device)
-            if self.streams is None:
-                self.streams = [torch.cuda.Stream(device=self.obs.device) for _ in range(G)]
-            bounds = [(g * self.N // G, (g + 1) * self.N // G) for g in range(G)]
-            for s in self.streams:
-                s.wait_stream(main)
-            for t in range(T):
-                for s, (a, b) in zip(self.streams, bounds):
-                    with torch.cuda.stream(s):
-                        k.forward(self.obs[t, a:b], seed=self.seed, env_id_base=self.env_base + a, counter=self.counter,
-                                  deterministic=deterministic, want_value=False, want_mu=False, ws_row=a, act=self.act[t, a:b],
-                                  logp=self.logp[t, a:b])
-                        env.step_range(a, b - a, self.act[t], self.obs[t + 1], self.tob_all[t], self.rew[t], self.done[t])
-                self.counter += 1
-            for s in self.streams:
-                main.wait_stream(s)
-        self._batched_values(self.obs[:T].reshape(T * self.N, -1), self.val.reshape(-1))
-        # V(terminal observation) is only read where a trajectory was TRUNCATED (max_traj_len) without terminating: the bootstrap
-        # of rl/workers/rollout_worker.py:163-190 (lhw_gae: `(f & 1) ? 0 : vterm`).  That is about one row per env and rollout --
-        # 0.25 % of the T x N terminal observations at T = max_traj_len = 400 -- so only those rows go through the critic
-        # (50 fewer 32768-row passes per iteration at 4096 envs); everywhere else vterm is 0 and unread.
-        need = ((self.done & 2) != 0) & ((self.done & 1) == 0)
-        idx = torch.nonzero(need.reshape(-1)).reshape(-1)
-        self.vterm.zero_()
-        if idx.numel():
-            vals = _lib.empty(idx.numel(), dtype=torch.float32, device=self.obs.device)
-            self._batched_values(self.tob_all.reshape(T * self.N, -1).index_select(0, idx), vals)
-            self.vterm.reshape(-1).index_copy_(0, idx, vals)
-        k.forward(self.obs[T], want_actor=False, value=self.vfinal)
-
-    def _batched_values(self, obs_flat, out_flat):
-        chunk = int(self.k.max_rows)
-        for a in range(0, obs_flat.shape[0], chunk):
-            b = min(a + chunk, obs_flat.shape[0])
-            self.k.forward(obs_flat[a:b], want_actor=False, value=out_flat[a:b])
-
-
-    def _collect_recurrent(self, deterministic):
-        """LSTM policies.  As in the reference's worker (rollout_worker.py:130-190: `current_state` / hidden state are only
-        initialised when they are None), episodes AND the LSTM hidden / cell state are carried from one batch to the next:
-        the envs are reset once, before the first batch; afterwards a batch starts from the last observation of the previous
-        one with the hidden state the previous batch left, zeroed only for envs whose episode ended on its last step.  The
-        hidden state advances with every policy / critic call; terminal and final values are evaluated without advancing it.
-        (The update, like the reference's, restarts every stored trajectory -- here every env column -- from a zero state.)"""
-        env, k, T = self.env, self.k, self.T
-        if not self.started:
-            self.obs[0].copy_(env.reset())
-            self._rec_reset = torch.ones(self.N, dtype=torch.uint8, device=self.obs.device)
-            self.started = True
-        else:
-            self.obs[0].copy_(self.obs[T])
+        self._start()
         reset = self._rec_reset
         for t in range(T):
             k.forward(self.obs[t], reset=reset, seed=self.seed, env_id_base=self.env_base, counter=self.counter,
@@ -460,8 +444,6 @@ class PPO:
         self.grad_clip, self.mirror_coeff = args.max_grad_norm, args.mirror_coeff
         self.eval_freq = args.eval_freq
         self.recurrent = bool(getattr(args, "recurrent", False))
-        if self.recurrent and getattr(args, "imitate", None):
-            raise NotImplementedError("--imitate together with --recurrent is not supported")
         self.imitate_coeff = float(getattr(args, "imitate_coeff", 0.3))
         self.batch_size = self.n_proc * self.max_traj_len
         self.total_steps = 0
@@ -482,71 +464,62 @@ class PPO:
         self.spec = spec
         obs_dim, act_dim = spec.obs_dim, spec.act_dim
         mirror = None if getattr(args, "no_mirror", False) else spec.mirror_tables()
-        continued = getattr(args, "continued", None)
-        self.obs_rms = None
+        hyper = dict(device=self.device, learn_std=args.learn_std, lr=self.lr, eps=self.eps, clip=self.clip, entropy_coeff=self.ent_coeff,
+                     mirror_coeff=self.mirror_coeff, max_grad_norm=self.grad_clip,
+                     mirror_obs=mirror[0] if mirror else None, mirror_act=mirror[1] if mirror else None)
+        # 1. the kernels, with the checkpoint loader and weight initialisation of the policy kind
         if self.recurrent:
             # LSTM actor / critic (ppo.py:84-86); a minibatch is `minibatch_size` whole env columns of the rollout
-            from .rnn_kernels import RnnKernels, reference_init_lstm
+            from .checkpoint import load_recurrent_checkpoint as load_checkpoint
+            from .rnn_kernels import RnnKernels, reference_init_lstm as init_weights
             hidden = int(getattr(args, "lstm_hidden", 256))
             cols = min(self.n_proc, int(self.minibatch_size or self.n_proc))
-            self.kernels = RnnKernels(
-                obs_dim, act_dim, hidden=hidden, seq_len=self.max_traj_len, seq_cols=cols, rollout_rows=self.n_proc, device=self.device,
-                learn_std=args.learn_std, lr=self.lr, eps=self.eps, clip=self.clip, entropy_coeff=self.ent_coeff,
-                mirror_coeff=self.mirror_coeff, max_grad_norm=self.grad_clip,
-                mirror_obs=mirror[0] if mirror else None, mirror_act=mirror[1] if mirror else None)
-            self.kernels.recurrent = True
-            if continued:
-                from .checkpoint import load_recurrent_checkpoint
-                cpath = Path(Path(continued).parent, "critic" + str(continued).split("actor")[1])
-                t, om, osd, _ = load_recurrent_checkpoint(continued, cpath)
-                t["stds"] = args.std_dev * torch.ones(act_dim)
-                self.kernels.set_tensors(t)
-                self.kernels.set_obs_norm(om.numpy(), osd.numpy())
-                self._log("Loaded (pre-trained) actor from: " + str(continued))
-                self._log("Loaded (pre-trained) critic from: " + str(cpath))
-            else:
-                self.kernels.set_tensors(reference_init_lstm(obs_dim, act_dim, hidden, args.std_dev, generator_seed=self._init_seed(seed)))
+            self.kernels = RnnKernels(obs_dim, act_dim, hidden=hidden, seq_len=self.max_traj_len, seq_cols=cols, rollout_rows=self.n_proc,
+                                      **hyper)
         else:
-            self.kernels = PpoKernels(
-                obs_dim, act_dim, hidden=256, max_rows=max(self.n_proc, int(self.minibatch_size or self.batch_size)),
-                device=self.device, learn_std=args.learn_std, lr=self.lr, eps=self.eps, clip=self.clip,
-                entropy_coeff=self.ent_coeff, mirror_coeff=self.mirror_coeff, max_grad_norm=self.grad_clip,
-                mirror_obs=mirror[0] if mirror else None, mirror_act=mirror[1] if mirror else None)
-        if getattr(args, "infer_fp16", False):
-            if self.recurrent:
+            from .checkpoint import load_reference_checkpoint as load_checkpoint
+            init_weights, hidden = reference_init, 256
+            self.kernels = PpoKernels(obs_dim, act_dim, hidden=hidden, max_rows=max(self.n_proc, int(self.minibatch_size or self.batch_size)),
+                                      **hyper)
+        # 2. the option combinations the LSTM path does not implement
+        fp16, infer_fp16 = getattr(args, "fp16", False), getattr(args, "infer_fp16", False)
+        if self.recurrent:
+            if getattr(args, "imitate", None):
+                raise NotImplementedError("--imitate together with --recurrent is not supported")
+            if infer_fp16:
                 raise NotImplementedError("--infer-fp16 is implemented for the feed-forward policies")
+            if fp16:
+                raise NotImplementedError("--fp16 is implemented for the feed-forward policies")
+            if task is not None:
+                raise NotImplementedError("a plugged-in task needs the feed-forward policies")
+        if infer_fp16 or fp16:
             self.kernels.set_inference_fp16(True)   # rollout inference on the fp16 MFMA; the update stays float32
-        if getattr(args, "fp16", False):
+        if fp16:
             # BASELINE config 5: fp16 actor / critic -- inference AND every GEMM of the update with fp16 operands (float32
             # accumulation, master weights, loss and Adam)
-            if self.recurrent:
-                raise NotImplementedError("--fp16 is implemented for the feed-forward policies")
-            self.kernels.set_inference_fp16(True)
             self.kernels.set_update_fp16(True)
-        if self.recurrent:
-            pass
-        elif continued:
-            # --continued actor_X.pt: load actor + sibling critic, re-initialise stds, keep the embedded obs
-            # normalisation (reference rl/algos/ppo.py:69-82)
-            from .checkpoint import load_reference_checkpoint
+        # 3. the weights: --continued actor_X.pt loads the actor + sibling critic, re-initialises stds and keeps the embedded obs
+        # normalisation (reference rl/algos/ppo.py:69-82); otherwise identical initial weights on every rank: the reference's init
+        # path under a fixed torch seed
+        continued = getattr(args, "continued", None)
+        if continued:
             cpath = Path(Path(continued).parent, "critic" + str(continued).split("actor")[1])
-            t, om, osd = load_reference_checkpoint(continued, cpath)
+            t, om, osd = load_checkpoint(continued, cpath)[:3]      # (the LSTM loader also returns the hidden width)
             t["stds"] = args.std_dev * torch.ones(act_dim)
             self.kernels.set_tensors(t)
             self.kernels.set_obs_norm(om.numpy(), osd.numpy())
-            self.obs_rms = None
             self._log("Loaded (pre-trained) actor from: " + str(continued))
             self._log("Loaded (pre-trained) critic from: " + str(cpath))
         else:
-            # identical initial weights on every rank: the reference's init path under a fixed torch seed
-            self.kernels.set_tensors(reference_init(obs_dim, act_dim, 256, args.std_dev, generator_seed=self._init_seed(seed)))
+            self.kernels.set_tensors(init_weights(obs_dim, act_dim, hidden, args.std_dev, generator_seed=self._init_seed(seed)))
+        # 4. observation normalisation: the checkpoint's, the env's fixed one, or a running one warmed up by train()
+        self.obs_rms = None
         if continued:
             pass
         elif spec.obs_mean is not None:
             if len(spec.obs_mean) != obs_dim or len(spec.obs_std) != obs_dim:
                 raise ValueError(f"{type(spec).__name__}: obs_mean / obs_std have {len(spec.obs_mean)} / {len(spec.obs_std)} entries "
                                  f"for an observation of {obs_dim} (base {getattr(spec, 'base_obs_dim', obs_dim)} x history)")
-            self.obs_rms = None
             self.kernels.set_obs_norm(spec.obs_mean, spec.obs_std)
             self._log("Using fixed observation normalization from environment.")
         else:
@@ -555,17 +528,19 @@ class PPO:
             self._log("Using running observation normalization (will update during training).")
         env_seed = (seed if seed is not None else int(time.time())) & 0x7FFFFFFF
         self.env_seed = env_seed
-        if task is not None and self.recurrent:
-            raise NotImplementedError("a plugged-in task needs the feed-forward policies")
         self.task = task(spec, self.device) if task is not None else None
         # A task that decides terminations itself is consulted after every control step and the env never ends an episode by itself:
-        # the rollout truncates and resets (Rollout._collect_hooked).  A reward-only task leaves all that to the kernel.
+        # the rollout truncates and resets (Rollout._task_step).  A reward-only task leaves all that to the kernel.
         # (reward_only counts only where the task declares this env's fused termination as its own: task_hook.reward_only_on)
         own_done = self.task is not None and not reward_only_on(self.task, getattr(spec, "task_code", None))
         self.env = spec.make_batched(self.n_proc, seed=env_seed, device=self.device, max_traj_len=0 if own_done else self.max_traj_len,
                                      env_id_base=dist_utils.shard_env_ids(self.n_proc, self.rank))
         self.env.env_id_base = dist_utils.shard_env_ids(self.n_proc, self.rank)
-        self.rollout = Rollout(self.env, self.kernels, self.max_traj_len, seed=env_seed ^ 0x5DEECE66D, task=self.task, max_traj_len=self.max_traj_len)
+        rollout_seed = env_seed ^ 0x5DEECE66D
+        if self.recurrent:
+            self.rollout = RecurrentRollout(self.env, self.kernels, self.max_traj_len, seed=rollout_seed)
+        else:
+            self.rollout = Rollout(self.env, self.kernels, self.max_traj_len, seed=rollout_seed, task=self.task, max_traj_len=self.max_traj_len)
         # --imitate: frozen expert + the env's projector (reference rl/algos/ppo.py:111-122)
         self.base_policy, self.imitation_projector = None, None
         if getattr(args, "imitate", None):
@@ -582,11 +557,7 @@ class PPO:
         # The reference deep-copies the actor into old_policy every iteration only to evaluate the behaviour log-probs; here
         # they are stored by the rollout (and recomputed in float32 for the fp16-inference mode), so old_policy is the policy.
         self.old_policy = self.kernels
-        names = list(getattr(self.kernels, "TENSORS", []))
-        if self.recurrent:       # RnnKernels addresses its tensors by (name, offset, shape) specs
-            specs = self.kernels.tensor_specs()
-            names = list(specs)
-            self.kernels._adam_view_specs = specs
+        names = self.kernels.TENSORS
         self.actor_optimizer = _AdamView(self.kernels, [n for n in names if n.startswith("a_") or n == "stds"], self.lr, self.eps)
         self.critic_optimizer = _AdamView(self.kernels, [n for n in names if n.startswith("c_")], self.lr, self.eps)
         self.last_losses = {}
@@ -727,7 +698,7 @@ class PPO:
         # Single process, no imitation term: an optimiser step is ONE graph launch (lhw_ppo_step) on a stream of its own -- a hipGraph is
         # captured from a stream, and torch's default stream is the legacy one, which cannot be captured.  With data parallelism the
         # gradient all-reduce sits between the two halves: lhw_ppo_grad, all-reduce, lhw_ppo_apply, eagerly.
-        fused = (self.imitation_projector is None and not dist_utils._active(dist_utils.dist()) and hasattr(k._L, "lhw_ppo_step")
+        fused = (self.imitation_projector is None and not dist_utils._active(dist_utils.dist())
                  and os.environ.get("LHW_PPO_GRAPH", "1") != "0")
         cur = torch.cuda.current_stream(self.device)
         if fused:
@@ -796,14 +767,13 @@ class PPO:
         if self.rank != 0:
             return
         from .checkpoint import save_recurrent_checkpoint, save_reference_checkpoint
-        if self.recurrent:
-            save_reference_checkpoint = save_recurrent_checkpoint    # Gaussian_LSTM_Actor / LSTM_V pickles
+        write = save_recurrent_checkpoint if self.recurrent else save_reference_checkpoint    # (Gaussian_LSTM_Actor / LSTM_V pickles)
         t = self.kernels.get_tensors()
         om, osd = self.kernels.obs_mean.cpu(), self.kernels.obs_std.cpu()
-        save_reference_checkpoint(t, om, osd, self.kernels.learn_std, self.save_path / f"actor_{itr}.pt", self.save_path / f"critic_{itr}.pt")
+        write(t, om, osd, self.kernels.learn_std, self.save_path / f"actor_{itr}.pt", self.save_path / f"critic_{itr}.pt")
         if metric is not None and metric > self.best_metric:
             self.best_metric = metric
-            save_reference_checkpoint(t, om, osd, self.kernels.learn_std, self.save_path / "actor.pt", self.save_path / "critic.pt")
+            write(t, om, osd, self.kernels.learn_std, self.save_path / "actor.pt", self.save_path / "critic.pt")
 
     def evaluate(self, itr, num_batches=5):
         """5 deterministic batches on the same persistent envs (ppo.py:408-426)."""

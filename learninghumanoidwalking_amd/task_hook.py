@@ -110,8 +110,8 @@ class VectorTask:
     `reward_only = True` declares that the task changes the REWARD only -- its termination rule is the fused task's (the common
     case: an edited tasks/rewards.py, other term weights).  The rollout then stays resident (one launch per rollout, the kernel's
     own termination / truncation / resets), exports the record of every control step, and `evaluate` is called ONCE over the whole
-    [T * N] batch after the launch; the `done` it returns is ignored (Rollout._collect_resident_hooked).  With False (default)
-    the task is consulted after every control step and decides terminations itself (Rollout._collect_hooked).  `fused_tasks` (optional)
+    [T * N] batch after the launch; the `done` it returns is ignored (Rollout._collect_resident, task_inputs=True).  With False
+    (default) the task is consulted after every control step and decides terminations itself (Rollout._task_step).  `fused_tasks` (optional)
     names the envs (batched_env.TASK_*) whose fused termination `done` equals; on any other env the task is consulted step by step
     whatever `reward_only` says (reward_only_on)."""
     reward_only = False

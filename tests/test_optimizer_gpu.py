@@ -289,3 +289,45 @@ def test_padding_stays_exactly_zero_through_real_updates(hidden, learn_std, path
         assert not torch.equal(k.theta, theta0)
         if not learn_std:
             assert torch.equal(k.theta[stds], theta0[stds]) and not k.adam_m[stds].any()
+
+
+@pytest.mark.parametrize("recurrent", [False, True])
+def test_optimizer_views_are_the_slices_of_the_adam_moments(recurrent, tmp_path):
+    """PPO.actor_optimizer / critic_optimizer (the reference's two torch.optim.Adam, rl/algos/ppo.py:128-129) as views of the flat Adam
+    moments, feed-forward and LSTM: after one iteration every entry's exp_avg / exp_avg_sq is that tensor's slice of adam_m / adam_v, the
+    two optimisers split the tensors between them, and (with every position of adam_m numbered) the entries have the shapes of the
+    reference's parameters and read disjoint positions."""
+    from types import SimpleNamespace
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS
+    from learninghumanoidwalking_amd.ppo import PPO
+    from learninghumanoidwalking_amd.ppo_kernels import reference_init
+    from learninghumanoidwalking_amd.rnn_kernels import reference_init_lstm
+    args = SimpleNamespace(gamma=0.99, lam=0.95, lr=3e-4, eps=1e-5, entropy_coeff=0.0, clip=0.2, minibatch_size=16 if recurrent else 256,
+                           epochs=1, max_traj_len=12, num_procs=32, num_envs=32, max_grad_norm=0.5, mirror_coeff=0.4, eval_freq=10**9,
+                           recurrent=recurrent, imitate=None, learn_std=False, std_dev=0.223, no_mirror=False, continued=None,
+                           logdir=str(tmp_path), device_index=0, lstm_hidden=64)
+    algo = PPO(ENVIRONMENTS["jvrc_walk"], args, seed=5)
+    algo.iterate(0)
+    k = algo.kernels
+    assert k.adam_step > 0
+    sa, sc = algo.actor_optimizer.state_dict(), algo.critic_optimizer.state_dict()
+    names = list(sa["state"]) + list(sc["state"])
+    assert sorted(names) == sorted(k.get_tensors()) and len(set(names)) == len(names)
+    assert all(n.startswith("a_") or n == "stds" for n in sa["state"]) and all(n.startswith("c_") for n in sc["state"])
+    m, v = k.get_tensors(k.adam_m), k.get_tensors(k.adam_v)
+    for st in (sa["state"], sc["state"]):
+        for n, e in st.items():
+            assert e["step"] == k.adam_step
+            assert torch.equal(e["exp_avg"], m[n]) and torch.equal(e["exp_avg_sq"], v[n]), n
+    assert any(e["exp_avg"].any() for e in sa["state"].values()) and any(e["exp_avg"].any() for e in sc["state"].values())
+    # number every position of adam_m: the entries then name the positions they read
+    assert k.n_params < 2 ** 24
+    k.adam_m.copy_(torch.arange(k.n_params, dtype=torch.float32, device=k.adam_m.device))
+    ref = (reference_init_lstm(k.obs_dim, k.act_dim, k.hidden) if recurrent else reference_init(k.obs_dim, k.act_dim, k.hidden))
+    pos = []
+    for opt in (algo.actor_optimizer, algo.critic_optimizer):
+        for n, e in opt.state_dict()["state"].items():
+            assert e["exp_avg"].shape == ref[n].shape, n
+            pos.append(e["exp_avg"].reshape(-1).long())
+    pos = torch.cat(pos)
+    assert pos.numel() == sum(t.numel() for t in ref.values()) == pos.unique().numel()

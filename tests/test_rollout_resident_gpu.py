@@ -214,3 +214,31 @@ def test_resident_rollout_against_the_oracle_directly(monkeypatch):
     assert (F_ & 2).sum() >= 3 * N * 0.8 and (F_ & 1).any(), "truncations / falls missing"
     assert env.pop_rerun_count() > 0, "no env took the in-wave one-env-per-wave re-run"
     assert env.pop_fault_stats() == (0, 0)
+
+
+@pytest.mark.parametrize("decline", ["no_policy_view", "env_id_base", "no_resident_kernel"])
+@pytest.mark.parametrize("task", ["fused", "reward_only"])
+def test_forced_resident_mode_raises_wherever_the_resident_rollout_declines(task, decline, monkeypatch):
+    """LHW_ROLLOUT_MODE=resident must not quietly run (and so measure or test) the launch-per-step pipeline: whichever way the resident
+    attempt declines -- the kernels give no in-wave policy view, the env's env_id_base is not the rollout's, or env.rollout reports no
+    kernel for the env / policy -- collect() raises, for the fused task and a reward-only plug-in alike.  Under `auto` the same
+    rollout falls back to the launch-per-step pipeline."""
+    from learninghumanoidwalking_amd import _lib
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS
+    from learninghumanoidwalking_amd.ppo import PPO
+    from learninghumanoidwalking_amd.task_hook import VectorWalkingTask
+    hook = None if task == "fused" else (lambda spec, dev: VectorWalkingTask(spec, dev))
+    algo = PPO(ENVIRONMENTS["jvrc_walk"], _args(32, 4), seed=1, task=hook)
+    assert algo.rollout.reward_only == (task == "reward_only")
+    if decline == "no_policy_view":
+        monkeypatch.setattr(algo.kernels, "rollout_policy", lambda **kw: None)
+    elif decline == "env_id_base":
+        monkeypatch.setattr(algo.env, "env_id_base", algo.env.env_id_base + 1)
+    else:
+        monkeypatch.setattr(algo.env, "rollout", lambda *a, **kw: False)
+    monkeypatch.setenv("LHW_ROLLOUT_MODE", "auto")
+    algo.rollout.collect()
+    assert algo.rollout.last_mode == ("steps" if task == "fused" else "hooked")
+    monkeypatch.setenv("LHW_ROLLOUT_MODE", "resident")
+    with pytest.raises(_lib.LhwError, match="LHW_ROLLOUT_MODE=resident"):
+        algo.rollout.collect()
