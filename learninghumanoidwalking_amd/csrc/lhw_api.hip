@@ -49,6 +49,7 @@ struct LhwEnv {
   HumanoidEnv* hum = nullptr;
   double* stage_q = nullptr;  // device staging for get/set state
   double* stage_v = nullptr;
+  LhwDevMem mem;              // the cartpole state and the staging buffers (the humanoid stepper owns its own)
 };
 
 extern "C" int lhw_version(void) { return 1; }
@@ -133,15 +134,11 @@ static int create_cartpole(LhwEnv* e, const LhwEnvConfig* cfg) {
   p.kp = cfg->kp ? cfg->kp[0] : 0; p.kd = cfg->kd ? cfg->kd[0] : 0;
   e->obs_dim = 5; e->act_dim = 1; e->n_terms = 4;
   const size_t N = e->n_envs;
-  HIPCHK(lhw_malloc(&e->cps.d, sizeof(double) * CARTPOLE_NFIELDS * N));
-  HIPCHK(hipMemset(e->cps.d, 0, sizeof(double) * CARTPOLE_NFIELDS * N));
-  HIPCHK(lhw_malloc(&e->cps.traj_len, sizeof(int32_t) * N));
-  HIPCHK(hipMemset(e->cps.traj_len, 0, sizeof(int32_t) * N));
-  HIPCHK(lhw_malloc(&e->cps.reset_count, sizeof(uint32_t) * N));
-  HIPCHK(hipMemset(e->cps.reset_count, 0, sizeof(uint32_t) * N));
-  HIPCHK(lhw_malloc(&e->cps.ep_stats, sizeof(double) * 3));
-  HIPCHK(hipMemset(e->cps.ep_stats, 0, sizeof(double) * 3));
-  return LHW_OK;
+  e->cps.d = e->mem.get<double>(CARTPOLE_NFIELDS * N);
+  e->cps.traj_len = e->mem.get<int32_t>(N);
+  e->cps.reset_count = e->mem.get<uint32_t>(N);
+  e->cps.ep_stats = e->mem.get<double>(3);
+  return e->mem.failed() ? lhw_fail(LHW_ERR_HIP, "cartpole state allocation failed (n_envs=%d)", e->n_envs) : LHW_OK;
 }
 
 extern "C" int lhw_env_create(const int32_t* model_i, int64_t n_model_i, const double* model_d, int64_t n_model_d,
@@ -159,15 +156,15 @@ extern "C" int lhw_env_create(const int32_t* model_i, int64_t n_model_i, const d
   LhwEnv* e = new LhwEnv();
   e->mi.assign(model_i, model_i + n_model_i);
   e->md.assign(model_d, model_d + n_model_d);
-  e->task = cfg->task; e->n_envs = cfg->n_envs; e->device = cfg->device;
+  e->task = cfg->task; e->n_envs = cfg->n_envs; e->device = e->mem.device = cfg->device;
   e->nq = model_i[LHW_IH_NQ]; e->nv = model_i[LHW_IH_NV]; e->nu = model_i[LHW_IH_NU];
   if (cfg->task == LHW_TASK_CARTPOLE) rc = create_cartpole(e, cfg);
   else if (cfg->task == LHW_TASK_JVRC_WALK || cfg->task == LHW_TASK_H1_STAND || cfg->task == LHW_TASK_JVRC_STEP || cfg->task == LHW_TASK_H1_WALK) rc = humanoid_create(&e->hum, e->mi, e->md, cfg, &e->obs_dim, &e->act_dim, &e->n_terms);
   else rc = lhw_fail(LHW_ERR_ARG, "unknown task %d", cfg->task);
   if (rc == LHW_OK) {
-    if (lhw_malloc(&e->stage_q, sizeof(double) * (size_t)e->n_envs * e->nq) != hipSuccess ||
-        lhw_malloc(&e->stage_v, sizeof(double) * (size_t)e->n_envs * e->nv) != hipSuccess)
-      rc = lhw_fail(LHW_ERR_HIP, "lhw_malloc(staging) failed");
+    e->stage_q = e->mem.get<double>((size_t)e->n_envs * e->nq, LhwDevMem::RAW);
+    e->stage_v = e->mem.get<double>((size_t)e->n_envs * e->nv, LhwDevMem::RAW);
+    if (e->mem.failed()) rc = lhw_fail(LHW_ERR_HIP, "lhw_malloc(staging) failed");
   }
   if (rc != LHW_OK) { lhw_env_destroy(e); return rc; }
   *out = e;
@@ -176,14 +173,7 @@ extern "C" int lhw_env_create(const int32_t* model_i, int64_t n_model_i, const d
 
 extern "C" int lhw_env_destroy(LhwEnv* e) {
   if (!e) return LHW_OK;
-  (void)hipSetDevice(e->device);
-  if (e->cps.d) (void)hipFree(e->cps.d);
-  if (e->cps.traj_len) (void)hipFree(e->cps.traj_len);
-  if (e->cps.reset_count) (void)hipFree(e->cps.reset_count);
-  if (e->cps.ep_stats) (void)hipFree(e->cps.ep_stats);
-  if (e->stage_q) (void)hipFree(e->stage_q);
-  if (e->stage_v) (void)hipFree(e->stage_v);
-  if (e->hum) humanoid_destroy(e->hum);
+  humanoid_destroy(e->hum);
   delete e;
   return LHW_OK;
 }
@@ -287,14 +277,20 @@ extern "C" int lhw_env_set_state(LhwEnv* e, const double* qpos_host, const doubl
   return LHW_OK;
 }
 
+// ep_stats[first .. first + count) -> host after a device synchronise, then cleared on the device
+static int pop_stats(LhwEnv* e, int first, int count, double* out) {
+  HIPCHK(hipSetDevice(e->device));
+  double* dev = (e->task == LHW_TASK_CARTPOLE ? e->cps.ep_stats : humanoid_ep_stats(e->hum)) + first;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, dev, sizeof(double) * count, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(dev, 0, sizeof(double) * count));
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len_sum, int64_t* count) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
-  HIPCHK(hipSetDevice(e->device));
-  double* dev = e->task == LHW_TASK_CARTPOLE ? e->cps.ep_stats : humanoid_ep_stats(e->hum);
   double h[3];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, dev, sizeof h, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(dev, 0, sizeof h));
+  if (const int rc = pop_stats(e, 0, 3, h)) return rc;
   if (ret_sum) *ret_sum = h[0];
   if (len_sum) *len_sum = h[1];
   if (count) *count = (int64_t)h[2];
@@ -327,11 +323,8 @@ extern "C" int lhw_env_pop_fault_stats(LhwEnv* e, int64_t* contact_overflow, int
   if (contact_overflow) *contact_overflow = 0;
   if (diverged) *diverged = 0;
   if (!e->hum) return LHW_OK;  // the cartpole kernel has neither contacts nor a divergence path
-  HIPCHK(hipSetDevice(e->device));
   double h[2];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, humanoid_ep_stats(e->hum) + 3, sizeof h, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(humanoid_ep_stats(e->hum) + 3, 0, sizeof h));
+  if (const int rc = pop_stats(e, 3, 2, h)) return rc;
   if (contact_overflow) *contact_overflow = (int64_t)h[0];
   if (diverged) *diverged = (int64_t)h[1];
   return LHW_OK;
@@ -340,38 +333,38 @@ extern "C" int lhw_env_pop_fault_stats(LhwEnv* e, int64_t* contact_overflow, int
 extern "C" int lhw_env_enable_task_inputs(LhwEnv* e, int enable) {
   if (!e || !e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "task inputs exist for the humanoid tasks only");
   HIPCHK(hipSetDevice(e->device));
-  if (humanoid_task_inputs(e->hum, enable ? 1 : 0, nullptr, nullptr)) return lhw_fail(LHW_ERR_HIP, "task input buffer");
+  if (humanoid_task_inputs(e->hum, false, enable ? 1 : 0, nullptr, nullptr)) return lhw_fail(LHW_ERR_HIP, "task input buffer");
   return LHW_OK;
 }
 extern "C" int lhw_env_get_task_inputs(LhwEnv* e, double* out_host) {
   if (!e || !e->hum || !out_host) return lhw_fail(LHW_ERR_ARG, "null argument / not a humanoid task");
   HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_task_inputs(e->hum, -1, out_host, nullptr);
+  const int rc = humanoid_task_inputs(e->hum, false, -1, out_host, nullptr);
   if (rc == -2) return lhw_fail(LHW_ERR_ARG, "lhw_env_get_task_inputs: call lhw_env_enable_task_inputs(env, 1) first");
   if (rc) return lhw_fail(LHW_ERR_HIP, "task input copy");
   return LHW_OK;
 }
 extern "C" int lhw_env_task_inputs_device(LhwEnv* e, double** out_dev) {
   if (!e || !e->hum || !out_dev) return lhw_fail(LHW_ERR_ARG, "null argument / not a humanoid task");
-  return humanoid_task_inputs(e->hum, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "task input buffer") : LHW_OK;
+  return humanoid_task_inputs(e->hum, false, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "task input buffer") : LHW_OK;
 }
 extern "C" int lhw_env_enable_step_task_inputs(LhwEnv* e, int enable) {
   if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "the stepping task-input record exists for the stepping task only");
   HIPCHK(hipSetDevice(e->device));
-  if (humanoid_step_task_inputs(e->hum, enable ? 1 : 0, nullptr, nullptr)) return lhw_fail(LHW_ERR_HIP, "stepping task input buffer");
+  if (humanoid_task_inputs(e->hum, true, enable ? 1 : 0, nullptr, nullptr)) return lhw_fail(LHW_ERR_HIP, "stepping task input buffer");
   return LHW_OK;
 }
 extern "C" int lhw_env_get_step_task_inputs(LhwEnv* e, double* out_host) {
   if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP || !out_host) return lhw_fail(LHW_ERR_ARG, "null argument / not a stepping-task env");
   HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_step_task_inputs(e->hum, -1, out_host, nullptr);
+  const int rc = humanoid_task_inputs(e->hum, true, -1, out_host, nullptr);
   if (rc == -2) return lhw_fail(LHW_ERR_ARG, "lhw_env_get_step_task_inputs: call lhw_env_enable_step_task_inputs(env, 1) first");
   if (rc) return lhw_fail(LHW_ERR_HIP, "stepping task input copy");
   return LHW_OK;
 }
 extern "C" int lhw_env_step_task_inputs_device(LhwEnv* e, double** out_dev) {
   if (!e || !e->hum || e->task != LHW_TASK_JVRC_STEP || !out_dev) return lhw_fail(LHW_ERR_ARG, "null argument / not a stepping-task env");
-  return humanoid_step_task_inputs(e->hum, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "stepping task input buffer") : LHW_OK;
+  return humanoid_task_inputs(e->hum, true, -1, nullptr, out_dev) ? lhw_fail(LHW_ERR_HIP, "stepping task input buffer") : LHW_OK;
 }
 extern "C" int lhw_env_get_actuator_state(LhwEnv* e, double* pos_host, double* vel_host, double* torque_host) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
@@ -385,11 +378,8 @@ extern "C" int lhw_env_pop_rerun_count(LhwEnv* e, int64_t* reruns) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
   if (reruns) *reruns = 0;
   if (!e->hum) return LHW_OK;
-  HIPCHK(hipSetDevice(e->device));
   double h = 0;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(&h, humanoid_ep_stats(e->hum) + 5, sizeof h, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(humanoid_ep_stats(e->hum) + 5, 0, sizeof h));
+  if (const int rc = pop_stats(e, 5, 1, &h)) return rc;
   if (reruns) *reruns = (int64_t)h;
   return LHW_OK;
 }

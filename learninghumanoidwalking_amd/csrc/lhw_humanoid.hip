@@ -1,5 +1,7 @@
 // Control-step kernels (one launch = one control step of a range of envs) and the host side of the humanoid stepper.
 // The device code -- layouts, sub-step, control_step -- lives in lhw_humanoid_dev.h (see its header for the design).
+#include <memory>
+
 #include "lhw_humanoid_dev.h"
 
 template <int MODE, int TASK, int W>  // MODE: 0 step, 1 reset(mask), 2 set_state, 3 get_state; TASK: TASK_WALK / TASK_STAND / TASK_STEP / TASK_H1WALK; W: lanes per env
@@ -52,53 +54,60 @@ static void h_quat2mat(double* R, const double* q) {
 }
 
 template <typename T>
-static DevTab<T> to_dev(HumanoidEnv* h, const T* src, size_t n) {
-  void* d = nullptr;
-  if (lhw_malloc(&d, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return DevTab<T>{nullptr};
-  if (n && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return DevTab<T>{nullptr};
-  h->dev_allocs.push_back(d);
-  return DevTab<T>{(const T*)d};
-}
+static DevTab<T> to_dev(HumanoidEnv* h, const T* src, size_t n) { return DevTab<T>{h->mem.put(src, n)}; }
 
 static bool humanoid_upload_params(HumanoidEnv* h) {
-  if (!h->p_dev) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, sizeof(HParams)) != hipSuccess) return false;
-    h->dev_allocs.push_back(d);
-    h->p_dev = (HParams*)d;
-  }
-  if (!h->m_dev) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, sizeof(HModel)) != hipSuccess) return false;
-    h->dev_allocs.push_back(d);
-    h->m_dev = (HModel*)d;
-  }
-  return hipMemcpy(h->p_dev, &h->p, sizeof(HParams), hipMemcpyHostToDevice) == hipSuccess &&
+  if (!h->p_dev) h->p_dev = h->mem.get<HParams>(1, LhwDevMem::RAW);
+  if (!h->m_dev) h->m_dev = h->mem.get<HModel>(1, LhwDevMem::RAW);
+  return h->p_dev && h->m_dev && hipMemcpy(h->p_dev, &h->p, sizeof(HParams), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(h->m_dev, &h->m, sizeof(HModel), hipMemcpyHostToDevice) == hipSuccess;
 }
 
-int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std::vector<double>& md, const LhwEnvConfig* cfg,
-                    int* obs_dim, int* act_dim, int* n_terms) {
-  auto IF = [&](int f) { return mi.data() + mi[LHW_IH_COUNT + f]; };
-  auto DF = [&](int f) { return md.data() + mi[LHW_IH_COUNT + LHW_IF_COUNT + f]; };
-  const int nq = mi[LHW_IH_NQ], nv = mi[LHW_IH_NV], nu = mi[LHW_IH_NU], nbm = mi[LHW_IH_NBODY], nj = mi[LHW_IH_NJNT],
-            ng = mi[LHW_IH_NGEOM], np = mi[LHW_IH_NPAIR];
+// The steps of humanoid_create, in the order they run, and what one step hands to the next.
+struct HumanoidCreate {
+  const std::vector<int32_t>& mi;
+  const std::vector<double>& md;
+  const LhwEnvConfig* cfg;
+  const int nq, nv, nu, nbm, nj, ng, np;
+  const bool stepping, h1walk;
+  const bool walk;    // JVRC robot + gait clock
+  const bool stand;   // H1 robot: observation noise, domain randomisation
+  const int32_t *jtype, *dparent, *djnt, *jdof;
+  int nb = 0, nplans = 0, primbox_pairs = 0, cyl_pairs = 0;
+  bool jvrc_perturb = false;
+  std::vector<int> bmap, bsrc;   // model body -> compacted body id (0: static, folded into the world) and back
+  std::vector<int32_t> parent, rootid, bdofadr, bdofnum;   // per-body model arrays re-indexed by the compacted body id
+
+  HumanoidCreate(const std::vector<int32_t>& mi_, const std::vector<double>& md_, const LhwEnvConfig* cfg_)
+      : mi(mi_), md(md_), cfg(cfg_), nq(mi[LHW_IH_NQ]), nv(mi[LHW_IH_NV]), nu(mi[LHW_IH_NU]), nbm(mi[LHW_IH_NBODY]), nj(mi[LHW_IH_NJNT]),
+        ng(mi[LHW_IH_NGEOM]), np(mi[LHW_IH_NPAIR]), stepping(cfg->task == LHW_TASK_JVRC_STEP), h1walk(cfg->task == LHW_TASK_H1_WALK),
+        walk(cfg->task == LHW_TASK_JVRC_WALK || stepping), stand(cfg->task == LHW_TASK_H1_STAND || h1walk),
+        jtype(IF(LHW_IF_JNT_TYPE)), dparent(IF(LHW_IF_DOF_PARENTID)), djnt(IF(LHW_IF_DOF_JNTID)), jdof(IF(LHW_IF_JNT_DOFADR)) {}
+  const int32_t* IF(int f) const { return mi.data() + mi[LHW_IH_COUNT + f]; }
+  const double* DF(int f) const { return md.data() + mi[LHW_IH_COUNT + LHW_IF_COUNT + f]; }
+  int BID(int f) const { const int b = cfg->task_iparams[f]; return (b >= 0 && b < nbm) ? bmap[b] : -1; }   // compacted id of a task body
+
+  int check();                            // model / config checks that need no device
+  int pack_model(HModel& m);              // derived structure and the packed per-role tables
+  bool task_params(HumanoidEnv* h);       // HParams (and the task's device tables); false: bad body ids or a failed allocation
+  bool alloc_state(HumanoidEnv* h);       // per-env records
+  int reset_template(HumanoidEnv* h);     // jvrc_walk: the template record every auto-reset copies
+};
+
+int HumanoidCreate::check() {
   // Static bodies (children of the world without joints: floor, terrain boxes) never move: their geoms are attached to
   // the world body with the composed pose and the bodies themselves are dropped from the kinematic tables.
-  std::vector<int> bmap(nbm, 0), bsrc(1, 0);
+  bmap.assign(nbm, 0); bsrc.assign(1, 0);
   for (int b = 1; b < nbm; b++) {
     if (IF(LHW_IF_BODY_ROOTID)[b] == 1) { bmap[b] = (int)bsrc.size(); bsrc.push_back(b); }
     else if (IF(LHW_IF_BODY_PARENTID)[b] != 0 || IF(LHW_IF_BODY_DOFNUM)[b] > 0)
       return lhw_fail(LHW_ERR_UNSUPPORTED, "exactly one dynamic tree (rooted at body 1) plus static children of the world is supported");
   }
-  const int nb = (int)bsrc.size();
+  nb = (int)bsrc.size();
   if (nq > NQ || nv > NVMAX || nu > NU || nb > NB || nj > NJ || ng > NG || np > NP || nb > 64 || np > 64)
     return lhw_fail(LHW_ERR_MODEL, "model exceeds compiled limits (nq %d/%d nv %d/%d nu %d/%d nbody %d/%d njnt %d/%d ngeom %d/%d npair %d/%d)%s",
                     nq, NQ, nv, NVMAX, nu, NU, nb, NB, nj, NJ, ng, NG, np, NP,
                     nb > NB ? ": fold the welded (joint-less) links into their parents first -- Model.fuse_static / fit_stepper_limits, or MuJoCo's fusestatic" : "");
-  const bool stepping = cfg->task == LHW_TASK_JVRC_STEP, h1walk = cfg->task == LHW_TASK_H1_WALK;
-  const bool walk = cfg->task == LHW_TASK_JVRC_WALK || stepping;             // JVRC robot + gait clock
-  const bool stand = cfg->task == LHW_TASK_H1_STAND || h1walk;               // H1 robot: observation noise, domain randomisation
   if (!walk && !stand) return lhw_fail(LHW_ERR_ARG, "humanoid stepper: unknown task");
   if (walk && (nu != 12 || nq != 19 || nv != 18)) return lhw_fail(LHW_ERR_UNSUPPORTED, "jvrc tasks need a free root + 12 actuated leg hinges");
   if (stand && (nu != 10 || nq != 17 || nv != 16)) return lhw_fail(LHW_ERR_UNSUPPORTED, "h1 needs a free root + 10 actuated leg hinges");
@@ -107,7 +116,6 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
   if ((walk || h1walk) && (!cfg->clock_lut || cfg->period <= 0)) return lhw_fail(LHW_ERR_ARG, "walking / stepping tasks need the gait clock table");
   if (stand && (cfg->n_task_params < LHW_TP_H1_OBS_NOISE + 35 || cfg->n_task_iparams < LHW_TI_H1_RAND_BODY + 11))
     return lhw_fail(LHW_ERR_ARG, "h1 task parameter arrays too short");
-  int nplans = 0;
   if (stepping) {
     if (cfg->n_task_iparams < LHW_TI_STEP_COUNT || cfg->n_task_params < LHW_TP_STEP_PLANS) return lhw_fail(LHW_ERR_ARG, "stepping task parameter arrays too short");
     nplans = (int)cfg->task_params[LHW_TP_STEP_NPLANS];
@@ -122,10 +130,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
       if (IF(LHW_IF_GEOM_TYPE)[g] != G_BOX || bmap[IF(LHW_IF_GEOM_BODYID)[g]] != 0) return lhw_fail(LHW_ERR_ARG, "stepping task: terrain geoms must be boxes on static bodies");
     if (IF(LHW_IF_GEOM_TYPE)[fg] != G_PLANE) return lhw_fail(LHW_ERR_ARG, "stepping task: floor geom must be a plane");
   }
-  const int32_t *jtype = IF(LHW_IF_JNT_TYPE), *dparent = IF(LHW_IF_DOF_PARENTID);
-  const int32_t *djnt = IF(LHW_IF_DOF_JNTID), *jdof = IF(LHW_IF_JNT_DOFADR);
-  // per-body model arrays re-indexed by the compacted body id
-  std::vector<int32_t> parent(nb, 0), rootid(nb, 0), bdofadr(nb, 0), bdofnum(nb, 0);
+  parent.assign(nb, 0); rootid.assign(nb, 0); bdofadr.assign(nb, 0); bdofnum.assign(nb, 0);
   for (int b = 1; b < nb; b++) {
     parent[b] = bmap[IF(LHW_IF_BODY_PARENTID)[bsrc[b]]]; rootid[b] = 1;
     bdofadr[b] = IF(LHW_IF_BODY_DOFADR)[bsrc[b]]; bdofnum[b] = IF(LHW_IF_BODY_DOFNUM)[bsrc[b]];
@@ -138,7 +143,6 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
     if (cd != 1 && cd != 3) return lhw_fail(LHW_ERR_UNSUPPORTED, "condim %d", cd);
   }
   if (mi[LHW_IH_CONE] != 0) return lhw_fail(LHW_ERR_UNSUPPORTED, "only the pyramidal cone is implemented");
-  int primbox_pairs = 0, cyl_pairs = 0;
   for (int q = 0; q < np; q++) {
     const int t1 = IF(LHW_IF_GEOM_TYPE)[IF(LHW_IF_PAIR_GEOM1)[q]], t2 = IF(LHW_IF_GEOM_TYPE)[IF(LHW_IF_PAIR_GEOM2)[q]];
     if (!stepping && t1 == G_BOX && t2 == G_BOX)
@@ -156,21 +160,15 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
                              "convex collider): mask the pair with contype / conaffinity or replace the geom by an enclosing capsule / box",
                              q, IF(LHW_IF_PAIR_GEOM1)[q], IF(LHW_IF_PAIR_GEOM2)[q], t1, t2);
   }
+  return LHW_OK;
+}
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return lhw_fail(LHW_ERR_NO_DEVICE, "no HIP device");
-  HumanoidEnv* h = new HumanoidEnv();
-  h->device = cfg->device;
-  h->p_dev = nullptr; h->m_dev = nullptr; h->iteration = 0;
-  // two envs per wave (W = 32) where the model fits half a wavefront; the stepping task needs the 16-contact layout throughout
-  h->fast = !stepping && np <= 32 && ng <= 16 && nj <= 32 && nb <= (stand ? 15 : 18) && !getenv("LHW_ONE_ENV_PER_WAVE");
-  HModel& m = h->m;
+int HumanoidCreate::pack_model(HModel& m) {
   memset(&m, 0, sizeof m);
   m.nq = nq; m.nv = nv; m.nu = nu; m.nbody = nb; m.njnt = nj; m.ngeom = ng; m.npair = np;
   m.iterations = mi[LHW_IH_ITERATIONS]; m.disableflags = mi[LHW_IH_DISABLEFLAGS];
   m.timestep = md[LHW_DH_TIMESTEP]; m.gravity[0] = md[LHW_DH_GRAVITY_X]; m.gravity[1] = md[LHW_DH_GRAVITY_Y]; m.gravity[2] = md[LHW_DH_GRAVITY_Z];
   m.tolerance = md[LHW_DH_TOLERANCE]; m.meaninertia = md[LHW_DH_MEANINERTIA]; m.totalmass = md[LHW_DH_TOTALMASS];
-  bool ok = true;
   // ---- derived structure
   std::vector<int> level(nb, 0), subend(nb, 0);
   std::vector<unsigned> bmask(nb, 0), pmask(nv, 0);
@@ -211,7 +209,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
     int* bi = &body_i[(size_t)BIS * b];
     bi[0] = parent[b]; bi[BI_LEVEL] = level[b]; bi[2] = -1; bi[3] = 0;
     bi[BI_ROOT] = rootid[b]; bi[BI_SUBEND] = subend[b]; bi[BI_DOFMASK] = (int)bmask[b]; bi[BI_JNTADR] = ja < 0 ? 0 : ja;
-    if (jn > 1) { humanoid_destroy(h); return lhw_fail(LHW_ERR_UNSUPPORTED, "bodies with more than one joint are not supported by the wave-per-env stepper"); }
+    if (jn > 1) return lhw_fail(LHW_ERR_UNSUPPORTED, "bodies with more than one joint are not supported by the wave-per-env stepper");
     if (jn == 1) {
       for (int a = 0; a < 3; a++) { k[BD_JAXIS + a] = DF(LHW_DF_JNT_AXIS)[3 * ja + a]; k[BD_JPOS + a] = DF(LHW_DF_JNT_POS)[3 * ja + a]; }
       for (int a = 0; a < 3; a++) {  // R_body * jnt_pos and R_body * jnt_axis (anchor / axis in the parent frame)
@@ -247,7 +245,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
     di[DI_ACT] = -1;
     for (int u = 0; u < nu; u++)
       if (jdof[IF(LHW_IF_ACTUATOR_TRNID)[u]] == d) {
-        if (di[DI_ACT] >= 0) { humanoid_destroy(h); return lhw_fail(LHW_ERR_UNSUPPORTED, "more than one actuator on dof %d", d); }
+        if (di[DI_ACT] >= 0) return lhw_fail(LHW_ERR_UNSUPPORTED, "more than one actuator on dof %d", d);
         di[DI_ACT] = u;
         k[DD_GEAR] = DF(LHW_DF_ACTUATOR_GEAR)[u];
       }
@@ -366,7 +364,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
   for (int d = 0; chain2 && d < 6; d++) chain2 = djnt[d] == djnt[0] && dparent[d] == d - 1;
   for (int c = 0; chain2 && c < 2; c++)
     for (int k = 0; chain2 && k < nch; k++) chain2 = dparent[6 + c * nch + k] == (k == 0 ? 5 : 6 + c * nch + k - 1);
-  if (!chain2) { humanoid_destroy(h); return lhw_fail(LHW_ERR_UNSUPPORTED, "the humanoid stepper needs a free root joint carrying two serial chains of (nv - 6) / 2 dofs each (the legs), dofs in that order"); }
+  if (!chain2) return lhw_fail(LHW_ERR_UNSUPPORTED, "the humanoid stepper needs a free root joint carrying two serial chains of (nv - 6) / 2 dofs each (the legs), dofs in that order");
   // bodies by owner dof (the last dof on their path from the root): a chain lane owns what moves with its dof, the root's
   // twelve lanes share what moves with the root
   std::vector<std::vector<int>> owned(32);
@@ -426,7 +424,7 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
       fix_i[b] = ow;
       okk = okk && rel(b, ow, &fix_d[(size_t)12 * b], &fix_d[(size_t)12 * b + 9]);
     }
-    if (!okk || body_i[(size_t)BIS * 1 + 2] != JT_FREE) { humanoid_destroy(h); return lhw_fail(LHW_ERR_UNSUPPORTED, "kinematic tables: the jointed bodies must form root -> chain A / chain B with only joint-less bodies in between"); }
+    if (!okk || body_i[(size_t)BIS * 1 + 2] != JT_FREE) return lhw_fail(LHW_ERR_UNSUPPORTED, "kinematic tables: the jointed bodies must form root -> chain A / chain B with only joint-less bodies in between");
   }
   size_t max_owned = 1;
   for (auto& o : owned) max_owned = std::max(max_owned, o.size());
@@ -442,9 +440,8 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
     m.npb = cnt <= 4 ? cnt : 0;
     for (int a = 0; a < 4; a++) m.pb_pair[a] = idx[a];
   }
-  auto BID = [&](int f) { const int b = cfg->task_iparams[f]; return (b >= 0 && b < nbm) ? bmap[b] : -1; };
   m.track_body[0] = BID(LHW_TI_ROOT_BODY); m.track_body[1] = BID(LHW_TI_RFOOT_BODY); m.track_body[2] = BID(LHW_TI_LFOOT_BODY);
-  if (max_owned > MAX_OWNED) { humanoid_destroy(h); return lhw_fail(LHW_ERR_UNSUPPORTED, "more than %d bodies move with one dof (%d): fold welded links first (Model.fuse_static)", MAX_OWNED, (int)max_owned); }
+  if (max_owned > MAX_OWNED) return lhw_fail(LHW_ERR_UNSUPPORTED, "more than %d bodies move with one dof (%d): fold welded links first (Model.fuse_static)", MAX_OWNED, (int)max_owned);
   // the tables are members of HModel (fixed capacities; the limits were checked above)
   std::copy(body_d.begin(), body_d.end(), m.body_d); std::copy(jnt_d.begin(), jnt_d.end(), m.jnt_d); std::copy(dof_d.begin(), dof_d.end(), m.dof_d);
   std::copy(geom_d.begin(), geom_d.end(), m.geom_d); std::copy(act_d.begin(), act_d.end(), m.act_d); std::copy(pair_d.begin(), pair_d.end(), m.pair_d);
@@ -454,6 +451,13 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
   std::copy(kin_i.begin(), kin_i.end(), m.kin_i); std::copy(fix_i.begin(), fix_i.end(), m.fix_i);
   for (int a = 0; a < 32 * MAX_OWNED; a++) m.own_tab[a] = -1;
   std::copy(own_tab.begin(), own_tab.end(), m.own_tab);
+  return LHW_OK;
+}
+
+bool HumanoidCreate::task_params(HumanoidEnv* h) {
+  HModel& m = h->m;
+  const int nb = m.nbody;
+  bool ok = true;
   HParams& p = h->p;
   memset(&p, 0, sizeof p);
   p.n_envs = cfg->n_envs; p.frame_skip = cfg->frame_skip; p.max_traj_len = cfg->max_traj_len; p.period = cfg->period;
@@ -489,7 +493,6 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
     p.env_params = 1;
   }
   if (cfg->init_noise > 0) p.init_noise = cfg->init_noise;   // any humanoid task (base_humanoid_env.py:260-263)
-  bool jvrc_perturb = false;
   if (walk && cfg->perturb_interval > 0) {   // apply_perturbation on a JVRC task: wrenches live in the per-env record (no LDS copy: see chain_dynamics)
     if (cfg->n_perturb_bodies < 1 || cfg->n_perturb_bodies > 2) ok = false;
     p.perturb_interval = cfg->perturb_interval; p.n_pbody = cfg->n_perturb_bodies;
@@ -508,9 +511,14 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
   for (int k = 0; k < nq; k++) p.nominal_qpos[k] = nominal[k];
   for (int k = 0; k < 35; k++) p.obs_noise[k] = obs_noise[k];
   ok = ok && (p.clock_lut = to_dev<double>(h, cfg->clock_lut, (walk || h1walk) ? (size_t)4 * cfg->period : 0));
+  return ok;
+}
+
+bool HumanoidCreate::alloc_state(HumanoidEnv* h) {
+  const HParams& p = h->p;
+  const int nb = h->m.nbody;
   const size_t N = cfg->n_envs;
-  h->st.prm = nullptr;
-  if (ok && (p.env_params || jvrc_perturb)) {
+  if (p.env_params || jvrc_perturb) {
     // per-env parameter records start from the model's defaults
     std::vector<double> one(PRM_D, 0.0), all((size_t)PRM_D * N);
     for (int d = 0; d < nv; d++) { one[P_DAMP + d] = DF(LHW_DF_DOF_DAMPING)[d]; one[P_FLOSS + d] = DF(LHW_DF_DOF_FRICTIONLOSS)[d]; }
@@ -519,67 +527,71 @@ int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std
       for (int a = 0; a < 3; a++) one[P_IPOS + 3 * b + a] = DF(LHW_DF_BODY_IPOS)[3 * bsrc[b] + a];
     }
     for (size_t n = 0; n < N; n++) std::copy(one.begin(), one.end(), all.begin() + n * PRM_D);
-    h->st.prm = const_cast<double*>(to_dev<double>(h, all.data(), all.size()).p);
-    ok = ok && h->st.prm != nullptr;
-    if (jvrc_perturb) p.xfrc_base = DevTab<double>{h->st.prm};
+    h->st.prm = h->mem.put(all.data(), all.size());
+    if (jvrc_perturb) h->p.xfrc_base = DevTab<double>{h->st.prm};
   }
-  h->st.ter = nullptr;
-  if (ok && stepping) {
+  if (stepping) {
     // before the first reset the boxes sit where the model file puts them (all at the pose of the first box) and the floor at 0
     std::vector<double> one(TER_D, 0.0), all((size_t)TER_D * N);
     const int g0 = p.box_geom0;
     for (int k = 0; k < MAX_SEQ; k++) {
-      const double* gd = &geom_d[(size_t)GDS * (g0 + k)];
+      const double* gd = &h->m.geom_d[(size_t)GDS * (g0 + k)];
       one[T_SEQ + 6 * k] = gd[GD_POS]; one[T_SEQ + 6 * k + 1] = gd[GD_POS + 1]; one[T_SEQ + 6 * k + 2] = gd[GD_POS + 2] + gd[GD_SIZE + 2];
       one[T_SEQ + 6 * k + 3] = 0; one[T_SEQ + 6 * k + 4] = 1; one[T_SEQ + 6 * k + 5] = 0;
     }
     for (size_t n = 0; n < N; n++) std::copy(one.begin(), one.end(), all.begin() + n * TER_D);
-    h->st.ter = const_cast<double*>(to_dev<double>(h, all.data(), all.size()).p);
-    ok = ok && h->st.ter != nullptr;
+    h->st.ter = h->mem.put(all.data(), all.size());
   }
-  h->st.bigd = nullptr; h->st.bigi = nullptr;
-  if (ok && stepping && !getenv("LHW_STEP_NO_BIG")) {   // many-contact workspace (newton_big): 51 KB per env
-    void *bdp = nullptr, *bip = nullptr;
-    ok = ok && lhw_malloc(&bdp, sizeof(double) * (size_t)BW_DOUBLES * N) == hipSuccess && lhw_malloc(&bip, sizeof(int) * (size_t)BW_INTS * N) == hipSuccess;
-    if (bdp) h->dev_allocs.push_back(bdp);
-    if (bip) h->dev_allocs.push_back(bip);
-    h->st.bigd = (double*)bdp; h->st.bigi = (int*)bip;
+  if (stepping && !getenv("LHW_STEP_NO_BIG")) {   // many-contact workspace (newton_big): 51 KB per env
+    h->st.bigd = h->mem.get<double>((size_t)BW_DOUBLES * N, LhwDevMem::RAW);
+    h->st.bigi = h->mem.get<int>((size_t)BW_INTS * N, LhwDevMem::RAW);
   }
-  void *rec = nullptr, *irec = nullptr, *eps = nullptr, *slow = nullptr;
-  ok = ok && lhw_malloc(&slow, N + 1) == hipSuccess && hipMemset(slow, 0, N + 1) == hipSuccess;
-  if (slow) h->dev_allocs.push_back(slow);
-  h->st.slow = (unsigned char*)slow;
+  h->st.slow = h->mem.get<unsigned char>(N + 1);
   // (one record more than envs: the reset template of the jvrc_walk kernels)
-  ok = ok && lhw_malloc(&rec, sizeof(double) * REC_D * (N + 1)) == hipSuccess && hipMemset(rec, 0, sizeof(double) * REC_D * (N + 1)) == hipSuccess &&
-       lhw_malloc(&irec, sizeof(int) * REC_I * (N + 1)) == hipSuccess && hipMemset(irec, 0, sizeof(int) * REC_I * (N + 1)) == hipSuccess &&
-       lhw_malloc(&eps, sizeof(double) * 8) == hipSuccess && hipMemset(eps, 0, sizeof(double) * 8) == hipSuccess;
-  if (rec) h->dev_allocs.push_back(rec);
-  if (irec) h->dev_allocs.push_back(irec);
-  if (eps) h->dev_allocs.push_back(eps);
-  h->st.rec = (double*)rec; h->st.irec = (int*)irec; h->st.ep_stats = (double*)eps; h->st.prof = nullptr; h->st.wave_cyc = nullptr; h->st.tin = nullptr; h->st.stin = nullptr;
-  if (!ok) { humanoid_destroy(h); return lhw_fail(LHW_ERR_HIP, "humanoid_create: device allocation failed or bad body ids"); }
-  *obs_dim = stepping ? 39 : (walk ? 37 : (h1walk ? 43 : 35)); *act_dim = nu; *n_terms = ((walk && !stepping) || h1walk) ? 10 : 6;
+  h->st.rec = h->mem.get<double>(REC_D * (N + 1));
+  h->st.irec = h->mem.get<int>(REC_I * (N + 1));
+  h->st.ep_stats = h->mem.get<double>(8);
+  return !h->mem.failed();
+}
+
+int HumanoidCreate::reset_template(HumanoidEnv* h) {
+  HParams& p = h->p;
+  const size_t N = cfg->n_envs;
   p.reset_template = -1;
   if (p.task == TASK_WALK && !(p.init_noise > 0) && !jvrc_perturb && !getenv("LHW_NO_RESET_TEMPLATE")) {   // (with init noise every reset has its own state: computed)
     // reset the template record (index N) once with the ordinary reset kernel; auto-resets copy its state from then on
-    if (!humanoid_upload_params(h)) { humanoid_destroy(h); return lhw_fail(LHW_ERR_HIP, "humanoid_create: parameter upload failed"); }
+    if (!humanoid_upload_params(h)) return lhw_fail(LHW_ERR_HIP, "humanoid_create: parameter upload failed");
     const HLaunch lz{(int)N, 1, 0, 0, 0};
     hipLaunchKernelGGL((humanoid_kernel<1, TASK_WALK, 64>), dim3(1), dim3(64), 0, 0, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, h->st, (const float*)nullptr, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, (double*)nullptr,
                        (double*)nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) { humanoid_destroy(h); return lhw_fail(LHW_ERR_HIP, "humanoid_create: reset template launch failed"); }
+    if (hipDeviceSynchronize() != hipSuccess) return lhw_fail(LHW_ERR_HIP, "humanoid_create: reset template launch failed");
     p.reset_template = (int)N;
   }
-  if (!humanoid_upload_params(h)) { humanoid_destroy(h); return lhw_fail(LHW_ERR_HIP, "humanoid_create: parameter upload failed"); }
-  *out = h;
   return LHW_OK;
 }
 
-void humanoid_destroy(HumanoidEnv* h) {
-  if (!h) return;
-  for (void* d : h->dev_allocs) (void)hipFree(d);
-  delete h;
+int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std::vector<double>& md, const LhwEnvConfig* cfg,
+                    int* obs_dim, int* act_dim, int* n_terms) {
+  HumanoidCreate c(mi, md, cfg);
+  if (const int rc = c.check()) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return lhw_fail(LHW_ERR_NO_DEVICE, "no HIP device");
+  std::unique_ptr<HumanoidEnv, void (*)(HumanoidEnv*)> guard(new HumanoidEnv(), humanoid_destroy);   // (zero-initialised)
+  HumanoidEnv* h = guard.get();
+  h->device = h->mem.device = cfg->device;
+  // two envs per wave (W = 32) where the model fits half a wavefront; the stepping task needs the 16-contact layout throughout
+  h->fast = !c.stepping && c.np <= 32 && c.ng <= 16 && c.nj <= 32 && c.nb <= (c.stand ? 15 : 18) && !getenv("LHW_ONE_ENV_PER_WAVE");
+  if (const int rc = c.pack_model(h->m)) return rc;
+  if (!c.task_params(h) || !c.alloc_state(h)) return lhw_fail(LHW_ERR_HIP, "humanoid_create: device allocation failed or bad body ids");
+  *obs_dim = c.stepping ? 39 : (c.walk ? 37 : (c.h1walk ? 43 : 35)); *act_dim = c.nu; *n_terms = ((c.walk && !c.stepping) || c.h1walk) ? 10 : 6;
+  if (const int rc = c.reset_template(h)) return rc;
+  if (!humanoid_upload_params(h)) return lhw_fail(LHW_ERR_HIP, "humanoid_create: parameter upload failed");
+  *out = guard.release();
+  return LHW_OK;
 }
+
+void humanoid_destroy(HumanoidEnv* h) { delete h; }   // (its LhwDevMem frees the device blocks)
 
 // (LHW_ONLY_WALK: development builds that compile the jvrc_walk kernels only -- a third of the compile time)
 #ifdef LHW_ONLY_WALK
@@ -646,66 +658,31 @@ int humanoid_occupancy() {
 // diagnostic: per-env duration of the last control-step launch (load balance across wavefronts)
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out) {
   const size_t N = h->p.n_envs;
-  if (!h->st.wave_cyc) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, (N + 1) * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(d, 0, (N + 1) * sizeof(long long));
-    h->dev_allocs.push_back(d);
-    h->st.wave_cyc = (long long*)d;
-    return 0;
-  }
+  if (!h->st.wave_cyc) return (h->st.wave_cyc = h->mem.get_lazy<long long>(N + 1)) ? 0 : -1;
   if (!out) return 0;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
   return hipMemcpy(out, h->st.wave_cyc, N * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
-// batched sim facade: per-env record of the task layer's inputs (LhwTaskInput); enable allocates, disable stops the export
-int humanoid_task_inputs(HumanoidEnv* h, int enable, double* out_host, double** out_dev) {
-  const size_t n = (size_t)h->p.n_envs * LHW_TASK_INPUT_DIM;
-  if (enable == 1 && !h->st.tin) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, n * sizeof(double)) != hipSuccess) return -1;
-    (void)hipMemset(d, 0, n * sizeof(double));
-    h->dev_allocs.push_back(d);
-    h->st.tin = (double*)d;
+// batched sim facade: per-env record of the task layer's inputs (LhwTaskInput) or, step_record, the stepping task's second record
+// (LhwStepTaskInput); enable allocates, disable stops the export
+int humanoid_task_inputs(HumanoidEnv* h, bool step_record, int enable, double* out_host, double** out_dev) {
+  double*& rec = step_record ? h->st.stin : h->st.tin;
+  const size_t n = (size_t)h->p.n_envs * (step_record ? LHW_STEP_TASK_INPUT_DIM : LHW_TASK_INPUT_DIM);
+  if (enable == 1 && !rec) {
+    if (!(rec = h->mem.get_lazy<double>(n))) return -1;
   } else if (enable == 0) {
-    h->st.tin = nullptr;   // (the buffer is released with the env)
+    rec = nullptr;   // (the buffer is released with the env)
   }
-  if (out_dev) *out_dev = h->st.tin;
+  if (out_dev) *out_dev = rec;
   if (out_host) {
-    if (!h->st.tin) return -2;
+    if (!rec) return -2;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(out_host, h->st.tin, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  }
-  return 0;
-}
-// the stepping task's second record (LhwStepTaskInput), the same way
-int humanoid_step_task_inputs(HumanoidEnv* h, int enable, double* out_host, double** out_dev) {
-  const size_t n = (size_t)h->p.n_envs * LHW_STEP_TASK_INPUT_DIM;
-  if (enable == 1 && !h->st.stin) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, n * sizeof(double)) != hipSuccess) return -1;
-    (void)hipMemset(d, 0, n * sizeof(double));
-    h->dev_allocs.push_back(d);
-    h->st.stin = (double*)d;
-  } else if (enable == 0) {
-    h->st.stin = nullptr;   // (the buffer is released with the env)
-  }
-  if (out_dev) *out_dev = h->st.stin;
-  if (out_host) {
-    if (!h->st.stin) return -2;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(out_host, h->st.stin, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(out_host, rec, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   }
   return 0;
 }
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16) {
-  if (enable && !h->st.prof) {
-    void* d = nullptr;
-    if (lhw_malloc(&d, 16 * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(d, 0, 16 * sizeof(long long));
-    h->dev_allocs.push_back(d);
-    h->st.prof = (long long*)d;
-  }
+  if (enable && !h->st.prof && !(h->st.prof = h->mem.get_lazy<long long>(16))) return -1;
   if (out16 && h->st.prof) {
     (void)hipDeviceSynchronize();
     (void)hipMemcpy(out16, h->st.prof, 16 * sizeof(long long), hipMemcpyDeviceToHost);

@@ -386,7 +386,7 @@ struct HumanoidEnv {
   HParams* p_dev;   // device copy the kernels read (passed by pointer: its fields need not live in SGPRs across the sub-steps)
   int iteration;
   HState st;
-  std::vector<void*> dev_allocs;
+  LhwDevMem mem;    // every device block of the env (p_dev, m_dev, the tables of p, the records of st, ro_queue)
   int device;
   bool fast;   // the model fits the two-envs-per-wave kernels (W = 32)
   unsigned* ro_queue = nullptr;   // job counter + per-group progress words of the resident rollout's queue mode (lhw_humanoid_rollout.hip)

@@ -315,7 +315,8 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) humanoid_rollout_kerne
 // ------------------------------------------------------------------------------------------------ host side
 // The stepping task's two instantiations live in a translation unit of their own, lhw_humanoid_rollout_step.hip (this file included with
 // LHW_ROLLOUT_STEP_TU defined): it is compiled with LLVM's iterative ILP scheduling strategy, which makes the one-env-per-wave kernels 3 % faster
-// (the two-envs-per-wave kernels keep the default strategy: profiles/r06_stepper_compiler_flags.txt) -- and the two halves compile in parallel.
+// (the two-envs-per-wave kernels are built with iterative-maxocc instead: _lib.EXTRA_FLAGS, profiles/r06_stepper_compiler_flags.txt) -- and the two
+// halves compile in parallel.
 void humanoid_rollout_launch_step(bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
 #ifdef LHW_ROLLOUT_STEP_TU
 void humanoid_rollout_launch_step(bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
@@ -376,12 +377,8 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
       slots = chip_slots;
     }
     if (!h->fast && chunk_env > 0 && n_groups > slots && T > chunk_env) {
-      if (!h->ro_queue) {   // two words per env: the ranges of concurrent launches (disjoint by contract) get disjoint pieces
-        void* d = nullptr;
-        if (lhw_malloc(&d, ((size_t)h->p.n_envs * 2 + 2) * sizeof(unsigned)) != hipSuccess) return -4;
-        h->dev_allocs.push_back(d);
-        h->ro_queue = (unsigned*)d;
-      }
+      // two words per env: the ranges of concurrent launches (disjoint by contract) get disjoint pieces
+      if (!h->ro_queue && !(h->ro_queue = h->mem.get_lazy<unsigned>((size_t)h->p.n_envs * 2 + 2, LhwDevMem::RAW))) return -4;
       ro.queue = h->ro_queue + 2 * (size_t)first;
       ro.chunk = chunk_env;
       if (hipMemsetAsync(ro.queue, 0, ((size_t)n_groups + 1) * sizeof(unsigned), s) != hipSuccess) return -4;

@@ -30,6 +30,55 @@ int lhw_fail(int code, const char* fmt, ...);
 hipError_t lhw_malloc(void** p, size_t n);
 template <class T> static inline hipError_t lhw_malloc(T** p, size_t n) { return lhw_malloc((void**)p, n); }
 
+// The device memory of one handle (LhwEnv, HumanoidEnv, LhwPpo, LhwRnn).  Every block is recorded the moment lhw_malloc returns it, so
+// no failure path can drop one, and the destructor frees them all on the handle's device.  A failed allocation or fill returns NULL and
+// latches failed(): the calls after it return NULL without trying, so a run of allocations needs ONE check at its end.
+// Lazy allocations on a live handle are transactions: m = mark() first, release_to(m) on failure -- the blocks obtained since are
+// freed, the latch is cleared, and the handle owns what it owned before.
+class LhwDevMem {
+ public:
+  int device = 0;
+  LhwDevMem() = default;
+  LhwDevMem(const LhwDevMem&) = delete;
+  LhwDevMem& operator=(const LhwDevMem&) = delete;
+  ~LhwDevMem() { release_to(0); }
+  enum Fill { RAW, ZERO };
+  // max(n, 1) elements of T, zero-filled unless RAW
+  template <class T> T* get(size_t n, Fill fill = ZERO) {
+    const size_t bytes = sizeof(T) * (n ? n : 1);
+    void* d = nullptr;
+    if (failed_ || lhw_malloc(&d, bytes) != hipSuccess || !d) { failed_ = true; return nullptr; }
+    blocks_.push_back(d);
+    if (fill == ZERO && hipMemset(d, 0, bytes) != hipSuccess) { failed_ = true; return nullptr; }
+    return (T*)d;
+  }
+  template <class T> void get(T** out, size_t n, Fill fill = ZERO) { *out = get<T>(n, fill); }
+  // a block of max(n, 1) elements holding a copy of host[0 .. n)
+  template <class T> T* put(const T* host, size_t n) {
+    T* d = get<T>(n, RAW);
+    if (d && n && hipMemcpy(d, host, sizeof(T) * n, hipMemcpyHostToDevice) != hipSuccess) { failed_ = true; return nullptr; }
+    return d;
+  }
+  // one block as a transaction of its own (diagnostic and export buffers enabled on a live handle)
+  template <class T> T* get_lazy(size_t n, Fill fill = ZERO) {
+    const size_t m = mark();
+    T* d = get<T>(n, fill);
+    if (!d) release_to(m);
+    return d;
+  }
+  bool failed() const { return failed_; }
+  size_t mark() const { return blocks_.size(); }
+  void release_to(size_t mark) {
+    if (blocks_.size() > mark) (void)hipSetDevice(device);
+    while (blocks_.size() > mark) { (void)hipFree(blocks_.back()); blocks_.pop_back(); }
+    failed_ = false;
+  }
+
+ private:
+  std::vector<void*> blocks_;
+  bool failed_ = false;
+};
+
 struct HumanoidEnv;
 int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std::vector<double>& md, const LhwEnvConfig* cfg,
                     int* obs_dim, int* act_dim, int* n_terms);
@@ -49,8 +98,8 @@ void humanoid_set_iteration(HumanoidEnv* h, int64_t it);
 int humanoid_occupancy();
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
-int humanoid_task_inputs(HumanoidEnv* h, int enable /* -1: leave */, double* out_host, double** out_dev);
-int humanoid_step_task_inputs(HumanoidEnv* h, int enable /* -1: leave */, double* out_host, double** out_dev);   // stepping task only
+// step_record: the stepping task's second record (LhwStepTaskInput) instead of LhwTaskInput; -1 HIP error, -2 not enabled
+int humanoid_task_inputs(HumanoidEnv* h, bool step_record, int enable /* -1: leave */, double* out_host, double** out_dev);
 int humanoid_actuator_state(HumanoidEnv* h, double* pos, double* vel, double* tq);
 int humanoid_step_record(HumanoidEnv* h, double* seq, double* floor_z, int32_t* istate);
 

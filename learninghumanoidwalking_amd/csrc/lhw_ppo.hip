@@ -21,6 +21,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/lhw.h"
@@ -677,20 +678,31 @@ struct HalfBufs {
   const _Float16* x; int ldx;          // gathered inputs [rows][ldx], ldx = Dp rounded up to 8 (16-byte rows), pad columns zero
   _Float16 *h1, *h2, *dh2, *dh1;       // [rows][H]
 };
-struct LhwPpo {
-  int device, D, A, H, learn_std, max_rows;  // max_rows: capacity of the minibatch workspace (rows per net)
-  _Float16 *xb_h = nullptr, *h1a_h = nullptr, *h2a_h = nullptr, *dh2a_h = nullptr, *dh1a_h = nullptr;   // --fp16 update: fp16 storage (actor: 2R rows)
-  _Float16 *h1c_h = nullptr, *h2c_h = nullptr, *dh2c_h = nullptr, *dh1c_h = nullptr;                    // critic: R rows
-  int ldxh = 0;
+// What the feed-forward and the recurrent learner share: shapes, hyper-parameters, the groups of the flat parameter vector
+// [actor | stds(A, padded to 4) | critic], the mirror tables, the loss / optimiser scratch -- and the owner of the handle's device memory.
+// learner_* below are the operations that read nothing else.
+struct LearnerCore {
+  int device = 0, D = 0, Dp = 0, A = 0, H = 0, learn_std = 0;   // Dp = pad4(D)
   float clip, ent_coeff, mirror_coeff, grad_clip, lr, adam_eps, beta1, beta2;
-  int use_mirror;
-  int infer_half = 0;     // rollout inference with fp16 operands (lhw_ppo_set_inference_dtype)
-  int update_half = 0;    // every GEMM of the update with fp16 operands (lhw_ppo_set_update_dtype)
-  MlpLayout la, lc;       // actor, critic
-  size_t off_actor, off_std, off_critic, n_params;  // flat theta: [actor | stds(A, padded to 4) | critic]
+  int use_mirror = 0;
+  size_t off_actor = 0, off_std = 0, off_critic = 0, n_critic = 0, n_params = 0;   // n_critic: parameters of the critic group
   // mirror tables (device): obs_src[Dp], obs_sign[Dp], act_src[A], act_sign[A]
   int *d_obs_src = nullptr, *d_act_src = nullptr;
   float *d_obs_sign = nullptr, *d_act_sign = nullptr;
+  float *stats = nullptr;       // [16] loss scalars; [8],[9] grad norm^2 actor/critic
+  float *stats_part = nullptr;  // per-block loss partials [blocks][NSTAT]
+  float *norm_part = nullptr;   // [2][SUMSQ_BLOCKS]
+  LhwDevMem mem;
+};
+
+struct LhwPpo : LearnerCore {
+  int max_rows;  // capacity of the minibatch workspace (rows per net)
+  _Float16 *xb_h = nullptr, *h1a_h = nullptr, *h2a_h = nullptr, *dh2a_h = nullptr, *dh1a_h = nullptr;   // --fp16 update: fp16 storage (actor: 2R rows)
+  _Float16 *h1c_h = nullptr, *h2c_h = nullptr, *dh2c_h = nullptr, *dh1c_h = nullptr;                    // critic: R rows
+  int ldxh = 0;
+  int infer_half = 0;     // rollout inference with fp16 operands (lhw_ppo_set_inference_dtype)
+  int update_half = 0;    // every GEMM of the update with fp16 operands (lhw_ppo_set_update_dtype)
+  MlpLayout la, lc;       // actor, critic
   // workspace
   float *xb = nullptr;   // [2R][Dp] gathered minibatch inputs (normal rows, then mirrored rows)
   float *h1a = nullptr, *h2a = nullptr, *ya = nullptr;      // actor activations [2R][H], [2R][H], [2R][Op]
@@ -698,7 +710,6 @@ struct LhwPpo {
   float *dya = nullptr, *dh2a = nullptr, *dh1a = nullptr;   // actor grads wrt activations
   float *dyc = nullptr, *dh2c = nullptr, *dh1c = nullptr;
   float *mb_act = nullptr, *mb_logp = nullptr, *mb_adv = nullptr, *mb_ret = nullptr;
-  float *stats = nullptr;  // [16] loss scalars; [8],[9] grad norm^2 actor/critic
   float *part = nullptr;       // split-K partial tiles [max slices][H*H]
   float *dstd = nullptr;       // per-row d loss / d std [R][Op]
   unsigned *bits_a = nullptr, *bits_c = nullptr;   // ReLU masks of h1 / h2 as bits, forward strip -> backward strip (2 layers x words(2R) / words(R)); NULL: max_rows % 64 != 0
@@ -707,11 +718,9 @@ struct LhwPpo {
                                             // forward workspace, so that concurrent calls (disjoint row ranges, different streams) do not share one
   float *wt_roll = nullptr;                 // ... and the pair made once per rollout by lhw_ppo_begin_rollout (read-only until end_rollout / apply)
   const float* roll_theta = nullptr;        // theta the wt_roll copies were made from (NULL: no rollout bracket open)
-  float *stats_part = nullptr; // per-block loss partials [blocks][NSTAT]
   const float* imit_target = nullptr;          // imitation term of the NEXT lhw_ppo_grad call (lhw_ppo_set_imitation)
   const unsigned char* imit_mask = nullptr;
   float imit_coeff = 0.f, imit_inv_count = 0.f;
-  float *norm_part = nullptr;  // [2][SUMSQ_BLOCKS]
   float *bwd_part = nullptr;   // split-K partials of the weight / bias gradients: actor (two passes), then critic
   int max_slices = 0;
   // the critic's forward / backward chain runs on its own stream beside the actor's (they share only the gathered inputs and
@@ -729,6 +738,14 @@ struct LhwPpo {
   const void* step_key[12] = {nullptr};
   int step_key_b = 0, step_key_half = 0;
   uint32_t step_key_gs = 0;
+  ~LhwPpo() {
+    (void)hipSetDevice(device);
+    if (step_exec) (void)hipGraphExecDestroy(step_exec);
+    if (step_graph) (void)hipGraphDestroy(step_graph);
+    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+  }
 };
 
 #define HIPCHK(x)                                                                                   \
@@ -1252,88 +1269,77 @@ extern "C" int lhw_debug_wgrad_skinny(int32_t H, int32_t Dp, int32_t O, int32_t 
   return LHW_OK;
 }
 
-extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
+// ---- the learner core: what lhw_ppo_* and lhw_rnn_* do the same way
+// the checks of a create call, before it touches the device (caps_ok: the handle's own capacities are positive)
+template <class Handle>
+static int learner_check(const LhwPpoConfig* c, Handle** out, bool caps_ok) {
   if (!c || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return lhw_fail(LHW_ERR_NO_DEVICE, "no HIP device visible: liblhw has no CPU fallback");
-  if (c->obs_dim <= 0 || c->act_dim <= 0 || c->act_dim > 32 || c->hidden <= 0 || c->hidden % 4 || c->max_rows <= 0)
-    return lhw_fail(LHW_ERR_ARG, "bad PPO dimensions (act_dim <= 32, hidden %% 4 == 0)");
+  if (c->obs_dim <= 0 || c->act_dim <= 0 || c->act_dim > 32 || c->hidden <= 0 || c->hidden % 4 || !caps_ok)
+    return lhw_fail(LHW_ERR_ARG, "bad PPO dimensions (act_dim <= 32, hidden %% 4 == 0, capacities > 0)");
   HIPCHK(hipSetDevice(c->device));
-  LhwPpo* p = new LhwPpo();
-  p->device = c->device; p->D = c->obs_dim; p->A = c->act_dim; p->H = c->hidden; p->learn_std = c->learn_std;
+  return LHW_OK;
+}
+static void learner_init(LearnerCore& k, const LhwPpoConfig* c, size_t n_actor, size_t n_critic) {
+  k.device = k.mem.device = c->device; k.D = c->obs_dim; k.Dp = pad4(k.D); k.A = c->act_dim; k.H = c->hidden; k.learn_std = c->learn_std;
+  k.clip = c->clip; k.ent_coeff = c->entropy_coeff; k.mirror_coeff = c->mirror_coeff; k.grad_clip = c->max_grad_norm;
+  k.lr = c->lr; k.adam_eps = c->eps; k.beta1 = 0.9f; k.beta2 = 0.999f;
+  k.use_mirror = c->mirror_obs_src != nullptr;
+  k.off_actor = 0; k.off_std = n_actor; k.off_critic = k.off_std + pad4(k.A); k.n_critic = n_critic; k.n_params = k.off_critic + n_critic;
+}
+// checks the mirror tables of the config and uploads them (no-op without); false: an index out of range (or a failed allocation: k.mem)
+static bool learner_mirror(LearnerCore& k, const LhwPpoConfig* c) {
+  if (!k.use_mirror) return true;
+  std::vector<int> osrc(k.Dp, 0), asrc(k.A, 0);
+  std::vector<float> osgn(k.Dp, 0.f), asgn(k.A, 0.f);
+  for (int j = 0; j < k.D; j++) { osrc[j] = c->mirror_obs_src[j]; osgn[j] = c->mirror_obs_sign[j]; if (osrc[j] < 0 || osrc[j] >= k.D) return false; }
+  for (int j = 0; j < k.A; j++) { asrc[j] = c->mirror_act_src[j]; asgn[j] = c->mirror_act_sign[j]; if (asrc[j] < 0 || asrc[j] >= k.A) return false; }
+  k.d_obs_src = k.mem.put(osrc.data(), osrc.size()); k.d_act_src = k.mem.put(asrc.data(), asrc.size());
+  k.d_obs_sign = k.mem.put(osgn.data(), osgn.size()); k.d_act_sign = k.mem.put(asgn.data(), asgn.size());
+  return !k.mem.failed();
+}
+
+extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
+  if (const int rc = learner_check(c, out, c && c->max_rows > 0)) return rc;
+  std::unique_ptr<LhwPpo> p(new LhwPpo());
   p->max_rows = c->max_rows;
-  p->clip = c->clip; p->ent_coeff = c->entropy_coeff; p->mirror_coeff = c->mirror_coeff; p->grad_clip = c->max_grad_norm;
-  p->lr = c->lr; p->adam_eps = c->eps; p->beta1 = 0.9f; p->beta2 = 0.999f;
-  p->use_mirror = c->mirror_obs_src != nullptr;
-  p->la = mlp_layout(p->D, p->H, p->A);
-  p->lc = mlp_layout(p->D, p->H, 1);
-  p->off_actor = 0;
-  p->off_std = p->la.total;
-  p->off_critic = p->off_std + pad4(p->A);
-  p->n_params = p->off_critic + p->lc.total;
+  p->la = mlp_layout(c->obs_dim, c->hidden, c->act_dim);
+  p->lc = mlp_layout(c->obs_dim, c->hidden, 1);
+  learner_init(*p, c, p->la.total, p->lc.total);
   const size_t R = p->max_rows, Dp = p->la.Dp, H = p->H, Op = p->la.Op;
-  auto alloc = [&](float** ptr, size_t n) { return lhw_malloc(ptr, sizeof(float) * n) == hipSuccess && hipMemset(*ptr, 0, sizeof(float) * n) == hipSuccess; };
-  bool ok = alloc(&p->xb, 2 * R * Dp) && alloc(&p->h1a, 2 * R * H) && alloc(&p->h2a, 2 * R * H) && alloc(&p->ya, 2 * R * Op) &&
-            alloc(&p->h1c, R * H) && alloc(&p->h2c, R * H) && alloc(&p->yc, R * 4) && alloc(&p->dya, 2 * R * Op) &&
-            alloc(&p->dh2a, 2 * R * H) && alloc(&p->dh1a, 2 * R * H) && alloc(&p->dyc, R * 4) && alloc(&p->dh2c, R * H) &&
-            alloc(&p->dh1c, R * H) && alloc(&p->mb_act, R * p->A) && alloc(&p->mb_logp, R) && alloc(&p->mb_adv, R) &&
-            alloc(&p->mb_ret, R) && alloc(&p->stats, 16) && alloc(&p->dstd, R * Op) && alloc(&p->stats_part, ((R + 255) / 256) * NSTAT) &&
-            alloc(&p->norm_part, 2 * SUMSQ_BLOCKS);
+  LhwDevMem& mem = p->mem;   // (zero-filled blocks; after a failure the calls below return NULL without trying: one check at the end)
+  mem.get(&p->xb, 2 * R * Dp); mem.get(&p->h1a, 2 * R * H); mem.get(&p->h2a, 2 * R * H); mem.get(&p->ya, 2 * R * Op);
+  mem.get(&p->h1c, R * H); mem.get(&p->h2c, R * H); mem.get(&p->yc, R * 4); mem.get(&p->dya, 2 * R * Op);
+  mem.get(&p->dh2a, 2 * R * H); mem.get(&p->dh1a, 2 * R * H); mem.get(&p->dyc, R * 4); mem.get(&p->dh2c, R * H);
+  mem.get(&p->dh1c, R * H); mem.get(&p->mb_act, R * p->A); mem.get(&p->mb_logp, R); mem.get(&p->mb_adv, R);
+  mem.get(&p->mb_ret, R); mem.get(&p->stats, 16); mem.get(&p->dstd, R * Op); mem.get(&p->stats_part, ((R + 255) / 256) * NSTAT);
+  mem.get(&p->norm_part, 2 * SUMSQ_BLOCKS);
   p->max_slices = (int)((R + 511) / 512);
-  ok = ok && alloc(&p->part, std::max<size_t>((size_t)p->max_slices * H * std::max<size_t>(H, Dp), (size_t)COLSUM_CHUNKS * H));
-  ok = ok && alloc(&p->bwd_part, bwd_parts_floats(p->la, R, 2) + bwd_parts_floats(p->lc, R, 1));
-  if (mlp_strip_supported(p->la.H, p->la.Dp, p->la.O, p->la.Op)) ok = ok && alloc(&p->wt_a, mlp_strip_wt_floats(p->la.Dp, p->la.Op));
-  if (mlp_strip_supported(p->lc.H, p->lc.Dp, p->lc.O, p->lc.Op)) ok = ok && alloc(&p->wt_c, mlp_strip_wt_floats(p->lc.Dp, p->lc.Op));
-  if (p->wt_a && p->wt_c && R % 64 == 0 && !(getenv("LHW_STRIP_BITS") && atoi(getenv("LHW_STRIP_BITS")) == 0))
-    ok = ok && alloc(reinterpret_cast<float**>(&p->bits_a), 4 * mlp_strip_bits_words(R)) && alloc(reinterpret_cast<float**>(&p->bits_c), 2 * mlp_strip_bits_words(R));
-  if (p->wt_a && p->wt_c) ok = ok && alloc(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op))) &&
-                               alloc(&p->wt_roll, mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op));
-  if (ok && p->use_mirror) {
-    std::vector<int> osrc(Dp, 0), asrc(p->A, 0);
-    std::vector<float> osgn(Dp, 0.f), asgn(p->A, 0.f);
-    for (int j = 0; j < p->D; j++) { osrc[j] = c->mirror_obs_src[j]; osgn[j] = c->mirror_obs_sign[j]; }
-    for (int j = 0; j < p->A; j++) { asrc[j] = c->mirror_act_src[j]; asgn[j] = c->mirror_act_sign[j]; }
-    for (int j = 0; j < p->D; j++) if (osrc[j] < 0 || osrc[j] >= p->D) { ok = false; }
-    for (int j = 0; j < p->A; j++) if (asrc[j] < 0 || asrc[j] >= p->A) { ok = false; }
-    ok = ok && lhw_malloc(&p->d_obs_src, sizeof(int) * Dp) == hipSuccess && lhw_malloc(&p->d_act_src, sizeof(int) * p->A) == hipSuccess &&
-         lhw_malloc(&p->d_obs_sign, sizeof(float) * Dp) == hipSuccess && lhw_malloc(&p->d_act_sign, sizeof(float) * p->A) == hipSuccess;
-    if (ok) {
-      (void)hipMemcpy(p->d_obs_src, osrc.data(), sizeof(int) * Dp, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_act_src, asrc.data(), sizeof(int) * p->A, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_obs_sign, osgn.data(), sizeof(float) * Dp, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_act_sign, asgn.data(), sizeof(float) * p->A, hipMemcpyHostToDevice);
-    }
+  mem.get(&p->part, std::max<size_t>((size_t)p->max_slices * H * std::max<size_t>(H, Dp), (size_t)COLSUM_CHUNKS * H));
+  mem.get(&p->bwd_part, bwd_parts_floats(p->la, R, 2) + bwd_parts_floats(p->lc, R, 1));
+  if (mlp_strip_supported(p->la.H, p->la.Dp, p->la.O, p->la.Op)) mem.get(&p->wt_a, mlp_strip_wt_floats(p->la.Dp, p->la.Op));
+  if (mlp_strip_supported(p->lc.H, p->lc.Dp, p->lc.O, p->lc.Op)) mem.get(&p->wt_c, mlp_strip_wt_floats(p->lc.Dp, p->lc.Op));
+  if (p->wt_a && p->wt_c && R % 64 == 0 && !(getenv("LHW_STRIP_BITS") && atoi(getenv("LHW_STRIP_BITS")) == 0)) {
+    mem.get(&p->bits_a, 4 * mlp_strip_bits_words(R)); mem.get(&p->bits_c, 2 * mlp_strip_bits_words(R));
   }
+  if (p->wt_a && p->wt_c) {
+    mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op)));
+    mem.get(&p->wt_roll, mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op));
+  }
+  bool ok = !mem.failed() && learner_mirror(*p, c);
   p->two_streams = !(getenv("LHW_PPO_TWO_STREAMS") && atoi(getenv("LHW_PPO_TWO_STREAMS")) == 0);
   ok = ok && hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess &&
        hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) == hipSuccess &&
        hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    lhw_ppo_destroy(p);
-    return lhw_fail(LHW_ERR_HIP, "PPO workspace allocation failed (max_rows=%d) or bad mirror table", c->max_rows);
-  }
-  *out = p;
+  if (!ok) return lhw_fail(LHW_ERR_HIP, "PPO workspace allocation failed (max_rows=%d) or bad mirror table", c->max_rows);
+  *out = p.release();
   return LHW_OK;
 }
 
 extern "C" int lhw_ppo_destroy(LhwPpo* p) {
-  if (!p) return LHW_OK;
-  (void)hipSetDevice(p->device);
-  float* bufs[] = {p->xb, p->h1a, p->h2a, p->ya, p->h1c, p->h2c, p->yc, p->dya, p->dh2a, p->dh1a, p->dyc, p->dh2c, p->dh1c,
-                   p->mb_act, p->mb_logp, p->mb_adv, p->mb_ret, p->stats, p->d_obs_sign, p->d_act_sign, p->part, p->dstd, p->stats_part,
-                   p->norm_part, p->bwd_part, p->wt_a, p->wt_c, p->wt_inf, p->wt_roll, reinterpret_cast<float*>(p->bits_a), reinterpret_cast<float*>(p->bits_c)};
-  for (float* b : bufs) if (b) (void)hipFree(b);
-  _Float16* hbufs[] = {p->xb_h, p->h1a_h, p->h2a_h, p->dh2a_h, p->dh1a_h, p->h1c_h, p->h2c_h, p->dh2c_h, p->dh1c_h};
-  for (_Float16* b : hbufs) if (b) (void)hipFree(b);
-  if (p->d_obs_src) (void)hipFree(p->d_obs_src);
-  if (p->d_act_src) (void)hipFree(p->d_act_src);
-  if (p->step_exec) (void)hipGraphExecDestroy(p->step_exec);
-  if (p->step_graph) (void)hipGraphDestroy(p->step_graph);
-  if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); }
-  if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-  if (p->ev_join) (void)hipEventDestroy(p->ev_join);
-  delete p;
+  delete p;   // (~LhwPpo: step graph, side stream, events; then the memory owner)
   return LHW_OK;
 }
 
@@ -1347,13 +1353,20 @@ extern "C" int lhw_ppo_set_update_dtype(LhwPpo* p, int fp16) {
   if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
   if (fp16 && !p->xb_h && !(getenv("LHW_FP16_STORAGE") && atoi(getenv("LHW_FP16_STORAGE")) == 0)) {
     // fp16 HBM storage of the minibatch activations (round 6; LHW_FP16_STORAGE=0: float32 storage rounded per GEMM, as through round 5)
+    // All or nothing: the handle's pointers are set once all nine blocks exist; a failure frees those obtained and leaves it as it was.
     HIPCHK(hipSetDevice(p->device));
-    const size_t R = p->max_rows, H = p->H;
-    p->ldxh = (p->la.Dp + 7) & ~7;
-    auto alloch = [&](_Float16** ptr, size_t n) { return lhw_malloc(ptr, sizeof(_Float16) * n) == hipSuccess && hipMemset(*ptr, 0, sizeof(_Float16) * n) == hipSuccess; };
-    const bool ok = alloch(&p->xb_h, 2 * R * p->ldxh) && alloch(&p->h1a_h, 2 * R * H) && alloch(&p->h2a_h, 2 * R * H) && alloch(&p->dh2a_h, 2 * R * H) &&
-                    alloch(&p->dh1a_h, 2 * R * H) && alloch(&p->h1c_h, R * H) && alloch(&p->h2c_h, R * H) && alloch(&p->dh2c_h, R * H) && alloch(&p->dh1c_h, R * H);
-    if (!ok) return lhw_fail(LHW_ERR_HIP, "fp16 workspace allocation failed (max_rows=%d)", p->max_rows);
+    const size_t R = p->max_rows, H = p->H, ldxh = (p->la.Dp + 7) & ~7;
+    _Float16** const dst[9] = {&p->xb_h, &p->h1a_h, &p->h2a_h, &p->dh2a_h, &p->dh1a_h, &p->h1c_h, &p->h2c_h, &p->dh2c_h, &p->dh1c_h};
+    const size_t n[9] = {2 * R * ldxh, 2 * R * H, 2 * R * H, 2 * R * H, 2 * R * H, R * H, R * H, R * H, R * H};
+    _Float16* got[9];
+    const size_t mark = p->mem.mark();
+    for (int i = 0; i < 9; i++) got[i] = p->mem.get<_Float16>(n[i]);
+    if (p->mem.failed()) {
+      p->mem.release_to(mark);
+      return lhw_fail(LHW_ERR_HIP, "fp16 workspace allocation failed (max_rows=%d)", p->max_rows);
+    }
+    for (int i = 0; i < 9; i++) *dst[i] = got[i];
+    p->ldxh = (int)ldxh;
   }
   p->update_half = fp16 ? 1 : 0;
   return LHW_OK;
@@ -1377,16 +1390,20 @@ extern "C" int lhw_ppo_layout(const LhwPpo* p, int64_t* out15) {
 }
 
 // normalised (and mirrored) copies of R raw observation rows: xn/xm [R][Dp]
-extern "C" int lhw_ppo_normalize(LhwPpo* p, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
-                                 float* xm, void* stream) {
-  if (!p || !obs || !xn || R <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
-  if (xm && !p->use_mirror) return lhw_fail(LHW_ERR_ARG, "mirror output requested but no mirror tables configured");
-  HIPCHK(hipSetDevice(p->device));
-  size_t n = (size_t)R * p->la.Dp;
-  hipLaunchKernelGGL(normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs, p->D, p->la.Dp, (size_t)R,
-                     obs_mean, obs_std, xn, xm, p->d_obs_src, p->d_obs_sign);
+static int learner_normalize(LearnerCore* k, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn, float* xm,
+                             void* stream) {
+  if (!k || !obs || !xn || R <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
+  if (xm && !k->use_mirror) return lhw_fail(LHW_ERR_ARG, "mirror output requested but no mirror tables configured");
+  HIPCHK(hipSetDevice(k->device));
+  size_t n = (size_t)R * k->Dp;
+  hipLaunchKernelGGL(normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs, k->D, k->Dp, (size_t)R,
+                     obs_mean, obs_std, xn, xm, k->d_obs_src, k->d_obs_sign);
   HIPCHK(hipGetLastError());
   return LHW_OK;
+}
+extern "C" int lhw_ppo_normalize(LhwPpo* p, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
+                                 float* xm, void* stream) {
+  return learner_normalize(p, obs, R, obs_mean, obs_std, xn, xm, stream);
 }
 
 // ws_row: first row of the forward workspace to use (concurrent calls on different streams must use disjoint row ranges)
@@ -1527,7 +1544,7 @@ extern "C" int lhw_moments(const float* x, int64_t n, double* out2_dev, void* st
   // process lifetime; one per device, so a process driving several GPUs never hands a kernel a foreign-device pointer)
   int dev = 0;
   if (device_of(x, &dev)) return LHW_ERR_HIP;
-  static double* scratch_of[LHW_MAX_DEVICES] = {nullptr};
+  static double* scratch_of[LHW_MAX_DEVICES] = {nullptr};   // (shared by the streams of a device: a behaviour question, left as it is)
   static std::mutex mu;
   double* scratch;
   {
@@ -1684,29 +1701,33 @@ static void clip_and_adam(float* theta, float* grad, float* adam_m, float* adam_
 
 // clip_grad_norm_ on the actor and critic parameter groups separately, then one Adam step each; zeroes grad.
 // grad_scale multiplies the gradient first (1/world_size after a sum all-reduce).  step is the 1-based Adam step count.
-extern "C" int lhw_ppo_apply(LhwPpo* p, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
-                             void* stream) {
-  if (!p || !theta || !grad || !adam_m || !adam_v || step <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
-  HIPCHK(hipSetDevice(p->device));
-  p->roll_theta = nullptr;   // theta changes: the weight copies of an open rollout bracket are stale
+static int learner_apply(LearnerCore* k, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale, void* stream) {
+  if (!k || !theta || !grad || !adam_m || !adam_v || step <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
+  HIPCHK(hipSetDevice(k->device));
   hipStream_t s = (hipStream_t)stream;
-  const size_t na = p->learn_std ? p->off_std + p->A : p->off_std;  // actor group (+ stds if they are parameters)
-  clip_and_adam(theta, grad, adam_m, adam_v, na, p->off_critic, p->lc.total, step, grad_scale, p->norm_part, p->stats, p->grad_clip,
-                p->lr, p->beta1, p->beta2, p->adam_eps, s);
-  if (!p->learn_std) HIPCHK(hipMemsetAsync(grad + p->off_std, 0, sizeof(float) * pad4(p->A), s));
+  const size_t na = k->learn_std ? k->off_std + k->A : k->off_std;  // actor group (+ stds if they are parameters)
+  clip_and_adam(theta, grad, adam_m, adam_v, na, k->off_critic, k->n_critic, step, grad_scale, k->norm_part, k->stats, k->grad_clip,
+                k->lr, k->beta1, k->beta2, k->adam_eps, s);
+  if (!k->learn_std) HIPCHK(hipMemsetAsync(grad + k->off_std, 0, sizeof(float) * pad4(k->A), s));
   HIPCHK(hipGetLastError());
   return LHW_OK;
 }
+extern "C" int lhw_ppo_apply(LhwPpo* p, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
+                             void* stream) {
+  if (p) p->roll_theta = nullptr;   // theta changes: the weight copies of an open rollout bracket are stale
+  return learner_apply(p, theta, grad, adam_m, adam_v, step, grad_scale, stream);
+}
 
 // Test hook: waits for the device, then copies the two squared gradient norms (actor group, critic group; after grad_scale, before
-// clipping) that the last lhw_ppo_apply / lhw_ppo_step wrote into stats[8..9] to the host
-extern "C" int lhw_ppo_debug_grad_sqnorms(LhwPpo* p, float* out2_host) {
-  if (!p || !out2_host) return lhw_fail(LHW_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(p->device));
+// clipping) that the last lhw_ppo_apply / lhw_ppo_step / lhw_rnn_apply wrote into stats[8..9] to the host
+static int learner_grad_sqnorms(LearnerCore* k, float* out2_host) {
+  if (!k || !out2_host) return lhw_fail(LHW_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(k->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out2_host, p->stats + 8, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out2_host, k->stats + 8, 2 * sizeof(float), hipMemcpyDeviceToHost));
   return LHW_OK;
 }
+extern "C" int lhw_ppo_debug_grad_sqnorms(LhwPpo* p, float* out2_host) { return learner_grad_sqnorms(p, out2_host); }
 
 // One optimiser step as ONE graph launch (round 6).  lhw_ppo_grad + lhw_ppo_apply are some forty launches on two streams, a dozen of
 // them small (gather, loss, ordered reductions, transposes, clip, Adam: 5-20 us of work each behind a launch gap of the same order);
@@ -1839,21 +1860,16 @@ struct SeqWs {  // activations of one network over a [T][Bt] minibatch (rows r =
   int Bt = 0;
 };
 
-struct LhwRnn {
-  int device, D, A, H, learn_std, T, Bmax, Nroll, use_mirror;
-  float clip, ent_coeff, mirror_coeff, grad_clip, lr, adam_eps, beta1, beta2;
+struct LhwRnn : LearnerCore {
+  int T, Bmax, Nroll;
   LstmLayout la, lc;
-  size_t off_actor, off_std, off_critic, n_params;
-  int *d_obs_src = nullptr, *d_act_src = nullptr;
-  float *d_obs_sign = nullptr, *d_act_sign = nullptr;
   // rollout: per network the concatenated step inputs hold the hidden state between calls, cells in rc
   float *rxh1[2] = {nullptr, nullptr}, *rxh2[2] = {nullptr, nullptr}, *rc1[2] = {nullptr, nullptr}, *rc2[2] = {nullptr, nullptr};
   float *rg = nullptr, *rh2 = nullptr, *ry = nullptr, *rcs = nullptr;  // step scratch: gates [N][4H], top hidden [N][H], read-out [N][Op], cells [N][H]
   SeqWs wa, wc;
   unsigned char* reset = nullptr;  // [T][Bmax]
   float *mb_act = nullptr, *mb_logp = nullptr, *mb_adv = nullptr, *mb_ret = nullptr, *dstd = nullptr;
-  float *stats = nullptr, *stats_part = nullptr, *norm_part = nullptr, *part = nullptr;
-  std::vector<void*> allocs;
+  float *part = nullptr;
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -2021,38 +2037,19 @@ static void lstm_seq_backward(const LstmLayout& L, const float* th, float* grad,
 }
 
 extern "C" int lhw_rnn_destroy(LhwRnn* p) {
-  if (!p) return LHW_OK;
-  (void)hipSetDevice(p->device);
-  for (void* a : p->allocs) (void)hipFree(a);
   delete p;
   return LHW_OK;
 }
 
 // seq_len / seq_cols: capacity of a BPTT minibatch (time steps x env columns); rollout_rows: envs stepped per call
 extern "C" int lhw_rnn_create(const LhwPpoConfig* c, int32_t seq_len, int32_t seq_cols, int32_t rollout_rows, LhwRnn** out) {
-  if (!c || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return lhw_fail(LHW_ERR_NO_DEVICE, "no HIP device visible: liblhw has no CPU fallback");
-  if (c->obs_dim <= 0 || c->act_dim <= 0 || c->act_dim > 32 || c->hidden <= 0 || c->hidden % 4 || seq_len <= 0 || seq_cols <= 0 || rollout_rows <= 0)
-    return lhw_fail(LHW_ERR_ARG, "bad recurrent PPO dimensions");
-  HIPCHK(hipSetDevice(c->device));
-  LhwRnn* p = new LhwRnn();
-  p->device = c->device; p->D = c->obs_dim; p->A = c->act_dim; p->H = c->hidden; p->learn_std = c->learn_std;
+  if (const int rc = learner_check(c, out, seq_len > 0 && seq_cols > 0 && rollout_rows > 0)) return rc;
+  std::unique_ptr<LhwRnn> p(new LhwRnn());
   p->T = seq_len; p->Bmax = seq_cols; p->Nroll = rollout_rows;
-  p->clip = c->clip; p->ent_coeff = c->entropy_coeff; p->mirror_coeff = c->mirror_coeff; p->grad_clip = c->max_grad_norm;
-  p->lr = c->lr; p->adam_eps = c->eps; p->beta1 = 0.9f; p->beta2 = 0.999f;
-  p->use_mirror = c->mirror_obs_src != nullptr;
-  p->la = lstm_layout(p->D, p->H, p->A);
-  p->lc = lstm_layout(p->D, p->H, 1);
-  p->off_actor = 0; p->off_std = p->la.total; p->off_critic = p->off_std + pad4(p->A); p->n_params = p->off_critic + p->lc.total;
-  bool ok = true;
-  auto alloc = [&](auto** ptr, size_t n) {
-    void* d = nullptr;
-    if (!ok || lhw_malloc(&d, sizeof(**ptr) * std::max<size_t>(n, 1)) != hipSuccess || hipMemset(d, 0, sizeof(**ptr) * std::max<size_t>(n, 1)) != hipSuccess) { ok = false; return; }
-    p->allocs.push_back(d);
-    *ptr = (decltype(*ptr))d;
-  };
+  p->la = lstm_layout(c->obs_dim, c->hidden, c->act_dim);
+  p->lc = lstm_layout(c->obs_dim, c->hidden, 1);
+  learner_init(*p, c, p->la.total, p->lc.total);
+  auto alloc = [&](auto** ptr, size_t n) { p->mem.get(ptr, n); };   // (zero-filled; one check of p->mem at the end)
   const size_t H = p->H, K1 = p->la.K1, Op = p->la.Op, N = p->Nroll;
   for (int n = 0; n < 2; n++) { alloc(&p->rxh1[n], N * K1); alloc(&p->rxh2[n], N * 2 * H); alloc(&p->rc1[n], N * H); alloc(&p->rc2[n], N * H); }
   alloc(&p->rg, N * 4 * H); alloc(&p->rh2, N * H); alloc(&p->ry, N * Op); alloc(&p->rcs, N * H);
@@ -2071,22 +2068,9 @@ extern "C" int lhw_rnn_create(const LhwPpoConfig* c, int32_t seq_len, int32_t se
   alloc(&p->stats, 16); alloc(&p->stats_part, ((Rm + 255) / 256) * NSTAT); alloc(&p->norm_part, 2 * SUMSQ_BLOCKS);
   const size_t max_slices = (2 * Rm + 2047) / 2048;
   alloc(&p->part, std::max<size_t>(max_slices * 4 * H * std::max<size_t>(K1, 2 * H), (size_t)COLSUM_CHUNKS * 4 * H));
-  if (ok && p->use_mirror) {
-    const size_t Dp = p->la.Dp;
-    std::vector<int> osrc(Dp, 0), asrc(p->A, 0);
-    std::vector<float> osgn(Dp, 0.f), asgn(p->A, 0.f);
-    for (int j = 0; j < p->D; j++) { osrc[j] = c->mirror_obs_src[j]; osgn[j] = c->mirror_obs_sign[j]; if (osrc[j] < 0 || osrc[j] >= p->D) ok = false; }
-    for (int j = 0; j < p->A; j++) { asrc[j] = c->mirror_act_src[j]; asgn[j] = c->mirror_act_sign[j]; if (asrc[j] < 0 || asrc[j] >= p->A) ok = false; }
-    alloc(&p->d_obs_src, Dp); alloc(&p->d_act_src, p->A); alloc(&p->d_obs_sign, Dp); alloc(&p->d_act_sign, p->A);
-    if (ok) {
-      (void)hipMemcpy(p->d_obs_src, osrc.data(), sizeof(int) * Dp, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_act_src, asrc.data(), sizeof(int) * p->A, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_obs_sign, osgn.data(), sizeof(float) * Dp, hipMemcpyHostToDevice);
-      (void)hipMemcpy(p->d_act_sign, asgn.data(), sizeof(float) * p->A, hipMemcpyHostToDevice);
-    }
-  }
-  if (!ok) { lhw_rnn_destroy(p); return lhw_fail(LHW_ERR_HIP, "recurrent PPO workspace allocation failed (T=%d cols=%d) or bad mirror table", seq_len, seq_cols); }
-  *out = p;
+  if (p->mem.failed() || !learner_mirror(*p, c))
+    return lhw_fail(LHW_ERR_HIP, "recurrent PPO workspace allocation failed (T=%d cols=%d) or bad mirror table", seq_len, seq_cols);
+  *out = p.release();
   return LHW_OK;
 }
 
@@ -2198,34 +2182,10 @@ extern "C" int lhw_rnn_grad(LhwRnn* p, const float* theta, float* grad, int32_t 
 
 extern "C" int lhw_rnn_apply(LhwRnn* p, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
                              void* stream) {
-  if (!p || !theta || !grad || !adam_m || !adam_v || step <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
-  HIPCHK(hipSetDevice(p->device));
-  hipStream_t s = (hipStream_t)stream;
-  const size_t na = p->learn_std ? p->off_std + p->A : p->off_std;
-  clip_and_adam(theta, grad, adam_m, adam_v, na, p->off_critic, p->lc.total, step, grad_scale, p->norm_part, p->stats, p->grad_clip,
-                p->lr, p->beta1, p->beta2, p->adam_eps, s);
-  if (!p->learn_std) HIPCHK(hipMemsetAsync(grad + p->off_std, 0, sizeof(float) * pad4(p->A), s));
-  HIPCHK(hipGetLastError());
-  return LHW_OK;
+  return learner_apply(p, theta, grad, adam_m, adam_v, step, grad_scale, stream);
 }
-
-// lhw_ppo_debug_grad_sqnorms on an LhwRnn handle (the norms of the last lhw_rnn_apply)
-extern "C" int lhw_rnn_debug_grad_sqnorms(LhwRnn* p, float* out2_host) {
-  if (!p || !out2_host) return lhw_fail(LHW_ERR_ARG, "null argument");
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out2_host, p->stats + 8, 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return LHW_OK;
-}
-
+extern "C" int lhw_rnn_debug_grad_sqnorms(LhwRnn* p, float* out2_host) { return learner_grad_sqnorms(p, out2_host); }
 extern "C" int lhw_rnn_normalize(LhwRnn* p, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
                                  float* xm, void* stream) {
-  if (!p || !obs || !xn || R <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
-  if (xm && !p->use_mirror) return lhw_fail(LHW_ERR_ARG, "mirror output requested but no mirror tables configured");
-  HIPCHK(hipSetDevice(p->device));
-  size_t n = (size_t)R * p->la.Dp;
-  hipLaunchKernelGGL(normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs, p->D, p->la.Dp, (size_t)R,
-                     obs_mean, obs_std, xn, xm, p->d_obs_src, p->d_obs_sign);
-  HIPCHK(hipGetLastError());
-  return LHW_OK;
+  return learner_normalize(p, obs, R, obs_mean, obs_std, xn, xm, stream);
 }
