@@ -287,6 +287,21 @@ int lhw_env_get_actuator_state(LhwEnv* env, double* pos_host, double* vel_host, 
 /* Episode statistics accumulated on device since the last call: sum of finished-episode returns,
  * sum of finished-episode lengths, number of finished episodes (host pointers, synchronous, resets them). */
 int lhw_env_pop_episode_stats(LhwEnv* env, double* ret_sum, double* len_sum, int64_t* count);
+/* Per-term episode statistics: the reward dictionary every env.step of the reference returns as `info` (robots/robot_base.py:88-96
+ * `rewards = self._task.calc_reward(...)`, `return obs, sum(rewards.values()), done, rewards`; envs/cartpole/cartpole_env.py:155-187),
+ * which a batched rollout otherwise drops.  While enabled, every control step -- launch per step, resident rollout, job queue, the
+ * in-wave re-run of an env with more than 8 contacts (counted once) -- adds the env's reward terms (float64, after the divergence guard)
+ * to per-env episode sums kept beside the env records; the step that ends an episode (LHW_DONE_*) moves those sums to the env's
+ * finished-episode sums and counts the episode as terminated (LHW_DONE_TERMINATED set) or truncated (LHW_DONE_TRUNCATED alone);
+ * lhw_env_reset zeroes the running sums of the envs it resets.  Each env's row has one writer (no atomics): what a pop returns does not
+ * depend on the order in which wavefronts finish.  No other output of a step changes by a bit.
+ * enable = 1 allocates [N][22] float64 (released with the env) and zeroes all sums; 0 stops the accumulation. */
+#define LHW_MAX_REWARD_TERMS 10 /* tasks/walking_task.py calc_reward: the longest dictionary of the implemented tasks */
+int lhw_env_enable_term_stats(LhwEnv* env, int enable);
+/* The sums over all envs since the last call, added up in env order (host pointers, any may be NULL; synchronous; resets the
+ * finished-episode sums only -- episodes still running keep their partial sums): term_sum [lhw_env_num_reward_terms] = sum over the finished episodes of the episode's sum of each
+ * term, in the reference's dict order (the order of rew_terms_dev); episodes = terminated + truncated.  LHW_ERR_ARG while disabled. */
+int lhw_env_pop_term_stats(LhwEnv* env, double* term_sum, int64_t* episodes, int64_t* terminated, int64_t* truncated);
 /* Fault counters since the last call (host pointers, synchronous, resets them): control steps in which contacts were
  * dropped because more than the compiled-in cap were active (16 per env; the stepping task, whose feet rest on the floor AND on
  * the terrain boxes under them, merges identical contacts and holds 192 found / 64 distinct ones per sub-step), and control steps in which an env's state became

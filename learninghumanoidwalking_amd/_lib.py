@@ -192,6 +192,8 @@ def declare(L):
     sig("lhw_env_get_state", [vp, vp, vp])
     sig("lhw_env_set_state", [vp, vp, vp])
     sig("lhw_env_pop_episode_stats", [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)])
+    sig("lhw_env_enable_term_stats", [vp, i32])
+    sig("lhw_env_pop_term_stats", [vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_set_iteration", [vp, i64])
     sig("lhw_env_pop_fault_stats", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_pop_rerun_count", [vp, ctypes.POINTER(i64)])

@@ -16,6 +16,21 @@ from .model import Model
 
 TASK_CARTPOLE, TASK_JVRC_WALK, TASK_H1_STAND, TASK_JVRC_STEP, TASK_H1_WALK = 0, 1, 2, 3, 4
 DONE_TERMINATED, DONE_TRUNCATED = 1, 2
+# The reward dictionary of each task in the reference's dict order -- the order of rew_terms and of lhw_env_pop_term_stats
+# (cartpole_env.py:182-187, walking_task.py:131-146, standing_task.py:99-106, stepping_task.py:109-122)
+_WALK_TERMS = ("foot_frc_score", "foot_vel_score", "root_accel", "height_error", "com_vel_error", "yaw_vel_error", "upper_body_reward",
+               "posture_error", "torque_penalty", "action_penalty")
+REWARD_TERMS = {TASK_CARTPOLE: ("upright", "center", "velocity", "action"), TASK_JVRC_WALK: _WALK_TERMS, TASK_H1_WALK: _WALK_TERMS,
+                TASK_H1_STAND: ("com_vel_error", "yaw_vel_error", "height", "upperbody", "joint_torque_reward", "posture"),
+                TASK_JVRC_STEP: ("foot_frc_score", "foot_vel_score", "orient_cost", "height_error", "step_reward", "upper_body_reward")}
+
+
+def term_stats_dict(term_sum, terminated: int, truncated: int, names) -> dict:
+    """dict(episodes, terminated, truncated, terms={name: mean over the finished episodes of the episode's sum of that term}) from the
+    sums lhw_env_pop_term_stats returns (NaN means while no episode has finished)."""
+    episodes = int(terminated) + int(truncated)
+    mean = [float(s) / episodes if episodes else float("nan") for s in term_sum]
+    return dict(episodes=episodes, terminated=int(terminated), truncated=int(truncated), terms=dict(zip(names, mean)))
 
 
 def _ptr(t):
@@ -239,6 +254,24 @@ class BatchedEnv:
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
         _lib.check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))
         return r.value, l.value, c.value
+
+    def enable_term_stats(self, enable: bool = True):
+        """Arm / disarm the per-term episode statistics (lhw_env_enable_term_stats): from the next control step on the kernels keep,
+        per env, the running episode's sum of every reward term -- the `info` dictionary of the reference's env.step
+        (robots/robot_base.py:88-96) -- and add it to global sums where the episode ends.  Arming zeroes all sums."""
+        _lib.check(self._L.lhw_env_enable_term_stats(self._h, int(bool(enable))))
+
+    def pop_term_sums(self):
+        """(term sums [n_terms] float64 over the episodes finished since the last call, terminated, truncated): the raw counters
+        (what data-parallel ranks add up); running episodes keep their partial sums."""
+        s = np.zeros(self.n_terms)
+        ep, te, tr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self._L.lhw_env_pop_term_stats(self._h, s.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr)))
+        return s, te.value, tr.value
+
+    def pop_term_stats(self) -> dict:
+        """dict(episodes, terminated, truncated, terms={name: mean episode sum}) of the episodes finished since the last call."""
+        return term_stats_dict(*self.pop_term_sums(), REWARD_TERMS[self.task])
 
     def phase_cycles(self, enable=True):
         """Per-phase shader-clock cycles of env 0 since the last call (diagnostic, wave-per-env stepper only)."""

@@ -49,7 +49,8 @@ struct LhwEnv {
   HumanoidEnv* hum = nullptr;
   double* stage_q = nullptr;  // device staging for get/set state
   double* stage_v = nullptr;
-  LhwDevMem mem;              // the cartpole state and the staging buffers (the humanoid stepper owns its own)
+  double* tstat = nullptr;    // the term-statistics block once enabled (kept across a disable; the kernels see it through set_term_stats_block)
+  LhwDevMem mem;              // the cartpole state, the staging buffers and the term statistics (the humanoid stepper owns the rest of its own)
 };
 
 extern "C" int lhw_version(void) { return 1; }
@@ -294,6 +295,47 @@ extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len
   if (ret_sum) *ret_sum = h[0];
   if (len_sum) *len_sum = h[1];
   if (count) *count = (int64_t)h[2];
+  return LHW_OK;
+}
+
+// the term-statistics block as this env's kernels see it (NULL while the export is off)
+static double* term_stats_block(LhwEnv* e) { return e->task == LHW_TASK_CARTPOLE ? e->cps.tstat : humanoid_term_stats(e->hum); }
+static int set_term_stats_block(LhwEnv* e, double* block) {
+  if (e->task == LHW_TASK_CARTPOLE) { e->cps.tstat = block; return LHW_OK; }
+  return humanoid_set_term_stats(e->hum, block) ? lhw_fail(LHW_ERR_HIP, "term statistics: parameter upload failed") : LHW_OK;
+}
+
+extern "C" int lhw_env_enable_term_stats(LhwEnv* e, int enable) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (!enable) return set_term_stats_block(e, nullptr);   // (the block is released with the env)
+  const size_t n = (size_t)e->n_envs * (LHW_MAX_REWARD_TERMS + LHW_TS_FIN_STRIDE);
+  if (!e->tstat && !(e->tstat = e->mem.get_lazy<double>(n))) return lhw_fail(LHW_ERR_HIP, "term statistics allocation failed (n_envs=%d)", e->n_envs);
+  HIPCHK(hipMemset(e->tstat, 0, sizeof(double) * n));
+  return set_term_stats_block(e, e->tstat);
+}
+
+extern "C" int lhw_env_pop_term_stats(LhwEnv* e, double* term_sum, int64_t* episodes, int64_t* terminated, int64_t* truncated) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  HIPCHK(hipSetDevice(e->device));
+  double* dev = term_stats_block(e);
+  if (!dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_pop_term_stats: call lhw_env_enable_term_stats(env, 1) first");
+  // the finished-episode rows come to the host (96 bytes per env), are added up in env order, and are cleared on the device; the running
+  // sums are not touched
+  double* fin = dev + (size_t)e->n_envs * LHW_MAX_REWARD_TERMS;
+  std::vector<double> rows((size_t)e->n_envs * LHW_TS_FIN_STRIDE);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(rows.data(), fin, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(fin, 0, sizeof(double) * rows.size()));
+  double sum[LHW_TS_FIN_STRIDE] = {0};
+  for (int n = 0; n < e->n_envs; n++)
+    for (int k = 0; k < LHW_TS_FIN_STRIDE; k++) sum[k] += rows[(size_t)n * LHW_TS_FIN_STRIDE + k];
+  const int64_t te = (int64_t)sum[LHW_TS_TERMINATED], tr = (int64_t)sum[LHW_TS_TRUNCATED];
+  for (int k = 0; term_sum && k < e->n_terms; k++) term_sum[k] = sum[k];
+  if (terminated) *terminated = te;
+  if (truncated) *truncated = tr;
+  if (episodes) *episodes = te + tr;
   return LHW_OK;
 }
 

@@ -26,6 +26,8 @@ struct CartpoleState {
   int32_t* traj_len;
   uint32_t* reset_count;
   double* ep_stats;  // [3]: sum of returns, sum of lengths, episode count
+  double* tstat;     // optional per-term episode statistics (lhw_env_enable_term_stats; layout: lhw_internal.h LHW_TS_*), NULL = off.  A plain
+                     // kernel argument: this lane-per-env kernel has registers to spare (the wave-per-env steppers read theirs from HParams)
 };
 
 void cartpole_launch_reset(const CartpoleParams& p, const CartpoleState& st, const uint8_t* mask, float* obs, hipStream_t s);

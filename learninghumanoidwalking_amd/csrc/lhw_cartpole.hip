@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lhw_cartpole.h"
+#include "lhw_internal.h"
 #include "lhw_rng.h"
 
 #define CP_MINVAL 1e-15
@@ -201,6 +202,8 @@ __global__ void __launch_bounds__(256) cartpole_reset_kernel(CartpoleParams p, C
   st.d[4 * N + n] = ws[0]; st.d[5 * N + n] = ws[1]; st.d[6 * N + n] = al; st.d[7 * N + n] = av;
   st.d[8 * N + n] = 0.0; // episode return
   st.traj_len[n] = 0;
+  if (st.tstat)
+    for (int k = 0; k < 4; k++) st.tstat[(size_t)n * LHW_MAX_REWARD_TERMS + k] = 0.0;
   if (obs) cp_obs(q, v, obs + 5 * n);
 }
 
@@ -252,7 +255,19 @@ __global__ void __launch_bounds__(256) cartpole_step_kernel(CartpoleParams p, Ca
   if (term_obs)
     for (int k = 0; k < 5; k++) term_obs[5 * n + k] = o[k];
 
-  if (p.max_traj_len > 0 && (terminated || truncated)) {
+  const bool ended = p.max_traj_len > 0 && (terminated || truncated);
+  if (st.tstat) {   // per-term episode statistics: running sums per env, moved to the env's finished-episode sums by the step that ends the episode
+    double* run = st.tstat + (size_t)n * LHW_MAX_REWARD_TERMS;
+    double* fin = st.tstat + (size_t)N * LHW_MAX_REWARD_TERMS + (size_t)n * LHW_TS_FIN_STRIDE;
+    const double terms[4] = {up, center, velr, actr};
+    for (int k = 0; k < 4; k++) {
+      double s = run[k] + terms[k];
+      if (ended) { fin[k] += s; s = 0.0; }
+      run[k] = s;
+    }
+    if (ended) fin[terminated ? LHW_TS_TERMINATED : LHW_TS_TRUNCATED] += 1.0;
+  }
+  if (ended) {
     atomicAdd(&st.ep_stats[0], ep_ret);
     atomicAdd(&st.ep_stats[1], (double)traj_len);
     atomicAdd(&st.ep_stats[2], 1.0);

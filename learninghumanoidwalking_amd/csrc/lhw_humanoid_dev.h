@@ -267,6 +267,10 @@ struct HParams {
   gtab_d clock_lut;
   gtab_d xfrc_base;                     // JVRC tasks with perturbations: the per-env parameter records [N][PRM_D] (chain_dynamics reads P_XFRC of its env); else NULL
   double kp[NU], kd[NU], nominal_qpos[NQ], action_offset[NU], neutral_pose[NU], obs_noise[36];   // (members, like the model tables)
+  double* tstat;                        // per-term episode statistics (lhw_env_enable_term_stats; layout: lhw_internal.h LHW_TS_*): the running episode's sum
+                                        // of every reward term per env, then the sums over each env's finished episodes -- a side array, not part of the
+                                        // env record.  Read by the STATS instantiations of the kernels only (launched while it is non-NULL); last member,
+                                        // so every other field sits where it sat
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const HModel LHW_GLOBAL_AS& HModelRef;
@@ -3374,7 +3378,9 @@ __device__ __forceinline__ bool store_record(HModelRef m, const HLaunch& lz, con
 // One control step (MODE 0), reset (1), set_state (2) or get_state (3) of env `env` by the group of W lanes that calls it
 // (`lane` = lane within the group, S = the group's LDS working set).  Returns true iff the env exceeded the contact capacity
 // of the two-envs-per-wave layout before anything of this control step was written: the caller repeats the step with W = 64.
-template <int MODE, int TASK, int W>
+// STATS: the instantiation that also keeps the per-term episode statistics (HParams::tstat).  A template parameter and not a run-time
+// branch: the kernels launched while the statistics are off are, instruction for instruction, the kernels without the feature.
+template <int MODE, int TASK, int W, bool STATS = false>
 __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, typename LayoutOf<TASK, W>::type* SG0,
                                              typename LayoutOf<TASK, W>::type& S, const int env,
                                              const int lane, const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ term_obs,
@@ -3821,6 +3827,25 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
         }
         if (lane < m.nu) { rec[R_PREVPRED + lane] = prevpred; rec[R_PREVACT + lane] = prevact; rec[R_PREVTQ + lane] = prevtq; }
         CTX_STORE();
+        if constexpr (STATS) {
+          double* const tstat = p.tstat;
+          // per-term episode statistics (lhw_env_enable_term_stats): this control step's terms -- zeroed above if the state diverged --
+          // join the env's running sums; the step that ends the episode (do_reset) moves them to the env's finished-episode sums and
+          // counts how it ended.  Lane 0 of the env's group is the only writer of the env's two rows: no atomics.  Reached once per
+          // control step, where it is committed (an env that overflows the two-envs-per-wave layout leaves before this epilogue and
+          // is repeated).  The pointer is read here and the rows are addressed from an opaque copy of the env index, as the
+          // perturbation block's above: nothing of it is live in the sub-steps.
+          if (lane == 0) {
+            double* run = tstat + (size_t)opaque_int(env) * LHW_MAX_REWARD_TERMS;
+            double* fin = tstat + (size_t)p.n_envs * LHW_MAX_REWARD_TERMS + (size_t)opaque_int(env) * LHW_TS_FIN_STRIDE;
+            for (int k = 0; k < NT; k++) {
+              double v = run[k] + terms[k];
+              if (do_reset) { fin[k] += v; v = 0.0; }
+              run[k] = v;
+            }
+            if (do_reset) fin[terminated ? LHW_TS_TERMINATED : LHW_TS_TRUNCATED] += 1.0;
+          }
+        }
         committed = true;
         stage = do_reset ? ST_RESET : ST_END;
       }
@@ -3910,6 +3935,9 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
         traj_len = 0;
         ep_ret = 0;
         prevpred = 0;
+        if constexpr (MODE == 1 && STATS) {   // lhw_env_reset abandons the running episode: its term sums go the way of ep_ret (an auto-reset zeroed them already)
+          if (lane < LHW_MAX_REWARD_TERMS) p.tstat[(size_t)opaque_int(env) * LHW_MAX_REWARD_TERMS + lane] = 0.0;
+        }
         SYNC();
         if (TASK == TASK_WALK) write_obs(m, p, S, lane, phase, mode, mode_ref, S.obsf());
         else if (TASK == TASK_STEP) write_obs_step(m, p, S, lane, phase, goal, S.obsf());

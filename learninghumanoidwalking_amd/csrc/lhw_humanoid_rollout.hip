@@ -196,7 +196,7 @@ __device__ __forceinline__ void policy_step(const LhwRolloutPolicy& q, float* sc
 }
 
 // Control steps [t0, t1) of env group `grp` of the range (the G envs one wave advances together).
-template <int TASK, int W>
+template <int TASK, int W, bool STATS>
 __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, const HRollout& ro, unsigned char* SGraw, int grp,
                                               int t0, int t1) {
   using L = typename LayoutOf<TASK, W>::type;
@@ -244,7 +244,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     HLaunch lzt = lz;
     lzt.tin_off = (long long)t * ro.tin_step;   // (the batched sim facade of EVERY control step, for reward-only task plug-ins: lhw_env_rollout_task_inputs)
     if (g < nlive)
-      ovf = control_step<0, TASK, W>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+      ovf = control_step<0, TASK, W, STATS>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
 #ifndef LHW_RO_NO_RERUN   // (analysis builds: without the in-wave re-run, to see what its code costs the hot path -- nothing measurable)
     if constexpr (W == 32) {
       GROUP_SYNC(64);
@@ -257,7 +257,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
           if ((ob >> (32 * gg)) & 1ull) {
             SYNC();
             // (as a call -- it is rare -- the kernel spills 12 fewer VGPRs and 200 fewer SGPRs and is 9 % SLOWER: profiles/r05_calls_and_scratch.txt)
-            control_step<0, TASK, 64>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+            control_step<0, TASK, 64, STATS>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
           }
       }
     }
@@ -278,58 +278,68 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 // control steps (control_step reads the HBM record and writes it back), so which wave runs a job does not matter to the bits.
 // A separate instantiation: wrapped into the job loop, the two-envs-per-wave kernels spill 25 more VGPRs and lose 2.8 % (round 5,
 // same box, jvrc_walk @ 4096), and at 8192 envs their waves are within +-2 % of each other anyway (queue +0.1 %).
-template <int TASK, int W, bool QUEUE>
-__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) humanoid_rollout_kernel(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, HRollout ro) {
-  using L = typename LayoutOf<TASK, W>::type;
-  using L1 = typename LayoutOf<TASK, 64>::type;
-  constexpr int G = 64 / W;
-  constexpr size_t LDS_BYTES = sizeof(L) * G > sizeof(L1) ? sizeof(L) * G : sizeof(L1);
-  static_assert(W == 64 || sizeof(L1) <= sizeof(L) * G, "the one-env-per-wave layout must fit the wave's two-env allocation (8 workgroups per CU)");
-  static_assert(L::USIZE_ * 2 - 48 >= PolicyLds<G>::FLOATS, "the policy step's activations must fit the stage region in front of the observation staging");
-  __shared__ __attribute__((aligned(16))) unsigned char SGraw[LDS_BYTES];
-  LHW_LDS_POISON(SGraw);
-  HParamsRef p = *(const HParams LHW_GLOBAL_AS*)pp;
-  HModelRef m = *(const HModel LHW_GLOBAL_AS*)mp;
-  const int n_groups = (lz.env_count + G - 1) / G;
-  if constexpr (!QUEUE) {
-    if ((int)blockIdx.x >= n_groups) return;
-    rollout_steps<TASK, W>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);
-  } else {
-    const int n_chunks = (ro.T + ro.chunk - 1) / ro.chunk;
-    for (;;) {
-      unsigned j = 0;
-      if (fresh_wave_lane() == 0) j = atomicAdd(ro.queue, 1u);
-      j = (unsigned)__builtin_amdgcn_readlane((int)j, 0);
-      if (j >= (unsigned)n_groups * (unsigned)n_chunks) break;
-      const int c = (int)(j / (unsigned)n_groups), grp = (int)(j % (unsigned)n_groups);
-      const int t0 = c * ro.chunk, t1 = min(ro.T, t0 + ro.chunk);
-      // the group's previous chunk was popped n_groups - 1 jobs ago by a wave that is running: it ends without waiting for anyone
-      while (lhw_load_agent(ro.queue + 1 + grp) < (unsigned)c) __builtin_amdgcn_s_sleep(32);
-      rollout_steps<TASK, W>(m, p, lz, st, ro, SGraw, grp, t0, t1);
-      __threadfence();   // the group's records, observations and flags of this chunk, before the chunk counts as done
-      if (fresh_wave_lane() == 0) lhw_store_agent(ro.queue + 1 + grp, (unsigned)(c + 1));
-    }
-  }
+// Two kernel families from one text: humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
+// statistics (control_step<.., STATS>) and is launched instead while lhw_env_enable_term_stats is in force.  Generated by a macro and not
+// through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
+#define DEFINE_ROLLOUT_KERNEL(NAME, STATS) \
+template <int TASK, int W, bool QUEUE>                                                                                                                              \
+__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, HRollout ro) { \
+  using L = typename LayoutOf<TASK, W>::type;                                                                                                                       \
+  using L1 = typename LayoutOf<TASK, 64>::type;                                                                                                                     \
+  constexpr int G = 64 / W;                                                                                                                                         \
+  constexpr size_t LDS_BYTES = sizeof(L) * G > sizeof(L1) ? sizeof(L) * G : sizeof(L1);                                                                             \
+  static_assert(W == 64 || sizeof(L1) <= sizeof(L) * G, "the one-env-per-wave layout must fit the wave's two-env allocation (8 workgroups per CU)");                \
+  static_assert(L::USIZE_ * 2 - 48 >= PolicyLds<G>::FLOATS, "the policy step's activations must fit the stage region in front of the observation staging");         \
+  __shared__ __attribute__((aligned(16))) unsigned char SGraw[LDS_BYTES];                                                                                           \
+  LHW_LDS_POISON(SGraw);                                                                                                                                            \
+  HParamsRef p = *(const HParams LHW_GLOBAL_AS*)pp;                                                                                                                 \
+  HModelRef m = *(const HModel LHW_GLOBAL_AS*)mp;                                                                                                                   \
+  const int n_groups = (lz.env_count + G - 1) / G;                                                                                                                  \
+  if constexpr (!QUEUE) {                                                                                                                                           \
+    if ((int)blockIdx.x >= n_groups) return;                                                                                                                        \
+    rollout_steps<TASK, W, STATS>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
+  } else {                                                                                                                                                          \
+    const int n_chunks = (ro.T + ro.chunk - 1) / ro.chunk;                                                                                                          \
+    for (;;) {                                                                                                                                                      \
+      unsigned j = 0;                                                                                                                                               \
+      if (fresh_wave_lane() == 0) j = atomicAdd(ro.queue, 1u);                                                                                                      \
+      j = (unsigned)__builtin_amdgcn_readlane((int)j, 0);                                                                                                           \
+      if (j >= (unsigned)n_groups * (unsigned)n_chunks) break;                                                                                                      \
+      const int c = (int)(j / (unsigned)n_groups), grp = (int)(j % (unsigned)n_groups);                                                                             \
+      const int t0 = c * ro.chunk, t1 = min(ro.T, t0 + ro.chunk);                                                                                                   \
+      /* the group's previous chunk was popped n_groups - 1 jobs ago by a wave that is running: it ends without waiting for anyone */                               \
+      while (lhw_load_agent(ro.queue + 1 + grp) < (unsigned)c) __builtin_amdgcn_s_sleep(32);                                                                        \
+      rollout_steps<TASK, W, STATS>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
+      __threadfence();   /* the group's records, observations and flags of this chunk, before the chunk counts as done */                                           \
+      if (fresh_wave_lane() == 0) lhw_store_agent(ro.queue + 1 + grp, (unsigned)(c + 1));                                                                           \
+    }                                                                                                                                                               \
+  }                                                                                                                                                                 \
 }
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true)
 
 // ------------------------------------------------------------------------------------------------ host side
 // The stepping task's two instantiations live in a translation unit of their own, lhw_humanoid_rollout_step.hip (this file included with
 // LHW_ROLLOUT_STEP_TU defined): it is compiled with LLVM's iterative ILP scheduling strategy, which makes the one-env-per-wave kernels 3 % faster
 // (the two-envs-per-wave kernels are built with iterative-maxocc instead: _lib.EXTRA_FLAGS, profiles/r06_stepper_compiler_flags.txt) -- and the two
 // halves compile in parallel.
-void humanoid_rollout_launch_step(bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
 #ifdef LHW_ROLLOUT_STEP_TU
-void humanoid_rollout_launch_step(bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
-  if (queued) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  else hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
+  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
+  if (!stats) {
+    if (queued) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+    else hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  else hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
 }
 #else
 #ifdef LHW_ONLY_WALK
-#define ROLLOUT_OTHER_TASKS(WIDTH)
+#define ROLLOUT_OTHER_TASKS(KERNEL, WIDTH)
 #else
-#define ROLLOUT_OTHER_TASKS(WIDTH)                                                                                                                              \
-  else if (h->p.task == TASK_H1WALK) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_H1WALK, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro); \
-  else hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STAND, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+#define ROLLOUT_OTHER_TASKS(KERNEL, WIDTH)                                                                                                                      \
+  else if (h->p.task == TASK_H1WALK) hipLaunchKernelGGL((KERNEL<TASK_H1WALK, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro); \
+  else hipLaunchKernelGGL((KERNEL<TASK_STAND, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
 #endif
 
 int humanoid_last_rollout_queued(const HumanoidEnv* h) { return h->last_rollout_queued; }
@@ -387,12 +397,17 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
   }
   const dim3 grid(grid_n);
   h->last_rollout_queued = ro.queue != nullptr;
-  if (h->fast) {
+  const bool stats = h->p.tstat != nullptr;   // per-term episode statistics armed: the kernels that keep them
+  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
+  if (h->fast && !stats) {
     if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(32)
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_kernel, 32)
+  } else if (h->fast) {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_stats_kernel, 32)
   } else {
 #ifndef LHW_ONLY_WALK
-    humanoid_rollout_launch_step(ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    humanoid_rollout_launch_step(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
 #endif
   }
   return 0;

@@ -79,6 +79,13 @@ class LhwDevMem {
   bool failed_ = false;
 };
 
+// The block of the per-term episode statistics (lhw_env_enable_term_stats), two arrays in one allocation: [N][LHW_MAX_REWARD_TERMS] sums
+// of each env's RUNNING episode, then [N][LHW_TS_FIN_STRIDE] per env the sums over its FINISHED episodes since the last pop [k] and how
+// many of those terminated / were truncated.  Only the env's own lane writes its rows, and lhw_env_pop_term_stats adds the finished rows
+// up on the host in env order and clears that array: no atomics, and the popped sums do not depend on which wavefront finished first
+// (two runs of the same rollout give the same bits).
+enum { LHW_TS_TERMINATED = LHW_MAX_REWARD_TERMS, LHW_TS_TRUNCATED = LHW_MAX_REWARD_TERMS + 1, LHW_TS_FIN_STRIDE = LHW_MAX_REWARD_TERMS + 2 };
+
 struct HumanoidEnv;
 int humanoid_create(HumanoidEnv** out, const std::vector<int32_t>& mi, const std::vector<double>& md, const LhwEnvConfig* cfg,
                     int* obs_dim, int* act_dim, int* n_terms);
@@ -94,6 +101,8 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
 void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t s);
 void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, hipStream_t s);
 double* humanoid_ep_stats(HumanoidEnv* h);
+double* humanoid_term_stats(HumanoidEnv* h);                   // the term-statistics block the kernels write (NULL = off)
+int humanoid_set_term_stats(HumanoidEnv* h, double* block);    // hands it to the kernels (NULL stops them); -1 HIP error
 void humanoid_set_iteration(HumanoidEnv* h, int64_t it);
 int humanoid_occupancy();
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);

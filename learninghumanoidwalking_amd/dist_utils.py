@@ -119,3 +119,15 @@ def global_episode_stats(ret_sum: float, len_sum: float, count: float, device=No
     d.all_reduce(pack)
     r, l, c = (float(v) for v in pack)
     return r, l, c
+
+
+def global_term_sums(term_sum, terminated: int, truncated: int, device=None):
+    """The per-term episode statistics (BatchedEnv.pop_term_sums) summed over all ranks, like global_episode_stats: every rank sees the
+    statistics of ALL envs of the run."""
+    d = dist()
+    if not _active(d):
+        return term_sum, terminated, truncated
+    pack = torch.tensor([float(v) for v in term_sum] + [float(terminated), float(truncated)], dtype=torch.float64, device=device)
+    d.all_reduce(pack)
+    v = pack.cpu().numpy()
+    return v[:-2], int(v[-2]), int(v[-1])

@@ -9,6 +9,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from ..batched_env import REWARD_TERMS, TASK_CARTPOLE, TASK_H1_STAND, TASK_JVRC_STEP, TASK_JVRC_WALK
 from .cartpole import CartpoleSpec
 from .h1 import H1Spec
 from .h1_walk import H1WalkSpec
@@ -94,7 +95,7 @@ class _SingleEnv:
 
 
 class CartpoleEnv(_SingleEnv):
-    TERMS = ["upright", "center", "velocity", "action"]          # cartpole_env.py:182-187
+    TERMS = list(REWARD_TERMS[TASK_CARTPOLE])
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
         super().__init__(CartpoleSpec(), seed=seed, device=device)
@@ -102,8 +103,7 @@ class CartpoleEnv(_SingleEnv):
 
 
 class JvrcWalkEnv(_SingleEnv):
-    TERMS = ["foot_frc_score", "foot_vel_score", "root_accel", "height_error", "com_vel_error", "yaw_vel_error",
-             "upper_body_reward", "posture_error", "torque_penalty", "action_penalty"]   # walking_task.py:131-146
+    TERMS = list(REWARD_TERMS[TASK_JVRC_WALK])
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
         spec = JvrcWalkSpec(yaml_path=path_to_yaml) if path_to_yaml else JvrcWalkSpec()
@@ -113,7 +113,7 @@ class JvrcWalkEnv(_SingleEnv):
 
 
 class JvrcStepEnv(_SingleEnv):
-    TERMS = ["foot_frc_score", "foot_vel_score", "orient_cost", "height_error", "step_reward", "upper_body_reward"]  # stepping_task.py:109-122
+    TERMS = list(REWARD_TERMS[TASK_JVRC_STEP])
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
         spec = JvrcStepSpec(yaml_path=path_to_yaml) if path_to_yaml else JvrcStepSpec()
@@ -128,7 +128,7 @@ class JvrcStepEnv(_SingleEnv):
 
 
 class H1Env(_SingleEnv):
-    TERMS = ["com_vel_error", "yaw_vel_error", "height", "upperbody", "joint_torque_reward", "posture"]   # standing_task.py:99-106
+    TERMS = list(REWARD_TERMS[TASK_H1_STAND])
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
         super().__init__(H1Spec(yaml_path=path_to_yaml) if path_to_yaml else H1Spec(), seed=seed, device=device)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, dist_utils
-from .batched_env import TASK_JVRC_STEP
+from .batched_env import REWARD_TERMS, TASK_JVRC_STEP, term_stats_dict
 from .ppo_kernels import PpoKernels, reference_init
 from .task_hook import reward_only_on
 
@@ -147,6 +147,7 @@ class Rollout(_RolloutStorage):
     def __init__(self, env, kernels: PpoKernels, T: int, seed: int = 0, task=None, max_traj_len: int | None = None):
         super().__init__(env, kernels, T, seed)
         self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
+        self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
         if task is not None and env.history_len > 1:
             # (the hooked paths write the reset observation / history rows themselves and know nothing of the env-side history deque)
             raise NotImplementedError("a plugged-in task with obs_history_len > 1 is not supported")
@@ -177,6 +178,12 @@ class Rollout(_RolloutStorage):
         self._tin_all = self._stin_all = None
         self._rare_path_warm = False
 
+    @property
+    def tin_all(self):
+        """[T][N][TASK_INPUT_DIM] float64 record of the last resident rollout (None unless one exported it: record_task_inputs or a
+        reward-only task)"""
+        return self._tin_all if getattr(self, "last_mode", None) == "resident" else None
+
     def collect(self, deterministic=False):
         self._start()
         # Only the actor sits on the step-to-step dependency chain.  The critic's weights do not change during a rollout
@@ -195,7 +202,7 @@ class Rollout(_RolloutStorage):
         """Fills obs / act / logp / tob_all / rew / done and sets last_mode: which path collected the rollout (tests, bench line)."""
         T = self.T
         hooked = self.task is not None and not self.reward_only
-        if not hooked and self._collect_resident(deterministic, task_inputs=self.reward_only):
+        if not hooked and self._collect_resident(deterministic, task_inputs=self.reward_only or self.record_task_inputs):
             self.last_mode = "resident"
             if self.reward_only:
                 self._evaluate_recorded_rewards()
@@ -429,9 +436,19 @@ class RecurrentRollout(_RolloutStorage):
         k.forward(self.obs[T], commit=False, want_actor=False, value=self.vfinal)
 
 
+# Whether a PPO learner arms the per-term episode statistics of its env unless told otherwise (PPO(term_stats=...), --term-stats /
+# --no-term-stats, LHW_TERM_STATS=0 / 1): decided by the A/B measurement of DESIGN.md section 1 -- armed, jvrc_walk @ 4096 ran 0.6 % below
+# the parent's mean and outside the spread of the parent's own runs, so it is opt-in.
+TERM_STATS_DEFAULT = False
+
+
 class PPO:
-    def __init__(self, env_fn, args, seed=None, task=None):
-        """`task`: None -- the task fused into the env's kernels (the reference's own) -- or a callable `task(spec, device)`
+    def __init__(self, env_fn, args, seed=None, task=None, term_stats=None):
+        """`term_stats`: arm the per-term episode statistics of the env's kernels (BatchedEnv.enable_term_stats): every
+        sample_parallel_with_workers() then leaves the statistics of the episodes it finished in `self.term_stats` and train() logs
+        them to reward_terms.csv.  None: args.term_stats, else LHW_TERM_STATS, else TERM_STATS_DEFAULT.  With a plugged-in `task` the
+        reward does not come from the kernels: the statistics stay off and `term_stats` is None.
+        `task`: None -- the task fused into the env's kernels (the reference's own) -- or a callable `task(spec, device)`
         returning a task_hook.VectorTask: reward and termination then come from that object, evaluated outside the kernels on the
         exported task inputs after every control step (feed-forward policies, humanoid envs; see task_hook.py)."""
         self.seed = seed
@@ -536,6 +553,14 @@ class PPO:
         self.env = spec.make_batched(self.n_proc, seed=env_seed, device=self.device, max_traj_len=0 if own_done else self.max_traj_len,
                                      env_id_base=dist_utils.shard_env_ids(self.n_proc, self.rank))
         self.env.env_id_base = dist_utils.shard_env_ids(self.n_proc, self.rank)
+        if term_stats is None:
+            term_stats = getattr(args, "term_stats", None)
+        if term_stats is None:
+            term_stats = os.environ.get("LHW_TERM_STATS", "1" if TERM_STATS_DEFAULT else "0") != "0"
+        self.term_stats_enabled = bool(term_stats) and self.task is None
+        self.term_stats = None
+        if self.term_stats_enabled:
+            self.env.enable_term_stats(True)
         rollout_seed = env_seed ^ 0x5DEECE66D
         if self.recurrent:
             self.rollout = RecurrentRollout(self.env, self.kernels, self.max_traj_len, seed=rollout_seed)
@@ -571,7 +596,11 @@ class PPO:
         self._adv, self._ret = adv, ret
         T, N = ro.T, ro.N
         rs, ls, cnt = ro.pop_episode_stats()
-        self._ep_stats = dist_utils.global_episode_stats(rs, ls, cnt, device=self.device if _dist() and _dist().get_backend() == 'nccl' else None)
+        coll_dev = self.device if _dist() and _dist().get_backend() == 'nccl' else None
+        self._ep_stats = dist_utils.global_episode_stats(rs, ls, cnt, device=coll_dev)
+        if self.term_stats_enabled:      # per-term sums of the episodes this rollout finished, over all ranks like the episode statistics
+            sums = dist_utils.global_term_sums(*self.env.pop_term_sums(), device=coll_dev)
+            self.term_stats = term_stats_dict(*sums, REWARD_TERMS[self.env.task])
         return BatchData(states=ro.obs[:T].reshape(T * N, -1), actions=ro.act.reshape(T * N, -1),
                          rewards=ro.rew.reshape(T * N, 1), values=ro.val.reshape(T * N, 1), returns=ret.reshape(T * N, 1),
                          dones=ro.done.reshape(T * N, 1), traj_idx=self._traj_idx(ro.done),
@@ -804,6 +833,21 @@ class PPO:
         if self.rank == 0:
             print(msg)
 
+    def _log_term_stats(self, itr):
+        """One row per training iteration in <logdir>/reward_terms.csv -- iteration, episodes, terminated, truncated, then the mean
+        episode sum of every reward term: the `info` dictionaries of the reference's env.step (robots/robot_base.py:88-96) that its
+        trainer never logs.  Rank 0; nothing is written while the statistics are off.  (stdout keeps the reference's lines.)"""
+        s = self.term_stats
+        if s is None or self.rank != 0:
+            return
+        path = self.save_path / "reward_terms.csv"
+        new = not path.exists()
+        with open(path, "a") as f:
+            if new:
+                f.write(",".join(["iteration", "episodes", "terminated", "truncated"] + list(s["terms"])) + "\n")
+            f.write(",".join([str(itr), str(s["episodes"]), str(s["terminated"]), str(s["truncated"])]
+                             + [repr(v) for v in s["terms"].values()]) + "\n")
+
     def train(self, env_fn, n_itr):
         train_start = time.time()
         k = self.kernels
@@ -843,6 +887,7 @@ class PPO:
                 w(f"| {'Mean noise std':>15} | {noise:>15.3g} |\n")
                 w("-" * 37 + "\n")
                 sys.stdout.flush()
+            self._log_term_stats(itr)
             total_time = time.time() - train_start
             fps = self.total_steps / total_time
             iter_avg = total_time / (itr + 1)

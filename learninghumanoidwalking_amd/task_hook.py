@@ -19,6 +19,9 @@ force sites, footstep targets, target state, root quaternion) -- and ``PerEnvRew
 OBSERVATION (gait phase, walk mode, mode_ref) stays in the kernel; the record carries it (``phase``, ``mode``, ``mode_ref``).
 With a task plugged in, the env never resets itself (it is created with ``max_traj_len = 0``): the rollout truncates and resets on
 the host through ``lhw_env_reset(mask)``, which runs the same reset code with the same random draws as the in-kernel auto-reset.
+The per-term episode statistics of the kernels (``BatchedEnv.enable_term_stats``, ``PPO(term_stats=True)``) describe the FUSED reward:
+with a task plugged in the reward does not come from the kernel, so ``PPO.term_stats`` is None and no reward_terms.csv is written
+(a plug-in keeps its own terms in ``last_terms``).
 """
 from __future__ import annotations
 

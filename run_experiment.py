@@ -1,16 +1,27 @@
-"""Entry point with the reference's `train` command line (reference run_experiment.py:153-208), running the
+"""Entry point with the reference's `train` and `eval` command lines (reference run_experiment.py:153-208, 245-292), running the
 on-device rollout + PPO of this repository.
 
     python run_experiment.py train --env jvrc_walk --logdir /tmp/logs --num-envs 4096 --n-itr 100 --seed 0
     python run_experiment.py train --env jvrc_walk --gpus 8 ...        (re-executes itself as 8 ranks under torch.distributed.run)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_experiment.py train --env jvrc_walk ...
+    python run_experiment.py eval --path RUN_DIR|ACTOR.pt [--num-envs 64] [--ep-len 10] [--seed S] [--out-dir DIR] [--trace-envs 16]
+    python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
 Differences from the reference, by design: no Ray (`--num-procs` is the number of on-device envs per GPU unless
 `--num-envs` is given); with `--recurrent` (LSTM actor / critic) `--minibatch-size` counts env columns = trajectories, as it
-counts trajectories in the reference; the `eval` sub-command (GL viewer on CPU MuJoCo) is not part of the path built here;
-`--imitate` needs an env description with `imitation_projector()` (as in the reference).
+counts trajectories in the reference; `--imitate` needs an env description with `imitation_projector()` (as in the reference).
+`train --term-stats` also writes <run dir>/reward_terms.csv, one row per iteration with the mean episode sum of every reward term (the
+`info` dictionaries of the reference's env.step, accumulated inside the stepping kernels).
+
+`eval` is headless (the reference's opens a GL viewer on CPU MuJoCo, run_experiment.py:277-292: not part of this repository): it runs
+`--num-envs` deterministic episodes of `--ep-len` seconds in parallel on the device, prints one JSON object -- checkpoint, env, seed,
+episodes, terminated, truncated, mean return, mean length, mean episode sum per reward term -- and writes it to eval_summary.json in
+`--out-dir` (default: the run directory).  With `--out-dir`, a feed-forward policy also leaves trajectory.npz there: qpos [T][K][nq],
+qvel, action, reward, done of the first `--trace-envs` envs, enough to replay the motion in a MuJoCo viewer elsewhere.
 """
 import argparse
+import json
+import math
 import os
 import pickle
 import shutil
@@ -52,6 +63,8 @@ def build_parser():
     p.add_argument("--yaml", type=str, default=None)
     p.add_argument("--device", type=str, default="auto", choices=["auto", "cpu", "cuda"])
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--term-stats", dest="term_stats", action=argparse.BooleanOptionalAction, default=None,
+                   help="per-term episode reward statistics from the stepping kernels, logged to reward_terms.csv (default: off; -0.6 % env-steps/s on jvrc_walk @ 4096)")
     p.add_argument("--gpus", type=int, default=1, help="GPUs of this node to train on (data parallel: envs sharded, gradients all-reduced over RCCL); "
                                                         "N > 1 outside a torch.distributed.run launcher re-executes this command as N ranks")
     return p
@@ -101,12 +114,124 @@ def run_experiment(args):
         dist.destroy_process_group()
 
 
+def build_eval_parser():
+    p = argparse.ArgumentParser(prog="run_experiment.py eval")
+    p.add_argument("--path", type=Path, default=None, help="an actor checkpoint (.pt) or a run directory (its latest actor)")
+    p.add_argument("--logdir", type=Path, default=None, help="a directory of runs: the latest run, its latest actor")
+    p.add_argument("--num-envs", type=int, default=64, help="episodes run in parallel")
+    p.add_argument("--ep-len", type=float, default=10.0, help="episode length in seconds")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--out-dir", type=Path, default=None, help="where eval_summary.json (and trajectory.npz) go; default: the run directory, summary only")
+    p.add_argument("--trace-envs", type=int, default=16, help="envs whose trajectory is written with --out-dir")
+    return p
+
+
+def get_latest_actor(run_dir: Path) -> Path:
+    """The checkpoint of the highest iteration, actor_<itr>.pt, else actor.pt (the best one)."""
+    numbered = [(int(f.stem.split("_")[1]), f) for f in Path(run_dir).glob("actor_*.pt") if f.stem.split("_")[1].isdigit()]
+    if numbered:
+        return max(numbered)[1]
+    if Path(run_dir, "actor.pt").is_file():
+        return Path(run_dir, "actor.pt")
+    raise SystemExit(f"eval: no actor checkpoint (actor_<itr>.pt / actor.pt) in {run_dir}")
+
+
+def get_latest_run(logdir: Path) -> Path:
+    """The newest run directory below `logdir` (run directories start with their time stamp, so the names sort by age)."""
+    runs = sorted(d for d in Path(logdir).iterdir() if d.is_dir() and Path(d, "experiment.pkl").is_file()) if Path(logdir).is_dir() else []
+    if not runs:
+        raise SystemExit(f"eval: no run directory (one holding experiment.pkl) in {logdir}")
+    return runs[-1]
+
+
+def resolve_checkpoint(path, logdir):
+    """(actor.pt, critic.pt, experiment.pkl) as the reference resolves them (run_experiment.py:245-269): --path names an actor file
+    or a run directory, --logdir a directory of runs; the critic and the pickled training arguments lie beside the actor."""
+    if (path is None) == (logdir is None):
+        raise SystemExit("eval: give exactly one of --path ACTOR.pt|RUN_DIR and --logdir DIR")
+    if logdir is not None:
+        path = get_latest_run(logdir)
+    path = Path(path)
+    if path.is_dir():
+        actor = get_latest_actor(path)
+    elif path.is_file() and path.suffix == ".pt" and path.name.startswith("actor"):
+        actor = path
+    else:
+        raise SystemExit(f"eval: {path} is neither an actor checkpoint (actor*.pt) nor a run directory")
+    critic = actor.with_name("critic" + actor.name[len("actor"):])
+    pkl = actor.with_name("experiment.pkl")
+    for f in (critic, pkl):
+        if not f.is_file():
+            raise SystemExit(f"eval: {f} is missing (it must lie beside {actor.name})")
+    return actor, critic, pkl
+
+
+def run_eval(argv):
+    ea = build_eval_parser().parse_args(argv)
+    actor, critic, pkl = resolve_checkpoint(ea.path, ea.logdir)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("this trainer runs on MI355X only: there is no CPU path (use the reference for --device cpu)")
+    import numpy as np
+    from learninghumanoidwalking_amd import _lib
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS
+    from learninghumanoidwalking_amd.ppo import PPO
+    with open(pkl, "rb") as f:
+        args = pickle.load(f)
+    if args.env not in ENVIRONMENTS:
+        raise SystemExit(f"eval: unknown env {args.env!r} in {pkl}")
+    Spec = ENVIRONMENTS[args.env]
+    yaml = Path(actor.parent, "config.yaml")      # the run's own copy of --yaml (run_experiment.py train)
+    env_fn = partial(Spec, yaml_path=str(yaml)) if (yaml.is_file() and args.env != "cartpole") else Spec
+    T = int(math.ceil(ea.ep_len / env_fn().control_dt - 1e-9))
+    out_dir = ea.out_dir if ea.out_dir is not None else actor.parent
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    # the learner of `train`, loaded like --continued (checkpoint.py's loaders, the checkpoint's observation normalisation), on a batch of
+    # its own: T control steps with max_traj_len = T, so every env finishes exactly one counted episode -- it falls, or it is truncated
+    # at the horizon -- and whatever a reset starts after a fall is cut by the horizon and not counted
+    args.continued, args.logdir, args.device_index = actor, out_dir, 0
+    args.num_envs, args.max_traj_len, args.imitate, args.gpus = ea.num_envs, T, None, 1
+    args.minibatch_size = min(int(args.minibatch_size or ea.num_envs), ea.num_envs) if getattr(args, "recurrent", False) else args.minibatch_size
+    torch.cuda.set_device(0)
+    torch.manual_seed(ea.seed)
+    algo = PPO(env_fn, args, seed=ea.seed, term_stats=True)
+    trace = ea.out_dir is not None and not algo.recurrent
+    if trace:
+        algo.rollout.record_task_inputs = True
+    algo.sample_parallel_with_workers(deterministic=True)      # Rollout.collect(deterministic=True), as PPO.evaluate
+    ls = algo._ep_stats[1]
+    ts = algo.term_stats
+    # (the return is the sum of its terms; the term sums are added up in env order, whereas the env's own return counter is a float atomic
+    # whose last bits follow the order in which wavefronts finish: the same command twice must write the same bytes)
+    summary = dict(checkpoint=str(actor), env=args.env, seed=ea.seed, num_envs=ea.num_envs, control_steps=T, episodes=ts["episodes"],
+                   terminated=ts["terminated"], truncated=ts["truncated"], mean_return=sum(ts["terms"].values()) if ts["episodes"] else float("nan"),
+                   mean_length=ls / ts["episodes"] if ts["episodes"] else float("nan"), terms=ts["terms"])
+    if ea.out_dir is not None:
+        if algo.recurrent:
+            summary["trajectory"] = "not written: the per-step record is exported by the resident rollout, which runs feed-forward actors only"
+        elif algo.rollout.tin_all is None:
+            summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
+        else:
+            ro, K = algo.rollout, max(1, min(ea.trace_envs, ea.num_envs))
+            rec = ro.tin_all[:, :K].cpu().numpy()
+            q0, v0, a0 = (_lib.TASK_INPUT_FIELDS[k][0] for k in ("qpos", "qvel", "action"))
+            env = algo.env
+            np.savez(Path(out_dir, "trajectory.npz"), qpos=rec[:, :, q0:q0 + env.nq], qvel=rec[:, :, v0:v0 + env.nv],
+                     action=rec[:, :, a0:a0 + env.act_dim], reward=ro.rew[:, :K].cpu().numpy(), done=ro.done[:, :K].cpu().numpy(),
+                     control_dt=np.float64(env_fn().control_dt))
+            summary["trajectory"] = "trajectory.npz"
+    text = json.dumps(summary, indent=1)
+    with open(Path(out_dir, "eval_summary.json"), "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in ("train", "eval"):
-        raise SystemExit("usage: run_experiment.py train --env <name> [...]")
+        raise SystemExit("usage: run_experiment.py train --env <name> [...] | run_experiment.py eval (--path ACTOR.pt|RUN_DIR | --logdir DIR) [...]")
     if sys.argv[1] == "eval":
-        raise SystemExit("`eval` (GL viewer / video on CPU MuJoCo) is outside the hot path of this repository; "
-                         "use the reference's run_experiment.py eval")
+        run_eval(sys.argv[2:])
+        sys.exit(0)
     sys.argv.remove("train")
     args = build_parser().parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
