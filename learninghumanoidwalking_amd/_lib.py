@@ -7,6 +7,8 @@ import glob
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("LHW_LIB") or os.path.join(_HERE, "liblhw.so")   # LHW_LIB: kernel-variant experiments (scripts/)
@@ -31,6 +33,47 @@ class LhwEnvConfig(ctypes.Structure):
         ("perturb_interval", ctypes.c_int32), ("n_perturb_bodies", ctypes.c_int32), ("perturb_bodies", ctypes.c_int32 * 2),
         ("perturb_force", ctypes.c_double), ("perturb_torque", ctypes.c_double),
     ]
+
+
+TASK_CARTPOLE, TASK_JVRC_WALK, TASK_H1_STAND, TASK_JVRC_STEP, TASK_H1_WALK = 0, 1, 2, 3, 4      # include/lhw.h: LhwEnvConfig.task
+
+
+def env_config(task, n_envs, *, frame_skip, kp, kd, seed=0, device=0, max_traj_len=0, env_id_base=0, action_smoothing=1.0,
+               nominal_qpos=None, action_offset=None, task_params=None, task_iparams=None, clock_lut=None, init_noise=0.0,
+               perturbation=None):
+    """(LhwEnvConfig, keep): the struct lhw_env_create reads, and the arrays its pointers refer to (the caller holds `keep` until
+    lhw_env_create has returned).  The one place that says what the kernels are told about an env; needs no GPU."""
+    keep = []
+
+    def arr(x, dt):
+        if x is None:
+            return None, 0
+        a = np.ascontiguousarray(x, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data, a.size
+
+    cfg = LhwEnvConfig()
+    cfg.task, cfg.n_envs, cfg.device = int(task), int(n_envs), int(device)
+    cfg.frame_skip, cfg.max_traj_len, cfg.env_id_base = int(frame_skip), int(max_traj_len), int(env_id_base)
+    cfg.seed, cfg.action_smoothing = int(seed) & (2**64 - 1), float(action_smoothing)
+    cfg.kp, _ = arr(np.atleast_1d(kp), np.float64)
+    cfg.kd, _ = arr(np.atleast_1d(kd), np.float64)
+    cfg.nominal_qpos, _ = arr(nominal_qpos, np.float64)
+    cfg.action_offset, _ = arr(action_offset, np.float64)
+    cfg.task_params, cfg.n_task_params = arr(task_params, np.float64)
+    cfg.task_iparams, cfg.n_task_iparams = arr(task_iparams, np.int32)
+    cfg.clock_lut, _ = arr(clock_lut, np.float64)
+    cfg.period = 0 if clock_lut is None else int(np.asarray(clock_lut).shape[-1])
+    cfg.init_noise = float(init_noise)      # radians (base_humanoid_env.py:287: cfg.init_noise degrees * pi / 180)
+    if perturbation:                        # JVRC tasks: dict(interval=<control steps>, bodies=[ids], force=, torque=)
+        bodies = [int(b) for b in perturbation.get("bodies", [])]
+        if len(bodies) > 2:
+            raise ValueError("perturbation: at most two bodies")
+        cfg.perturb_interval, cfg.n_perturb_bodies = int(perturbation["interval"]), len(bodies)
+        for i, b in enumerate(bodies):
+            cfg.perturb_bodies[i] = b
+        cfg.perturb_force, cfg.perturb_torque = float(perturbation.get("force", 0.0)), float(perturbation.get("torque", 0.0))
+    return cfg, keep
 
 
 class LhwPpoConfig(ctypes.Structure):      # include/lhw.h: hyper-parameters and shapes of a PPO / LSTM handle

@@ -12,9 +12,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import TASK_CARTPOLE, TASK_H1_STAND, TASK_H1_WALK, TASK_JVRC_STEP, TASK_JVRC_WALK  # noqa: F401
 from .model import Model
 
-TASK_CARTPOLE, TASK_JVRC_WALK, TASK_H1_STAND, TASK_JVRC_STEP, TASK_H1_WALK = 0, 1, 2, 3, 4
 DONE_TERMINATED, DONE_TRUNCATED = 1, 2
 # The reward dictionary of each task in the reference's dict order -- the order of rew_terms and of lhw_env_pop_term_stats
 # (cartpole_env.py:182-187, walking_task.py:131-146, standing_task.py:99-106, stepping_task.py:109-122)
@@ -61,10 +61,8 @@ class BatchedEnv:
     ``max_traj_len > 0``.
     """
 
-    def __init__(self, model: Model, task: int, n_envs: int, *, frame_skip: int, kp, kd, seed: int = 0,
-                 device: int | torch.device = 0, max_traj_len: int = 0, env_id_base: int = 0,
-                 action_smoothing: float = 1.0, nominal_qpos=None, action_offset=None, task_params=None,
-                 task_iparams=None, clock_lut=None, history_len: int = 1, init_noise: float = 0.0, perturbation: dict | None = None):
+    def __init__(self, model: Model, task: int, n_envs: int, *, device: int | torch.device = 0, history_len: int = 1, **config):
+        """`config`: the keywords of _lib.env_config (frame_skip, kp, kd, seed, max_traj_len, env_id_base, action_smoothing, ...)."""
         if not torch.cuda.is_available():
             raise _lib.LhwError(-5, "no GPU visible: BatchedEnv has no CPU fallback")
         self.device = torch.device("cuda", device) if isinstance(device, int) else device
@@ -72,38 +70,8 @@ class BatchedEnv:
         self.n_envs = int(n_envs)
         self.task = task
         self._ib, self._db = model.pack()
-        keep = []
-
-        def arr(x, dt):
-            if x is None:
-                return None, 0
-            a = np.ascontiguousarray(x, dtype=dt)
-            keep.append(a)
-            return a.ctypes.data, a.size
-
-        cfg = _lib.LhwEnvConfig()
-        cfg.task, cfg.n_envs, cfg.device = task, self.n_envs, self.device.index or 0
-        cfg.frame_skip, cfg.max_traj_len, cfg.env_id_base = int(frame_skip), int(max_traj_len), int(env_id_base)
-        self.env_id_base = int(env_id_base)      # global index of env 0: every RNG key of the kernels uses env_id_base + n
-        cfg.seed, cfg.action_smoothing = int(seed) & (2**64 - 1), float(action_smoothing)
-        cfg.kp, _ = arr(np.atleast_1d(kp), np.float64)
-        cfg.kd, _ = arr(np.atleast_1d(kd), np.float64)
-        cfg.nominal_qpos, _ = arr(nominal_qpos, np.float64)
-        cfg.action_offset, _ = arr(action_offset, np.float64)
-        cfg.task_params, cfg.n_task_params = arr(task_params, np.float64)
-        cfg.task_iparams, cfg.n_task_iparams = arr(task_iparams, np.int32)
-        lut, _ = arr(clock_lut, np.float64)
-        cfg.clock_lut = lut
-        cfg.period = 0 if clock_lut is None else int(np.asarray(clock_lut).shape[-1])
-        cfg.init_noise = float(init_noise)      # radians (base_humanoid_env.py:287: cfg.init_noise degrees * pi / 180)
-        if perturbation:                        # JVRC tasks: dict(interval=<control steps>, bodies=[ids], force=, torque=)
-            bodies = [int(b) for b in perturbation.get("bodies", [])]
-            if len(bodies) > 2:
-                raise ValueError("perturbation: at most two bodies")
-            cfg.perturb_interval, cfg.n_perturb_bodies = int(perturbation["interval"]), len(bodies)
-            for i, b in enumerate(bodies):
-                cfg.perturb_bodies[i] = b
-            cfg.perturb_force, cfg.perturb_torque = float(perturbation.get("force", 0.0)), float(perturbation.get("torque", 0.0))
+        cfg, _keep = _lib.env_config(task, self.n_envs, device=self.device.index or 0, **config)    # (_keep: until lhw_env_create has copied them)
+        self.env_id_base = cfg.env_id_base      # global index of env 0: every RNG key of the kernels uses env_id_base + n
         self._h = ctypes.c_void_p()
         L = _lib.lib()
         _lib.check(L.lhw_env_create(self._ib.ctypes.data, self._ib.size, self._db.ctypes.data, self._db.size,
@@ -146,22 +114,27 @@ class BatchedEnv:
         ([N, obs_dim], rows of the other envs untouched) or, by default, to self.obs."""
         if mask is not None:
             assert mask.dtype == torch.uint8 and mask.is_cuda and mask.numel() == self.n_envs
-        if obs_out is not None and self.history_len == 1:
+        if obs_out is None or self.history_len > 1:     # (a history env always resets into its own buffer)
+            obs_out = self.obs
+        else:
             assert obs_out.is_cuda and obs_out.dtype == torch.float32 and obs_out.is_contiguous() and obs_out.shape == self.obs.shape
-            _lib.check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(obs_out), _stream_ptr(self.device)))
-            return obs_out
+        _lib.check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(self._kernel_out(obs_out)[0]), _stream_ptr(self.device)))
         if self.history_len > 1:
-            _lib.check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(self._base), _stream_ptr(self.device)))
             sel = slice(None) if mask is None else mask.bool()
             self._full[sel] = 0
             self._full[sel, :self.base_obs_dim] = self._base[sel]
             self.obs.copy_(self._full)
-            return self.obs
-        _lib.check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(self.obs), _stream_ptr(self.device)))
-        return self.obs
+        return obs_out
+
+    def _kernel_out(self, obs, tob=None):
+        """The (observation, terminal observation) buffers the kernels write: the caller's, or the base-observation buffers of a
+        history env (whose full observations _history then builds)."""
+        return (obs, tob) if self.history_len == 1 else (self._base, self._tbase)
 
     def _history(self, a, b, obs, tob, done):
-        """full observation / terminal observation of envs [a, b) from the kernel's base outputs"""
+        """full observation / terminal observation of envs [a, b) from the kernel's base outputs (history envs only)"""
+        if self.history_len == 1:
+            return
         full, term = history_update(self._full[a:b], self._base[a:b], self._tbase[a:b], done[a:b], self.base_obs_dim)
         self._full[a:b] = full
         obs[a:b] = full
@@ -175,13 +148,10 @@ class BatchedEnv:
         tob = self.term_obs if term_obs_out is None else term_obs_out
         rew = self.rew if rew_out is None else rew_out
         done = self.done if done_out is None else done_out
-        if self.history_len > 1:
-            _lib.check(self._L.lhw_env_step(self._h, _ptr(act), _ptr(self._base), _ptr(self._tbase), _ptr(rew), _ptr(done),
-                                            _ptr(self.rew_terms), _stream_ptr(self.device)))
-            self._history(0, self.n_envs, obs, tob, done)
-            return obs, rew, done, tob
-        _lib.check(self._L.lhw_env_step(self._h, _ptr(act), _ptr(obs), _ptr(tob), _ptr(rew), _ptr(done),
-                                        _ptr(self.rew_terms), _stream_ptr(self.device)))
+        kobs, ktob = self._kernel_out(obs, tob)
+        _lib.check(self._L.lhw_env_step(self._h, _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done), _ptr(self.rew_terms),
+                                        _stream_ptr(self.device)))
+        self._history(0, self.n_envs, obs, tob, done)
         return obs, rew, done, tob
 
     def step_range(self, first: int, count: int, act: torch.Tensor, obs: torch.Tensor, term_obs: torch.Tensor, rew: torch.Tensor,
@@ -189,13 +159,10 @@ class BatchedEnv:
         """Advance envs [first, first + count) only, on the current stream.  All tensors are the FULL-batch buffers ([N, ...]);
         independent groups issued on different streams overlap on the GPU (no batch-wide barrier per control step)."""
         assert act.is_cuda and act.dtype == torch.float32 and act.is_contiguous() and act.numel() == self.n_envs * self.act_dim
-        if self.history_len > 1:
-            _lib.check(self._L.lhw_env_step_range(self._h, int(first), int(count), _ptr(act), _ptr(self._base), _ptr(self._tbase), _ptr(rew),
-                                                  _ptr(done), _ptr(self.rew_terms), _stream_ptr(self.device)))
-            self._history(int(first), int(first) + int(count), obs, term_obs, done)
-            return
-        _lib.check(self._L.lhw_env_step_range(self._h, int(first), int(count), _ptr(act), _ptr(obs), _ptr(term_obs), _ptr(rew),
-                                              _ptr(done), _ptr(self.rew_terms), _stream_ptr(self.device)))
+        kobs, ktob = self._kernel_out(obs, term_obs)
+        _lib.check(self._L.lhw_env_step_range(self._h, int(first), int(count), _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done),
+                                              _ptr(self.rew_terms), _stream_ptr(self.device)))
+        self._history(int(first), int(first) + int(count), obs, term_obs, done)
 
     def rollout(self, policy, T: int, obs: torch.Tensor, act: torch.Tensor, logp: torch.Tensor, term_obs: torch.Tensor, rew: torch.Tensor,
                 done: torch.Tensor, first: int = 0, count: int | None = None, task_inputs: torch.Tensor | None = None,
@@ -210,7 +177,7 @@ class BatchedEnv:
         (lhw_env_rollout_step_task_inputs).  Returns False (nothing launched) where the library has no resident kernel for this env /
         policy; a HIP failure raises."""
         N = self.n_envs
-        if self.history_len > 1 or policy is None or not hasattr(self._L, "lhw_env_rollout"):
+        if self.history_len > 1 or policy is None:
             return False
         assert obs.shape == (T + 1, N, self.obs_dim) and act.shape == (T, N, self.act_dim) and term_obs.shape == (T, N, self.obs_dim)
         assert logp.shape == (T, N) and rew.shape == (T, N) and done.shape == (T, N) and done.dtype == torch.uint8
@@ -237,7 +204,7 @@ class BatchedEnv:
 
     def last_rollout_queued(self) -> bool:
         """the most recent resident rollout drained the job queue (stepping task with more envs than wave slots)"""
-        return bool(getattr(self._L, "lhw_env_last_rollout_queued", lambda h: 0)(self._h) == 1)
+        return self._L.lhw_env_last_rollout_queued(self._h) == 1
 
     def get_state(self):
         qpos = np.zeros((self.n_envs, self.nq))

@@ -9,7 +9,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from ..batched_env import REWARD_TERMS, TASK_CARTPOLE, TASK_H1_STAND, TASK_JVRC_STEP, TASK_JVRC_WALK
+from ..batched_env import REWARD_TERMS
 from .cartpole import CartpoleSpec
 from .h1 import H1Spec
 from .h1_walk import H1WalkSpec
@@ -53,17 +53,20 @@ class _DataView:
 
 
 class _SingleEnv:
-    TERMS: list = []
+    SPEC = None     # the env's spec class
 
-    def __init__(self, spec, seed=0, device=0):
-        self.spec = spec
+    def __init__(self, path_to_yaml=None, seed=0, device=0):
+        spec = self.spec = self.SPEC(yaml_path=path_to_yaml) if path_to_yaml else self.SPEC()
+        self.TERMS = list(REWARD_TERMS[spec.task_code])
         self._env = spec.make_batched(1, seed=seed, device=device, max_traj_len=0)
         self.observation_space = np.zeros(spec.obs_dim)
         self.action_space = np.zeros(spec.act_dim)
-        self.base_obs_len, self.history_len = getattr(spec, "base_obs_dim", spec.obs_dim), getattr(spec, "history_len", 1)
+        self.base_obs_len, self.history_len = spec.base_obs_dim, spec.history_len
         if spec.obs_mean is not None:
             self.obs_mean, self.obs_std = np.asarray(spec.obs_mean), np.asarray(spec.obs_std)
         self.robot = SimpleNamespace(iteration_count=np.inf)
+        if spec.mirror_inds() is not None:
+            self.robot.mirrored_obs, self.robot.mirrored_acts, self.robot.clock_inds = spec.mirror_inds()
         # reference attribute names (tests/test_environments.py:232-246): the task runs inside the kernel, so `task` only
         # describes it; `interface` / `data` are read-only views of the device state, `model` is the compiled model
         self.task = SimpleNamespace(name=type(spec).__name__.replace("Spec", ""), reward_terms=list(self.TERMS))
@@ -95,31 +98,22 @@ class _SingleEnv:
 
 
 class CartpoleEnv(_SingleEnv):
-    TERMS = list(REWARD_TERMS[TASK_CARTPOLE])
+    SPEC = CartpoleSpec
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
-        super().__init__(CartpoleSpec(), seed=seed, device=device)
+        super().__init__(seed=seed, device=device)      # (cartpole has no YAML)
         self.robot.iteration_count = 0
 
 
 class JvrcWalkEnv(_SingleEnv):
-    TERMS = list(REWARD_TERMS[TASK_JVRC_WALK])
-
-    def __init__(self, path_to_yaml=None, seed=0, device=0):
-        spec = JvrcWalkSpec(yaml_path=path_to_yaml) if path_to_yaml else JvrcWalkSpec()
-        super().__init__(spec, seed=seed, device=device)
-        mo, ma, clock = spec.mirror_inds()
-        self.robot.mirrored_obs, self.robot.mirrored_acts, self.robot.clock_inds = mo, ma, clock
+    SPEC = JvrcWalkSpec
 
 
 class JvrcStepEnv(_SingleEnv):
-    TERMS = list(REWARD_TERMS[TASK_JVRC_STEP])
+    SPEC = JvrcStepSpec
 
     def __init__(self, path_to_yaml=None, seed=0, device=0):
-        spec = JvrcStepSpec(yaml_path=path_to_yaml) if path_to_yaml else JvrcStepSpec()
-        super().__init__(spec, seed=seed, device=device)
-        mo, ma, clock = spec.mirror_inds()
-        self.robot.mirrored_obs, self.robot.mirrored_acts, self.robot.clock_inds = mo, ma, clock
+        super().__init__(path_to_yaml, seed=seed, device=device)
         self.robot.iteration_count = 0
 
     def reset(self):
@@ -128,17 +122,11 @@ class JvrcStepEnv(_SingleEnv):
 
 
 class H1Env(_SingleEnv):
-    TERMS = list(REWARD_TERMS[TASK_H1_STAND])
-
-    def __init__(self, path_to_yaml=None, seed=0, device=0):
-        super().__init__(H1Spec(yaml_path=path_to_yaml) if path_to_yaml else H1Spec(), seed=seed, device=device)
+    SPEC = H1Spec
 
 
 class H1WalkEnv(_SingleEnv):
-    TERMS = JvrcWalkEnv.TERMS          # same WalkingTask reward dictionary
+    SPEC = H1WalkSpec
 
-    def __init__(self, path_to_yaml=None, seed=0, device=0):
-        spec = H1WalkSpec(yaml_path=path_to_yaml) if path_to_yaml else H1WalkSpec()
-        super().__init__(spec, seed=seed, device=device)
-        mo, ma, clock = spec.mirror_inds()
-        self.robot.mirrored_obs, self.robot.mirrored_acts, self.robot.clock_inds = mo, ma, clock
+
+SINGLE_ENVS = {"cartpole": CartpoleEnv, "jvrc_walk": JvrcWalkEnv, "jvrc_step": JvrcStepEnv, "h1": H1Env, "h1_walk": H1WalkEnv}

@@ -5,13 +5,14 @@ import os
 from dataclasses import dataclass
 
 from .. import mjcf
-from ..batched_env import TASK_CARTPOLE, BatchedEnv
+from .._lib import TASK_CARTPOLE
+from .humanoid import BatchedFactory
 
 CARTPOLE_XML = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "cartpole.xml")
 
 
 @dataclass
-class CartpoleSpec:
+class CartpoleSpec(BatchedFactory):
     sim_dt: float = 0.005      # cartpole_env.py:84
     control_dt: float = 0.02   # cartpole_env.py:85
     kp: float = 100.0          # cartpole_env.py:93
@@ -19,6 +20,8 @@ class CartpoleSpec:
     obs_dim: int = 5
     act_dim: int = 1
     name: str = "cartpole"
+    task_code = TASK_CARTPOLE
+    base_obs_dim, history_len = 5, 1
     obs_mean = None            # no fixed normalisation: PPO warms up a RunningMeanStd (ppo.py:99-103)
     obs_std = None
 
@@ -39,15 +42,16 @@ class CartpoleSpec:
         """~0.3 kFLOP per sim sub-step x frame_skip + reward/obs."""
         return 300 * self.frame_skip + 60
 
-    def mirror_tables(self):
+    def mirror_inds(self):
         return None            # cartpole has no mirror symmetry (run_experiment.py:127-128 falls back)
 
-    def make_batched(self, n_envs, seed=0, device=0, max_traj_len=0, env_id_base=0):
-        return make_cartpole(n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base, spec=self)
+    def mirror_tables(self):
+        return None
+
+    def env_args(self):
+        """(model, task, kwargs) of BatchedEnv, as HumanoidSpec.env_args"""
+        return self.model(), TASK_CARTPOLE, dict(frame_skip=self.frame_skip, kp=[self.kp], kd=[self.kd])
 
 
-def make_cartpole(n_envs: int, seed: int = 0, device=0, max_traj_len: int = 0, env_id_base: int = 0,
-                  spec: CartpoleSpec | None = None) -> BatchedEnv:
-    spec = spec or CartpoleSpec()
-    return BatchedEnv(spec.model(), TASK_CARTPOLE, n_envs, frame_skip=spec.frame_skip, kp=[spec.kp], kd=[spec.kd],
-                      seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base)
+def make_cartpole(n_envs: int, seed: int = 0, device=0, max_traj_len: int = 0, env_id_base: int = 0, spec: CartpoleSpec | None = None):
+    return (spec or CartpoleSpec()).make_batched(n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base)

@@ -8,9 +8,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ..batched_env import TASK_H1_WALK, BatchedEnv
+from .._lib import TASK_H1_WALK
 from .h1 import _ASSETS, H1Spec
-from .jvrc_walk import phase_clock_lut
+from .humanoid import WalkingTask
 
 H1_WALK_YAML = os.path.join(_ASSETS, "h1_walk.yaml")
 
@@ -23,48 +23,30 @@ MIRROR_ACTS = [-5, -6, 7, 8, 9, -0.1, -1, 2, 3, 4]   # h1_walk.py:113
 
 
 @dataclass
-class H1WalkSpec(H1Spec):
+class H1WalkSpec(WalkingTask, H1Spec):
     yaml_path: str = H1_WALK_YAML
-    name: str = "h1_walk"
-    task_code = TASK_H1_WALK      # the kernels' task (a class attribute, not a field): which fused task a plugged-in VectorTask replaces
-    obs_dim: int = 43
-    step_kernel_name: str = "humanoid_kernel<0, 4, 32>"
 
-    def __post_init__(self):
-        super().__post_init__()
-        t = self.cfg["task"]
-        self.goal_height = float(t["goal_height"])
-        self.total_duration, self.swing_duration, self.stance_duration = (
-            float(t["total_duration"]), float(t["swing_duration"]), float(t["stance_duration"]))
-        self.period = int(np.floor(2 * self.total_duration * (1 / self.control_dt)))   # walking_task.py:204
+    name = "h1_walk"
+    task_code = TASK_H1_WALK
+    base_obs_dim = 43
+    step_kernel_name = "humanoid_kernel<0, 4, 32>"
+
+    def _configure(self, c):
+        super()._configure(c)
+        self._configure_walking_task(c["task"])
         # h1_walk.py:125-148
         self.obs_mean = np.concatenate([np.zeros(5), self.half_sitting_pose, np.zeros(10), np.zeros(10), [0, 0], [0.5, 0.5, 0.5, 0, 0, 0]])
         self.obs_std = np.concatenate([[0.2, 0.2, 1, 1, 1], 0.5 * np.ones(10), 4 * np.ones(10), 100 * np.ones(10), [1, 1],
                                        [1, 1, 1, 0.5, 0.5, 0.5]])
-        self._apply_history()
-
-    def clock_lut(self):
-        return phase_clock_lut(self.swing_duration, self.stance_duration, 0.1, 1 / self.control_dt, self.period)
 
     def mirror_inds(self):
         ext = [len(BASE_MIRROR_OBS) + i for i in range(self.base_obs_dim - 35)]
         return BASE_MIRROR_OBS + ext, MIRROR_ACTS, ext[0:2]
 
-    def mirror_tables(self):
-        from .jvrc_walk import JvrcWalkSpec
-        return JvrcWalkSpec.mirror_tables(self)       # same signed-permutation construction over this env's index lists
-
     def task_params(self):
         tp = super().task_params()
         tp[0] = self.goal_height
         return tp
-
-    def make_batched(self, n_envs, seed=0, device=0, max_traj_len=0, env_id_base=0) -> BatchedEnv:
-        return BatchedEnv(self.model(), TASK_H1_WALK, n_envs, frame_skip=self.frame_skip, kp=self.kp, kd=self.kd, seed=seed,
-                          device=device, max_traj_len=max_traj_len, env_id_base=env_id_base,
-                          action_smoothing=self.action_smoothing, nominal_qpos=self.nominal_pose,
-                          action_offset=self.action_offset(), task_params=self.task_params(), task_iparams=self.task_iparams(),
-                          clock_lut=self.clock_lut(), history_len=self.history_len)
 
     def algorithmic_bytes_per_env_step(self) -> int:
         return 2 * (168 + 128) * 8 + 10 * 4 + 2 * 43 * 4 + 4 + 1 + 10 * 4

@@ -1,0 +1,185 @@
+"""What the humanoid task specs share: the part of reference envs/common/base_humanoid_env.py and robots/robot_base.py that reads
+the YAML config, and the one place that says what a spec hands to the kernels (``env_args``).  Nothing here needs a GPU or torch."""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+
+import numpy as np
+import yaml
+
+ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
+
+
+def load_config(path):
+    """YAML config with an optional ``inherits: <file in the same directory>`` key (values of the child win)."""
+    with open(path) as f:
+        cfg = yaml.safe_load(f)
+    cfg.pop("timing", None)
+    parent = cfg.pop("inherits", None)
+    if parent:
+        base = load_config(os.path.join(os.path.dirname(os.path.abspath(path)), parent))
+        base.update(cfg)
+        cfg = base
+    return cfg
+
+
+def phase_clock_lut(swing_duration, stance_duration, strict_relaxer, freq, period):
+    """[4][period] table r_frc, r_vel, l_frc, l_vel of the "grounded" gait clocks at integer phases.
+
+    Restates the knot construction of reference tasks/rewards.py:196-300 (create_phase_reward):
+    8 knots per cycle (relaxed ends of right swing, first double stance, left swing, second double
+    stance), repeated over three cycles, interpolated with scipy's PchipInterpolator exactly as the
+    reference does.  The reference only ever evaluates the splines at integer phases, so the table
+    is the whole function.
+    """
+    from scipy.interpolate import PchipInterpolator
+    sw, st = swing_duration * freq, stance_duration * freq
+    segs = [(0.0, sw), (sw, sw + st), (sw + st, 2 * sw + st), (2 * sw + st, 2 * (sw + st))]
+    x = []
+    for a, b in segs:
+        off = (b - a) * strict_relaxer
+        x += [a + off, b - off]
+    x = np.array(x)
+    last_off = (segs[3][1] - segs[3][0]) * strict_relaxer
+    # right foot force clock: -1 in right swing, +1 otherwise; velocity clocks are the negation; left is the mirror
+    r_frc = np.array([-1, -1, 1, 1, 1, 1, 1, 1], dtype=float)
+    l_frc = np.array([1, 1, 1, 1, -1, -1, 1, 1], dtype=float)
+    r_vel = np.array([1, 1, -1, -1, -1, -1, -1, -1], dtype=float)
+    l_vel = np.array([-1, -1, -1, -1, 1, 1, -1, -1], dtype=float)
+    xs = np.concatenate([x - x[-1] - last_off, x, x + x[-1] + last_off])
+    ph = np.arange(int(period))
+    return np.stack([PchipInterpolator(xs, np.tile(y, 3))(ph) for y in (r_frc, r_vel, l_frc, l_vel)])
+
+
+def mirror_table(mirrored, clock_inds=()):
+    """(src, sign): a signed permutation of rl/envs/wrappers.py:78-85 as a gather."""
+    n = len(mirrored)
+    src, sign = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    for i, v in enumerate(mirrored):
+        j = int(abs(v))
+        src[j], sign[j] = i, np.sign(v)
+    for c in clock_inds:
+        sign[c] = -sign[c]  # sin(arcsin(c) + pi) == -c (wrappers.py:69-74)
+    return src, sign
+
+
+class WalkingTask:
+    """Mixin: the ``task:`` block and gait clock of tasks/walking_task.py (jvrc_walk, jvrc_step, h1_walk)."""
+
+    def _configure_walking_task(self, t):
+        self.goal_height = float(t["goal_height"])
+        self.total_duration, self.swing_duration, self.stance_duration = (
+            float(t["total_duration"]), float(t["swing_duration"]), float(t["stance_duration"]))
+        self.period = int(np.floor(2 * self.total_duration * (1 / self.control_dt)))  # walking_task.py:204
+
+    def clock_lut(self):
+        return phase_clock_lut(self.swing_duration, self.stance_duration, 0.1, 1 / self.control_dt, self.period)
+
+
+# The class make_batched instantiates.  None: batched_env.BatchedEnv, looked up at call time so that importing a spec needs no torch.
+# A module attribute because callers substitute it (an emulated backend, a recorder of the constructor arguments).
+BatchedEnv = None
+
+
+class BatchedFactory:
+    """Mixin of every spec (cartpole included): the GPU env of ``env_args()``."""
+
+    def make_batched(self, n_envs, seed=0, device=0, max_traj_len=0, env_id_base=0):
+        cls = BatchedEnv
+        if cls is None:
+            from ..batched_env import BatchedEnv as cls
+        model, task, kw = self.env_args()
+        return cls(model, task, n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base, **kw)
+
+
+@dataclass
+class HumanoidSpec(BatchedFactory):
+    """One task on one robot, read from a YAML config.  A subclass states the class attributes below and implements
+    ``_configure`` (kp, kd, half_sitting_pose, nominal_pose, obs_mean / obs_std of the BASE observation, task fields),
+    ``_build_model``, ``task_params`` and ``task_iparams``."""
+    yaml_path: str = ""
+    xml_path: str = ""
+    obs_dim: int | None = None      # derived (base_obs_dim x obs_history_len); a caller's value is only checked
+
+    name = ""
+    task_code = -1                  # the kernels' task: which fused task a plugged-in VectorTask replaces
+    base_obs_dim = 0                # width of the observation the task's kernel produces
+    act_dim = 0
+    step_kernel_name = ""           # rocprof name of the control-step kernel
+    leg_joints = ()                 # actuated joints, in action order
+    task_bodies = ()                # root, upper body, right foot, left foot
+
+    def __post_init__(self):
+        if self.obs_dim not in (None, self.base_obs_dim):
+            # the base observation is produced by the task's kernel: its width is not a free parameter of the Spec
+            raise ValueError(f"{type(self).__name__}: obs_dim is fixed by the task ({self.base_obs_dim}); got obs_dim={self.obs_dim}")
+        c = self.cfg = load_config(self.yaml_path)
+        self.sim_dt, self.control_dt = float(c["sim_dt"]), float(c["control_dt"])
+        self.history_len = int(c.get("obs_history_len", 1))     # base_humanoid_env.py:53,177-197 (kept above the kernels: BatchedEnv)
+        if self.history_len < 1:
+            raise ValueError("obs_history_len must be >= 1")
+        self.action_smoothing = float(c["action_smoothing"])
+        self.init_noise_deg = float(c.get("init_noise") or 0.0)     # base_humanoid_env.py:260-263, 278-305
+        pc = c.get("perturbation") or {}                            # base_humanoid_env.py:86-92; domain_randomization.py:10-26
+        self.perturb_interval = int(pc["interval"] / self.control_dt) if pc.get("enable") else 0
+        self.perturb_bodies = list(pc.get("bodies", []))
+        self.force_magnitude, self.torque_magnitude = float(pc.get("force_magnitude", 0)), float(pc.get("torque_magnitude", 0))
+        self._model = None
+        self._configure(c)
+        # jvrc_walk.py:62-63, h1_env.py:54-55: np.tile over the history
+        self.obs_dim = self.base_obs_dim * self.history_len
+        self.obs_mean, self.obs_std = np.tile(self.obs_mean, self.history_len), np.tile(self.obs_std, self.history_len)
+
+    @property
+    def frame_skip(self) -> int:
+        if np.around(self.control_dt % self.sim_dt, 6):  # robot_base.py:37-38
+            raise Exception("Control dt should be an integer multiple of Simulation dt.")
+        return int(self.control_dt / self.sim_dt)
+
+    def model(self):
+        if self._model is None:
+            self._model = self._build_model()
+        return self._model
+
+    def body_ids(self):
+        m = self.model()
+        return [m.body_id(b) for b in self.task_bodies]
+
+    def action_offset(self):
+        m = self.model()
+        return np.array([self.nominal_pose[m.jnt_qposadr[m.jnt_id(j)]] for j in self.leg_joints])  # base_humanoid_env.py:238-245
+
+    def perturbation_config(self):
+        """BatchedEnv(perturbation=...) for this YAML (None: off): interval in control steps, packed-model body ids, magnitudes"""
+        if self.perturb_interval <= 0:
+            return None
+        m = self.model()
+        return dict(interval=self.perturb_interval, bodies=[m.body_id(b) for b in self.perturb_bodies], force=self.force_magnitude, torque=self.torque_magnitude)
+
+    def clock_lut(self):
+        return None     # (a task with a gait clock mixes in WalkingTask)
+
+    def mirror_inds(self):
+        return None     # (mirrored_obs, mirrored_acts, clock_inds) of the env, where the reference defines them
+
+    def mirror_tables(self):
+        """((obs_src, obs_sign), (act_src, act_sign)), or None for an env without mirror indices (run_experiment.py:127-128 falls
+        back to no mirror)."""
+        inds = self.mirror_inds()
+        if inds is None:
+            return None
+        if self.history_len > 1:
+            # the reference's mirrored_obs lists base_obs_len indices only (jvrc_walk.py, h1_walk.py): its SymmetricEnv cannot
+            # mirror a history observation either
+            raise NotImplementedError("mirror loss with obs_history_len > 1: the reference defines mirror indices for the base observation only; train with --no-mirror")
+        mo, ma, clock = inds
+        return mirror_table(mo, clock), mirror_table(ma)
+
+    def env_args(self):
+        """(model, task, kwargs): what BatchedEnv is built from, apart from the per-call n_envs / seed / device / max_traj_len /
+        env_id_base.  Pure host arithmetic on the config and the compiled model."""
+        return self.model(), self.task_code, dict(
+            frame_skip=self.frame_skip, kp=self.kp, kd=self.kd, action_smoothing=self.action_smoothing, nominal_qpos=self.nominal_pose,
+            action_offset=self.action_offset(), task_params=self.task_params(), task_iparams=self.task_iparams(),
+            clock_lut=self.clock_lut(), history_len=self.history_len)

@@ -148,7 +148,7 @@ class OracleJvrcWalkEnv:
         """nominal pose, with BaseHumanoidEnv._apply_init_noise when the YAML sets init_noise (envs/common/base_humanoid_env.py:
         260-263, 278-305): RESET-stream slots 64 root z, 65 / 66 roll / pitch, 67.. joints (the slots the H1 envs use)"""
         qpos = np.array(self.spec.nominal_pose, dtype=float).copy()
-        cn = np.deg2rad(getattr(self.spec, "init_noise_deg", 0.0))
+        cn = np.deg2rad(self.spec.init_noise_deg)
         if cn > 0:
             from .env_h1 import euler2quat_sxyz
             s, e = self.seed, self.env_id

@@ -131,3 +131,112 @@ def test_jvrc_yaml_keys_of_base_humanoid_env_follow_the_reference_key_by_key(tmp
     assert sp.perturb_interval == 200 and sp.perturbation_config()["force"] == 10.0
     assert spec_with(perturbation=dict(enable=False, interval=5.0, bodies=["PELVIS_S"])).perturbation_config() is None
     spec_with(dynamics_randomization=dict(enable=False, interval=0.5), init_noise=0)      # configured but off: fine
+
+
+def test_env_args_of_every_spec_needs_no_torch():
+    """what a spec hands to the kernels is host arithmetic: it must be computable where torch cannot even be imported"""
+    code = ("import sys; sys.modules['torch'] = None\n"
+            "from learninghumanoidwalking_amd.envs import ENVIRONMENTS\n"
+            "for name, cls in ENVIRONMENTS.items():\n"
+            "    model, task, kw = cls().env_args()\n"
+            "    assert task == cls.task_code and kw['frame_skip'] > 0, name\n"
+            "assert sys.modules['torch'] is None\n"
+            "print('ok', len(ENVIRONMENTS))\n")
+    out = subprocess.check_output([sys.executable, "-c", code], cwd=ROOT).decode()
+    assert out.split() == ["ok", "5"]
+
+
+def test_env_args_contents():
+    import inspect
+    from learninghumanoidwalking_amd import _lib
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS
+    accepted = set(inspect.signature(_lib.env_config).parameters) | {"history_len"}
+    per_call = {"n_envs", "seed", "device", "max_traj_len", "env_id_base"}
+    codes = dict(cartpole=_lib.TASK_CARTPOLE, jvrc_walk=_lib.TASK_JVRC_WALK, jvrc_step=_lib.TASK_JVRC_STEP, h1=_lib.TASK_H1_STAND,
+                 h1_walk=_lib.TASK_H1_WALK)
+    for name, cls in ENVIRONMENTS.items():
+        spec = cls()
+        model, task, kw = spec.env_args()
+        assert task == spec.task_code == codes[name]
+        assert set(kw) <= accepted and not set(kw) & per_call, name
+        assert kw["frame_skip"] == spec.frame_skip
+        if name == "cartpole":
+            assert kw.get("clock_lut") is None and kw.get("nominal_qpos") is None
+            continue
+        assert len(kw["nominal_qpos"]) == model.nq and len(kw["action_offset"]) == len(kw["kp"]) == len(kw["kd"]) == spec.act_dim
+        assert kw["history_len"] == 1
+        if name == "h1":
+            assert kw["clock_lut"] is None
+        else:
+            assert np.asarray(kw["clock_lut"]).shape == (4, spec.period)
+        # the two encodings of init noise / perturbation: H1 through the task parameters, JVRC through the config record
+        assert ("init_noise" in kw and "perturbation" in kw) == name.startswith("jvrc")
+
+
+def test_emulated_env_built_from_env_args_steps_jvrc_walk():
+    from tests import emu
+    spec = JvrcWalkSpec()
+    model, task, kw = spec.env_args()
+    env = emu.EmuBatchedEnv(model, task, 2, seed=3, **kw)
+    obs = env.reset().copy()
+    assert obs.shape == (2, 37) and np.isfinite(obs).all()
+    obs2, rew, done, _ = env.step(np.zeros((2, 12), np.float32))
+    assert np.isfinite(obs2).all() and np.isfinite(rew).all() and not np.array_equal(obs, obs2)
+    assert env.pop_fault_stats() == (0, 0)
+    env.close()
+
+
+def test_config_filler_refuses_three_perturbation_bodies():
+    import pytest
+    from learninghumanoidwalking_amd import _lib
+    from tests import emu
+    model, task, kw = JvrcWalkSpec().env_args()
+    three = dict(interval=200, bodies=[1, 2, 3], force=10.0, torque=2.0)
+    with pytest.raises(ValueError, match="at most two bodies"):
+        _lib.env_config(task, 1, **dict({k: v for k, v in kw.items() if k != "history_len"}, perturbation=three))
+    with pytest.raises(ValueError, match="at most two bodies"):      # the emulated env goes through the same filler
+        emu.EmuBatchedEnv(model, task, 1, **dict(kw, perturbation=three))
+    cfg, keep = _lib.env_config(task, 1, **dict({k: v for k, v in kw.items() if k != "history_len"}, perturbation=dict(three, bodies=[1, 2])))
+    assert (cfg.perturb_interval, cfg.n_perturb_bodies, list(cfg.perturb_bodies), cfg.perturb_force) == (200, 2, [1, 2], 10.0)
+    assert cfg.period == 88 and cfg.n_task_params == 1 and cfg.n_task_iparams == 4 and len(keep) == 7
+
+
+def test_control_dt_must_be_a_multiple_of_sim_dt_for_both_robots(tmp_path):
+    """robots/robot_base.py:37-38, constructed by H1BaseEnv (h1_base.py:64) and by JvrcBaseEnv (jvrc_base.py:63) alike"""
+    import pytest
+    import yaml
+    from learninghumanoidwalking_amd.envs import H1Spec
+    from learninghumanoidwalking_amd.envs.h1 import H1_BASE_YAML, load_config
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JVRC_BASE_YAML
+    for cls, base in ((H1Spec, load_config(H1_BASE_YAML)), (JvrcWalkSpec, yaml.safe_load(open(JVRC_BASE_YAML)))):
+        p = tmp_path / (cls.name + ".yaml")
+        p.write_text(yaml.safe_dump(dict(base, sim_dt=0.001, control_dt=0.0255)))
+        spec = cls(yaml_path=str(p))
+        with pytest.raises(Exception, match="integer multiple"):
+            spec.frame_skip
+        with pytest.raises(Exception, match="integer multiple"):
+            spec.env_args()
+        assert cls().frame_skip == 25
+
+
+def test_make_batched_builds_the_substitutable_env_class_from_env_args(monkeypatch):
+    """envs.humanoid.BatchedEnv is the seam an emulated backend or a recorder replaces: make_batched hands it env_args() plus the
+    per-call arguments, for every spec"""
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS, humanoid
+    got = {}
+
+    class Recorder:
+        def __init__(self, model, task, n_envs, **kw):
+            got.update(model=model, task=task, n_envs=n_envs, kw=kw)
+
+    assert humanoid.BatchedEnv is None          # (the GPU class is looked up at call time: importing a spec needs no torch)
+    monkeypatch.setattr(humanoid, "BatchedEnv", Recorder)
+    for name, cls in ENVIRONMENTS.items():
+        spec = cls()
+        env = spec.make_batched(3, seed=5, max_traj_len=7, env_id_base=11)
+        model, task, kw = spec.env_args()
+        assert isinstance(env, Recorder) and (got["task"], got["n_envs"]) == (task, 3), name
+        for a, b in zip(got["model"].pack(), model.pack()):
+            np.testing.assert_array_equal(a, b)
+        assert set(got["kw"]) == set(kw) | {"seed", "device", "max_traj_len", "env_id_base"}
+        assert (got["kw"]["seed"], got["kw"]["device"], got["kw"]["max_traj_len"], got["kw"]["env_id_base"]) == (5, 0, 7, 11)
