@@ -201,6 +201,38 @@ int lhw_env_rollout(LhwEnv* env, const LhwRolloutPolicy* policy, int32_t first, 
 int lhw_env_rollout_task_inputs(LhwEnv* env, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev,
                                 float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev,
                                 double* tin_dev, void* stream);
+/* The frozen LSTM actor (Gaussian_LSTM_Actor, rl/policies/actor.py:191-286: two stacked LSTMCells of `hidden` units and a linear
+ * read-out) as lhw_env_rollout_lstm evaluates it inside the stepper's wavefronts -- the reference's worker calls it once per control
+ * step and carries its hidden / cell state from step to step, zeroed where an episode starts (rl/workers/rollout_worker.py:130-190).
+ * Device pointers, filled by lhw_rnn_rollout_policy. */
+typedef struct {
+  const float *w1t, *bi1, *bh1;      /* W1cat^T [obs_pad + hidden][4 hidden]: the TRANSPOSED [W_ih | W_hh] of cell 1 (rows in the order of the
+                                        concatenated input [x | h1_prev], padded observation columns included; columns gate-major i f g o),
+                                        and its two bias vectors [4 hidden] */
+  const float *w2t, *bi2, *bh2;      /* W2cat^T [2 hidden][4 hidden] (input [h1 | h2_prev]) and the biases of cell 2 */
+  const float *wot, *bo;             /* Wout^T [hidden][act_pad] and the read-out bias */
+  const float *stdv;                 /* [act_dim] standard deviations of the Gaussian head */
+  const float *obs_mean, *obs_std;   /* [obs_dim] observation normalisation */
+  float *h1, *h2, *c1, *c2;          /* the recurrent state, READ AND WRITTEN, one row per env of the batch: hidden states with row strides
+                                        h1_ld / h2_ld floats, cell states [state_rows][hidden].  For an LhwRnn handle these are its own actor
+                                        state buffers, the ones lhw_rnn_forward(commit = 1) advances */
+  int32_t h1_ld, h2_ld, state_rows;
+  int32_t obs_dim, obs_pad, act_dim, act_pad, hidden;
+  int32_t deterministic;             /* != 0: act = mean (evaluation) */
+  uint64_t seed;                     /* policy-noise key, as lhw_rnn_forward's */
+  uint32_t counter;                  /* policy-stream counter of the FIRST control step; step t uses counter + t */
+} LhwRolloutLstmPolicy;
+/* lhw_env_rollout for an LSTM actor: T control steps of envs [first, first + count) in ONE launch, every wavefront evaluating the two
+ * LSTM cells and the read-out for its own env(s) -- the loop of RolloutWorker.sample with a recurrent policy
+ * (rl/workers/rollout_worker.py:130-190).  Bitwise the values of T x { lhw_rnn_forward(actor outputs, commit = 1) ; lhw_env_step } on the
+ * same buffers, the state buffers of the view included, so rollouts of either kind may follow each other on one LhwRnn handle.  Buffers as
+ * for lhw_env_rollout.  reset0_dev [N] u8: rows whose episode starts with slice 0 of obs_dev (their stored state counts as zero); at step
+ * t > 0 the state is zero where done_dev[t - 1] is set.  tin_dev / stin_dev: nullable, the records of every control step as in
+ * lhw_env_rollout_task_inputs / lhw_env_rollout_step_task_inputs.  Float32 LSTM actor with hidden width 256 and act_dim <= 12, a state
+ * row per env of the batch (LHW_ERR_UNSUPPORTED otherwise, and wherever lhw_env_rollout refuses). */
+int lhw_env_rollout_lstm(LhwEnv* env, const LhwRolloutLstmPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
+                         float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, const uint8_t* reset0_dev,
+                         double* tin_dev, double* stin_dev, void* stream);
 /* 1 if the most recent lhw_env_rollout of this env drained the job queue (rocprof name humanoid_rollout_kernel<TASK, 64, true>), 0 if
  * every wavefront kept its env group (<.., false>); what bench.py names as the dominant kernel. */
 int lhw_env_last_rollout_queued(LhwEnv* env);
@@ -356,6 +388,12 @@ int lhw_debug_mlp_strip_backward_bits(int32_t H, int32_t O, int32_t Op, const fl
  * y [R][act_pad] receives the means.  The reference of lhw_env_rollout's in-wave policy step (bitwise). */
 int lhw_debug_policy_step(const LhwRolloutPolicy* policy, const float* obs, int32_t R, uint32_t env_id_base, uint32_t counter, float* y,
                           float* act, float* logp, void* stream);
+/* Test hook: lhw_rnn_forward's actor step (normalisation -> two LSTM cells -> read-out -> Gaussian head, commit = 1) on R raw observation
+ * rows [R][obs_dim] as ONE plain launch from an LSTM actor view -- a thread per hidden unit, the fmaf chains and the cell function of the
+ * in-wave step.  reset [R] u8 (nullable): rows that start an episode.  Advances rows 0 .. R - 1 of the view's state; y [R][act_pad] receives
+ * the means.  The per-step reference of lhw_env_rollout_lstm where lhw_rnn_forward is not built (SIMT emulator); bitwise equal to both. */
+int lhw_debug_lstm_policy_step(const LhwRolloutLstmPolicy* policy, const float* obs, int32_t R, const uint8_t* reset, uint32_t env_id_base,
+                               uint32_t counter, float* y, float* act, float* logp, void* stream);
 /* Diagnostic (load balance): the first call arms the recording; later calls return, per env, the shader-clock cycles its
  * wavefront group spent in the most recent control-step launch.  HOST pointer [N] int64, synchronous; humanoid tasks only. */
 int lhw_env_debug_wave_cycles(LhwEnv* env, int64_t* cycles_host);
@@ -482,6 +520,13 @@ int lhw_rnn_layout(const LhwRnn* rnn, int64_t* out19);
 int lhw_rnn_forward(LhwRnn* rnn, const float* theta, const float* obs, int64_t N, const float* obs_mean, const float* obs_std,
                     const uint8_t* reset, uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic, int commit,
                     float* mu, float* act, float* logp, float* value, void* stream);
+/* The actor of theta as lhw_env_rollout_lstm reads it: makes the [in][out] copies of the three weight matrices on `stream` (theta is
+ * frozen during a rollout: rl/workers/rollout_worker.py:62-77 sync_policy) and fills the view with them, the biases and stds inside
+ * theta, the caller's normalisation vectors and the handle's own actor state buffers.  Valid until the next lhw_rnn_apply (or any other
+ * write to theta) or lhw_rnn_destroy.  LHW_ERR_UNSUPPORTED for hidden != 256 or shapes the in-wave lane mapping does not cover
+ * (padded observation width > 64, act_dim > 16): the caller keeps the launch-per-step path. */
+int lhw_rnn_rollout_policy(LhwRnn* rnn, const float* theta, const float* obs_mean, const float* obs_std, uint64_t seed, uint32_t counter,
+                           int deterministic, LhwRolloutLstmPolicy* out, void* stream);
 /* BPTT of one minibatch = columns cols[0..B) of the time-major [T][N] rollout (xn / xm [T*N][pad4(obs)] normalised /
  * mirrored observations from lhw_ppo_normalize-compatible layout, done = LHW_DONE_* flags); accumulates grad, stats_dev[0..5] */
 int lhw_rnn_grad(LhwRnn* rnn, const float* theta, float* grad, int32_t T, int32_t N, const float* xn, const float* xm,

@@ -92,6 +92,13 @@ class LhwRolloutPolicy(ctypes.Structure):      # include/lhw.h: the frozen actor
         ("seed", ctypes.c_uint64), ("counter", ctypes.c_uint32)]
 
 
+class LhwRolloutLstmPolicy(ctypes.Structure):      # include/lhw.h: the frozen LSTM actor as lhw_env_rollout_lstm reads it
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w1t", "bi1", "bh1", "w2t", "bi2", "bh2", "wot", "bo", "stdv", "obs_mean", "obs_std",
+                                               "h1", "h2", "c1", "c2")] + [
+        (n, ctypes.c_int32) for n in ("h1_ld", "h2_ld", "state_rows", "obs_dim", "obs_pad", "act_dim", "act_pad", "hidden", "deterministic")] + [
+        ("seed", ctypes.c_uint64), ("counter", ctypes.c_uint32)]
+
+
 # include/lhw.h: enum LhwTaskInput (offsets into one env's record, length)
 TASK_INPUT_DIM = 176
 TASK_INPUT_FIELDS = dict(grf_r=(0, 1), grf_l=(1, 1), contact_z=(2, 1), foot_contact=(3, 1), self_collision=(4, 1), phase=(5, 1), mode=(6, 1),
@@ -293,6 +300,9 @@ def declare(L):
     sig("lhw_env_rollout_step_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutPolicy)])
     sig("lhw_debug_policy_step", [ctypes.POINTER(LhwRolloutPolicy), vp, i32, u32, u32, vp, vp, vp, vp])
+    sig("lhw_rnn_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutLstmPolicy), vp])
+    sig("lhw_env_rollout_lstm", [vp, ctypes.POINTER(LhwRolloutLstmPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_debug_lstm_policy_step", [ctypes.POINTER(LhwRolloutLstmPolicy), vp, i32, vp, u32, u32, vp, vp, vp, vp])
     return L
 
 

@@ -202,6 +202,35 @@ class BatchedEnv:
         _lib.check(rc)
         return True
 
+    def rollout_lstm(self, policy, T: int, obs: torch.Tensor, act: torch.Tensor, logp: torch.Tensor, term_obs: torch.Tensor, rew: torch.Tensor,
+                     done: torch.Tensor, reset0: torch.Tensor, first: int = 0, count: int | None = None, task_inputs: torch.Tensor | None = None,
+                     step_task_inputs: torch.Tensor | None = None) -> bool:
+        """The resident rollout for an LSTM actor (lhw_env_rollout_lstm): as `rollout`, with `policy` = RnnKernels.rollout_policy() --
+        whose state buffers the launch reads and writes -- and `reset0` [N] uint8: the envs whose episode starts with obs[0] (their state
+        counts as zero; afterwards the state is zeroed wherever the previous step's done flag is set: reference
+        rl/workers/rollout_worker.py:130-190).  Returns False (nothing launched) where the library has no such kernel for this env / policy."""
+        N = self.n_envs
+        if self.history_len > 1 or policy is None:
+            return False
+        assert obs.shape == (T + 1, N, self.obs_dim) and act.shape == (T, N, self.act_dim) and term_obs.shape == (T, N, self.obs_dim)
+        assert logp.shape == (T, N) and rew.shape == (T, N) and done.shape == (T, N) and done.dtype == torch.uint8
+        assert reset0.shape == (N,) and reset0.dtype == torch.uint8
+        for x in (obs, act, logp, term_obs, rew, done, reset0):
+            assert x.is_cuda and x.is_contiguous()
+        if step_task_inputs is not None:
+            assert task_inputs is not None, "the stepping record is exported together with the LhwTaskInput one"
+            assert step_task_inputs.shape == (T, N, _lib.STEP_TASK_INPUT_DIM) and step_task_inputs.dtype == torch.float64
+            assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
+        if task_inputs is not None:
+            assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
+        rc = self._L.lhw_env_rollout_lstm(self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), _ptr(obs),
+                                          _ptr(act), _ptr(logp), _ptr(term_obs), _ptr(rew), _ptr(done), _ptr(self.rew_terms), _ptr(reset0),
+                                          _ptr(task_inputs), _ptr(step_task_inputs), _stream_ptr(self.device))
+        if rc == -4:      # LHW_ERR_UNSUPPORTED
+            return False
+        _lib.check(rc)
+        return True
+
     def last_rollout_queued(self) -> bool:
         """the most recent resident rollout drained the job queue (stepping task with more envs than wave slots)"""
         return self._L.lhw_env_last_rollout_queued(self._h) == 1

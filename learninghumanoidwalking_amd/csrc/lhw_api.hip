@@ -248,6 +248,24 @@ extern "C" int lhw_env_rollout_step_task_inputs(LhwEnv* e, const LhwRolloutPolic
   return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
 }
 
+extern "C" int lhw_env_rollout_lstm(LhwEnv* e, const LhwRolloutLstmPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
+                                    float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, const uint8_t* reset0_dev,
+                                    double* tin_dev, double* stin_dev, void* stream) {
+  if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev || !reset0_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: wave-per-env (humanoid) steppers only");
+  if (stin_dev && e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: the stepping record needs a stepping-task env");
+  if (stin_dev && !tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_lstm: the stepping record is exported together with the task-input record");
+  HIPCHK(hipSetDevice(e->device));
+  const int rc = humanoid_rollout_lstm(e->hum, first, count, T, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, reset0_dev, tin_dev,
+                                       stin_dev, (hipStream_t)stream);
+  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
+  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout_lstm: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
+  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: needs a float32 LSTM actor obs %d -> 256 -> 256 -> act %d (<= 12) with a state row per env and a model "
+                          "that fits the task's resident kernel", e->obs_dim, e->act_dim);
+  HIPCHK(hipGetLastError());
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_last_rollout_queued(LhwEnv* e) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
   return e->task == LHW_TASK_CARTPOLE ? 0 : humanoid_last_rollout_queued(e->hum);

@@ -26,6 +26,7 @@
 // control_step<0, TASK, 64> for the flagged env with all 64 lanes -- same code, same bits as the second launch.
 #define LHW_SUBSTEP_PRIO 1   // the sub-steps of these kernels alternate the wave's issue priority with its SIMD partner's (substep(), lhw_humanoid_dev.h)
 #include "lhw_humanoid_dev.h"
+#include "lhw_lstm_cell.h"
 #include "lhw_policy.h"
 
 #define PH 256      // hidden width of the actor (rl/policies/actor.py:127)
@@ -42,7 +43,8 @@ __device__ __forceinline__ unsigned lhw_load_agent(const unsigned* p) { return _
 __device__ __forceinline__ void lhw_store_agent(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
-struct HRollout {
+template <class POL>
+struct HRolloutT {
   int T;                 // control steps of this launch
   int n_total;           // envs of the batch: row count of one time slice of the buffers below
   float* obs;            // [T + 1][n_total][obs_dim]: slice 0 is read (the observation to act on first), 1 .. T are written
@@ -59,8 +61,19 @@ struct HRollout {
   int chunk;
   long long tin_step;    // doubles per control step of the task-input export (n_total * LHW_TASK_INPUT_DIM), 0: the per-launch record (or none);
                          // the stepping task's second record (HState::stin) follows it at LHW_STEP_TASK_INPUT_DIM doubles per env
-  LhwRolloutPolicy pol;
+  POL pol;
 };
+// Policy kinds of the resident rollout: the feed-forward 256-256 actor (policy_step) and the two-cell LSTM actor (lstm_policy_step).  The kind
+// is a template parameter of rollout_steps and picks the kernel's argument struct, so a feed-forward kernel holds nothing of the LSTM step.
+enum { POLICY_MLP = 0, POLICY_LSTM = 1 };
+struct LstmPolicyArg {
+  LhwRolloutLstmPolicy q;
+  const unsigned char* reset0;   // [n_total] rows whose episode starts with the rollout's first observation (their state counts as zero)
+};
+typedef HRolloutT<LhwRolloutPolicy> HRollout;
+typedef HRolloutT<LstmPolicyArg> HRolloutLstm;
+template <int PK> struct RolloutOf { typedef HRollout type; };
+template <> struct RolloutOf<POLICY_LSTM> { typedef HRolloutLstm type; };
 
 // One 256-wide ReLU layer for the wave's G rows: hout[r][n] = relu(chain_k fmaf(W^T[k][n], xin[r][k]) + bias[n]), n = 4 wl .. 4 wl + 3.
 // The weight rows of PU consecutive k are requested as one batch of independent 16-byte loads, a batch ahead of the one being
@@ -195,9 +208,173 @@ __device__ __forceinline__ void policy_step(const LhwRolloutPolicy& q, float* sc
   SYNC();
 }
 
+// ------------------------------------------------------------------------------------------------ LSTM actor
+// Gaussian_LSTM_Actor (rl/policies/actor.py:191-286: two stacked LSTMCells of 256 units and a linear read-out) for the wave's G rows, as
+// lhw_rnn_forward evaluates it per control step (lhw_ppo.hip): the same values bit for bit, so a resident rollout and a launch-per-step
+// rollout can follow each other on the same LhwRnn handle.  Lane l owns hidden units 4l .. 4l + 3 of all FOUR gates of both rows: per
+// row k of a transposed weight matrix ([in][4 x 256], gate-major columns) four 16-byte loads per lane, each gate's 1 KB coalesced; the
+// cell update and the cell state are then lane-local.  Every gate pre-activation is ONE fmaf chain over ascending k from +0 over the
+// concatenated input [x | h_prev] -- what gemm_f32_kernel's v_mfma_f32_32x32x2_f32 loop computes -- followed by lhw_lstm_cell.
+// LPU weight rows (4 LPU loads per lane) are requested a batch ahead of the one being multiplied, as in policy_hidden: 32 accumulators
+// and two batches of 16 LPU registers.  LPU = 2: with 4 the two-envs-per-wave kernels spill 6 - 8 VGPRs where their feed-forward twins spill none.
+#ifndef LPU
+#define LPU 2
+#endif
+template <int G>
+__device__ __forceinline__ void lstm_gates(float (&acc)[G][4][4], const float* __restrict__ wt, const int K, const float* xin, const int ldx, const int wl) {
+  const float4* w4 = reinterpret_cast<const float4*>(wt) + wl;      // (a weight row is 4 PH floats = PH float4)
+  float4 wa[LPU][4], wb[LPU][4];
+  auto load = [&](float4 (&w)[LPU][4], const int k0) {
+#pragma unroll
+    for (int j = 0; j < LPU; j++)
+#pragma unroll
+      for (int g = 0; g < 4; g++) w[j][g] = w4[(size_t)min(k0 + j, K - 1) * PH + g * (PH / 4)];
+  };
+  auto mul = [&](const float4 (&w)[LPU][4], const int k0) {
+#pragma unroll
+    for (int j = 0; j < LPU; j++)
+#pragma unroll
+      for (int r = 0; r < G; r++) {
+        const float x = xin[r * ldx + k0 + j];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+          acc[r][g][0] = fmaf(w[j][g].x, x, acc[r][g][0]); acc[r][g][1] = fmaf(w[j][g].y, x, acc[r][g][1]);
+          acc[r][g][2] = fmaf(w[j][g].z, x, acc[r][g][2]); acc[r][g][3] = fmaf(w[j][g].w, x, acc[r][g][3]);
+        }
+      }
+  };
+  load(wa, 0);      // (K is a multiple of LPU; the loads past the end are clamped copies of the last row and are not multiplied)
+  for (int k0 = 0; k0 < K; k0 += 2 * LPU) {
+    load(wb, k0 + LPU);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(wa, k0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(wa, k0 + 2 * LPU);
+    __builtin_amdgcn_sched_barrier(0);
+    if (k0 + LPU < K) mul(wb, k0 + LPU);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The cell update of the lane's four units for every live row: reads and writes the cell state in HBM (c, [rows][PH]), writes the new
+// hidden state to its HBM slot (hs, row stride ld) and returns it in hnew (zero for rows beyond nlive).
+template <int G>
+__device__ __forceinline__ void lstm_cells(const float (&acc)[G][4][4], const float* __restrict__ bi, const float* __restrict__ bh, float* c, float* hs, const int ld,
+                                           const bool (&rst)[G], const int env0, const int nlive, const int wl, float (&hnew)[G][4]) {
+  float b_ih[4][4], b_hh[4][4];      // [unit][gate]
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const float4 a = reinterpret_cast<const float4*>(bi)[g * (PH / 4) + wl], b = reinterpret_cast<const float4*>(bh)[g * (PH / 4) + wl];
+    b_ih[0][g] = a.x; b_ih[1][g] = a.y; b_ih[2][g] = a.z; b_ih[3][g] = a.w;
+    b_hh[0][g] = b.x; b_hh[1][g] = b.y; b_hh[2][g] = b.z; b_hh[3][g] = b.w;
+  }
+#pragma unroll
+  for (int r = 0; r < G; r++) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) hnew[r][u] = 0.f;
+    if (r < nlive) {
+      float4* crow = reinterpret_cast<float4*>(c + (size_t)(env0 + r) * PH) + wl;
+      const float4 c4 = rst[r] ? make_float4(0.f, 0.f, 0.f, 0.f) : *crow;
+      const float cp[4] = {c4.x, c4.y, c4.z, c4.w};
+      float cn[4], gt[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) hnew[r][u] = lhw_lstm_cell(acc[r][0][u], acc[r][1][u], acc[r][2][u], acc[r][3][u], b_ih[u], b_hh[u], cp[u], gt, &cn[u]);
+      *crow = make_float4(cn[0], cn[1], cn[2], cn[3]);
+      *reinterpret_cast<float4*>(hs + (size_t)(env0 + r) * ld + 4 * wl) = make_float4(hnew[r][0], hnew[r][1], hnew[r][2], hnew[r][3]);
+    }
+  }
+}
+
+// LSTM actor forward + Gaussian head for the wave's rows; all 64 lanes take part.  rst_t [n_total]: rows whose episode starts with this
+// observation (the rollout's reset0 at its first step, the previous step's done flags afterwards) -- their stored state counts as zero,
+// which is what rnn_reset_kernel does to it in front of lhw_rnn_forward's GEMMs.  LDS as PolicyLds<G>: xs, h1 (the previous hidden state,
+// overwritten by the new one once layer 1 is done), h2 likewise, the Gaussian head's terms.
+template <int G>
+__device__ __forceinline__ void lstm_policy_step(const LhwRolloutLstmPolicy& q, float* sc, const float* __restrict__ obs_t, float* __restrict__ act_t,
+                                                 float* __restrict__ logp_t, const unsigned char* rst_t, const int env0, const int nlive, const unsigned genv0,
+                                                 const unsigned counter) {
+  typedef PolicyLds<G> PL;
+  const int wl = fresh_wave_lane();
+  const int D = q.obs_dim, O = q.act_dim, Op = q.act_pad, Dp = q.obs_pad;
+  float *xs = sc + PL::XS, *h1 = sc + PL::H1, *h2 = sc + PL::H2, *Tm = sc + PL::TM;
+  bool rst[G];
+#pragma unroll
+  for (int r = 0; r < G; r++) rst[r] = r < nlive && rst_t[env0 + r] != 0;
+  for (int i = wl; i < G * PXK; i += 64) {      // (the expression of normalize_ld_kernel, zero beyond the observation width)
+    const int r = i / PXK, k = i - r * PXK;
+    float v = 0.f;
+    if (k < D && r < nlive) v = (obs_t[(size_t)(env0 + r) * D + k] - q.obs_mean[k]) / q.obs_std[k];
+    xs[i] = v;
+  }
+  for (int i = wl; i < G * PH; i += 64) {
+    const int r = i / PH, k = i - r * PH;
+    const bool keep = r < nlive && !rst[r];
+    h1[i] = keep ? q.h1[(size_t)(env0 + r) * q.h1_ld + k] : 0.f;
+    h2[i] = keep ? q.h2[(size_t)(env0 + r) * q.h2_ld + k] : 0.f;
+  }
+  SYNC();
+  float acc[G][4][4], hn[G][4];
+  auto zero = [&]() {
+#pragma unroll
+    for (int r = 0; r < G; r++)
+#pragma unroll
+      for (int g = 0; g < 4; g++)
+#pragma unroll
+        for (int u = 0; u < 4; u++) acc[r][g][u] = 0.f;
+  };
+  auto put = [&](float* h) {
+#pragma unroll
+    for (int r = 0; r < G; r++) *reinterpret_cast<float4*>(h + r * PH + 4 * wl) = make_float4(hn[r][0], hn[r][1], hn[r][2], hn[r][3]);
+  };
+  // cell 1 over [x | h1_prev]: rows 0 .. Dp - 1 of W1cat^T, then its 256 recurrent rows
+  zero();
+  lstm_gates<G>(acc, q.w1t, Dp, xs, PXK, wl);
+  lstm_gates<G>(acc, q.w1t + (size_t)Dp * 4 * PH, PH, h1, PH, wl);
+  lstm_cells<G>(acc, q.bi1, q.bh1, q.c1, q.h1, q.h1_ld, rst, env0, nlive, wl, hn);
+  SYNC();      // every lane has read the previous h1
+  put(h1);
+  SYNC();
+  // cell 2 over [h1 | h2_prev]
+  zero();
+  lstm_gates<G>(acc, q.w2t, PH, h1, PH, wl);
+  lstm_gates<G>(acc, q.w2t + (size_t)PH * 4 * PH, PH, h2, PH, wl);
+  lstm_cells<G>(acc, q.bi2, q.bh2, q.c2, q.h2, q.h2_ld, rst, env0, nlive, wl, hn);
+  SYNC();
+  put(h2);
+  SYNC();
+  // read-out: lane = (row, output unit), ONE chain over k = 0 .. 255 from +0 and the bias after it (the read-out GEMM of lhw_rnn_forward;
+  // not the eight partial sums of policy_step, which mirror the strip kernel), 16 weight loads in flight
+  if (wl < 16 * G) {
+    const int rr = wl >> 4, col = wl & 15;
+    if (col < O && rr < nlive) {
+      const float* w = q.wot + col;
+      float s = 0.f;
+      for (int k0 = 0; k0 < PH; k0 += 16) {
+        float wv[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) wv[j] = w[(size_t)(k0 + j) * Op];
+#pragma unroll
+        for (int j = 0; j < 16; j++) s = fmaf(h2[rr * PH + k0 + j], wv[j], s);
+      }
+      s += q.bo[col];
+      float term;
+      const float a = lhw_policy_sample(s, q.stdv[col], q.seed, genv0 + (unsigned)rr, counter, col, q.deterministic, &term);
+      act_t[(size_t)(env0 + rr) * O + col] = a;
+      Tm[rr * 16 + col] = term;
+    }
+  }
+  SYNC();
+  if (wl < nlive) {
+    float lp = 0.f;
+    for (int k = 0; k < O; k++) lp += Tm[wl * 16 + k];     // (the order of sample_kernel's sum)
+    logp_t[env0 + wl] = lp;
+  }
+  SYNC();
+}
+
 // Control steps [t0, t1) of env group `grp` of the range (the G envs one wave advances together).
-template <int TASK, int W, bool STATS>
-__device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, const HRollout& ro, unsigned char* SGraw, int grp,
+template <int TASK, int W, bool STATS, int PK>
+__device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro, unsigned char* SGraw, int grp,
                                               int t0, int t1) {
   using L = typename LayoutOf<TASK, W>::type;
   using L1 = typename LayoutOf<TASK, 64>::type;
@@ -223,16 +400,27 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     __threadfence();
     const float* obs_t = ro.obs + (size_t)t * N * OBS;
     float* act_t = ro.act + (size_t)t * N * m.nu;
-    if (ro.pol.fp16_operands)
-      policy_step<G, true>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
-                           ro.pol.counter + (unsigned)t);
-    else
+    if constexpr (PK == POLICY_LSTM) {
+      // (the flags of the step before: read here, at the start of the policy step, so they also hold where the job queue cut the rollout)
+      const unsigned char* rst_t = t == 0 ? ro.pol.reset0 : ro.done + (size_t)(t - 1) * N;
+      lstm_policy_step<G>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, rst_t, env0, nlive, p.env_id_base + (unsigned)env0,
+                          ro.pol.q.counter + (unsigned)t);
+#ifdef LHW_RO_POLICY2X   // (analysis builds only: the second call advances the state once more -- a timing, not a rollout)
+      lstm_policy_step<G>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, rst_t, env0, nlive, p.env_id_base + (unsigned)env0,
+                          ro.pol.q.counter + (unsigned)t);
+#endif
+    } else {
+      if (ro.pol.fp16_operands)
+        policy_step<G, true>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+                             ro.pol.counter + (unsigned)t);
+      else
+        policy_step<G, false>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+                              ro.pol.counter + (unsigned)t);
+#ifdef LHW_RO_POLICY2X   // (analysis builds: the policy step twice -- the difference in rollout time is its cost)
       policy_step<G, false>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
                             ro.pol.counter + (unsigned)t);
-#ifdef LHW_RO_POLICY2X   // (analysis builds: the policy step twice -- the difference in rollout time is its cost)
-    policy_step<G, false>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
-                          ro.pol.counter + (unsigned)t);
 #endif
+    }
     __threadfence();   // the action rows are read back by the lanes of their env's group
     const int wl = fresh_wave_lane();
     const int g = W == 32 ? (wl >> 5) : 0, lane = wl & (W - 1);
@@ -278,12 +466,12 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 // control steps (control_step reads the HBM record and writes it back), so which wave runs a job does not matter to the bits.
 // A separate instantiation: wrapped into the job loop, the two-envs-per-wave kernels spill 25 more VGPRs and lose 2.8 % (round 5,
 // same box, jvrc_walk @ 4096), and at 8192 envs their waves are within +-2 % of each other anyway (queue +0.1 %).
-// Two kernel families from one text: humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
+// Kernel families from one text (each once more for the LSTM actor, policy kind POLICY_LSTM): humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
 // statistics (control_step<.., STATS>) and is launched instead while lhw_env_enable_term_stats is in force.  Generated by a macro and not
 // through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
-#define DEFINE_ROLLOUT_KERNEL(NAME, STATS) \
+#define DEFINE_ROLLOUT_KERNEL(NAME, STATS, PK) \
 template <int TASK, int W, bool QUEUE>                                                                                                                              \
-__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, HRollout ro) { \
+__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, typename RolloutOf<PK>::type ro) { \
   using L = typename LayoutOf<TASK, W>::type;                                                                                                                       \
   using L1 = typename LayoutOf<TASK, 64>::type;                                                                                                                     \
   constexpr int G = 64 / W;                                                                                                                                         \
@@ -297,7 +485,7 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
   const int n_groups = (lz.env_count + G - 1) / G;                                                                                                                  \
   if constexpr (!QUEUE) {                                                                                                                                           \
     if ((int)blockIdx.x >= n_groups) return;                                                                                                                        \
-    rollout_steps<TASK, W, STATS>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
+    rollout_steps<TASK, W, STATS, PK>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
   } else {                                                                                                                                                          \
     const int n_chunks = (ro.T + ro.chunk - 1) / ro.chunk;                                                                                                          \
     for (;;) {                                                                                                                                                      \
@@ -309,14 +497,17 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
       const int t0 = c * ro.chunk, t1 = min(ro.T, t0 + ro.chunk);                                                                                                   \
       /* the group's previous chunk was popped n_groups - 1 jobs ago by a wave that is running: it ends without waiting for anyone */                               \
       while (lhw_load_agent(ro.queue + 1 + grp) < (unsigned)c) __builtin_amdgcn_s_sleep(32);                                                                        \
-      rollout_steps<TASK, W, STATS>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
+      rollout_steps<TASK, W, STATS, PK>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
       __threadfence();   /* the group's records, observations and flags of this chunk, before the chunk counts as done */                                           \
       if (fresh_wave_lane() == 0) lhw_store_agent(ro.queue + 1 + grp, (unsigned)(c + 1));                                                                           \
     }                                                                                                                                                               \
   }                                                                                                                                                                 \
 }
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false, POLICY_MLP)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, POLICY_MLP)
+// the same two families with the LSTM actor's in-wave step (lhw_env_rollout_lstm)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, POLICY_LSTM)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, POLICY_LSTM)
 
 // ------------------------------------------------------------------------------------------------ host side
 // The stepping task's two instantiations live in a translation unit of their own, lhw_humanoid_rollout_step.hip (this file included with
@@ -324,6 +515,7 @@ DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true)
 // (the two-envs-per-wave kernels are built with iterative-maxocc instead: _lib.EXTRA_FLAGS, profiles/r06_stepper_compiler_flags.txt) -- and the two
 // halves compile in parallel.
 void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutLstm ro);
 #ifdef LHW_ROLLOUT_STEP_TU
 void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
   // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
@@ -332,6 +524,13 @@ void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_
     else hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
   } else if (queued) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
   else hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+}
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutLstm ro) {
+  if (!stats) {
+    if (queued) hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+    else hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  else hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
 }
 #else
 #ifdef LHW_ONLY_WALK
@@ -344,17 +543,33 @@ void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_
 
 int humanoid_last_rollout_queued(const HumanoidEnv* h) { return h->last_rollout_queued; }
 
-int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
-  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
-  const int obs_dim = h->p.task == TASK_STEP ? 39 : (h->p.task == TASK_WALK ? 37 : (h->p.task == TASK_H1WALK ? 43 : 35));
-  if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
-      pol->obs_pad < obs_dim || pol->obs_pad > PXK || (pol->obs_pad & 3))
-    return -2;
-  HRollout ro;
+// the two-envs-per-wave launches of one policy kind
+static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRollout& ro) {
+  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
+  if (!stats) {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_kernel, 32)
+  } else {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_stats_kernel, 32)
+  }
+}
+static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRolloutLstm& ro) {
+  if (!stats) {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_lstm_kernel, 32)
+  } else {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_lstm_stats_kernel, 32)
+  }
+}
+
+// everything of a resident rollout but the policy view (ro.pol, filled by the caller); -1 bad range, -3 unsupported, -4 HIP error
+template <class RO>
+static int rollout_launch(HumanoidEnv* h, RO& ro, int first, int count, int T, float* obs, float* act, float* logp, float* term_obs, float* rew, uint8_t* done,
+                          float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
   ro.T = T; ro.n_total = h->p.n_envs;
   ro.obs = obs; ro.act = act; ro.logp = logp; ro.tob = term_obs; ro.rew = rew; ro.done = done; ro.rew_terms = rew_terms;
-  ro.pol = *pol;
   ro.queue = nullptr; ro.chunk = 0;
   ro.tin_step = tin_all ? (long long)h->p.n_envs * LHW_TASK_INPUT_DIM : 0;
   HState st = h->st;
@@ -398,18 +613,39 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
   const dim3 grid(grid_n);
   h->last_rollout_queued = ro.queue != nullptr;
   const bool stats = h->p.tstat != nullptr;   // per-term episode statistics armed: the kernels that keep them
-  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
-  if (h->fast && !stats) {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_kernel, 32)
-  } else if (h->fast) {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_stats_kernel, 32)
-  } else {
+  if (h->fast) rollout_launch_fast(h, stats, grid, s, lz, st, ro);
 #ifndef LHW_ONLY_WALK
-    humanoid_rollout_launch_step(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+  else humanoid_rollout_launch_step(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
 #endif
-  }
   return 0;
+}
+
+static int rollout_obs_dim(const HumanoidEnv* h) { return h->p.task == TASK_STEP ? 39 : (h->p.task == TASK_WALK ? 37 : (h->p.task == TASK_H1WALK ? 43 : 35)); }
+
+int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
+                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
+  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
+  const int obs_dim = rollout_obs_dim(h);
+  if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
+      pol->obs_pad < obs_dim || pol->obs_pad > PXK || (pol->obs_pad & 3))
+    return -2;
+  HRollout ro;
+  ro.pol = *pol;
+  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
+}
+
+// the LSTM actor's resident rollout (lhw_env_rollout_lstm); the policy's state buffers must hold a row per env of the batch
+int humanoid_rollout_lstm(HumanoidEnv* h, int first, int count, int T, const LhwRolloutLstmPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
+                          float* rew, uint8_t* done, float* rew_terms, const uint8_t* reset0, double* tin_all, double* stin_all, hipStream_t s) {
+  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
+  const int obs_dim = rollout_obs_dim(h);
+  if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
+      pol->obs_pad < obs_dim || pol->obs_pad > PXK || (pol->obs_pad & 3) || pol->state_rows < h->p.n_envs || (pol->h1_ld & 3) || (pol->h2_ld & 3) ||
+      pol->h1_ld < PH || pol->h2_ld < PH)
+    return -2;
+  HRolloutLstm ro;
+  ro.pol.q = *pol;
+  ro.pol.reset0 = reset0;
+  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
 }
 #endif   // LHW_ROLLOUT_STEP_TU

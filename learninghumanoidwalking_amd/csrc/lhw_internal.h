@@ -98,6 +98,8 @@ int humanoid_step_range(HumanoidEnv* h, int first, int count, const float* act, 
 int humanoid_last_rollout_queued(const HumanoidEnv* h);
 int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
                      float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // lhw_humanoid_rollout.hip; -1 bad range, -2 / -3 unsupported, -4 HIP error
+int humanoid_rollout_lstm(HumanoidEnv* h, int first, int count, int T, const LhwRolloutLstmPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
+                          float* rew, uint8_t* done, float* rew_terms, const uint8_t* reset0, double* tin_all, double* stin_all, hipStream_t s);   // same codes
 void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t s);
 void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, hipStream_t s);
 double* humanoid_ep_stats(HumanoidEnv* h);
@@ -138,6 +140,9 @@ struct MlpStripBwd {
 size_t mlp_strip_bits_words(size_t rows);    // words per layer of the mask bits of a launch over `rows` rows (64-row slabs)
 bool mlp_strip_supported(int H, int Dp, int O, int Op);
 size_t mlp_strip_wt_floats(int Dp, int Op);
+// WT [cols][ldt] <- W [rows][ld] for up to three matrices in one launch (mlp_strip_prepare's kernel; rows == 0: no matrix)
+struct LhwTransposeJob { const float* W; float* WT; int rows, cols, ld, ldt; };
+void lhw_transpose3(const LhwTransposeJob (&jobs)[3], hipStream_t s);
 void mlp_strip_prepare(const float* w1, const float* w2, const float* w3, int Dp, int O, int Op, float* wt, hipStream_t s);
 void mlp_strip_forward(const MlpStripFwd& a, hipStream_t s, int shape = 0);   // shape: 0 by row count, 1 small (32-row slabs), 2 big (64-row)
 void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s);

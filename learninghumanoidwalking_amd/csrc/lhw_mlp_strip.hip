@@ -28,6 +28,7 @@
 
 #include "../../include/lhw.h"
 #include "lhw_internal.h"
+#include "lhw_lstm_cell.h"
 #include "lhw_policy.h"
 
 #ifndef __HIP_EMU__
@@ -404,6 +405,16 @@ void mlp_strip_prepare(const float* w1, const float* w2, const float* w3, int Dp
   hipLaunchKernelGGL(transpose3_kernel, dim3(J.j[2].first + tiles(O, SH)), dim3(256), 0, s, J);
 }
 
+void lhw_transpose3(const LhwTransposeJob (&jobs)[3], hipStream_t s) {
+  TransposeJobs J;
+  int first = 0;
+  for (int m = 0; m < 3; m++) {
+    J.j[m] = TransposeJob{jobs[m].W, jobs[m].WT, jobs[m].rows, jobs[m].cols, jobs[m].ld, jobs[m].ldt, first};
+    first += ((jobs[m].rows + 31) / 32) * ((jobs[m].cols + 31) / 32);
+  }
+  if (first > 0) hipLaunchKernelGGL(transpose3_kernel, dim3(first), dim3(256), 0, s, J);
+}
+
 size_t mlp_strip_bits_words(size_t rows) { return (rows + StripBig::ROWS - 1) / StripBig::ROWS * StripBig::THR * StripBig::CT; }
 
 bool mlp_strip_supported(int H, int Dp, int O, int Op) { return H == SH && Dp > 0 && Dp <= SXK && (Dp & 3) == 0 && O > 0 && O <= 32 && Op >= O; }
@@ -470,4 +481,73 @@ extern "C" int lhw_debug_policy_step(const LhwRolloutPolicy* q, const float* obs
   const char* sh = getenv("LHW_DEBUG_STRIP_SHAPE");
   mlp_strip_forward(a, (hipStream_t)stream, sh ? (sh[0] == 's' ? 1 : 2) : 0);
   return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "mlp_fwd_strip_kernel launch failed");
+}
+
+// The LSTM actor's rollout step as a plain launch: a workgroup per row, a thread per hidden unit (all four gates of it), the chains of
+// lstm_policy_step (lhw_humanoid_rollout.hip) and of lhw_rnn_forward's MFMA GEMMs -- one fmaf chain per gate pre-activation over ascending
+// k of [x | h_prev] from +0 -- and the shared cell function.
+#define LSH 256
+#define LSXK 64
+__global__ void __launch_bounds__(LSH) lstm_policy_ref_kernel(LhwRolloutLstmPolicy q, const float* __restrict__ obs, int R, const unsigned char* __restrict__ reset,
+                                                              unsigned env_base, unsigned counter, float* __restrict__ y, float* __restrict__ act,
+                                                              float* __restrict__ logp) {
+  __shared__ float xs[LSXK], h1[LSH], h2[LSH], terms[32];
+  LHW_LDS_POISON(xs);
+  LHW_LDS_POISON(h1);
+  LHW_LDS_POISON(h2);
+  LHW_LDS_POISON(terms);
+  const int row = (int)blockIdx.x, j = (int)threadIdx.x;
+  const int D = q.obs_dim, Dp = q.obs_pad, O = q.act_dim, Op = q.act_pad;
+  const bool rst = reset && reset[row];
+  if (j < LSXK) xs[j] = j < D ? (obs[(size_t)row * D + j] - q.obs_mean[j]) / q.obs_std[j] : 0.f;
+  h1[j] = rst ? 0.f : q.h1[(size_t)row * q.h1_ld + j];
+  h2[j] = rst ? 0.f : q.h2[(size_t)row * q.h2_ld + j];
+  __syncthreads();
+  auto cell = [&](const float* wt, const float* xa, int Ka, const float* xb, const float* bi, const float* bh, float* c) {
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < Ka; k++)
+      for (int n = 0; n < 4; n++) g[n] = fmaf(wt[(size_t)k * 4 * LSH + n * LSH + j], xa[k], g[n]);
+    for (int k = 0; k < LSH; k++)
+      for (int n = 0; n < 4; n++) g[n] = fmaf(wt[(size_t)(Ka + k) * 4 * LSH + n * LSH + j], xb[k], g[n]);
+    const float b_ih[4] = {bi[j], bi[LSH + j], bi[2 * LSH + j], bi[3 * LSH + j]}, b_hh[4] = {bh[j], bh[LSH + j], bh[2 * LSH + j], bh[3 * LSH + j]};
+    float gt[4], cn;
+    const float h = lhw_lstm_cell(g[0], g[1], g[2], g[3], b_ih, b_hh, rst ? 0.f : c[(size_t)row * LSH + j], gt, &cn);
+    c[(size_t)row * LSH + j] = cn;
+    return h;
+  };
+  const float hn1 = cell(q.w1t, xs, Dp, h1, q.bi1, q.bh1, q.c1);
+  __syncthreads();
+  h1[j] = hn1;
+  q.h1[(size_t)row * q.h1_ld + j] = hn1;
+  __syncthreads();
+  const float hn2 = cell(q.w2t, h1, LSH, h2, q.bi2, q.bh2, q.c2);
+  __syncthreads();
+  h2[j] = hn2;
+  q.h2[(size_t)row * q.h2_ld + j] = hn2;
+  __syncthreads();
+  if (j < O) {
+    float s = 0.f;
+    for (int k = 0; k < LSH; k++) s = fmaf(h2[k], q.wot[(size_t)k * Op + j], s);
+    s += q.bo[j];
+    y[(size_t)row * Op + j] = s;
+    float term;
+    act[(size_t)row * O + j] = lhw_policy_sample(s, q.stdv[j], q.seed, env_base + (unsigned)row, counter, j, q.deterministic, &term);
+    terms[j] = term;
+  }
+  __syncthreads();
+  if (j == 0) {
+    float lp = 0.f;
+    for (int k = 0; k < O; k++) lp += terms[k];     // (the order of sample_kernel's sum)
+    logp[row] = lp;
+  }
+}
+
+extern "C" int lhw_debug_lstm_policy_step(const LhwRolloutLstmPolicy* q, const float* obs, int32_t R, const uint8_t* reset, uint32_t env_id_base,
+                                          uint32_t counter, float* y, float* act, float* logp, void* stream) {
+  if (!q || !obs || !y || !act || !logp || R <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
+  if (q->hidden != LSH || q->obs_pad > LSXK || (q->obs_pad & 3) || q->obs_pad < q->obs_dim || q->act_dim > 32 || q->act_pad < q->act_dim)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "LSTM policy step: hidden width 256, padded input width <= 64, outputs <= 32");
+  if (R > q->state_rows) return lhw_fail(LHW_ERR_ARG, "R = %d rows, the view's state holds %d", R, q->state_rows);
+  hipLaunchKernelGGL(lstm_policy_ref_kernel, dim3(R), dim3(LSH), 0, (hipStream_t)stream, *q, obs, R, reset, env_id_base, counter, y, act, logp);
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "lstm_policy_ref_kernel launch failed");
 }

@@ -26,6 +26,7 @@
 
 #include "../../include/lhw.h"
 #include "lhw_internal.h"
+#include "lhw_lstm_cell.h"
 #include "lhw_policy.h"
 #include "lhw_rng.h"
 
@@ -1870,11 +1871,10 @@ struct LhwRnn : LearnerCore {
   unsigned char* reset = nullptr;  // [T][Bmax]
   float *mb_act = nullptr, *mb_logp = nullptr, *mb_adv = nullptr, *mb_ret = nullptr, *dstd = nullptr;
   float *part = nullptr;
+  float *wt_roll = nullptr;        // the actor's [in][out] weight copies for the resident rollout (lhw_rnn_rollout_policy), allocated by its first call
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-// gates G [B][4H] (pre-activation, biases not yet added) -> activated in place; c, h of this step.
+// gates G [B][4H] (pre-activation, biases not yet added) -> activated in place; c, h of this step (lhw_lstm_cell.h: the arithmetic of one unit).
 // h goes to dest_a (always) and dest_b (zeroed for rows whose NEXT step starts an episode: the recurrent slot).
 __global__ void __launch_bounds__(256) lstm_cell_fwd_kernel(int B, int H, float* __restrict__ G, const float* __restrict__ bi,
                                                             const float* __restrict__ bh, const float* __restrict__ c_prev,
@@ -1885,14 +1885,11 @@ __global__ void __launch_bounds__(256) lstm_cell_fwd_kernel(int B, int H, float*
   if (i >= (size_t)B * H) return;
   const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
   float* g = G + (size_t)b * 4 * H;
-  const float gi = sigmoidf_(g[j] + bi[j] + bh[j]);
-  const float gf = sigmoidf_(g[H + j] + bi[H + j] + bh[H + j]);
-  const float gg = tanhf(g[2 * H + j] + bi[2 * H + j] + bh[2 * H + j]);
-  const float go = sigmoidf_(g[3 * H + j] + bi[3 * H + j] + bh[3 * H + j]);
   const float cp = (c_prev && !(reset_t && reset_t[b])) ? c_prev[(size_t)b * H + j] : 0.f;
-  const float c = gf * cp + gi * gg;
-  const float h = go * tanhf(c);
-  g[j] = gi; g[H + j] = gf; g[2 * H + j] = gg; g[3 * H + j] = go;
+  const float b_ih[4] = {bi[j], bi[H + j], bi[2 * H + j], bi[3 * H + j]}, b_hh[4] = {bh[j], bh[H + j], bh[2 * H + j], bh[3 * H + j]};
+  float gt[4], c;
+  const float h = lhw_lstm_cell(g[j], g[H + j], g[2 * H + j], g[3 * H + j], b_ih, b_hh, cp, gt, &c);
+  g[j] = gt[0]; g[H + j] = gt[1]; g[2 * H + j] = gt[2]; g[3 * H + j] = gt[3];
   c_out[(size_t)b * H + j] = c;
   dest_a[(size_t)b * lda + j] = h;
   if (dest_b) dest_b[(size_t)b * ldb + j] = (reset_next && reset_next[b]) ? 0.f : h;
@@ -2138,6 +2135,37 @@ extern "C" int lhw_rnn_forward(LhwRnn* p, const float* theta, const float* obs, 
     }
   }
   HIPCHK(hipGetLastError());
+  return LHW_OK;
+}
+
+// The actor as the resident rollout's in-wave LSTM step reads it (lhw_humanoid_rollout.hip: lstm_policy_step): [in][out] copies of
+// W1cat, W2cat and Wout made here, everything else pointers into theta and the handle's own actor state.
+extern "C" int lhw_rnn_rollout_policy(LhwRnn* p, const float* theta, const float* obs_mean, const float* obs_std, uint64_t seed, uint32_t counter,
+                                      int deterministic, LhwRolloutLstmPolicy* out, void* stream) {
+  if (!p || !theta || !obs_mean || !obs_std || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
+  const LstmLayout& L = p->la;
+  if (L.H != 256 || L.Dp > 64 || L.O > 16 || L.Op > 16)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_rnn_rollout_policy: the in-wave LSTM step covers hidden width 256 (this actor: %d), padded observation width <= 64, "
+                                         "act_dim <= 16", L.H);
+  HIPCHK(hipSetDevice(p->device));
+  const size_t H = L.H, n1 = (size_t)L.K1 * 4 * H, n2 = 2 * H * 4 * H;
+  if (!p->wt_roll && !(p->wt_roll = p->mem.get_lazy<float>(n1 + n2 + H * L.Op)))
+    return lhw_fail(LHW_ERR_HIP, "lhw_rnn_rollout_policy: allocation of the transposed weights failed");
+  const float* th = theta + p->off_actor;
+  float *w1t = p->wt_roll, *w2t = w1t + n1, *wot = w2t + n2;
+  const LhwTransposeJob jobs[3] = {{th + L.w1, w1t, 4 * L.H, L.K1, L.K1, 4 * L.H}, {th + L.w2, w2t, 4 * L.H, 2 * L.H, 2 * L.H, 4 * L.H}, {th + L.wo, wot, L.O, L.H, L.H, L.Op}};
+  lhw_transpose3(jobs, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  out->w1t = w1t; out->bi1 = th + L.bi1; out->bh1 = th + L.bh1;
+  out->w2t = w2t; out->bi2 = th + L.bi2; out->bh2 = th + L.bh2;
+  out->wot = wot; out->bo = th + L.bo;
+  out->stdv = theta + p->off_std; out->obs_mean = obs_mean; out->obs_std = obs_std;
+  out->h1 = p->rxh1[0] + L.Dp; out->h1_ld = L.K1;
+  out->h2 = p->rxh2[0] + L.H; out->h2_ld = 2 * L.H;
+  out->c1 = p->rc1[0]; out->c2 = p->rc2[0];
+  out->state_rows = p->Nroll;
+  out->obs_dim = p->D; out->obs_pad = L.Dp; out->act_dim = L.O; out->act_pad = L.Op; out->hidden = L.H;
+  out->deterministic = deterministic; out->seed = seed; out->counter = counter;
   return LHW_OK;
 }
 

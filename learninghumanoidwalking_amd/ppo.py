@@ -406,24 +406,51 @@ class Rollout(_RolloutStorage):
         return float(s[0]), float(s[1]), int(s[2])
 
 
+# Whether LHW_ROLLOUT_MODE=auto sends an LSTM actor through the resident rollout (RecurrentRollout): decided by the A/B measurement of
+# DESIGN.md section 1 (profiles/r07_lstm_resident_ab.txt) under the rule of the term-statistics work -- resident by default only if its
+# mean sample time lies below every run of the launch-per-step parent.
+LSTM_RESIDENT_AUTO = False
+
+
 class RecurrentRollout(_RolloutStorage):
     """LSTM policies.  As in the reference's worker (rollout_worker.py:130-190: `current_state` / hidden state are only
     initialised when they are None), episodes AND the LSTM hidden / cell state are carried from one batch to the next:
     the envs are reset once, before the first batch; afterwards a batch starts from the last observation of the previous
     one with the hidden state the previous batch left, zeroed only for envs whose episode ended on its last step.  The
     hidden state advances with every policy / critic call; terminal and final values are evaluated without advancing it.
-    (The update, like the reference's, restarts every stored trajectory -- here every env column -- from a zero state.)"""
+    (The update, like the reference's, restarts every stored trajectory -- here every env column -- from a zero state.)
+
+    Two ways to collect, bitwise the same buffers (tests/test_rollout_lstm_gpu.py): launch per control step, or the resident rollout
+    (BatchedEnv.rollout_lstm: one launch, the actor's two cells evaluated inside the stepper's wavefronts) followed by the critic over
+    the stored time slices.  LHW_ROLLOUT_MODE = auto (LSTM_RESIDENT_AUTO decides) | resident (declining raises) | steps; `last_mode`
+    names the path the last collect() took."""
 
     def __init__(self, env, kernels, T: int, seed: int = 0):
         super().__init__(env, kernels, T, seed)
         N, D, A, dev = self.N, env.obs_dim, env.act_dim, env.device
-        self.mu = torch.zeros(N, A, dtype=torch.float32, device=dev)
+        self.mu = torch.zeros(N, A, dtype=torch.float32, device=dev)      # the last step's means (launch-per-step path only: nothing reads them)
         self.tob = torch.zeros(N, D, dtype=torch.float32, device=dev)
         self._rec_reset = torch.ones(N, dtype=torch.uint8, device=dev)      # every env starts from a zero state
+        self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
+        self._tob_all = self._tin_all = None      # [T][N][D] terminal observations / [T][N][176] records: allocated by the first resident rollout
+        self.last_mode = None
+
+    @property
+    def tin_all(self):
+        """[T][N][TASK_INPUT_DIM] float64 record of the last resident rollout (None unless one exported it: record_task_inputs)"""
+        return self._tin_all if self.last_mode == "resident" else None
 
     def collect(self, deterministic=False):
-        env, k, T = self.env, self.k, self.T
         self._start()
+        if self._collect_resident(deterministic):
+            self.last_mode = "resident"
+        else:
+            self.last_mode = "steps"
+            self._collect_steps(deterministic)
+        self.k.forward(self.obs[self.T], commit=False, want_actor=False, value=self.vfinal)
+
+    def _collect_steps(self, deterministic):
+        env, k, T = self.env, self.k, self.T
         reset = self._rec_reset
         for t in range(T):
             k.forward(self.obs[t], reset=reset, seed=self.seed, env_id_base=self.env_base, counter=self.counter,
@@ -433,7 +460,47 @@ class RecurrentRollout(_RolloutStorage):
             reset = (self.done[t] != 0).to(torch.uint8)
             self.counter += 1
         self._rec_reset = reset
-        k.forward(self.obs[T], commit=False, want_actor=False, value=self.vfinal)
+
+    def _collect_resident(self, deterministic) -> bool:
+        """All T control steps in one launch, then the critic over the stored slices in the order of the launch-per-step loop
+        (V(s_t) advancing the critic's state, V(terminal observation) without): the same calls on the same values, so not a bit of
+        `val` / `vterm` changes, and the critic no longer sits between two control steps.  The means of the last step (`self.mu`) are
+        not produced here: nothing reads them.  Returns False where the launch-per-step loop is to run instead."""
+        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
+        if mode not in ("auto", "resident") or (mode == "auto" and not (LSTM_RESIDENT_AUTO or self.record_task_inputs)):
+            return False      # (the per-step record exists only on the resident path: asking for it selects that path)
+        env, k, T = self.env, self.k, self.T
+        if env.task == 0:
+            why = "the cartpole env has no wave-per-env stepper to host a policy step"
+        elif k.hidden != 256:
+            why = f"the in-wave LSTM step covers hidden width 256 only (this actor: {k.hidden})"
+        elif env.env_id_base != self.env_base:
+            why = "the env's env_id_base is not the rollout's"
+        elif env.history_len > 1:
+            why = "the env keeps an observation history above the kernels"
+        else:
+            pol = k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
+            if pol is None:
+                why = "the kernels have no in-wave policy step for this actor"
+            else:
+                if self._tob_all is None:
+                    self._tob_all = _lib.empty(T, self.N, env.obs_dim, dtype=torch.float32, device=self.obs.device)
+                if self.record_task_inputs and self._tin_all is None:
+                    self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+                if env.rollout_lstm(pol, T, self.obs, self.act, self.logp, self._tob_all, self.rew, self.done, self._rec_reset,
+                                    task_inputs=self._tin_all if self.record_task_inputs else None):
+                    reset = self._rec_reset
+                    for t in range(T):
+                        k.forward(self.obs[t], reset=reset, commit=True, want_actor=False, value=self.val[t])
+                        k.forward(self._tob_all[t], commit=False, want_actor=False, value=self.vterm[t])
+                        reset = (self.done[t] != 0).to(torch.uint8)
+                    self._rec_reset = reset
+                    self.counter += T
+                    return True
+                why = "the library has no resident LSTM rollout kernel for this env / policy"
+        if mode == "resident":
+            raise _lib.LhwError(-4, f"LHW_ROLLOUT_MODE=resident, but {why}")
+        return False
 
 
 # Whether a PPO learner arms the per-term episode statistics of its env unless told otherwise (PPO(term_stats=...), --term-stats /

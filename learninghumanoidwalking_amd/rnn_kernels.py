@@ -2,6 +2,8 @@
 reference (rl/policies/actor.py:191-286, critic.py:52-112) as one flat float32 parameter vector on the GPU."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -53,6 +55,19 @@ class RnnKernels(_Kernels):
                                            _p(mu) if want_actor else None, _p(act) if want_actor else None,
                                            _p(logp) if want_actor else None, _p(value) if want_value else None, self._stream()))
         return mu, act, logp, value
+
+    def rollout_policy(self, *, seed=0, counter=0, deterministic=False):
+        """The frozen LSTM actor as the resident rollout (BatchedEnv.rollout_lstm -> lhw_env_rollout_lstm) evaluates it inside the
+        stepper's wavefronts: [in][out] weight copies made on the current stream, and this handle's own actor state buffers -- the ones
+        ``forward(commit=True)`` advances -- which the rollout reads and writes.  Valid until theta changes (``apply``, ``set_tensors``).
+        Returns None where the in-wave step does not apply (hidden width other than 256): the caller keeps the launch-per-step path."""
+        view = _lib.LhwRolloutLstmPolicy()
+        rc = self._L.lhw_rnn_rollout_policy(self._h, _p(self.theta), _p(self.obs_mean), _p(self.obs_std), int(seed) & (2**64 - 1),
+                                            int(counter) & 0xFFFFFFFF, int(bool(deterministic)), ctypes.byref(view), self._stream())
+        if rc == -4:      # LHW_ERR_UNSUPPORTED
+            return None
+        _lib.check(rc)
+        return view
 
     def grad_columns(self, T, N, xn, xm, act, old_logp, adv, ret, done, cols):
         """BPTT over columns ``cols`` (int32 device tensor) of the time-major [T][N] rollout."""

@@ -195,9 +195,8 @@ def run_eval(argv):
     torch.cuda.set_device(0)
     torch.manual_seed(ea.seed)
     algo = PPO(env_fn, args, seed=ea.seed, term_stats=True)
-    trace = ea.out_dir is not None and not algo.recurrent
-    if trace:
-        algo.rollout.record_task_inputs = True
+    if ea.out_dir is not None:
+        algo.rollout.record_task_inputs = True      # (kept by the resident rollout; asking for it selects that path for an LSTM actor too)
     algo.sample_parallel_with_workers(deterministic=True)      # Rollout.collect(deterministic=True), as PPO.evaluate
     ls = algo._ep_stats[1]
     ts = algo.term_stats
@@ -207,9 +206,7 @@ def run_eval(argv):
                    terminated=ts["terminated"], truncated=ts["truncated"], mean_return=sum(ts["terms"].values()) if ts["episodes"] else float("nan"),
                    mean_length=ls / ts["episodes"] if ts["episodes"] else float("nan"), terms=ts["terms"])
     if ea.out_dir is not None:
-        if algo.recurrent:
-            summary["trajectory"] = "not written: the per-step record is exported by the resident rollout, which runs feed-forward actors only"
-        elif algo.rollout.tin_all is None:
+        if algo.rollout.tin_all is None:
             summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
         else:
             ro, K = algo.rollout, max(1, min(ea.trace_envs, ea.num_envs))
