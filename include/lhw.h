@@ -383,6 +383,27 @@ int lhw_debug_mlp_strip_forward_bits(int32_t H, int32_t Dp, int32_t O, int32_t O
 int lhw_debug_mlp_strip_backward_bits(int32_t H, int32_t O, int32_t Op, const float* w2, const float* w3, const float* dy, int32_t R,
                                       const float* h1, const float* h2, float* dh2, float* dh1, const uint32_t* bits1, const uint32_t* bits2,
                                       void* stream);
+/* Test hook for the update's train strip kernel (csrc/lhw_mlp_strip.hip: forward layers, PPO head, backward layers of one network on slabs
+ * that stay in LDS): one network's pass over a minibatch of B rows.  critic = 0: the actor (O = act_dim outputs in rows of Op <= 64; act [B][O],
+ * old_logp / adv [B], stdv [O]); twin0 > 0 adds the mirror term: rows [twin0, twin0 + B) of x / h1 / h2 / y / dy / dh2 / dh1 are the mirrored
+ * twins of rows [0, B) (twin0 >= B; act_src / act_sign [O]).  critic = 1: the value head (O = 1, Op = 4; ret [B]).  Outputs, device buffers:
+ * h1 / h2 / dh2 / dh1 [rows][256], y / dy [rows][Op], dstd [B][Op] (actor, nullable), stat_rows [6][stat_ld]: every row's terms of the loss
+ * scalars in lhw_ppo_grad's order (the actor writes all but term 1, the critic term 1).  fused = 1: one launch.  fused = 0: the forward
+ * strip, the head as a thread-per-row kernel on y in HBM, the backward strip -- the same arithmetic, bit for bit. */
+typedef struct LhwTrainStripArgs {
+  int32_t H, Dp, O, Op;
+  const float *w1, *b1, *w2, *b2, *w3, *b3;   /* torch Linear layout, as lhw_debug_mlp_strip_forward */
+  const float* x;
+  int32_t ldx, B, twin0, critic;
+  const float *act, *old_logp, *adv, *ret, *stdv;
+  float clip, mirror_coeff;
+  const int32_t* act_src;
+  const float* act_sign;
+  float *h1, *h2, *y, *dy, *dh2, *dh1, *dstd, *stat_rows;
+  int32_t stat_ld;
+  float* wt_scratch;                          /* (Dp + 256 + Op) * 256 floats */
+} LhwTrainStripArgs;
+int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* args, int32_t fused, void* stream);
 /* Test hook: the rollout's per-control-step policy launch (observation normalisation -> actor -> Gaussian head, one strip launch;
  * what lhw_ppo_forward_at runs when only act / logp are requested) on R raw observation rows [R][obs_dim], from an actor view.
  * y [R][act_pad] receives the means.  The reference of lhw_env_rollout's in-wave policy step (bitwise). */
@@ -467,6 +488,12 @@ int lhw_ppo_set_inference_dtype(LhwPpo* ppo, int fp16);
  * runs on the fp16 MFMA with float32 accumulation -- BASELINE config 5 "fp16 actor/critic": fp16 weights and activations per
  * GEMM, float32 master weights, loss, gradient accumulation and Adam.  The reference has no counterpart (it trains in float32). */
 int lhw_ppo_set_update_dtype(LhwPpo* ppo, int fp16);
+/* debug / A-B: on != 0: lhw_ppo_grad runs each network's forward, loss head and backward layers as ONE train strip launch where it can
+ * (float32 update, no armed imitation term, hidden width 256); 0: forward strip, ppo_loss_kernel, backward strip.  Same bits either way.
+ * A new handle takes the environment's LHW_STRIP_FUSED (default 1). */
+int lhw_ppo_debug_set_strip_fused(LhwPpo* ppo, int32_t on);
+/* test hook: 1 if the last lhw_ppo_grad of this handle (a captured one included) ran the train strip launches, 0 if the three-launch path */
+int lhw_ppo_debug_last_grad_fused(const LhwPpo* ppo);
 /* time-major [T][N] GAE(lambda); done holds LHW_DONE_* flags, vterm the critic value of the terminal
  * observation, vfinal [N] the value of the observation after the last step */
 int lhw_gae(int32_t T, int32_t N, const float* rew, const float* val, const uint8_t* done, const float* vterm,

@@ -92,6 +92,14 @@ class LhwRolloutPolicy(ctypes.Structure):      # include/lhw.h: the frozen actor
         ("seed", ctypes.c_uint64), ("counter", ctypes.c_uint32)]
 
 
+class LhwTrainStripArgs(ctypes.Structure):      # include/lhw.h: arguments of the test hook lhw_debug_mlp_train_strip
+    _fields_ = ([(n, ctypes.c_int32) for n in ("H", "Dp", "O", "Op")] + [(n, ctypes.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "x")] +
+                [(n, ctypes.c_int32) for n in ("ldx", "B", "twin0", "critic")] + [(n, ctypes.c_void_p) for n in ("act", "old_logp", "adv", "ret", "stdv")] +
+                [("clip", ctypes.c_float), ("mirror_coeff", ctypes.c_float), ("act_src", ctypes.c_void_p), ("act_sign", ctypes.c_void_p)] +
+                [(n, ctypes.c_void_p) for n in ("h1", "h2", "y", "dy", "dh2", "dh1", "dstd", "stat_rows")] +
+                [("stat_ld", ctypes.c_int32), ("wt_scratch", ctypes.c_void_p)])
+
+
 class LhwRolloutLstmPolicy(ctypes.Structure):      # include/lhw.h: the frozen LSTM actor as lhw_env_rollout_lstm reads it
     _fields_ = [(n, ctypes.c_void_p) for n in ("w1t", "bi1", "bh1", "w2t", "bi2", "bh2", "wot", "bo", "stdv", "obs_mean", "obs_std",
                                                "h1", "h2", "c1", "c2")] + [
@@ -260,6 +268,9 @@ def declare(L):
     sig("lhw_debug_mlp_strip_backward", [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp])
     sig("lhw_debug_mlp_strip_forward_bits", [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_debug_mlp_strip_backward_bits", [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_debug_mlp_train_strip", [ctypes.POINTER(LhwTrainStripArgs), i32, vp])
+    sig("lhw_ppo_debug_set_strip_fused", [vp, i32])
+    sig("lhw_ppo_debug_last_grad_fused", [vp])
     sig("lhw_debug_wgrad_wide", [vp, vp, i32, i32, vp, vp, vp])
     sig("lhw_debug_wgrad_skinny", [i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_phase_cycles", [vp, ctypes.c_int, vp])

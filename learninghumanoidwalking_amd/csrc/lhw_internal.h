@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/lhw.h"
+#include "lhw_ppo_head.h"
 
 int lhw_fail(int code, const char* fmt, ...);
 
@@ -137,6 +138,21 @@ struct MlpStripBwd {
   float *dh2, *dh1;                          // [R][256] each
   const unsigned *bits1 = nullptr, *bits2 = nullptr;   // the forward launch's mask bits: h1 / h2 are then not read
 };
+// One network's whole pass over a minibatch in ONE launch (mlp_train_strip_kernel): forward layers, the PPO head on the read-out while it
+// is still in LDS, backward layers -- a 64-row slab never leaves its workgroup, and y, dy's read-back and the ReLU mask bits never
+// touch HBM.  f: the forward launch's arguments (R = live rows B; h1 / h2 are written, y only if not NULL; no inference fusions).
+struct MlpStripTrain {
+  MlpStripFwd f;
+  const float *w2, *w3;                      // torch layout, as MlpStripBwd
+  float *dy, *dh2, *dh1;                     // dy [.][Op] is still written once: the weight-gradient kernels read it
+  int twin0;                                 // 0: slabs of 64 consecutive rows.  > 0 (actor with mirroring): row tile 0 = rows [r0, r0 + 32), row
+                                             // tile 1 = their mirrored twins [twin0 + r0, twin0 + r0 + 32): a row and its twin meet in one workgroup
+  int critic;                                // 0: actor head (lhw_ppo_actor_row), 1: critic head (O = 1)
+  LhwPpoHead head;
+  float* stat_rows; int stat_ld;             // [NSTAT][stat_ld]: every live row's terms of the loss scalars (the actor's launch writes all but
+};                                           // term 1, the critic's term 1)
+bool mlp_train_strip_supported(int H, int Dp, int O, int Op, int critic);
+void mlp_train_strip(const MlpStripTrain& t, hipStream_t s);
 size_t mlp_strip_bits_words(size_t rows);    // words per layer of the mask bits of a launch over `rows` rows (64-row slabs)
 bool mlp_strip_supported(int H, int Dp, int O, int Op);
 size_t mlp_strip_wt_floats(int Dp, int Op);

@@ -57,7 +57,7 @@ typedef StripShape<1, 1, 8> StripSmall;
 // -DLHW_STRIP_CLOCK (analysis builds, scripts/strip_clock.py): every wave of the first 2048 workgroups stamps the 100 MHz wall clock at
 // the phase boundaries of the strip kernels; lhw_debug_strip_clock_read copies the stamps out.
 #ifdef LHW_STRIP_CLOCK
-#define SCLK_N 16
+#define SCLK_N 32
 __device__ unsigned long long g_strip_clk[2048 * 4 * SCLK_N];
 #define SCLK(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 2048 && (threadIdx.x >> 6) < 4) g_strip_clk[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * SCLK_N + (k)] = wall_clock64(); } while (0)
 extern "C" int lhw_debug_strip_clock_read(unsigned long long* host) {
@@ -71,6 +71,45 @@ template <class C>
 struct StripLds {
   float S[SH][C::LD];       // activation slab, k-major (Big: 69 632 B).  The input slab (x / dy, at most SXK columns) occupies
 };                          // its last SXK rows until the first layer's products are done
+
+// Which global rows a slab holds: row tile i = the 32 rows from base[i]; a tile's rows from end[i] on are not live (staged as zeros,
+// never stored).  Consecutive: ROWS rows from row0.  Twins (the update's actor with mirroring): tile 0 = rows [r0, r0 + 32), tile 1 = the
+// same rows of the mirrored pass, twin0 rows further on.  A row's values are fmaf chains over k: they do not depend on its slab mates.
+template <class C>
+struct SlabRows {
+  int base[C::RT], end[C::RT];
+  __device__ __forceinline__ static SlabRows consecutive(const int row0, const int R) {
+    SlabRows s;
+#pragma unroll
+    for (int i = 0; i < C::RT; i++) { s.base[i] = row0 + 32 * i; s.end[i] = R; }
+    return s;
+  }
+  __device__ __forceinline__ static SlabRows twins(const int r0, const int B, const int twin0) {
+    SlabRows s;
+#pragma unroll
+    for (int i = 0; i < C::RT; i++) { s.base[i] = r0 + i * twin0; s.end[i] = B + i * twin0; }
+    return s;
+  }
+  __device__ __forceinline__ bool full() const {
+    bool f = true;
+#pragma unroll
+    for (int i = 0; i < C::RT; i++) f = f && base[i] + 32 <= end[i];
+    return f;
+  }
+  // global row of slab row r, and whether it is live
+  __device__ __forceinline__ int grow(const int r) const {
+    int g = base[0] + r;
+#pragma unroll
+    for (int i = 1; i < C::RT; i++) g = r >= 32 * i ? base[i] + r - 32 * i : g;
+    return g;
+  }
+  __device__ __forceinline__ bool live(const int r) const {
+    bool v = base[0] + r < end[0];
+#pragma unroll
+    for (int i = 1; i < C::RT; i++) v = r >= 32 * i ? base[i] + r - 32 * i < end[i] : v;
+    return v;
+  }
+};
 
 template <class C>
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[C::RT][C::CT]) {
@@ -146,18 +185,25 @@ __device__ __forceinline__ void slab_mma(const float (*A)[C::LD], const int K, c
 // (i, j) owns slab row 32 i + l % 32 and, in registers 4 g .. 4 g + 3, the output units (wave's first) + 32 j + 8 g + 4 (l / 32) +
 // 0..3 -- one 16-byte store (and one 16-byte mask / bias load) per register quad.  Rows beyond R are computed (finite values
 // from zero inputs) but never stored to HBM.
-template <class C, bool TO_SLAB, bool FULL>
+template <class C, bool TO_SLAB, bool FULL, int RB>
 __device__ __forceinline__ void store_act_t(StripLds<C>& L, const f32x16 (&acc)[C::RT][C::CT], const float* __restrict__ bias, const bool relu,
-                                            const float* __restrict__ mask, float* __restrict__ out, const int row0, const int R,
-                                            unsigned* __restrict__ bits_out, const unsigned* __restrict__ bits_in) {
+                                            const float* __restrict__ mask, float* __restrict__ out, const SlabRows<C>& sr,
+                                            unsigned* __restrict__ bits_out, const unsigned* __restrict__ bits_in, unsigned (&rb)[C::CT]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, kh = lane >> 5;
   // ReLU masks as BITS (round 6): the forward pass leaves, per thread and column tile, one word with bit (g RT + i) 4 + c set where its
   // output is positive; the backward pass -- same workgroup shape, same thread-to-element map -- reads that word instead of sixteen
-  // 16-byte loads of the activations themselves (2 MB instead of 33.5 MB per layer and 32768 rows)
+  // 16-byte loads of the activations themselves (2 MB instead of 33.5 MB per layer and 32768 rows).  RB = 1 / 2: the words are written to /
+  // read from rb, the thread's own registers, instead of HBM, where one kernel runs both passes (mlp_train_strip_kernel); RB = 0: rb unused.
+  // (A template flag and an array REFERENCE on purpose: as optional pointers -- NULL in the plain kernels, a local array in the train kernel --
+  // the words made this ROCm's clang crash in the inliner's call-graph update.  So every caller hands an array over, used or not, and the
+  // kernels that keep no words declare a dummy that the optimiser drops: profiles/r08_train_strip_resources.txt -- within three VGPRs of
+  // the kernels before the flag, no scratch, the same occupancy; the backward kernel now parks 6 SGPRs in VGPR lanes (106 against 104
+  // SGPRs: no memory traffic, and a VGPR budget of 256 it uses 117 of).)
   unsigned wbits[C::CT];
+  const bool use_bits = RB == 2 || bits_in;
 #pragma unroll
-  for (int j = 0; j < C::CT; j++) wbits[j] = bits_in ? bits_in[((size_t)blockIdx.x * C::THR + tid) * C::CT + j] : 0u;
+  for (int j = 0; j < C::CT; j++) wbits[j] = RB == 2 ? rb[j] : (bits_in ? bits_in[((size_t)blockIdx.x * C::THR + tid) * C::CT + j] : 0u);
 #pragma unroll
   for (int j = 0; j < C::CT; j++) {
     const int nb = wave * 32 * C::CT + 32 * j + 4 * kh;
@@ -168,9 +214,8 @@ __device__ __forceinline__ void store_act_t(StripLds<C>& L, const f32x16 (&acc)[
     for (int i = 0; i < C::RT; i++)
 #pragma unroll
       for (int g = 0; g < 4; g++) {
-        const int row = 32 * i + l31;
         mk[i][g] = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (mask && !bits_in && (FULL || row0 + row < R)) mk[i][g] = *reinterpret_cast<const float4*>(mask + (size_t)(row0 + row) * SH + nb + 8 * g);
+        if (mask && !use_bits && (FULL || sr.base[i] + l31 < sr.end[i])) mk[i][g] = *reinterpret_cast<const float4*>(mask + (size_t)(sr.base[i] + l31) * SH + nb + 8 * g);
       }
     unsigned ob = 0u;
 #pragma unroll
@@ -181,11 +226,11 @@ __device__ __forceinline__ void store_act_t(StripLds<C>& L, const f32x16 (&acc)[
 #pragma unroll
       for (int i = 0; i < C::RT; i++) {
         const int row = 32 * i + l31;
-        const bool live = FULL || row0 + row < R;
+        const bool live = FULL || sr.base[i] + l31 < sr.end[i];
         float4 v = make_float4(acc[i][j][4 * g] + bv.x, acc[i][j][4 * g + 1] + bv.y, acc[i][j][4 * g + 2] + bv.z, acc[i][j][4 * g + 3] + bv.w);
         if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
         const int b0 = (g * C::RT + i) * 4;
-        if (bits_in) {
+        if (use_bits) {
           const unsigned w = wbits[j] >> b0;
           v.x = (live && (w & 1u)) ? v.x : 0.f; v.y = (live && (w & 2u)) ? v.y : 0.f;
           v.z = (live && (w & 4u)) ? v.z : 0.f; v.w = (live && (w & 8u)) ? v.w : 0.f;
@@ -193,27 +238,28 @@ __device__ __forceinline__ void store_act_t(StripLds<C>& L, const f32x16 (&acc)[
           v.x = (live && mk[i][g].x > 0.f) ? v.x : 0.f; v.y = (live && mk[i][g].y > 0.f) ? v.y : 0.f;
           v.z = (live && mk[i][g].z > 0.f) ? v.z : 0.f; v.w = (live && mk[i][g].w > 0.f) ? v.w : 0.f;
         }
-        if (bits_out) ob |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << b0;
+        if (RB == 1 || bits_out) ob |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << b0;
         if (TO_SLAB) { L.S[n][row] = v.x; L.S[n + 1][row] = v.y; L.S[n + 2][row] = v.z; L.S[n + 3][row] = v.w; }
-        if (live && out) *reinterpret_cast<float4*>(out + (size_t)(row0 + row) * SH + n) = v;   // (out == NULL: inference, the hidden layers stay in LDS)
+        if (live && out) *reinterpret_cast<float4*>(out + (size_t)(sr.base[i] + l31) * SH + n) = v;   // (out == NULL: inference, the hidden layers stay in LDS)
       }
     }
     if (bits_out) bits_out[((size_t)blockIdx.x * C::THR + tid) * C::CT + j] = ob;
+    if (RB == 1) rb[j] = ob;
   }
 }
-template <class C, bool TO_SLAB>
+template <class C, bool TO_SLAB, int RB>
 __device__ __forceinline__ void store_act(StripLds<C>& L, const f32x16 (&acc)[C::RT][C::CT], const float* __restrict__ bias, const bool relu,
-                                          const float* __restrict__ mask, float* __restrict__ out, const int row0, const int R,
-                                          unsigned* __restrict__ bits_out = nullptr, const unsigned* __restrict__ bits_in = nullptr) {
-  if (row0 + C::ROWS <= R) store_act_t<C, TO_SLAB, true>(L, acc, bias, relu, mask, out, row0, R, bits_out, bits_in);   // (all but the last slab: no per-row tests)
-  else store_act_t<C, TO_SLAB, false>(L, acc, bias, relu, mask, out, row0, R, bits_out, bits_in);
+                                          const float* __restrict__ mask, float* __restrict__ out, const SlabRows<C>& sr,
+                                          unsigned* __restrict__ bits_out, const unsigned* __restrict__ bits_in, unsigned (&rb)[C::CT]) {
+  if (sr.full()) store_act_t<C, TO_SLAB, true, RB>(L, acc, bias, relu, mask, out, sr, bits_out, bits_in, rb);   // (all but the last slab: no per-row tests)
+  else store_act_t<C, TO_SLAB, false, RB>(L, acc, bias, relu, mask, out, sr, bits_out, bits_in, rb);
 }
 
 // stage a [rows][K] row-major slab (row stride ld) k-major into X, zero-padded to a multiple of SBK in k and beyond R in rows
 // (mean / stdv: the input is a raw observation row of in_dim entries, normalised on the way in -- the same expression as
 // normalize_kernel, so the update, which normalises its minibatches there, sees the same bits)
 template <class C>
-__device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __restrict__ x, const int ld, const int K, const int row0, const int R,
+__device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __restrict__ x, const int ld, const int K, const SlabRows<C>& sr,
                                             const float* __restrict__ mean = nullptr, const float* __restrict__ stdv = nullptr, const int in_dim = 0) {
   const int Kp = (K + SBK - 1) & ~(SBK - 1);
   if (!mean && !(ld & 3) && !(reinterpret_cast<size_t>(x) & 15)) {
@@ -228,8 +274,8 @@ __device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __re
     for (int q = 0; q < NQ; q++) {
       const int idx = (int)threadIdx.x + q * C::THR, r = (int)(((float)idx + 0.5f) * rk4), k = 4 * (idx - r * k4);
       v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < C::ROWS * k4 && k < K && row0 + r < R) {
-        v[q] = *reinterpret_cast<const float4*>(x + (size_t)(row0 + r) * ld + k);
+      if (idx < C::ROWS * k4 && k < K && sr.live(r)) {
+        v[q] = *reinterpret_cast<const float4*>(x + (size_t)sr.grow(r) * ld + k);
         if (k + 1 >= K) v[q].y = 0.f;
         if (k + 2 >= K) v[q].z = 0.f;
         if (k + 3 >= K) v[q].w = 0.f;
@@ -246,24 +292,22 @@ __device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __re
     const int r = i / Kp, k = i - r * Kp;
     float v = 0.f;
     if (mean) {
-      if (k < in_dim && row0 + r < R) v = (x[(size_t)(row0 + r) * ld + k] - mean[k]) / stdv[k];
-    } else if (k < K && row0 + r < R) v = x[(size_t)(row0 + r) * ld + k];
+      if (k < in_dim && sr.live(r)) v = (x[(size_t)sr.grow(r) * ld + k] - mean[k]) / stdv[k];
+    } else if (k < K && sr.live(r)) v = x[(size_t)sr.grow(r) * ld + k];
     X[k][r] = v;
   }
 }
 
-template <class C>
-__global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a) {
-  __shared__ StripLds<C> L;
-  LHW_LDS_POISON(L);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l31 = lane & 31, kh = lane >> 5;
-  const int row0 = (int)blockIdx.x * C::ROWS;
+// The phases of the kernels below.  Stamps: forward 0 .. 11, backward from stamp c0.
+// forward, hidden layers: x slab -> h1 -> h2; returns behind the barrier that leaves h2 in the slab.  bits1 / bits2 (HBM) or rb1 / rb2 (the
+// thread's registers, with RB) take the ReLU mask words
+template <class C, bool RB>
+__device__ __forceinline__ void fwd_hidden(StripLds<C>& L, const MlpStripFwd& a, const SlabRows<C>& sr, unsigned (&rb1)[C::CT], unsigned (&rb2)[C::CT]) {
   float (*X)[C::LD] = &L.S[SH - SXK];
   WOp<C> w;
   SCLK(0);
   wload<C>(w, a.w1t, SH, a.Dp, 0);   // (the first weights of a layer are in flight while the slab is staged / the previous epilogue runs)
-  stage_input<C>(X, a.x, a.ldx, a.Dp, row0, a.R, a.in_mean, a.in_std, a.in_dim);
+  stage_input<C>(X, a.x, a.ldx, a.Dp, sr, a.in_mean, a.in_std, a.in_dim);
   __syncthreads();
   SCLK(1);
   f32x16 acc[C::RT][C::CT];
@@ -273,7 +317,7 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a)
   SCLK(2);
   __syncthreads();   // every wave is done with the input slab
   SCLK(3);
-  store_act<C, true>(L, acc, a.b1, true, nullptr, a.h1, row0, a.R, a.bits1);
+  store_act<C, true, RB ? 1 : 0>(L, acc, a.b1, true, nullptr, a.h1, sr, a.bits1, nullptr, rb1);
   SCLK(4);
   __syncthreads();
   SCLK(5);
@@ -282,13 +326,20 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a)
   SCLK(6);
   __syncthreads();
   SCLK(7);
-  store_act<C, true>(L, acc, a.b2, true, nullptr, a.h2, row0, a.R, a.bits2);
+  store_act<C, true, RB ? 1 : 0>(L, acc, a.b2, true, nullptr, a.h2, sr, a.bits2, nullptr, rb2);
   SCLK(8);
   __syncthreads();
   SCLK(9);
-  // read-out: y = h2 W3^T + b3, N = O <= 32: one column tile.  The K range is cut into SH / SKQ partial products of SKQ k each
-  // (the same cut for every workgroup shape, so every shape returns the same bits); a wave takes QW consecutive ones for all
-  // row tiles, and the partials are summed in ascending k order afterwards.
+}
+
+// read-out: y = h2 W3^T + b3, N = O <= 32: one column tile.  The K range is cut into SH / SKQ partial products of SKQ k each
+// (the same cut for every workgroup shape, so every shape returns the same bits); a wave takes QW consecutive ones for all
+// row tiles, and the partials are summed in ascending k order afterwards.  Returns behind the barrier that leaves the partials in the
+// slab's memory as P [SH / SKQ][ROWS][32].
+template <class C>
+__device__ __forceinline__ float (*fwd_readout_partials(StripLds<C>& L, const MlpStripFwd& a))[C::ROWS][32] {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, kh = lane >> 5;
   constexpr int NQ = SH / SKQ, QW = NQ / C::NW;
   f32x16 p[QW][C::RT];
 #pragma unroll
@@ -318,6 +369,47 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a)
 #pragma unroll
       for (int r = 0; r < 16; r++) P[wave * QW + q][32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh][l31] = p[q][i][r];
   __syncthreads();
+  return P;
+}
+
+// backward layers from the dy slab in X (complete, behind a barrier; `w` holds the first K step of W3): dh2 = (dy W3) * (h2 > 0) ->
+// dh1 = (dh2 W2) * (h1 > 0).  The masks: the activations h1 / h2, or their bits from HBM (bits1 / bits2) or, with RB, registers (rb1 / rb2)
+template <class C, bool RB>
+__device__ __forceinline__ void bwd_layers(StripLds<C>& L, WOp<C>& w, const float* __restrict__ w2, const float* __restrict__ w3, const int O,
+                                           const SlabRows<C>& sr, const float* __restrict__ h1, const float* __restrict__ h2, float* __restrict__ dh2,
+                                           float* __restrict__ dh1, const unsigned* __restrict__ bits1, const unsigned* __restrict__ bits2,
+                                           unsigned (&rb1)[C::CT], unsigned (&rb2)[C::CT], const int c0) {
+  float (*X)[C::LD] = &L.S[SH - SXK];
+  SCLK(c0);
+  f32x16 acc[C::RT][C::CT];
+  zero_acc<C>(acc);
+  slab_mma<C>(X, O, w3, SH, w, acc);                                        // dy W3: B[k = o][n] = W3[o][n]
+  wload<C>(w, w2, SH, SH, 0);
+  SCLK(c0 + 1);
+  __syncthreads();
+  SCLK(c0 + 2);
+  store_act<C, true, RB ? 2 : 0>(L, acc, nullptr, false, h2, dh2, sr, nullptr, bits2, rb2);
+  SCLK(c0 + 3);
+  __syncthreads();
+  SCLK(c0 + 4);
+  zero_acc<C>(acc);
+  slab_mma<C>(L.S, SH, w2, SH, w, acc);                                     // dh2 W2: B[k = o][n = i] = W2[o][i]
+  SCLK(c0 + 5);
+  store_act<C, false, RB ? 2 : 0>(L, acc, nullptr, false, h1, dh1, sr, nullptr, bits1, rb1);
+  SCLK(c0 + 6);
+}
+
+template <class C>
+__global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a) {
+  __shared__ StripLds<C> L;
+  LHW_LDS_POISON(L);
+  const int tid = threadIdx.x;
+  const int row0 = (int)blockIdx.x * C::ROWS;
+  const SlabRows<C> sr = SlabRows<C>::consecutive(row0, a.R);
+  unsigned rb1[C::CT], rb2[C::CT];   // (RB = 0: never touched; see store_act_t)
+  fwd_hidden<C, false>(L, a, sr, rb1, rb2);
+  float (*P)[C::ROWS][32] = fwd_readout_partials<C>(L, a);
+  constexpr int NQ = SH / SKQ;
   for (int i = tid; i < C::ROWS * 32; i += C::THR) {
     const int row = i >> 5, col = i & 31;
     if (col < a.O && row0 + row < a.R) {
@@ -349,30 +441,104 @@ template <class C>
 __global__ void __launch_bounds__(C::THR, 2) mlp_bwd_strip_kernel(MlpStripBwd a) {
   __shared__ StripLds<C> L;
   LHW_LDS_POISON(L);
-  const int row0 = (int)blockIdx.x * C::ROWS;
+  const SlabRows<C> sr = SlabRows<C>::consecutive((int)blockIdx.x * C::ROWS, a.R);
   float (*X)[C::LD] = &L.S[SH - SXK];
   WOp<C> w;
   SCLK(0);
   wload<C>(w, a.w3, SH, a.O, 0);
-  stage_input<C>(X, a.dy, a.Op, a.O, row0, a.R);
+  stage_input<C>(X, a.dy, a.Op, a.O, sr);
   __syncthreads();
-  SCLK(1);
-  f32x16 acc[C::RT][C::CT];
-  zero_acc<C>(acc);
-  slab_mma<C>(X, a.O, a.w3, SH, w, acc);                                    // dy W3: B[k = o][n] = W3[o][n]
-  wload<C>(w, a.w2, SH, SH, 0);
-  SCLK(2);
+  unsigned rb1[C::CT], rb2[C::CT];   // (RB = 0: never touched; see store_act_t)
+  bwd_layers<C, false>(L, w, a.w2, a.w3, a.O, sr, a.h1, a.h2, a.dh2, a.dh1, a.bits1, a.bits2, rb1, rb2, 1);
+}
+
+// One network's forward layers, PPO head and backward layers on a slab that stays in its workgroup (MlpStripTrain).  Against the
+// forward launch -> ppo_loss_kernel -> backward launch it drops: one slab tear-down and set-up (each reached in lock-step by the two
+// workgroups of a CU), the loss launch and its dependency edges, and the HBM round trips of y, dy and the mask bits.  Every product and
+// every row's arithmetic is the other path's: the same fwd_hidden / fwd_readout_partials / bwd_layers on the same per-row fmaf chains, the same
+// ascending-k sum of the read-out partials, lhw_ppo_head.h's head -- bit-identical h1, h2, y, dy, dh2, dh1.
+//   read-out sum: y = sum of the partials + b3 -> P[0] in place (each thread its own entries) and, if asked for, HBM
+//   head: a thread per minibatch row reads its y (and its twin's) from P[0], writes dy k-major into the input-slab region X (disjoint from
+//         P[0]), zero-padded as stage_input would, and the row's loss terms / dstd to HBM
+//   dy slab -> HBM once (the weight-gradient kernels read it), then bwd_layers with the mask words still in registers
+// Stamps: forward 0 .. 11, 12 read-out sum done, 13 head done (behind the barrier), backward 14 .. 20.
+template <class C, int CRITIC>
+__global__ void __launch_bounds__(C::THR, 2) mlp_train_strip_kernel(MlpStripTrain t) {
+  static_assert(C::RT == 2, "a twin slab is two row tiles");
+  __shared__ StripLds<C> L;
+  LHW_LDS_POISON(L);
+  const MlpStripFwd& a = t.f;
+  const int tid = threadIdx.x;
+  const int nrow = t.twin0 > 0 ? 32 : C::ROWS;   // minibatch rows per slab
+  const SlabRows<C> sr = t.twin0 > 0 ? SlabRows<C>::twins((int)blockIdx.x * 32, a.R, t.twin0) : SlabRows<C>::consecutive((int)blockIdx.x * C::ROWS, a.R);
+  unsigned rb1[C::CT], rb2[C::CT];
+  fwd_hidden<C, true>(L, a, sr, rb1, rb2);
+  float (*P)[C::ROWS][32] = fwd_readout_partials<C>(L, a);
+  constexpr int NQ = SH / SKQ;
+  for (int i = tid; i < C::ROWS * 32; i += C::THR) {
+    const int row = i >> 5, col = i & 31;
+    if (col < a.O) {
+      float s = P[0][row][col];
+#pragma unroll
+      for (int q = 1; q < NQ; q++) s += P[q][row][col];
+      s += a.b3[col];
+      if (a.y && sr.live(row)) a.y[(size_t)sr.grow(row) * a.Op + col] = s;
+      P[0][row][col] = s;
+    }
+  }
+  SCLK(12);
+  WOp<C> w;
+  wload<C>(w, t.w3, SH, a.O, 0);
+  __syncthreads();   // y is complete in P[0]; the other partials are spent
+  float (*X)[C::LD] = &L.S[SH - SXK];
+  const int Kp = (a.O + SBK - 1) & ~(SBK - 1), Kz = max(Kp, a.Op);
+  if (tid < nrow) {
+    const int m = (int)blockIdx.x * nrow + tid;
+    const bool twin = t.twin0 > 0;
+    if (m < a.R) {
+      if (CRITIC) {
+        float dv;
+        const float e2 = lhw_ppo_critic_row(t.head, m, P[0][tid][0], &dv);
+        X[0][tid] = dv;
+        for (int k = 1; k < Kz; k++) X[k][tid] = 0.f;
+        t.stat_rows[(size_t)t.stat_ld + m] = e2;
+      } else {
+        float st[NSTAT];
+        lhw_ppo_actor_row(t.head, m, &P[0][tid][0], twin ? &P[0][32 + tid][0] : nullptr, &X[0][tid], twin ? &X[0][32 + tid] : nullptr, C::LD, st);
+        for (int k = a.Op; k < Kz; k++) { X[k][tid] = 0.f; if (twin) X[k][32 + tid] = 0.f; }
+#pragma unroll
+        for (int k = 0; k < NSTAT; k++)
+          if (k != 1) t.stat_rows[(size_t)k * t.stat_ld + m] = st[k];
+      }
+    } else {
+      for (int k = 0; k < Kz; k++) { X[k][tid] = 0.f; if (twin) X[k][32 + tid] = 0.f; }
+    }
+  }
   __syncthreads();
-  SCLK(3);
-  store_act<C, true>(L, acc, nullptr, false, a.h2, a.dh2, row0, a.R, nullptr, a.bits2);
-  SCLK(4);
-  __syncthreads();
-  SCLK(5);
-  zero_acc<C>(acc);
-  slab_mma<C>(L.S, SH, a.w2, SH, w, acc);                                   // dh2 W2: B[k = o][n = i] = W2[o][i]
-  SCLK(6);
-  store_act<C, false>(L, acc, nullptr, false, a.h1, a.dh1, row0, a.R, nullptr, a.bits1);
-  SCLK(7);
+  SCLK(13);
+  for (int i = tid; i < C::ROWS * a.Op; i += C::THR) {
+    const int row = i / a.Op, k = i - row * a.Op;
+    if (sr.live(row)) t.dy[(size_t)sr.grow(row) * a.Op + k] = X[k][row];
+  }
+  bwd_layers<C, true>(L, w, t.w2, t.w3, a.O, sr, nullptr, nullptr, t.dh2, t.dh1, nullptr, nullptr, rb1, rb2, 14);
+}
+
+// the head on outputs in HBM, a thread per minibatch row: the unfused twin of mlp_train_strip_kernel's head (lhw_debug_mlp_train_strip)
+template <int CRITIC>
+__global__ void __launch_bounds__(256) ppo_head_rows_kernel(LhwPpoHead h, const float* y, int Op, int twin0, float* dy, float* stat_rows, int stat_ld) {
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= h.B) return;
+  if (CRITIC) {
+    float dv;
+    stat_rows[(size_t)stat_ld + m] = lhw_ppo_critic_row(h, m, y[(size_t)m * Op], &dv);
+    dy[(size_t)m * Op] = dv;
+    for (int k = 1; k < Op; k++) dy[(size_t)m * Op + k] = 0.f;
+  } else {
+    float st[NSTAT];
+    lhw_ppo_actor_row(h, m, y + (size_t)m * Op, y + ((size_t)twin0 + m) * Op, dy + (size_t)m * Op, dy + ((size_t)twin0 + m) * Op, 1, st);
+    for (int k = 0; k < NSTAT; k++)
+      if (k != 1) stat_rows[(size_t)k * stat_ld + m] = st[k];
+  }
 }
 
 // WT [cols][rows] <- W [rows][ld] for three matrices in one launch (the forward pass multiplies by W^T: its weight operand must
@@ -433,6 +599,57 @@ void mlp_strip_forward(const MlpStripFwd& a, hipStream_t s, int shape /* 0: by r
 void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s) {
   if (a.R <= 0) return;
   hipLaunchKernelGGL((mlp_bwd_strip_kernel<StripBig>), dim3((a.R + StripBig::ROWS - 1) / StripBig::ROWS), dim3(StripBig::THR), 0, s, a);
+}
+
+// (the head keeps dy's slab in the input-slab region: Op <= SXK; the critic head is ppo_loss_kernel's: one value in rows of four)
+bool mlp_train_strip_supported(int H, int Dp, int O, int Op, int critic) {
+  return mlp_strip_supported(H, Dp, O, Op) && Op <= SXK && (!critic || (O == 1 && Op == 4));
+}
+
+void mlp_train_strip(const MlpStripTrain& t, hipStream_t s) {
+  if (t.f.R <= 0) return;
+  const int nrow = t.twin0 > 0 ? 32 : StripBig::ROWS;
+  const dim3 grid((t.f.R + nrow - 1) / nrow), block(StripBig::THR);
+  if (t.critic) hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 1>), grid, block, 0, s, t);
+  else hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 0>), grid, block, 0, s, t);
+}
+
+// One network's forward + head + backward over a minibatch, outside an LhwPpo (tests, SIMT emulator).  fused = 1: mlp_train_strip_kernel.
+// fused = 0: the forward strip launch(es), the head as a thread-per-row kernel on y in HBM, the backward strip launch(es) -- the reference
+// the fused kernel must match bit for bit.
+extern "C" int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* q, int32_t fused, void* stream) {
+  if (!q || !q->w1 || !q->b1 || !q->w2 || !q->b2 || !q->w3 || !q->b3 || !q->x || !q->h1 || !q->h2 || !q->y || !q->dy || !q->dh2 || !q->dh1 ||
+      !q->stat_rows || !q->wt_scratch || (q->critic ? !q->ret : (!q->act || !q->old_logp || !q->adv || !q->stdv)))
+    return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (!mlp_train_strip_supported(q->H, q->Dp, q->O, q->Op, q->critic) || q->ldx < q->Dp || (q->ldx & 3))
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "train strip kernel: hidden width 256, padded input width <= 64, outputs <= 32 in rows of <= 64, critic 1 in 4");
+  const int mir = !q->critic && q->twin0 > 0;
+  if (q->B <= 0 || q->stat_ld < q->B || (mir && (q->twin0 < q->B || !q->act_src || !q->act_sign))) return lhw_fail(LHW_ERR_ARG, "bad row counts / mirror tables");
+  hipStream_t s = (hipStream_t)stream;
+  const int Dp = q->Dp, O = q->O, Op = q->Op, B = q->B;
+  mlp_strip_prepare(q->w1, q->w2, q->w3, Dp, O, Op, q->wt_scratch, s);
+  const float *w1t = q->wt_scratch, *w2t = w1t + (size_t)Dp * SH, *w3t = w2t + (size_t)SH * SH;
+  const LhwPpoHead h{B, O, Op, q->act, q->old_logp, q->adv, q->ret, q->stdv, q->clip, q->mirror_coeff, mir, q->act_src, q->act_sign, q->dstd,
+                     nullptr, nullptr, 0.f, 0.f, 1.f};
+  if (fused) {
+    MlpStripTrain t{MlpStripFwd{w1t, q->b1, w2t, q->b2, w3t, q->b3, q->x, q->ldx, Dp, O, Op, B, q->h1, q->h2, q->y}, q->w2, q->w3, q->dy, q->dh2, q->dh1,
+                    mir ? q->twin0 : 0, q->critic, h, q->stat_rows, q->stat_ld};
+    mlp_train_strip(t, s);
+  } else {
+    for (int pass = 0; pass <= mir; pass++) {
+      const size_t r0 = pass ? (size_t)q->twin0 : 0;
+      MlpStripFwd a{w1t, q->b1, w2t, q->b2, w3t, q->b3, q->x + r0 * q->ldx, q->ldx, Dp, O, Op, B, q->h1 + r0 * SH, q->h2 + r0 * SH, q->y + r0 * Op};
+      mlp_strip_forward(a, s, 2);
+    }
+    if (q->critic) hipLaunchKernelGGL(ppo_head_rows_kernel<1>, dim3((B + 255) / 256), dim3(256), 0, s, h, q->y, Op, 0, q->dy, q->stat_rows, q->stat_ld);
+    else hipLaunchKernelGGL(ppo_head_rows_kernel<0>, dim3((B + 255) / 256), dim3(256), 0, s, h, q->y, Op, q->twin0, q->dy, q->stat_rows, q->stat_ld);
+    for (int pass = 0; pass <= mir; pass++) {
+      const size_t r0 = pass ? (size_t)q->twin0 : 0;
+      MlpStripBwd a{q->w2, q->w3, q->dy + r0 * Op, q->h1 + r0 * SH, q->h2 + r0 * SH, O, Op, B, q->dh2 + r0 * SH, q->dh1 + r0 * SH};
+      mlp_strip_backward(a, s);
+    }
+  }
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "train strip launch failed");
 }
 
 extern "C" int lhw_debug_mlp_strip_forward_bits(int32_t H, int32_t Dp, int32_t O, int32_t Op, const float* w1, const float* b1, const float* w2,

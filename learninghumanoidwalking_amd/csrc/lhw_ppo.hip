@@ -727,8 +727,13 @@ struct LhwPpo : LearnerCore {
   // the critic's forward / backward chain runs on its own stream beside the actor's (they share only the gathered inputs and
   // the loss kernel): the load / multiply / store phases of one network's GEMMs overlap the other's
   hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_head = nullptr;
   int two_streams = 1;
+  // each network's forward, loss head and backward layers as one train strip launch (lhw_mlp_strip.hip) where the step allows it;
+  // LHW_STRIP_FUSED=0 / lhw_ppo_debug_set_strip_fused: forward strip, ppo_loss_kernel, backward strip
+  int strip_fused = 1;
+  float* stat_rows = nullptr;   // [NSTAT][max_rows]: the rows' loss terms the train strip launches leave for ppo_stats_rows_kernel
+  int last_grad_fused = 0;      // which path the last lhw_ppo_grad took (lhw_ppo_debug_last_grad_fused)
   // lhw_ppo_step: one optimiser step (lhw_ppo_grad + lhw_ppo_apply) captured once per (buffers, minibatch size, grad_scale) as a hipGraph
   // and replayed; the two things that change from step to step -- the minibatch's index pointer (gather_kernel) and Adam's bias
   // corrections (adam2_kernel) -- are patched into the executable graph's kernel nodes before each launch.  grad_scale is part of the key
@@ -737,7 +742,7 @@ struct LhwPpo : LearnerCore {
   hipGraphExec_t step_exec = nullptr;
   hipGraphNode_t node_gather = nullptr, node_adam = nullptr;
   const void* step_key[12] = {nullptr};
-  int step_key_b = 0, step_key_half = 0;
+  int step_key_b = 0, step_key_half = 0, step_key_fused = 0;
   uint32_t step_key_gs = 0;
   ~LhwPpo() {
     (void)hipSetDevice(device);
@@ -746,6 +751,7 @@ struct LhwPpo : LearnerCore {
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
+    if (ev_head) (void)hipEventDestroy(ev_head);
   }
 };
 
@@ -838,7 +844,9 @@ static BwdParts bwd_parts_carve(const MlpLayout& L, size_t rows, int passes, flo
 // (same seed -> bitwise identical weights, the property the reference's tests/test_determinism.py checks).
 static void mlp_backward(const MlpLayout& L, const float* theta, const float* x, int ldx, int R, const float* h1, const float* h2,
                          const float* dy, float* dh2, float* dh1, const BwdParts& P, BwdSlices& z, hipStream_t s, int half = 0,
-                         const HalfBufs* hb = nullptr, const unsigned* bits1 = nullptr, const unsigned* bits2 = nullptr) {
+                         const HalfBufs* hb = nullptr, const unsigned* bits1 = nullptr, const unsigned* bits2 = nullptr,
+                         bool have_dh = false /* dh2 / dh1 are already there (train strip launch): the weight gradients only.  Only where
+                                                 the strip path below would have made them: float32, a shape the strips take */) {
   GemmArgs g{};
   if (hb && half) {   // --fp16 update with fp16 storage: the same five GEMMs on the fp16 copies (dy and the weights are float32)
     auto H16 = [](const _Float16* q) { return reinterpret_cast<const float*>(q); };
@@ -869,8 +877,9 @@ static void mlp_backward(const MlpLayout& L, const float* theta, const float* x,
     z.w3 += nsl(R, KC_SKINNY); z.w2 += nsl(R, KC_WIDE); z.w1 += nsl(R, KC_SKINNY);
     return;
   }
-  const bool strip = strip_mode() >= 1 && !half && mlp_strip_supported(L.H, L.Dp, L.O, L.Op);
-  if (strip) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
+  // (have_dh: a train strip launch has taken the strip launch's place, so neither it nor the GEMMs below compute dh2 / dh1 again)
+  const bool strip = have_dh || (strip_mode() >= 1 && !half && mlp_strip_supported(L.H, L.Dp, L.O, L.Op));
+  if (strip && !have_dh) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
     MlpStripBwd a{theta + L.w2, theta + L.w3, dy, h1, h2, L.O, L.Op, R, dh2, dh1};
     a.bits1 = bits1; a.bits2 = bits2;
     mlp_strip_backward(a, s);
@@ -994,14 +1003,21 @@ __global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ m
   }
 }
 
-// PPO losses and their gradients wrt network outputs (reference rl/algos/ppo.py:302-384, FF path, mask = 1).
-// No atomics: bias / std gradients are column sums of dya / dyc / dstd taken afterwards in a fixed order, and the loss
-// scalars are written as per-block partials [gridDim.x][6]: 0 actor_loss 1 critic_loss 2 mirror_loss 3 approx_kl
-// 4 clip_fraction (already divided by B) 5 imitation_loss.
-// Imitation term (ppo.py:360-368): imitation_loss = mean over the selected (sample, action dim) entries of
-// (mu - expert)^2; the host evaluates the env's projector and the frozen expert and hands over the dense target / mask
-// in minibatch order (lhw_ppo_set_imitation); here the term enters the loss scalar and d loss / d mu.
-#define NSTAT 6
+// PPO losses and their gradients wrt network outputs: the per-row arithmetic is lhw_ppo_head.h's, here a thread per row on outputs
+// in HBM.  No atomics: bias / std gradients are column sums of dya / dyc / dstd taken afterwards in a fixed order, and the loss
+// scalars are written as per-block partials [gridDim.x][NSTAT] (clip_fraction already divided by B).
+// block reduction of the row terms (already scaled) in a fixed order: xor butterfly inside the wave, then waves 0..3
+__device__ __forceinline__ void ppo_stats_block(float (&vals)[NSTAT], float* __restrict__ stats_part) {
+  __shared__ float red[NSTAT][4];
+  LHW_LDS_POISON(red);
+  for (int o = 32; o > 0; o >>= 1)
+    for (int k = 0; k < NSTAT; k++) vals[k] += __shfl_xor(vals[k], o);
+  int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int k = 0; k < NSTAT; k++) red[k][wave] = vals[k];
+  __syncthreads();
+  if (threadIdx.x < NSTAT) stats_part[(size_t)blockIdx.x * NSTAT + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
 __global__ void __launch_bounds__(256) ppo_loss_kernel(int B, int Rcap, int A, int Op, const float* __restrict__ ya,
                                                        const float* __restrict__ yc, const float* __restrict__ act,
                                                        const float* __restrict__ old_logp, const float* __restrict__ adv,
@@ -1019,66 +1035,32 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(int B, int Rcap, int A, i
   // (time-major, seqB columns per step, mirrored columns appended per step): t * 2 seqB + b and + seqB
   size_t rn = (size_t)m, rm = (size_t)Rcap + m;
   if (seqB > 0 && use_mirror) { rn = (size_t)(m / seqB) * (2 * (size_t)seqB) + (size_t)(m % seqB); rm = rn + seqB; }
-  float s_actor = 0, s_critic = 0, s_mirror = 0, s_kl = 0, s_cf = 0, s_imit = 0;
+  const LhwPpoHead h{B, A, Op, act, old_logp, adv, ret, stdv, clip, mirror_coeff, use_mirror, act_src, act_sign, dstd, imit_target, imit_mask,
+                     imit_coeff, imit_inv_count, gscale};
+  float t[NSTAT] = {0, 0, 0, 0, 0, 0};
   const float invB = 1.f / (float)B, invBA = 1.f / ((float)B * (float)A);
-  __shared__ float red[NSTAT][4];
-  LHW_LDS_POISON(red);
   if (m < B) {
-    float lp = 0.f;
-    for (int a = 0; a < A; a++) {
-      float d = (act[(size_t)m * A + a] - ya[rn * Op + a]) / stdv[a];
-      lp += -0.5f * d * d - logf(stdv[a]) - 0.9189385332046727f;
-    }
-    float logr = lp - old_logp[m];
-    float ratio = expf(logr);
-    float ad = adv[m];
-    float cl = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
-    float cpi = ratio * ad, cll = cl * ad;
-    s_actor = -fminf(cpi, cll);
-    float dratio = (cpi <= cll) ? ad : 0.f;  // torch.min backward; ties inside the clip range carry the full gradient
-    float dlp = -invB * dratio * ratio;
-    s_kl = (ratio - 1.f) - logr;
-    s_cf = fabsf(ratio - 1.f) > clip ? 1.f : 0.f;
-    float v = yc[(size_t)m * 4];
-    float e = ret[m] - v;
-    s_critic = e * e;
-    dyc[(size_t)m * 4] = -2.f * e * invB * gscale;
+    lhw_ppo_actor_row(h, m, ya + rn * Op, ya + rm * Op, dya + rn * Op, dya + rm * Op, 1, t);
+    float dv;
+    t[1] = lhw_ppo_critic_row(h, m, yc[(size_t)m * 4], &dv);
+    dyc[(size_t)m * 4] = dv;
     dyc[(size_t)m * 4 + 1] = 0.f; dyc[(size_t)m * 4 + 2] = 0.f; dyc[(size_t)m * 4 + 3] = 0.f;
-    if (use_mirror) for (int a = 0; a < Op; a++) dya[rm * Op + a] = 0.f;
-    for (int a = 0; a < Op; a++) {
-      float g = 0.f, gs = 0.f;
-      if (a < A) {
-        float mu = ya[rn * Op + a], sd = stdv[a], x = act[(size_t)m * A + a];
-        g = dlp * (x - mu) / (sd * sd);
-        gs = dlp * ((x - mu) * (x - mu) / (sd * sd * sd) - 1.f / sd);
-        if (use_mirror) {
-          // mirror_actions[a] = sign[a] * mu_mir[src[a]]  (== mu_mir @ M_a, rl/envs/wrappers.py:49-51)
-          float mm = act_sign[a] * ya[rm * Op + act_src[a]];
-          float diff = mu - mm;
-          s_mirror += diff * diff;
-          g += mirror_coeff * 2.f * diff * invBA;
-          // gradient wrt the mirrored-pass output it came from (act_src is a permutation: each slot written once)
-          dya[rm * Op + act_src[a]] = -mirror_coeff * 2.f * diff * invBA * act_sign[a] * gscale;
-        }
-        if (imit_target && imit_mask[(size_t)m * A + a]) {
-          float diff = mu - imit_target[(size_t)m * A + a];
-          s_imit += diff * diff;
-          g += imit_coeff * 2.f * diff * imit_inv_count;
-        }
-      }
-      dya[rn * Op + a] = g * gscale;
-      if (dstd) dstd[(size_t)m * Op + a] = gs;
-    }
   }
-  // block reduction of the scalars in a fixed order (xor butterfly inside the wave, then waves 0..3)
-  float vals[NSTAT] = {s_actor * invB, s_critic * invB, s_mirror * invBA, s_kl * invB, s_cf * invB, s_imit * imit_inv_count};
-  for (int o = 32; o > 0; o >>= 1)
-    for (int k = 0; k < NSTAT; k++) vals[k] += __shfl_xor(vals[k], o);
-  int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int k = 0; k < NSTAT; k++) red[k][wave] = vals[k];
-  __syncthreads();
-  if (threadIdx.x < NSTAT) stats_part[(size_t)blockIdx.x * NSTAT + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  float vals[NSTAT] = {t[0] * invB, t[1] * invB, t[2] * invBA, t[3] * invB, t[4] * invB, t[5] * imit_inv_count};
+  ppo_stats_block(vals, stats_part);
+}
+
+// The loss scalars of a step whose heads ran inside the train strip kernels: those leave every row's terms in rows [NSTAT][ld] (term-major);
+// the same per-block partials as ppo_loss_kernel's, from the same values in the same order
+__global__ void __launch_bounds__(256) ppo_stats_rows_kernel(int B, int A, const float* __restrict__ rows, int ld, float imit_inv_count,
+                                                             float* __restrict__ stats_part) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  float t[NSTAT] = {0, 0, 0, 0, 0, 0};
+  if (m < B)
+    for (int k = 0; k < NSTAT; k++) t[k] = rows[(size_t)k * ld + m];
+  const float invB = 1.f / (float)B, invBA = 1.f / ((float)B * (float)A);
+  float vals[NSTAT] = {t[0] * invB, t[1] * invB, t[2] * invBA, t[3] * invB, t[4] * invB, t[5] * imit_inv_count};
+  ppo_stats_block(vals, stats_part);
 }
 
 // out[k] += sum_b part[b][n] in block order (single block; n small)
@@ -1325,7 +1307,9 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
   if (p->wt_a && p->wt_c && R % 64 == 0 && !(getenv("LHW_STRIP_BITS") && atoi(getenv("LHW_STRIP_BITS")) == 0)) {
     mem.get(&p->bits_a, 4 * mlp_strip_bits_words(R)); mem.get(&p->bits_c, 2 * mlp_strip_bits_words(R));
   }
+  p->strip_fused = !(getenv("LHW_STRIP_FUSED") && atoi(getenv("LHW_STRIP_FUSED")) == 0);
   if (p->wt_a && p->wt_c) {
+    mem.get(&p->stat_rows, NSTAT * R);
     mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op)));
     mem.get(&p->wt_roll, mlp_strip_wt_floats(p->la.Dp, p->la.Op) + mlp_strip_wt_floats(p->lc.Dp, p->lc.Op));
   }
@@ -1333,7 +1317,8 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
   p->two_streams = !(getenv("LHW_PPO_TWO_STREAMS") && atoi(getenv("LHW_PPO_TWO_STREAMS")) == 0);
   ok = ok && hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess &&
        hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
+       hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&p->ev_head, hipEventDisableTiming) == hipSuccess;
   if (!ok) return lhw_fail(LHW_ERR_HIP, "PPO workspace allocation failed (max_rows=%d) or bad mirror table", c->max_rows);
   *out = p.release();
   return LHW_OK;
@@ -1372,6 +1357,14 @@ extern "C" int lhw_ppo_set_update_dtype(LhwPpo* p, int fp16) {
   p->update_half = fp16 ? 1 : 0;
   return LHW_OK;
 }
+
+extern "C" int lhw_ppo_debug_set_strip_fused(LhwPpo* p, int32_t on) {
+  if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
+  p->strip_fused = on ? 1 : 0;
+  return LHW_OK;
+}
+
+extern "C" int lhw_ppo_debug_last_grad_fused(const LhwPpo* p) { return p ? p->last_grad_fused : LHW_ERR_ARG; }
 
 extern "C" int64_t lhw_ppo_param_count(const LhwPpo* p) { return p ? (int64_t)p->n_params : LHW_ERR_ARG; }
 
@@ -1633,6 +1626,56 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
     ham = HalfBufs{p->xb_h + (size_t)R * ldh, ldh, p->h1a_h + (size_t)R * p->H, p->h2a_h + (size_t)R * p->H, p->dh2a_h + (size_t)R * p->H, p->dh1a_h + (size_t)R * p->H};
   }
   const HalfBufs *pha = hstore ? &ha : nullptr, *phc = hstore ? &hc : nullptr, *pham = hstore ? &ham : nullptr;
+  const BwdParts Pa = bwd_parts_carve(p->la, R, 2, p->bwd_part);
+  const BwdParts Pc = bwd_parts_carve(p->lc, R, 1, p->bwd_part + bwd_parts_floats(p->la, R, 2));
+  BwdSlices za, zc;
+  // Train strips: per network ONE launch runs the forward layers, the loss head and the backward layers (mlp_train_strip_kernel) -- no join
+  // between the passes, no loss launch, no mask bits; the weight-gradient kernels follow as on the other path.  With mirroring a slab pairs
+  // 32 rows with their twins, whatever B (a ragged last slab has dead rows in both tiles).  Not for an armed imitation term, --fp16, or
+  // shapes the strips reject: those take the path below.
+  if (strips && p->strip_fused && !p->imit_target && p->stat_rows && mlp_train_strip_supported(p->la.H, p->la.Dp, p->la.O, p->la.Op, 0) &&
+      mlp_train_strip_supported(p->lc.H, p->lc.Dp, p->lc.O, p->lc.Op, 1)) {
+    const size_t H = p->H;
+    p->last_grad_fused = 1;
+    const LhwPpoHead head{B, p->A, Op, p->mb_act, p->mb_logp, p->mb_adv, p->mb_ret, theta + p->off_std, p->clip, p->mirror_coeff, mir, p->d_act_src,
+                          p->d_act_sign, p->learn_std ? p->dstd : (float*)nullptr, nullptr, nullptr, 0.f, 0.f, 1.f};
+    auto train = [&](const MlpLayout& L, const float* th, float* wt, float* h1, float* h2, float* dy, float* dh2, float* dh1, int twin0, int critic, hipStream_t st) {
+      MlpStripTrain t{MlpStripFwd{wt, th + L.b1, wt + (size_t)L.Dp * L.H, th + L.b2, wt + (size_t)L.Dp * L.H + (size_t)L.H * L.H, th + L.b3, p->xb, Dp, L.Dp, L.O, L.Op,
+                                  B, h1, h2, nullptr},
+                      th + L.w2, th + L.w3, dy, dh2, dh1, twin0, critic, head, p->stat_rows, R};
+      mlp_train_strip(t, st);
+    };
+    fork();
+    train(p->lc, th_c, p->wt_c, p->h1c, p->h2c, p->dyc, p->dh2c, p->dh1c, 0, 1, sc);
+    mlp_backward(p->lc, th_c, p->xb, Dp, B, p->h1c, p->h2c, p->dyc, p->dh2c, p->dh1c, Pc, zc, sc, 0, nullptr, nullptr, nullptr, true);
+    train(p->la, th_a, p->wt_a, p->h1a, p->h2a, p->dya, p->dh2a, p->dh1a, mir ? R : 0, 0, s);
+    // (the step's loss statistics -- logging only -- are summed at the tail of the side stream, off both chains, once the actor's rows are there)
+    const int nblk = (B + 255) / 256;
+    if (sc != s) { (void)hipEventRecord(p->ev_head, s); (void)hipStreamWaitEvent(sc, p->ev_head, 0); }
+    hipLaunchKernelGGL(ppo_stats_rows_kernel, dim3(nblk), dim3(256), 0, sc, B, p->A, p->stat_rows, R, p->imit_inv_count, p->stats_part);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, sc, p->stats_part, nblk, NSTAT, stats_dev);
+    if (p->learn_std) {
+      colsum_det(p->dstd, B, Op, p->A, grad + p->off_std, p->part, s);
+      hipLaunchKernelGGL(entropy_grad_kernel, dim3(1), dim3(64), 0, s, theta + p->off_std, p->A, p->ent_coeff, grad + p->off_std);
+    }
+    if (mir && B == R) {
+      mlp_backward(p->la, th_a, p->xb, Dp, 2 * B, p->h1a, p->h2a, p->dya, p->dh2a, p->dh1a, Pa, za, s, 0, nullptr, nullptr, nullptr, true);
+    } else {
+      mlp_backward(p->la, th_a, p->xb, Dp, B, p->h1a, p->h2a, p->dya, p->dh2a, p->dh1a, Pa, za, s, 0, nullptr, nullptr, nullptr, true);
+      if (mir)
+        mlp_backward(p->la, th_a, p->xb + (size_t)R * Dp, Dp, B, p->h1a + (size_t)R * H, p->h2a + (size_t)R * H, p->dya + (size_t)R * Op,
+                     p->dh2a + (size_t)R * H, p->dh1a + (size_t)R * H, Pa, za, s, 0, nullptr, nullptr, nullptr, true);
+    }
+    join();
+    SegList S;
+    S.n = 0; S.scale = 1.f;
+    mlp_backward_segments(S, p->la, grad + p->off_actor, Pa, za);
+    mlp_backward_segments(S, p->lc, grad + p->off_critic, Pc, zc);
+    launch_reduce_segments(S, s);
+    HIPCHK(hipGetLastError());
+    return LHW_OK;
+  }
+  p->last_grad_fused = 0;
   // forward: rows [0,B) and, if mirroring, rows [R, R+B)
   // ReLU masks as bits from the forward strips to the backward strips (per layer: normal rows, then the mirrored rows' launch)
   const size_t bw = mlp_strip_bits_words(R);
@@ -1662,9 +1705,6 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
     colsum_det(p->dstd, B, Op, p->A, grad + p->off_std, p->part, s);
     hipLaunchKernelGGL(entropy_grad_kernel, dim3(1), dim3(64), 0, s, theta + p->off_std, p->A, p->ent_coeff, grad + p->off_std);
   }
-  const BwdParts Pa = bwd_parts_carve(p->la, R, 2, p->bwd_part);
-  const BwdParts Pc = bwd_parts_carve(p->lc, R, 1, p->bwd_part + bwd_parts_floats(p->la, R, 2));
-  BwdSlices za, zc;
   fork();
   // (the step's loss statistics -- logging only -- are summed at the head of the side stream, off the actor's chain)
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, sc, p->stats_part, nblk, NSTAT, stats_dev);
@@ -1756,7 +1796,7 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
   HIPCHK(hipSetDevice(p->device));
   const void* key[12] = {theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream};
   uint32_t gs_key; memcpy(&gs_key, &grad_scale, sizeof gs_key);
-  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_gs == gs_key;
+  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_fused == p->strip_fused && p->step_key_gs == gs_key;
   for (int i = 0; same && i < 12; i++) same = p->step_key[i] == key[i];
   const size_t na = p->learn_std ? p->off_std + p->A : p->off_std;
   const float bc1 = 1.f - powf(p->beta1, (float)step), bc2s = sqrtf(1.f - powf(p->beta2, (float)step));
@@ -1787,7 +1827,7 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
     if (!p->node_gather || !p->node_adam) return lhw_fail(LHW_ERR_HIP, "lhw_ppo_step: gather / Adam nodes not found in the captured graph (%zu nodes)", nn);
     HIPCHK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
     for (int i = 0; i < 12; i++) p->step_key[i] = key[i];
-    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_gs = gs_key;
+    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_fused = p->strip_fused; p->step_key_gs = gs_key;
   }
   // patch the two nodes: the kernels' full argument lists, as lhw_ppo_grad / clip_and_adam pass them
   {

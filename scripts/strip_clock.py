@@ -1,6 +1,8 @@
 """Phase timeline of the MLP strip kernels from a -DLHW_STRIP_CLOCK build (scripts/build_variant.sh clock -DLHW_STRIP_CLOCK; run with
 LHW_LIB=<that library>): per-wave wall-clock stamps at the phase boundaries -> when the workgroups start, how long each phase takes, how much of
-it is waiting at a barrier.  usage: python scripts/strip_clock.py [rows] [fwd|bwd]"""
+it is waiting at a barrier.  usage: python scripts/strip_clock.py [rows] [fwd|bwd|train|train-mirror|train-critic]
+(train*: mlp_train_strip_kernel through lhw_debug_mlp_train_strip, fused = 1 -- the actor on `rows` rows, the actor on rows / 2 rows and their
+mirrored twins, the critic)"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -28,20 +30,34 @@ def bwd():
     _lib.check(L.lhw_debug_mlp_strip_backward(256, O, Op, p(d["w2"]), p(d["w3"]), p(d["dy"]), R, p(h1), p(h2), p(dh2), p(dh1), None))
 
 
-f = fwd if which == "fwd" else bwd
-names = {"fwd": ["stage x", "L1 products", "barrier", "L1 epilogue", "barrier", "L2 products", "barrier", "L2 epilogue", "barrier", "read-out products", "barrier",
-                 "read-out sum + store"],
-         "bwd": ["stage dy", "dh2 products", "barrier", "dh2 epilogue", "barrier", "dh1 products", "dh1 epilogue"]}[which]
+def train():
+    run_train_strip(L, tc, 1, **targs)
+
+
+if which.startswith("train"):
+    # (the train strip's inputs -- weights plus a PPO minibatch whose ratios cross the clip range -- and its argument struct are built by the
+    # test module's helpers, as make_case above: an analysis run measures exactly the call the tests check, and there is one builder to keep)
+    from tests.test_emu_train_strip import make_train_case, run_train_strip
+    B = R // 2 if which == "train-mirror" else R
+    tc = make_train_case(B=B, Dp=Dp, critic=which == "train-critic", twin0=B if which == "train-mirror" else 0, seed=0)
+    dt = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32}
+    targs = dict(ptr=lambda t: t.data_ptr(), alloc=lambda shape, t, fill: torch.full(shape, fill, dtype=dt[np.dtype(t)], device="cuda"),
+                 dev=lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda())
+FWD = ["stage x", "L1 products", "barrier", "L1 epilogue", "barrier", "L2 products", "barrier", "L2 epilogue", "barrier", "read-out products", "barrier"]
+f = {"fwd": fwd, "bwd": bwd}.get(which, train)
+BWD = ["dh2 products", "barrier", "dh2 epilogue", "barrier", "dh1 products", "dh1 epilogue"]
+names = {"fwd": FWD + ["read-out sum + store"], "bwd": ["stage dy"] + BWD}.get(
+    which, FWD + ["read-out sum to LDS", "barrier + head + barrier", "dy slab -> HBM"] + BWD)
 for _ in range(3):
     f()
 torch.cuda.synchronize()
 f()
 torch.cuda.synchronize()
-buf = np.zeros(2048 * 4 * 16, np.uint64)
+buf = np.zeros(2048 * 4 * 32, np.uint64)      # SCLK_N stamps per wave (lhw_mlp_strip.hip)
 L.lhw_debug_strip_clock_read.argtypes = [ctypes.c_void_p]
 assert L.lhw_debug_strip_clock_read(buf.ctypes.data) == 0
-nb = min(2048, (R + 63) // 64)
-t = buf.reshape(2048, 4, 16)[:nb].astype(np.int64)
+nb = min(2048, (R + 63) // 64)      # (train-mirror: rows / 2 rows in slabs of 32 + 32: the same count)
+t = buf.reshape(2048, 4, 32)[:nb].astype(np.int64)
 t0 = t[:, :, 0].min()
 ns = 10.0   # 100 MHz
 n = len(names)
