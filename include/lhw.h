@@ -415,6 +415,25 @@ int lhw_debug_policy_step(const LhwRolloutPolicy* policy, const float* obs, int3
  * the means.  The per-step reference of lhw_env_rollout_lstm where lhw_rnn_forward is not built (SIMT emulator); bitwise equal to both. */
 int lhw_debug_lstm_policy_step(const LhwRolloutLstmPolicy* policy, const float* obs, int32_t R, const uint8_t* reset, uint32_t env_id_base,
                                uint32_t counter, float* y, float* act, float* logp, void* stream);
+/* Test hook for the recurrent update's whole-sequence strip kernels (csrc/lhw_mlp_strip.hip: lstm_seq_fwd_strip_kernel /
+ * lstm_seq_bwd_strip_kernel; the time loops of lhw_rnn_grad, reference rl/algos/ppo.py:512-533 over Gaussian_LSTM_Actor / LSTM_V,
+ * rl/policies/actor.py:191-286, critic.py:52-112): the forward pass and the BPTT of ONE network's two stacked cells over a [T][Bt] sequence
+ * minibatch (rows r = t * Bt + b) on caller-owned device buffers, without the read-out, the loss and the weight gradients.  w1 [4H][Dp + H] =
+ * [W_ih1 | W_hh1], w2 [4H][2H] = [W_ih2 | W_hh2], biases [4H] (gate order i f g o); reset [T][Bt] u8: an episode starts at step t of row b.
+ * passes & 1, forward: reads the x columns of xh1 [R][Dp + H]; writes its recurrent columns, xh2 [R][2H], the activated gates g1 / g2 [R][4H],
+ * c1 / c2 / h2 [R][H].  passes & 2, backward: reads those and dh2 [R][H] (d loss / d h2) and overwrites g1 / g2 with d loss / d pre-activation.
+ * scratch: (Dp + 3H) * 4H + 5 * Bt * H floats.  fused = 1: one launch per pass (LHW_ERR_UNSUPPORTED outside the LHW_LSTM_SEQ_* bounds; every
+ * buffer 16-byte aligned).  fused = 0: the launch-per-step loops with a thread-per-output fmaf-chain kernel for the products and the two
+ * functions of csrc/lhw_lstm_cell.h -- any shape, the same arithmetic, bit for bit. */
+typedef struct LhwLstmSeqArgs {
+  int32_t H, Dp, T, Bt, passes;
+  const float *w1, *bi1, *bh1, *w2, *bi2, *bh2;
+  const uint8_t* reset;
+  const float* dh2;
+  float *xh1, *xh2, *g1, *g2, *c1, *c2, *h2;
+  float* scratch;
+} LhwLstmSeqArgs;
+int lhw_debug_lstm_seq(const LhwLstmSeqArgs* args, int32_t fused, void* stream);
 /* Diagnostic (load balance): the first call arms the recording; later calls return, per env, the shader-clock cycles its
  * wavefront group spent in the most recent control-step launch.  HOST pointer [N] int64, synchronous; humanoid tasks only. */
 int lhw_env_debug_wave_cycles(LhwEnv* env, int64_t* cycles_host);
@@ -561,6 +580,18 @@ int lhw_rnn_grad(LhwRnn* rnn, const float* theta, float* grad, int32_t T, int32_
                  const int32_t* cols, int32_t B, float* stats_dev, void* stream);
 int lhw_rnn_apply(LhwRnn* rnn, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
                   void* stream);
+/* Shapes the whole-sequence strip kernels cover (a workgroup of hidden / 32 waves per 32 minibatch rows; the slabs [pad4(obs) + 3 hidden][32]
+ * forward and [4 hidden][32] backward must fit the 160 KB of LDS): hidden a multiple of 32 in [MIN_HIDDEN, MAX_HIDDEN], pad4(obs) <= MAX_OBS_PAD.
+ * Other shapes keep lhw_rnn_grad's launch-per-step loops. */
+#define LHW_LSTM_SEQ_MIN_HIDDEN 32
+#define LHW_LSTM_SEQ_MAX_HIDDEN 256
+#define LHW_LSTM_SEQ_MAX_OBS_PAD 128
+/* debug / A-B: on != 0: lhw_rnn_grad runs each network's forward time loop and its BPTT time loop (rl/algos/ppo.py:512-533) as ONE launch each
+ * (the whole-sequence strip kernels, the critic's on a side stream) where the shape is covered; 0: four launches per time step and network.
+ * Same bits either way.  A new handle takes the environment's LHW_RNN_SEQ_FUSED (default 1: the A/B of DESIGN.md 4.2c). */
+int lhw_rnn_debug_set_seq_fused(LhwRnn* rnn, int32_t on);
+/* test hook: 1 if the last lhw_rnn_grad of this handle ran the whole-sequence strip kernels, 0 if the launch-per-step loops */
+int lhw_rnn_debug_last_grad_fused(const LhwRnn* rnn);
 /* lhw_ppo_debug_grad_sqnorms for the recurrent handle (the norms of the last lhw_rnn_apply) */
 int lhw_rnn_debug_grad_sqnorms(LhwRnn* rnn, float* out2_host);
 /* xn (and xm) for the recurrent path: same as lhw_ppo_normalize but on an LhwRnn handle */

@@ -162,3 +162,21 @@ void lhw_transpose3(const LhwTransposeJob (&jobs)[3], hipStream_t s);
 void mlp_strip_prepare(const float* w1, const float* w2, const float* w3, int Dp, int O, int Op, float* wt, hipStream_t s);
 void mlp_strip_forward(const MlpStripFwd& a, hipStream_t s, int shape = 0);   // shape: 0 by row count, 1 small (32-row slabs), 2 big (64-row)
 void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s);
+
+// Whole-sequence LSTM strip kernels of the recurrent update (lhw_mlp_strip.hip: lstm_seq_fwd_strip_kernel / lstm_seq_bwd_strip_kernel): the
+// time loops of lhw_rnn_grad's forward pass and BPTT for one network (two stacked cells) as one launch each.  A workgroup owns 32 rows b of
+// the [T][Bt] minibatch for all T steps.  Buffers are lhw_ppo.hip's SeqWs (rows r = t * Bt + b).
+struct LstmSeqStrip {
+  const float *w1t, *w2t;                    // forward: [in][out] copies from lstm_seq_strip_prepare, [Dp + H][4H] and [2H][4H]
+  const float *w1, *w2;                      // backward: theta's own [4H][Dp + H] = [W_ih1 | W_hh1] and [4H][2H] = [W_ih2 | W_hh2]
+  const float *bi1, *bh1, *bi2, *bh2;        // [4H] each
+  float *xh1, *xh2, *g1, *g2, *c1, *c2, *h2; // [R][Dp + H] (x columns: input), [R][2H], [R][4H] x 2, [R][H] x 3
+  const float* dh2;                          // backward: d loss / d h2 [R][H]
+  const unsigned char* reset;                // [T][Bt]: an episode starts at step t of row b
+  int T, Bt, H, Dp;
+};
+bool lstm_seq_strip_supported(int H, int Dp);   // LHW_LSTM_SEQ_* bounds of include/lhw.h
+size_t lstm_seq_strip_wt_floats(int H, int Dp);
+void lstm_seq_strip_prepare(const float* w1, const float* w2, int H, int Dp, float* wt, hipStream_t s);   // wt -> w1t, then w2t
+void lstm_seq_strip_forward(const LstmSeqStrip& a, hipStream_t s);
+void lstm_seq_strip_backward(const LstmSeqStrip& a, hipStream_t s);

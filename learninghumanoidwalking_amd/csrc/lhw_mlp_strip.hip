@@ -768,3 +768,378 @@ extern "C" int lhw_debug_lstm_policy_step(const LhwRolloutLstmPolicy* q, const f
   hipLaunchKernelGGL(lstm_policy_ref_kernel, dim3(R), dim3(LSH), 0, (hipStream_t)stream, *q, obs, R, reset, env_id_base, counter, y, act, logp);
   return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "lstm_policy_ref_kernel launch failed");
 }
+
+// =========================================================================================== whole-sequence LSTM strip kernels
+// The time loops of the recurrent update (lhw_rnn_grad, lhw_ppo.hip; reference rl/algos/ppo.py:512-533, the BPTT over whole trajectories of
+// Gaussian_LSTM_Actor / LSTM_V) for one network as ONE launch per pass instead of four launches per time step.  The rows of a sequence
+// minibatch are independent -- a row's h_t, c_t depend on its own x_t, h_{t-1}, c_{t-1} and the weights -- so a workgroup that owns a slab of
+// 32 rows b of the [T][Bt] minibatch runs all T steps by itself: no grid synchronisation, no flag, no waiting on another workgroup.
+//
+// Workgroup = H / 32 waves (64 .. 512 threads); wave w owns the hidden units 32 w .. 32 w + 31 of both cells.  As in the MLP strips above the
+// weights are the MFMA's A operand, read from global memory (L2) with the output unit contiguous, and the slab, k-major in LDS (S[k][row]),
+// is its B operand, so lane l of an accumulator tile owns slab row l % 32 and the units 8 g + 4 (l / 32) + 0..3 of register quad g.
+//   forward   per step and cell the wave multiplies FOUR tiles -- the gate columns j, H + j, 2H + j, 3H + j of its units -- over ascending k of
+//             [x_t | h1_{t-1}] resp. [h1_t | h2_{t-1}]: every gate pre-activation is the fmaf chain from +0 that gemm_f32_kernel computes, all
+//             four gates of a (row, unit) land in ONE lane, and lhw_lstm_cell runs on the accumulators.  c1 / c2 stay in registers for the whole
+//             sequence, h1_t / h2_t reach the next product through the LDS slabs [Dp + H][32] and [2H][32]; x_{t+1} is staged while cell 1's
+//             epilogue runs.  Three barriers per step.  Every buffer of SeqWs is written exactly as the launch-per-step loop writes it.
+//   backward  t = T - 1 .. 0: lhw_lstm_cell_bwd for cell 2 on values from HBM, d [h1_t | h2_{t-1}] = dG2 W2 (two tiles per wave: its units of
+//             d h1_t and of d h2_{t-1}), cell 1 on the first tile, d h1_{t-1} = dG1 W1[:, Dp:] (one tile).  The outputs of both products land in
+//             the lanes that need them next, so the two d c carries and the two d h carries never leave registers; LDS holds only the product's
+//             operand, the slab's d pre-activations [4H][32] (128 KB at H = 256), written by the cell phase as it stores them to g1 / g2.
+//             Four barriers per step.
+// Rows beyond Bt in the last slab load nothing and store nothing (their slab entries are zeros).
+#define QH 256          // largest hidden width (8 waves)
+#define QDP 128         // largest padded input width: (QDP + 3 QH) * 128 B + 16 KB of biases = 128 KB of LDS forward, 4 QH * 128 B = 128 KB backward, of 160 KB
+#define QCH 4           // MFMAs (k pairs) per weight register buffer
+
+struct SeqFwdLds { float S1[QDP + QH][32]; float S2[2 * QH][32]; float B[4][4 * QH]; };   // B: b_ih1, b_hh1, b_ih2, b_hh2
+struct SeqBwdLds { float G[4 * QH][32]; };
+
+// the wave's index as a value the compiler knows to be uniform: the weight addresses built from it are scalar bases plus one 32-bit lane offset
+#ifdef __HIP_EMU__
+#define SEQ_WAVE() ((int)(threadIdx.x >> 6))
+#else
+#define SEQ_WAVE() __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+#endif
+
+__device__ __forceinline__ void seq_zero(f32x16& acc) {
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0.f;
+}
+
+// acc[q] += (S[0 .. K)[32 rows] ^T Bg[0 .. K)[n0[q] .. n0[q] + 32))^T for the wave's NT tiles: chains over ascending k, two k per MFMA.  K even.
+// The weights of the next QCH k pairs are in flight while the current ones are multiplied (loads clamped to the last k pair, products guarded).
+// n0 must be wave-uniform (SEQ_WAVE).
+template <int NT>
+__device__ __forceinline__ void seq_mma(const float (*S)[32], const int K, const float* __restrict__ Bg, const int ldb, const int (&n0)[NT], f32x16 (&acc)[NT]) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, kh = lane >> 5;
+  const unsigned voff = (unsigned)(kh * ldb + l31);
+  float w0[QCH][NT], w1[QCH][NT];
+  auto load = [&](float (&w)[QCH][NT], const int k0) {
+#pragma unroll
+    for (int kk = 0; kk < QCH; kk++) {
+      const float* __restrict__ row = Bg + (size_t)min(k0 + 2 * kk, K - 2) * ldb;
+#pragma unroll
+      for (int q = 0; q < NT; q++) w[kk][q] = (row + n0[q])[voff];
+    }
+  };
+  auto mul = [&](const float (&w)[QCH][NT], const int k0) {
+#pragma unroll
+    for (int kk = 0; kk < QCH; kk++)
+      if (k0 + 2 * kk < K) {
+        const float s = S[k0 + 2 * kk + kh][l31];
+#pragma unroll
+        for (int q = 0; q < NT; q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[kk][q], s, acc[q], 0, 0, 0);
+      }
+  };
+  load(w0, 0);
+  for (int k0 = 0; k0 < K; k0 += 4 * QCH) {
+    load(w1, k0 + 2 * QCH);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(w0, k0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(w0, k0 + 4 * QCH);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(w1, k0 + 2 * QCH);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+__device__ __forceinline__ void seq_ld4(float (&v)[4], const float* __restrict__ p) {
+  const float4 t = *reinterpret_cast<const float4*>(p);
+  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+__device__ __forceinline__ void seq_st4(float* __restrict__ p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+
+// One cell's forward epilogue on the wave's four gate tiles: lhw_lstm_cell per (row, unit); activated gates -> G, c -> C, h -> dest_a (always)
+// and dest_b (the next step's recurrent slot, zeroed where that step starts an episode; NULL at the last step), for live rows; h k-major into
+// the slabs sa (NULL: not needed) and sb (with dest_b's zeroing).  row: this lane's row r of the step's [Bt][.] blocks.  bi / bh: the bias vectors
+// in LDS (read from global memory they are loop-invariant loads, which the compiler hoists out of the time loop -- 256 values per lane: 79 spilled VGPRs)
+__device__ __forceinline__ void seq_cell_fwd(const f32x16 (&acc)[4], float (&c)[16], const float* bi, const float* bh, const int H,
+                                             const bool first, const bool rst, const bool rnext, const bool live, const size_t row,
+                                             float* __restrict__ G, float* __restrict__ C, float* __restrict__ dest_a, const int lda,
+                                             float* __restrict__ dest_b, const int ldb, float (*sa)[32], float (*sb)[32]) {
+  const int lane = threadIdx.x & 63, wave = SEQ_WAVE(), l31 = lane & 31, kh = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const int j0 = 32 * wave + 8 * g + 4 * kh;
+    float b_i[4][4], b_h[4][4], gt[4][4], hv[4], hz[4], cv[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { seq_ld4(b_i[q], bi + q * H + j0); seq_ld4(b_h[q], bh + q * H + j0); }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int r = 4 * g + e;
+      const float b_ih[4] = {b_i[0][e], b_i[1][e], b_i[2][e], b_i[3][e]}, b_hh[4] = {b_h[0][e], b_h[1][e], b_h[2][e], b_h[3][e]};
+      float gq[4], cn;
+      hv[e] = lhw_lstm_cell(acc[0][r], acc[1][r], acc[2][r], acc[3][r], b_ih, b_hh, (first || rst) ? 0.f : c[r], gq, &cn);
+      c[r] = cn; cv[e] = cn;
+      hz[e] = rnext ? 0.f : hv[e];
+      gt[0][e] = gq[0]; gt[1][e] = gq[1]; gt[2][e] = gq[2]; gt[3][e] = gq[3];
+      if (sa) sa[j0 + e][l31] = hv[e];
+      if (sb) sb[j0 + e][l31] = hz[e];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) seq_st4(G + row * 4 * H + q * H + j0, gt[q]);
+      seq_st4(C + row * H + j0, cv);
+      seq_st4(dest_a + row * lda + j0, hv);
+      if (dest_b) seq_st4(dest_b + row * ldb + j0, hz);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // one register quad at a time
+  }
+}
+
+__global__ void __launch_bounds__(2 * QH) lstm_seq_fwd_strip_kernel(LstmSeqStrip a) {
+  __shared__ SeqFwdLds L;
+  LHW_LDS_POISON(L);
+  const int tid = threadIdx.x, lane = tid & 63, wave = SEQ_WAVE(), l31 = lane & 31, nthr = (int)blockDim.x;
+  const int H = a.H, Dp = a.Dp, K1 = Dp + H, Bt = a.Bt, T = a.T;
+  const int b0 = (int)blockIdx.x * 32, b = b0 + l31;
+  const bool live = b < Bt;
+  // x_t of the slab's rows, k-major, zeros for the rows beyond Bt
+  auto stage_x = [&](const int t) {
+    for (int i = tid; i < 32 * Dp; i += nthr) {
+      const int row = i / Dp, k = i - row * Dp;
+      L.S1[k][row] = b0 + row < Bt ? a.xh1[((size_t)t * Bt + b0 + row) * K1 + k] : 0.f;
+    }
+  };
+  // the recurrent slots of step 0 start from zero: in the slabs and in the workspaces (the backward pass and the weight-gradient GEMMs read those)
+  for (int i = tid; i < 4 * H; i += nthr) { L.B[0][i] = a.bi1[i]; L.B[1][i] = a.bh1[i]; L.B[2][i] = a.bi2[i]; L.B[3][i] = a.bh2[i]; }
+  for (int i = tid; i < 32 * H; i += nthr) {
+    L.S1[Dp + (i >> 5)][i & 31] = 0.f;
+    L.S2[H + (i >> 5)][i & 31] = 0.f;
+    const int row = i / H, k = i - row * H;
+    if (b0 + row < Bt) { a.xh1[(size_t)(b0 + row) * K1 + Dp + k] = 0.f; a.xh2[(size_t)(b0 + row) * 2 * H + H + k] = 0.f; }
+  }
+  stage_x(0);
+  __syncthreads();
+  float c1[16], c2[16];
+#pragma unroll
+  for (int r = 0; r < 16; r++) { c1[r] = 0.f; c2[r] = 0.f; }
+  const int n0[4] = {32 * wave, H + 32 * wave, 2 * H + 32 * wave, 3 * H + 32 * wave};
+  for (int t = 0; t < T; t++) {
+    const size_t row = (size_t)t * Bt + b;
+    const bool last = t + 1 == T;
+    const bool rst = live && a.reset[row] != 0, rnext = !last && live && a.reset[row + Bt] != 0;
+    f32x16 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+    seq_mma<4>(L.S1, K1, a.w1t, 4 * H, n0, acc);
+    __syncthreads();   // every wave is done with [x_t | h1_{t-1}]
+    seq_cell_fwd(acc, c1, L.B[0], L.B[1], H, t == 0, rst, rnext, live, row, a.g1, a.c1, a.xh2, 2 * H, last ? (float*)nullptr : a.xh1 + (size_t)Bt * K1 + Dp, K1,
+                 L.S2, last ? (float (*)[32])nullptr : &L.S1[Dp]);
+    if (!last) stage_x(t + 1);
+    __syncthreads();   // h1_t is in both slabs
+#pragma unroll
+    for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+    seq_mma<4>(L.S2, 2 * H, a.w2t, 4 * H, n0, acc);
+    __syncthreads();   // every wave is done with [h1_t | h2_{t-1}]
+    seq_cell_fwd(acc, c2, L.B[2], L.B[3], H, t == 0, rst, rnext, live, row, a.g2, a.c2, a.h2, H, last ? (float*)nullptr : a.xh2 + (size_t)Bt * 2 * H + H, 2 * H,
+                 (float (*)[32])nullptr, last ? (float (*)[32])nullptr : &L.S2[H]);
+  }
+}
+
+// One cell's backward on the lane's (row, units): activated gates from G, c / c_prev from C, dh_a from DH [R][H] in HBM (cell 2) or, DH == NULL,
+// from the accumulator tile dacc (cell 1), dh_b / the d c carry from registers; d pre-activation -> G (live rows) and k-major into the slab S
+// (zeros for the rows beyond Bt)
+__device__ __forceinline__ void seq_cell_bwd(const float* __restrict__ DH, const f32x16& dacc, const float (&dhb)[16], float (&dcar)[16], const int H, const bool first, const bool rst,
+                                             const bool no_next, const bool live, const size_t row, const int Bt, float* __restrict__ G,
+                                             const float* __restrict__ C, float (*S)[32]) {
+  const int lane = threadIdx.x & 63, wave = SEQ_WAVE(), l31 = lane & 31, kh = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const int j0 = 32 * wave + 8 * g + 4 * kh;
+    float gt[4][4], cv[4], cp[4], d[4][4], dha[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { cv[e] = 0.f; cp[e] = 0.f; gt[0][e] = 0.f; gt[1][e] = 0.f; gt[2][e] = 0.f; gt[3][e] = 0.f; dha[e] = DH ? 0.f : dacc[4 * g + e]; }
+    if (live) {
+      if (DH) seq_ld4(dha, DH + row * H + j0);
+#pragma unroll
+      for (int q = 0; q < 4; q++) seq_ld4(gt[q], G + row * 4 * H + q * H + j0);
+      seq_ld4(cv, C + row * H + j0);
+      if (!first) seq_ld4(cp, C + (row - Bt) * H + j0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int r = 4 * g + e;
+      const float gq[4] = {gt[0][e], gt[1][e], gt[2][e], gt[3][e]};
+      float dq[4];
+      lhw_lstm_cell_bwd(gq, cv[e], cp[e], rst, dha[e], dhb[r], no_next, &dcar[r], dq);
+#pragma unroll
+      for (int q = 0; q < 4; q++) { d[q][e] = dq[q]; S[q * H + j0 + e][l31] = dq[q]; }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) seq_st4(G + row * 4 * H + q * H + j0, d[q]);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // (as in seq_cell_fwd)
+  }
+}
+
+__global__ void __launch_bounds__(2 * QH) lstm_seq_bwd_strip_kernel(LstmSeqStrip a) {
+  __shared__ SeqBwdLds L;
+  LHW_LDS_POISON(L);
+  const int tid = threadIdx.x, lane = tid & 63, wave = SEQ_WAVE(), l31 = lane & 31;
+  const int H = a.H, Dp = a.Dp, K1 = Dp + H, Bt = a.Bt, T = a.T;
+  const int b = (int)blockIdx.x * 32 + l31;
+  const bool live = b < Bt;
+  float dc1[16], dc2[16], dh1c[16], dh2c[16];   // the carries: d c of both cells, d h1_t / d h2_t from step t + 1
+#pragma unroll
+  for (int r = 0; r < 16; r++) { dc1[r] = 0.f; dc2[r] = 0.f; dh1c[r] = 0.f; dh2c[r] = 0.f; }
+  const int n2[2] = {32 * wave, H + 32 * wave}, n1[1] = {Dp + 32 * wave};
+  for (int t = T - 1; t >= 0; t--) {
+    const size_t row = (size_t)t * Bt + b;
+    const bool last = t + 1 == T;
+    const bool rst = live && a.reset[row] != 0, no_next = last || (live && a.reset[row + Bt] != 0);
+    f32x16 acc2[2];
+    seq_cell_bwd(a.dh2, acc2[0], dh2c, dc2, H, t == 0, rst, no_next, live, row, Bt, a.g2, a.c2, L.G);
+    __syncthreads();   // dG2 of the slab is in LDS
+    seq_zero(acc2[0]); seq_zero(acc2[1]);
+    seq_mma<2>(L.G, 4 * H, a.w2, 2 * H, n2, acc2);       // d [h1_t | h2_{t-1}] = dG2 W2
+#pragma unroll
+    for (int r = 0; r < 16; r++) dh2c[r] = acc2[1][r];
+    __syncthreads();   // every wave is done with dG2
+    seq_cell_bwd(nullptr, acc2[0], dh1c, dc1, H, t == 0, rst, no_next, live, row, Bt, a.g1, a.c1, L.G);
+    __syncthreads();   // dG1 of the slab is in LDS
+    f32x16 acc1[1];
+    seq_zero(acc1[0]);
+    seq_mma<1>(L.G, 4 * H, a.w1, K1, n1, acc1);          // d h1_{t-1} = dG1 W1[:, Dp:]
+#pragma unroll
+    for (int r = 0; r < 16; r++) dh1c[r] = acc1[0][r];
+    __syncthreads();   // every wave is done with dG1
+  }
+}
+
+bool lstm_seq_strip_supported(int H, int Dp) {
+  return H >= LHW_LSTM_SEQ_MIN_HIDDEN && H <= LHW_LSTM_SEQ_MAX_HIDDEN && H % 32 == 0 && Dp > 0 && Dp <= LHW_LSTM_SEQ_MAX_OBS_PAD && Dp % 4 == 0;
+}
+static_assert(LHW_LSTM_SEQ_MAX_HIDDEN == QH && LHW_LSTM_SEQ_MAX_OBS_PAD == QDP, "include/lhw.h states the kernels' bounds");
+
+size_t lstm_seq_strip_wt_floats(int H, int Dp) { return (size_t)(Dp + H) * 4 * H + (size_t)2 * H * 4 * H; }
+
+void lstm_seq_strip_prepare(const float* w1, const float* w2, int H, int Dp, float* wt, hipStream_t s) {
+  const LhwTransposeJob jobs[3] = {{w1, wt, 4 * H, Dp + H, Dp + H, 4 * H}, {w2, wt + (size_t)(Dp + H) * 4 * H, 4 * H, 2 * H, 2 * H, 4 * H}, {nullptr, nullptr, 0, 0, 0, 0}};
+  lhw_transpose3(jobs, s);
+}
+
+void lstm_seq_strip_forward(const LstmSeqStrip& a, hipStream_t s) {
+  if (a.T <= 0 || a.Bt <= 0) return;
+  hipLaunchKernelGGL(lstm_seq_fwd_strip_kernel, dim3((a.Bt + 31) / 32), dim3(2 * a.H), 0, s, a);
+}
+void lstm_seq_strip_backward(const LstmSeqStrip& a, hipStream_t s) {
+  if (a.T <= 0 || a.Bt <= 0) return;
+  hipLaunchKernelGGL(lstm_seq_bwd_strip_kernel, dim3((a.Bt + 31) / 32), dim3(2 * a.H), 0, s, a);
+}
+
+// ---- the plain reference of lhw_debug_lstm_seq: the launch-per-step loops of lhw_rnn_grad with a thread per output in place of the MFMA GEMM
+// C [M][N] (ld ldc) = A [M][K] (ld lda) B, B[k][n] at B[k * sk + n * sn]: one fmaf chain over ascending k from +0 per output
+__global__ void __launch_bounds__(256) seq_ref_gemm_kernel(int M, int N, int K, const float* __restrict__ A, int lda, const float* __restrict__ B, int sk, int sn,
+                                                           float* __restrict__ C, int ldc) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)M * N) return;
+  const int m = (int)(i / N), n = (int)(i - (size_t)m * N);
+  float s = 0.f;
+  for (int k = 0; k < K; k++) s = fmaf(A[(size_t)m * lda + k], B[(size_t)k * sk + (size_t)n * sn], s);
+  C[(size_t)m * ldc + n] = s;
+}
+// (lstm_cell_fwd_kernel / lstm_cell_bwd_kernel of lhw_ppo.hip: the same two header functions on the same operands)
+__global__ void __launch_bounds__(256) seq_ref_cell_fwd_kernel(int B, int H, float* __restrict__ G, const float* __restrict__ bi, const float* __restrict__ bh,
+                                                               const float* __restrict__ c_prev, const unsigned char* __restrict__ reset_t, float* __restrict__ c_out,
+                                                               float* __restrict__ dest_a, int lda, float* __restrict__ dest_b, int ldb,
+                                                               const unsigned char* __restrict__ reset_next) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * H) return;
+  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
+  float* g = G + (size_t)b * 4 * H;
+  const float cp = (c_prev && !reset_t[b]) ? c_prev[(size_t)b * H + j] : 0.f;
+  const float b_ih[4] = {bi[j], bi[H + j], bi[2 * H + j], bi[3 * H + j]}, b_hh[4] = {bh[j], bh[H + j], bh[2 * H + j], bh[3 * H + j]};
+  float gt[4], c;
+  const float h = lhw_lstm_cell(g[j], g[H + j], g[2 * H + j], g[3 * H + j], b_ih, b_hh, cp, gt, &c);
+  g[j] = gt[0]; g[H + j] = gt[1]; g[2 * H + j] = gt[2]; g[3 * H + j] = gt[3];
+  c_out[(size_t)b * H + j] = c;
+  dest_a[(size_t)b * lda + j] = h;
+  if (dest_b) dest_b[(size_t)b * ldb + j] = reset_next[b] ? 0.f : h;
+}
+__global__ void __launch_bounds__(256) seq_ref_cell_bwd_kernel(int B, int H, float* __restrict__ G, const float* __restrict__ c, const float* __restrict__ c_prev,
+                                                               const unsigned char* __restrict__ reset_t, const float* __restrict__ dh_a, int lda,
+                                                               const float* __restrict__ dh_b, int ldb, const unsigned char* __restrict__ reset_next,
+                                                               float* __restrict__ dcar) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * H) return;
+  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
+  float* g = G + (size_t)b * 4 * H;
+  const float gt[4] = {g[j], g[H + j], g[2 * H + j], g[3 * H + j]};
+  const bool rst = reset_t[b] != 0, no_next = !dh_b || reset_next[b];
+  float dc = dcar[(size_t)b * H + j], d[4];
+  lhw_lstm_cell_bwd(gt, c[(size_t)b * H + j], (c_prev && !rst) ? c_prev[(size_t)b * H + j] : 0.f, rst, dh_a[(size_t)b * lda + j],
+                    no_next ? 0.f : dh_b[(size_t)b * ldb + j], no_next, &dc, d);
+  dcar[(size_t)b * H + j] = dc;
+  g[j] = d[0]; g[H + j] = d[1]; g[2 * H + j] = d[2]; g[3 * H + j] = d[3];
+}
+__global__ void __launch_bounds__(256) seq_ref_zero_kernel(int B, int H, float* __restrict__ p, int ld) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)B * H) p[(i / H) * ld + i % H] = 0.f;
+}
+
+extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* stream) {
+  if (!q || !q->w1 || !q->bi1 || !q->bh1 || !q->w2 || !q->bi2 || !q->bh2 || !q->reset || !q->xh1 || !q->xh2 || !q->g1 || !q->g2 || !q->c1 || !q->c2 || !q->h2 ||
+      !q->scratch || ((q->passes & 2) && !q->dh2))
+    return lhw_fail(LHW_ERR_ARG, "null argument");
+  const int H = q->H, Dp = q->Dp, T = q->T, Bt = q->Bt, K1 = Dp + H;
+  if (H <= 0 || Dp <= 0 || (Dp & 3) || T <= 0 || Bt <= 0 || !(q->passes & 3)) return lhw_fail(LHW_ERR_ARG, "bad shape (H=%d Dp=%d T=%d Bt=%d passes=%d)", H, Dp, T, Bt, q->passes);
+  hipStream_t s = (hipStream_t)stream;
+  if (fused) {
+    if (!lstm_seq_strip_supported(H, Dp))
+      return lhw_fail(LHW_ERR_UNSUPPORTED, "LSTM sequence strip kernels: hidden width a multiple of 32 in [%d, %d], padded input width <= %d", LHW_LSTM_SEQ_MIN_HIDDEN,
+                      LHW_LSTM_SEQ_MAX_HIDDEN, LHW_LSTM_SEQ_MAX_OBS_PAD);
+    const void* al[] = {q->bi1, q->bh1, q->bi2, q->bh2, q->xh1, q->xh2, q->g1, q->g2, q->c1, q->c2, q->h2, q->dh2};
+    for (const void* p : al)
+      if (reinterpret_cast<size_t>(p) & 15) return lhw_fail(LHW_ERR_ARG, "buffers must be 16-byte aligned");
+    float* wt = q->scratch;
+    LstmSeqStrip a{wt, wt + (size_t)K1 * 4 * H, q->w1, q->w2, q->bi1, q->bh1, q->bi2, q->bh2, q->xh1, q->xh2, q->g1, q->g2, q->c1, q->c2, q->h2, q->dh2, q->reset, T, Bt, H, Dp};
+    if (q->passes & 1) {
+      lstm_seq_strip_prepare(q->w1, q->w2, H, Dp, wt, s);
+      lstm_seq_strip_forward(a, s);
+    }
+    if (q->passes & 2) lstm_seq_strip_backward(a, s);
+    return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence strip launch failed");
+  }
+  const int nb = (int)(((size_t)Bt * H + 255) / 256);
+  auto gemm = [&](int M, int N, int K, const float* A, int lda, const float* B, int sk, int sn, float* C, int ldc) {
+    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, B, sk, sn, C, ldc);
+  };
+  if (q->passes & 1) {
+    hipLaunchKernelGGL(seq_ref_zero_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->xh1 + Dp, K1);
+    hipLaunchKernelGGL(seq_ref_zero_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->xh2 + H, 2 * H);
+    for (int t = 0; t < T; t++) {
+      const size_t r0 = (size_t)t * Bt;
+      const bool last = t + 1 == T;
+      const unsigned char* rnext = last ? nullptr : q->reset + r0 + Bt;
+      gemm(Bt, 4 * H, K1, q->xh1 + r0 * K1, K1, q->w1, 1, K1, q->g1 + r0 * 4 * H, 4 * H);
+      hipLaunchKernelGGL(seq_ref_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g1 + r0 * 4 * H, q->bi1, q->bh1, t ? q->c1 + (r0 - Bt) * H : (const float*)nullptr,
+                         q->reset + r0, q->c1 + r0 * H, q->xh2 + r0 * 2 * H, 2 * H, last ? (float*)nullptr : q->xh1 + (r0 + Bt) * K1 + Dp, K1, rnext);
+      gemm(Bt, 4 * H, 2 * H, q->xh2 + r0 * 2 * H, 2 * H, q->w2, 1, 2 * H, q->g2 + r0 * 4 * H, 4 * H);
+      hipLaunchKernelGGL(seq_ref_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g2 + r0 * 4 * H, q->bi2, q->bh2, t ? q->c2 + (r0 - Bt) * H : (const float*)nullptr,
+                         q->reset + r0, q->c2 + r0 * H, q->h2 + r0 * H, H, last ? (float*)nullptr : q->xh2 + (r0 + Bt) * 2 * H + H, 2 * H, rnext);
+    }
+  }
+  if (q->passes & 2) {
+    float *dx2 = q->scratch, *dx1h = dx2 + (size_t)Bt * 2 * H, *dcar1 = dx1h + (size_t)Bt * H, *dcar2 = dcar1 + (size_t)Bt * H;
+    (void)hipMemsetAsync(dcar1, 0, sizeof(float) * 2 * Bt * H, s);
+    for (int t = T - 1; t >= 0; t--) {
+      const size_t r0 = (size_t)t * Bt;
+      const bool last = t + 1 == T;
+      const unsigned char* rnext = last ? nullptr : q->reset + r0 + Bt;
+      hipLaunchKernelGGL(seq_ref_cell_bwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g2 + r0 * 4 * H, q->c2 + r0 * H, t ? q->c2 + (r0 - Bt) * H : (const float*)nullptr,
+                         q->reset + r0, q->dh2 + r0 * H, H, last ? (const float*)nullptr : dx2 + H, 2 * H, rnext, dcar2);
+      gemm(Bt, 2 * H, 4 * H, q->g2 + r0 * 4 * H, 4 * H, q->w2, 2 * H, 1, dx2, 2 * H);
+      hipLaunchKernelGGL(seq_ref_cell_bwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g1 + r0 * 4 * H, q->c1 + r0 * H, t ? q->c1 + (r0 - Bt) * H : (const float*)nullptr,
+                         q->reset + r0, dx2, 2 * H, last ? (const float*)nullptr : dx1h, H, rnext, dcar1);
+      gemm(Bt, H, 4 * H, q->g1 + r0 * 4 * H, 4 * H, q->w1 + Dp, K1, 1, dx1h, H);
+    }
+  }
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence reference launch failed");
+}

@@ -1912,6 +1912,18 @@ struct LhwRnn : LearnerCore {
   float *mb_act = nullptr, *mb_logp = nullptr, *mb_adv = nullptr, *mb_ret = nullptr, *dstd = nullptr;
   float *part = nullptr;
   float *wt_roll = nullptr;        // the actor's [in][out] weight copies for the resident rollout (lhw_rnn_rollout_policy), allocated by its first call
+  // whole-sequence strip kernels (lhw_mlp_strip.hip) in place of the two time loops of lhw_rnn_grad: LHW_RNN_SEQ_FUSED / lhw_rnn_debug_set_seq_fused
+  int seq_fused = 1;
+  int last_grad_fused = 0;         // which path the last lhw_rnn_grad took (lhw_rnn_debug_last_grad_fused)
+  float* wt_seq[2] = {nullptr, nullptr};   // [in][out] copies of W1cat, W2cat for the forward strip kernel (actor, critic), made once per lhw_rnn_grad; NULL: shape not covered
+  hipStream_t side = nullptr;      // the critic's time loops run beside the actor's, as in lhw_ppo_grad
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  ~LhwRnn() {
+    (void)hipSetDevice(device);
+    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+  }
 };
 
 // gates G [B][4H] (pre-activation, biases not yet added) -> activated in place; c, h of this step (lhw_lstm_cell.h: the arithmetic of one unit).
@@ -1945,18 +1957,15 @@ __global__ void __launch_bounds__(256) lstm_cell_bwd_kernel(int B, int H, float*
   if (i >= (size_t)B * H) return;
   const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
   float* g = G + (size_t)b * 4 * H;
-  const float gi = g[j], gf = g[H + j], gg = g[2 * H + j], go = g[3 * H + j];
+  const float gt[4] = {g[j], g[H + j], g[2 * H + j], g[3 * H + j]};
   const bool rst = reset_t && reset_t[b];
   const float cp = (c_prev && !rst) ? c_prev[(size_t)b * H + j] : 0.f;
-  float dh = dh_a[(size_t)b * lda + j];
-  if (dh_b && !(reset_next && reset_next[b])) dh += dh_b[(size_t)b * ldb + j];
-  const float tc = tanhf(c[(size_t)b * H + j]);
-  const float dct = dh * go * (1.f - tc * tc) + dcar[(size_t)b * H + j];
-  dcar[(size_t)b * H + j] = rst ? 0.f : dct * gf;
-  g[j] = dct * gg * gi * (1.f - gi);
-  g[H + j] = dct * cp * gf * (1.f - gf);
-  g[2 * H + j] = dct * gi * (1.f - gg * gg);
-  g[3 * H + j] = dh * tc * go * (1.f - go);
+  const bool no_next = !dh_b || (reset_next && reset_next[b]);
+  const float dhb = no_next ? 0.f : dh_b[(size_t)b * ldb + j];
+  float dc = dcar[(size_t)b * H + j], d[4];
+  lhw_lstm_cell_bwd(gt, c[(size_t)b * H + j], cp, rst, dh_a[(size_t)b * lda + j], dhb, no_next, &dc, d);
+  dcar[(size_t)b * H + j] = dc;
+  g[j] = d[0]; g[H + j] = d[1]; g[2 * H + j] = d[2]; g[3 * H + j] = d[3];
 }
 
 // (obs - mean) / std written into the x part of a concatenated input buffer (row stride ld)
@@ -2002,8 +2011,21 @@ __global__ void seq_gather_kernel(const int* __restrict__ idx, int T, int N, int
   }
 }
 
-static void lstm_seq_forward(const LstmLayout& L, const float* th, SeqWs& w, int T, const unsigned char* reset, hipStream_t s) {
+static LstmSeqStrip seq_strip_args(const LstmLayout& L, const float* th, const SeqWs& w, int T, const unsigned char* reset, const float* wt) {
+  return LstmSeqStrip{wt, wt + (size_t)L.K1 * 4 * L.H, th + L.w1, th + L.w2, th + L.bi1, th + L.bh1, th + L.bi2, th + L.bh2,
+                      w.xh1, w.xh2, w.g1, w.g2, w.c1, w.c2, w.h2, w.dh2, reset, T, w.Bt, L.H, L.Dp};
+}
+
+// wt != NULL: the time loop as one launch (lstm_seq_fwd_strip_kernel; wt = the [in][out] weight copies), else four launches per step
+static void lstm_seq_forward(const LstmLayout& L, const float* th, SeqWs& w, int T, const unsigned char* reset, hipStream_t s, const float* wt = nullptr) {
   const int Bt = w.Bt, H = L.H, K1 = L.K1;
+  if (wt) {
+    lstm_seq_strip_forward(seq_strip_args(L, th, w, T, reset, wt), s);
+    GemmArgs g{};
+    g.A = w.h2; g.lda = H; g.B = th + L.wo; g.ldb = H; g.C = w.y; g.ldc = L.Op; g.M = T * Bt; g.N = L.O; g.K = H; g.bias = th + L.bo;
+    launch_gemm<true, true>(g, s);
+    return;
+  }
   const int nb = (int)(((size_t)Bt * H + 255) / 256);
   // the recurrent slots of step 0 start from zero
   (void)hipMemset2DAsync(w.xh1 + L.Dp, sizeof(float) * K1, 0, sizeof(float) * H, Bt, s);
@@ -2029,14 +2051,14 @@ static void lstm_seq_forward(const LstmLayout& L, const float* th, SeqWs& w, int
   launch_gemm<true, true>(g, s);
 }
 
-// BPTT given w.dy; accumulates the parameter gradients of this network into grad (same layout as theta)
-static void lstm_seq_backward(const LstmLayout& L, const float* th, float* grad, SeqWs& w, int T, const unsigned char* reset,
-                              float* part, int k_chunk, hipStream_t s) {
+// BPTT given w.dy: d loss / d pre-activation of every step into w.g1 / w.g2 (wt != NULL: the time loop as one launch, lstm_seq_bwd_strip_kernel)
+static void lstm_seq_bptt(const LstmLayout& L, const float* th, SeqWs& w, int T, const unsigned char* reset, hipStream_t s, const float* wt = nullptr) {
   const int Bt = w.Bt, H = L.H, K1 = L.K1, R = T * Bt;
   const int nb = (int)(((size_t)Bt * H + 255) / 256);
   GemmArgs g{};
   g.A = w.dy; g.lda = L.Op; g.B = th + L.wo; g.ldb = H; g.C = w.dh2; g.ldc = H; g.M = R; g.N = H; g.K = L.O;
   launch_gemm<true, false>(g, s);
+  if (wt) { lstm_seq_strip_backward(seq_strip_args(L, th, w, T, reset, wt), s); return; }
   (void)hipMemsetAsync(w.dcar1, 0, sizeof(float) * Bt * H, s);
   (void)hipMemsetAsync(w.dcar2, 0, sizeof(float) * Bt * H, s);
   for (int t = T - 1; t >= 0; t--) {
@@ -2056,8 +2078,12 @@ static void lstm_seq_backward(const LstmLayout& L, const float* th, float* grad,
     g.A = w.g1 + r0 * 4 * H; g.lda = 4 * H; g.B = th + L.w1 + L.Dp; g.ldb = K1; g.C = w.dx1h; g.ldc = H; g.M = Bt; g.N = H; g.K = 4 * H;
     launch_gemm<true, false>(g, s);
   }
-  // parameter gradients: contractions over all R = T * Bt rows at once
-  g = GemmArgs{};
+}
+
+// accumulates the parameter gradients of this network into grad (same layout as theta): contractions over all R = T * Bt rows at once
+static void lstm_seq_wgrad(const LstmLayout& L, float* grad, SeqWs& w, int T, float* part, int k_chunk, hipStream_t s) {
+  const int Bt = w.Bt, H = L.H, K1 = L.K1, R = T * Bt;
+  GemmArgs g{};
   g.A = w.g2; g.lda = 4 * H; g.B = w.xh2; g.ldb = 2 * H; g.C = grad + L.w2; g.ldc = 2 * H; g.M = 4 * H; g.N = 2 * H; g.K = R; g.part = part; g.k_chunk = k_chunk;
   launch_gemm<false, false>(g, s);
   colsum_det(w.g2, R, 4 * H, 4 * H, grad + L.bi2, part, s);
@@ -2105,11 +2131,25 @@ extern "C" int lhw_rnn_create(const LhwPpoConfig* c, int32_t seq_len, int32_t se
   alloc(&p->stats, 16); alloc(&p->stats_part, ((Rm + 255) / 256) * NSTAT); alloc(&p->norm_part, 2 * SUMSQ_BLOCKS);
   const size_t max_slices = (2 * Rm + 2047) / 2048;
   alloc(&p->part, std::max<size_t>(max_slices * 4 * H * std::max<size_t>(K1, 2 * H), (size_t)COLSUM_CHUNKS * 4 * H));
+  p->seq_fused = !(getenv("LHW_RNN_SEQ_FUSED") && atoi(getenv("LHW_RNN_SEQ_FUSED")) == 0);
+  if (lstm_seq_strip_supported(p->H, p->la.Dp)) {
+    for (int n = 0; n < 2; n++) alloc(&p->wt_seq[n], lstm_seq_strip_wt_floats(p->H, p->la.Dp));
+    if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess)
+      return lhw_fail(LHW_ERR_HIP, "recurrent PPO: side stream / event creation failed");
+  }
   if (p->mem.failed() || !learner_mirror(*p, c))
     return lhw_fail(LHW_ERR_HIP, "recurrent PPO workspace allocation failed (T=%d cols=%d) or bad mirror table", seq_len, seq_cols);
   *out = p.release();
   return LHW_OK;
 }
+
+extern "C" int lhw_rnn_debug_set_seq_fused(LhwRnn* p, int32_t on) {
+  if (!p) return lhw_fail(LHW_ERR_ARG, "null argument");
+  p->seq_fused = on ? 1 : 0;
+  return LHW_OK;
+}
+extern "C" int lhw_rnn_debug_last_grad_fused(const LhwRnn* p) { return p ? p->last_grad_fused : LHW_ERR_ARG; }
 
 extern "C" int64_t lhw_rnn_param_count(const LhwRnn* p) { return p ? (int64_t)p->n_params : LHW_ERR_ARG; }
 
@@ -2227,8 +2267,23 @@ extern "C" int lhw_rnn_grad(LhwRnn* p, const float* theta, float* grad, int32_t 
   hipLaunchKernelGGL(seq_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, cols, T, N, B, Bt, Dp, K1, p->A, xn, mir ? xm : (const float*)nullptr,
                      act, old_logp, adv, ret, done, p->wa.xh1, p->wc.xh1, p->mb_act, p->mb_logp, p->mb_adv, p->mb_ret, reset_a, reset_c);
   const float *th_a = theta + p->off_actor, *th_c = theta + p->off_critic;
-  lstm_seq_forward(p->la, th_a, p->wa, T, reset_a, s);
-  lstm_seq_forward(p->lc, th_c, p->wc, T, reset_c, s);
+  // Whole-sequence strips: each network's forward time loop and BPTT time loop are one launch each; a slab of 32 rows occupies one CU for the whole
+  // sequence, so the critic's launches run on the side stream beside the actor's.  Everything that accumulates into grad or uses the shared
+  // split-K scratch stays on `s` in the order of the other path: the same seed gives the same bits on either path.
+  const bool fused = p->seq_fused && p->wt_seq[0] && p->wt_seq[1] && p->side;
+  p->last_grad_fused = fused ? 1 : 0;
+  hipStream_t sc = fused ? p->side : s;
+  auto fork = [&]() { if (sc != s) { (void)hipEventRecord(p->ev_fork, s); (void)hipStreamWaitEvent(sc, p->ev_fork, 0); } };
+  auto join = [&]() { if (sc != s) { (void)hipEventRecord(p->ev_join, sc); (void)hipStreamWaitEvent(s, p->ev_join, 0); } };
+  const float *wt_a = fused ? p->wt_seq[0] : nullptr, *wt_c = fused ? p->wt_seq[1] : nullptr;
+  fork();
+  if (fused) {
+    lstm_seq_strip_prepare(th_c + p->lc.w1, th_c + p->lc.w2, p->H, Dp, p->wt_seq[1], sc);
+    lstm_seq_strip_prepare(th_a + p->la.w1, th_a + p->la.w2, p->H, Dp, p->wt_seq[0], s);
+  }
+  lstm_seq_forward(p->la, th_a, p->wa, T, reset_a, s, wt_a);
+  lstm_seq_forward(p->lc, th_c, p->wc, T, reset_c, sc, wt_c);
+  join();
   const int nblk = (R + 255) / 256;
   // the loss kernel writes d loss / d read-out for the normal rows (and the mirrored rows); rows it does not own stay zero
   HIPCHK(hipMemsetAsync(p->wa.dy, 0, sizeof(float) * (size_t)T * Bt * Op, s));
@@ -2242,8 +2297,12 @@ extern "C" int lhw_rnn_grad(LhwRnn* p, const float* theta, float* grad, int32_t 
     hipLaunchKernelGGL(entropy_grad_kernel, dim3(1), dim3(64), 0, s, theta + p->off_std, p->A, p->ent_coeff, grad + p->off_std);
   }
   const int kc = 2048;
-  lstm_seq_backward(p->la, th_a, grad + p->off_actor, p->wa, T, reset_a, p->part, kc, s);
-  lstm_seq_backward(p->lc, th_c, grad + p->off_critic, p->wc, T, reset_c, p->part, kc, s);
+  fork();
+  lstm_seq_bptt(p->lc, th_c, p->wc, T, reset_c, sc, wt_c);
+  lstm_seq_bptt(p->la, th_a, p->wa, T, reset_a, s, wt_a);
+  lstm_seq_wgrad(p->la, grad + p->off_actor, p->wa, T, p->part, kc, s);
+  join();
+  lstm_seq_wgrad(p->lc, grad + p->off_critic, p->wc, T, p->part, kc, s);
   HIPCHK(hipGetLastError());
   return LHW_OK;
 }

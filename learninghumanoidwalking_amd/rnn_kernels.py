@@ -74,6 +74,16 @@ class RnnKernels(_Kernels):
         _lib.check(self._L.lhw_rnn_grad(self._h, _p(self.theta), _p(self.grad), int(T), int(N), _p(xn), _p(xm), _p(act), _p(old_logp),
                                         _p(adv), _p(ret), _p(done), _p(cols), int(cols.numel()), _p(self.stats), self._stream()))
 
+    def set_seq_fused(self, on):
+        """A/B switch: the forward and BPTT time loops of ``grad_columns`` as one whole-sequence strip launch each per network (``True``)
+        or as four launches per time step (``False``).  Same bits either way; a new handle takes ``LHW_RNN_SEQ_FUSED`` from the environment."""
+        _lib.check(self._L.lhw_rnn_debug_set_seq_fused(self._h, int(bool(on))))
+
+    @property
+    def last_grad_fused(self):
+        """1 if the last ``grad_columns`` ran the whole-sequence strip kernels, 0 if the launch-per-step loops (shape not covered, or switched off)."""
+        return int(self._L.lhw_rnn_debug_last_grad_fused(self._h))
+
 
 def reference_init_lstm(obs_dim, act_dim, hidden=256, init_std=0.2, generator_seed=None):
     """Initial weights with the RNG consumption of the reference's recurrent constructors (reference
