@@ -353,11 +353,11 @@ int lhw_env_pop_rerun_count(LhwEnv* env, int64_t* reruns);
 int lhw_debug_gemm(int32_t a_kc, int32_t b_kc, int32_t wt, int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* B,
                    int32_t ldb, float* C, int32_t ldc, const float* bias, int32_t relu, const float* mask, int32_t ldmask,
                    int32_t k_chunk, float* part, float* colsum, float* colsum_out, void* stream);
-/* Test hook for the wide weight gradient of the update (csrc/lhw_ppo.hip: wgrad_wide_kernel; reference /root/reference/rl/algos/ppo.py:387-396,
+/* Test hook for the wide weight gradient of the update (csrc/lhw_gemm.hip: wgrad_wide_kernel; reference /root/reference/rl/algos/ppo.py:387-396,
  * the hidden layer's part of loss.backward()): per k slice z of k_chunk rows, part[z] [256][256] = A[rows of z]^T B[rows of z] and
  * colsum[z] [256] = column sums of A's rows (A, B: [K][256] device buffers, dh2 and h1; colsum may be NULL).  The caller reduces the slices. */
 int lhw_debug_wgrad_wide(const float* A, const float* B, int32_t K, int32_t k_chunk, float* part, float* colsum, void* stream);
-/* Test hook for the fused skinny weight gradients of the update (csrc/lhw_ppo.hip: wgrad_skinny_kernel; reference
+/* Test hook for the fused skinny weight gradients of the update (csrc/lhw_gemm.hip: wgrad_skinny_kernel; reference
  * /root/reference/rl/algos/ppo.py:387-396, the first- and last-layer parts of loss.backward()): dW1 [H][Dp] += dh1^T x, db1 += colsum(dh1),
  * dW3 [O][H] += dy^T h2, db3 += colsum(dy) over R rows in one launch.  H = 256, Dp <= 64 (multiple of 4), O <= Op <= 32; device buffers;
  * scratch: ceil(R / max(128, ceil(R / 256))) x (256 Dp + 256 + 256 O + O) floats. */

@@ -210,7 +210,7 @@ __device__ __forceinline__ void policy_step(const LhwRolloutPolicy& q, float* sc
 
 // ------------------------------------------------------------------------------------------------ LSTM actor
 // Gaussian_LSTM_Actor (rl/policies/actor.py:191-286: two stacked LSTMCells of 256 units and a linear read-out) for the wave's G rows, as
-// lhw_rnn_forward evaluates it per control step (lhw_ppo.hip): the same values bit for bit, so a resident rollout and a launch-per-step
+// lhw_rnn_forward evaluates it per control step (lhw_rnn.hip): the same values bit for bit, so a resident rollout and a launch-per-step
 // rollout can follow each other on the same LhwRnn handle.  Lane l owns hidden units 4l .. 4l + 3 of all FOUR gates of both rows: per
 // row k of a transposed weight matrix ([in][4 x 256], gate-major columns) four 16-byte loads per lane, each gate's 1 KB coalesced; the
 // cell update and the cell state are then lane-local.  Every gate pre-activation is ONE fmaf chain over ascending k from +0 over the

@@ -9,6 +9,12 @@
 #include "lhw_ppo_head.h"
 
 int lhw_fail(int code, const char* fmt, ...);
+#define HIPCHK(x)                                                                                   \
+  do {                                                                                              \
+    hipError_t e_ = (x);                                                                            \
+    if (e_ != hipSuccess) return lhw_fail(LHW_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_)); \
+  } while (0)
+static inline int pad4(int x) { return (x + 3) & ~3; }
 
 // POISON MODE (debug): nothing on the GPU zero-fills LDS, and what a workgroup finds there is whatever the previous occupant
 // of the CU left -- another kernel, another process.  LHW_LDS_POISON(obj), placed right behind a __shared__ declaration,
@@ -165,7 +171,7 @@ void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s);
 
 // Whole-sequence LSTM strip kernels of the recurrent update (lhw_mlp_strip.hip: lstm_seq_fwd_strip_kernel / lstm_seq_bwd_strip_kernel): the
 // time loops of lhw_rnn_grad's forward pass and BPTT for one network (two stacked cells) as one launch each.  A workgroup owns 32 rows b of
-// the [T][Bt] minibatch for all T steps.  Buffers are lhw_ppo.hip's SeqWs (rows r = t * Bt + b).
+// the [T][Bt] minibatch for all T steps.  Buffers are lhw_rnn.hip's SeqWs (rows r = t * Bt + b).
 struct LstmSeqStrip {
   const float *w1t, *w2t;                    // forward: [in][out] copies from lstm_seq_strip_prepare, [Dp + H][4H] and [2H][4H]
   const float *w1, *w2;                      // backward: theta's own [4H][Dp + H] = [W_ih1 | W_hh1] and [4H][2H] = [W_ih2 | W_hh2]

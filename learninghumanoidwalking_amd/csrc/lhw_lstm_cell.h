@@ -1,10 +1,10 @@
 // One hidden unit of one LSTMCell step (torch.nn.LSTMCell, gate order i f g o; the reference's Gaussian_LSTM_Actor / LSTM_V,
 // rl/policies/actor.py:191-286, critic.py:52-112), shared by the stand-alone cell kernel of the launch-per-step path
-// (lstm_cell_fwd_kernel, lhw_ppo.hip), the in-wave policy step of the resident rollout (lstm_policy_step, lhw_humanoid_rollout.hip)
+// (lstm_cell_fwd_kernel, lhw_lstm_steps.h), the in-wave policy step of the resident rollout (lstm_policy_step, lhw_humanoid_rollout.hip)
 // and its plain reference launch (lhw_debug_lstm_policy_step, lhw_mlp_strip.hip), and by the whole-sequence strip kernels of the recurrent update
 // (lstm_seq_fwd_strip_kernel / lstm_seq_bwd_strip_kernel, lhw_mlp_strip.hip).  One definition, so all of them produce the same bits.
 //
-// Those translation units are compiled with different -ffp-contract settings (lhw_ppo.hip and lhw_mlp_strip.hip with hipcc's default,
+// Those translation units are compiled with different -ffp-contract settings (lhw_rnn.hip and lhw_mlp_strip.hip with hipcc's default,
 // fast, where the back end decides which multiply feeds which add; the stepper units with `on`), so every multiply-add is spelled out:
 // the cell update is the form the back end chose for `gf * cp + gi * gg` in lstm_cell_fwd_kernel before this header existed --
 // the product gf * cp rounded on its own, then one fused gi * gg + (gf * cp) -- and nothing is left for the contraction to decide.
@@ -30,7 +30,7 @@ LHW_HD float lhw_lstm_cell(float g_i, float g_f, float g_g, float g_o, const flo
   return go * tanhf(cn);
 }
 
-// Backward of one hidden unit of one cell step (BPTT of the recurrent update: lstm_cell_bwd_kernel of the launch-per-step path, lhw_ppo.hip,
+// Backward of one hidden unit of one cell step (BPTT of the recurrent update: lstm_cell_bwd_kernel of the launch-per-step path, lhw_lstm_steps.h,
 // and lstm_seq_bwd_strip_kernel, lhw_mlp_strip.hip).  gates: the unit's activated gates i f g o of step t; c: its cell state of step t;
 // c_prev: of step t - 1 (0 at t = 0); reset_t: an episode starts at step t (the state before it was zero, and nothing is carried across it);
 // dh_a: d loss / d h_t from the layer above at step t; dh_b: from this cell's own recurrent input at step t + 1, which counts unless

@@ -8,7 +8,7 @@
 //             (h1 / h2 are written to HBM once, for the backward pass, and never read back by the forward pass)
 //   backward  dy slab -> dh2 = (dy W3) * (h2 > 0) -> dh1 = (dh2 W2) * (h1 > 0)
 //             (dh2 / dh1 are written once, for the weight-gradient GEMMs, which contract over the minibatch rows and stay
-//             split-K GEMMs in lhw_ppo.hip)
+//             split-K GEMMs in lhw_gemm.hip)
 //
 // The slab sits k-major in LDS (S[k][row]): that is the A-operand layout of v_mfma_f32_32x32x2_f32 (lane l: A[row = l % 32]
 // [k = l / 32]), so a layer's output tile, written back column by column, IS the next layer's A operand.  The weights are the
@@ -29,6 +29,7 @@
 #include "../../include/lhw.h"
 #include "lhw_internal.h"
 #include "lhw_lstm_cell.h"
+#include "lhw_lstm_steps.h"
 #include "lhw_policy.h"
 
 #ifndef __HIP_EMU__
@@ -770,7 +771,7 @@ extern "C" int lhw_debug_lstm_policy_step(const LhwRolloutLstmPolicy* q, const f
 }
 
 // =========================================================================================== whole-sequence LSTM strip kernels
-// The time loops of the recurrent update (lhw_rnn_grad, lhw_ppo.hip; reference rl/algos/ppo.py:512-533, the BPTT over whole trajectories of
+// The time loops of the recurrent update (lhw_rnn_grad, lhw_rnn.hip; reference rl/algos/ppo.py:512-533, the BPTT over whole trajectories of
 // Gaussian_LSTM_Actor / LSTM_V) for one network as ONE launch per pass instead of four launches per time step.  The rows of a sequence
 // minibatch are independent -- a row's h_t, c_t depend on its own x_t, h_{t-1}, c_{t-1} and the weights -- so a workgroup that owns a slab of
 // 32 rows b of the [T][Bt] minibatch runs all T steps by itself: no grid synchronisation, no flag, no waiting on another workgroup.
@@ -1034,7 +1035,7 @@ void lstm_seq_strip_backward(const LstmSeqStrip& a, hipStream_t s) {
   hipLaunchKernelGGL(lstm_seq_bwd_strip_kernel, dim3((a.Bt + 31) / 32), dim3(2 * a.H), 0, s, a);
 }
 
-// ---- the plain reference of lhw_debug_lstm_seq: the launch-per-step loops of lhw_rnn_grad with a thread per output in place of the MFMA GEMM
+// ---- the plain reference of lhw_debug_lstm_seq: the launch-per-step loops of lhw_rnn_grad (lhw_lstm_steps.h) with a thread per output in place of the MFMA GEMM
 // C [M][N] (ld ldc) = A [M][K] (ld lda) B, B[k][n] at B[k * sk + n * sn]: one fmaf chain over ascending k from +0 per output
 __global__ void __launch_bounds__(256) seq_ref_gemm_kernel(int M, int N, int K, const float* __restrict__ A, int lda, const float* __restrict__ B, int sk, int sn,
                                                            float* __restrict__ C, int ldc) {
@@ -1044,44 +1045,6 @@ __global__ void __launch_bounds__(256) seq_ref_gemm_kernel(int M, int N, int K, 
   float s = 0.f;
   for (int k = 0; k < K; k++) s = fmaf(A[(size_t)m * lda + k], B[(size_t)k * sk + (size_t)n * sn], s);
   C[(size_t)m * ldc + n] = s;
-}
-// (lstm_cell_fwd_kernel / lstm_cell_bwd_kernel of lhw_ppo.hip: the same two header functions on the same operands)
-__global__ void __launch_bounds__(256) seq_ref_cell_fwd_kernel(int B, int H, float* __restrict__ G, const float* __restrict__ bi, const float* __restrict__ bh,
-                                                               const float* __restrict__ c_prev, const unsigned char* __restrict__ reset_t, float* __restrict__ c_out,
-                                                               float* __restrict__ dest_a, int lda, float* __restrict__ dest_b, int ldb,
-                                                               const unsigned char* __restrict__ reset_next) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)B * H) return;
-  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
-  float* g = G + (size_t)b * 4 * H;
-  const float cp = (c_prev && !reset_t[b]) ? c_prev[(size_t)b * H + j] : 0.f;
-  const float b_ih[4] = {bi[j], bi[H + j], bi[2 * H + j], bi[3 * H + j]}, b_hh[4] = {bh[j], bh[H + j], bh[2 * H + j], bh[3 * H + j]};
-  float gt[4], c;
-  const float h = lhw_lstm_cell(g[j], g[H + j], g[2 * H + j], g[3 * H + j], b_ih, b_hh, cp, gt, &c);
-  g[j] = gt[0]; g[H + j] = gt[1]; g[2 * H + j] = gt[2]; g[3 * H + j] = gt[3];
-  c_out[(size_t)b * H + j] = c;
-  dest_a[(size_t)b * lda + j] = h;
-  if (dest_b) dest_b[(size_t)b * ldb + j] = reset_next[b] ? 0.f : h;
-}
-__global__ void __launch_bounds__(256) seq_ref_cell_bwd_kernel(int B, int H, float* __restrict__ G, const float* __restrict__ c, const float* __restrict__ c_prev,
-                                                               const unsigned char* __restrict__ reset_t, const float* __restrict__ dh_a, int lda,
-                                                               const float* __restrict__ dh_b, int ldb, const unsigned char* __restrict__ reset_next,
-                                                               float* __restrict__ dcar) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)B * H) return;
-  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
-  float* g = G + (size_t)b * 4 * H;
-  const float gt[4] = {g[j], g[H + j], g[2 * H + j], g[3 * H + j]};
-  const bool rst = reset_t[b] != 0, no_next = !dh_b || reset_next[b];
-  float dc = dcar[(size_t)b * H + j], d[4];
-  lhw_lstm_cell_bwd(gt, c[(size_t)b * H + j], (c_prev && !rst) ? c_prev[(size_t)b * H + j] : 0.f, rst, dh_a[(size_t)b * lda + j],
-                    no_next ? 0.f : dh_b[(size_t)b * ldb + j], no_next, &dc, d);
-  dcar[(size_t)b * H + j] = dc;
-  g[j] = d[0]; g[H + j] = d[1]; g[2 * H + j] = d[2]; g[3 * H + j] = d[3];
-}
-__global__ void __launch_bounds__(256) seq_ref_zero_kernel(int B, int H, float* __restrict__ p, int ld) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < (size_t)B * H) p[(i / H) * ld + i % H] = 0.f;
 }
 
 extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* stream) {
@@ -1107,39 +1070,14 @@ extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* 
     if (q->passes & 2) lstm_seq_strip_backward(a, s);
     return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence strip launch failed");
   }
-  const int nb = (int)(((size_t)Bt * H + 255) / 256);
-  auto gemm = [&](int M, int N, int K, const float* A, int lda, const float* B, int sk, int sn, float* C, int ldc) {
-    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, B, sk, sn, C, ldc);
+  auto gemm = [&](int M, int N, int K, const float* A, int lda, const float* B, int ldb, bool b_kc, float* C, int ldc) {
+    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, B, b_kc ? 1 : ldb, b_kc ? ldb : 1, C, ldc);
   };
-  if (q->passes & 1) {
-    hipLaunchKernelGGL(seq_ref_zero_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->xh1 + Dp, K1);
-    hipLaunchKernelGGL(seq_ref_zero_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->xh2 + H, 2 * H);
-    for (int t = 0; t < T; t++) {
-      const size_t r0 = (size_t)t * Bt;
-      const bool last = t + 1 == T;
-      const unsigned char* rnext = last ? nullptr : q->reset + r0 + Bt;
-      gemm(Bt, 4 * H, K1, q->xh1 + r0 * K1, K1, q->w1, 1, K1, q->g1 + r0 * 4 * H, 4 * H);
-      hipLaunchKernelGGL(seq_ref_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g1 + r0 * 4 * H, q->bi1, q->bh1, t ? q->c1 + (r0 - Bt) * H : (const float*)nullptr,
-                         q->reset + r0, q->c1 + r0 * H, q->xh2 + r0 * 2 * H, 2 * H, last ? (float*)nullptr : q->xh1 + (r0 + Bt) * K1 + Dp, K1, rnext);
-      gemm(Bt, 4 * H, 2 * H, q->xh2 + r0 * 2 * H, 2 * H, q->w2, 1, 2 * H, q->g2 + r0 * 4 * H, 4 * H);
-      hipLaunchKernelGGL(seq_ref_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g2 + r0 * 4 * H, q->bi2, q->bh2, t ? q->c2 + (r0 - Bt) * H : (const float*)nullptr,
-                         q->reset + r0, q->c2 + r0 * H, q->h2 + r0 * H, H, last ? (float*)nullptr : q->xh2 + (r0 + Bt) * 2 * H + H, 2 * H, rnext);
-    }
-  }
+  const LstmSeqStrip a{nullptr, nullptr, q->w1, q->w2, q->bi1, q->bh1, q->bi2, q->bh2, q->xh1, q->xh2, q->g1, q->g2, q->c1, q->c2, q->h2, q->dh2, q->reset, T, Bt, H, Dp};
+  if (q->passes & 1) lstm_steps_forward(a, s, gemm);
   if (q->passes & 2) {
     float *dx2 = q->scratch, *dx1h = dx2 + (size_t)Bt * 2 * H, *dcar1 = dx1h + (size_t)Bt * H, *dcar2 = dcar1 + (size_t)Bt * H;
-    (void)hipMemsetAsync(dcar1, 0, sizeof(float) * 2 * Bt * H, s);
-    for (int t = T - 1; t >= 0; t--) {
-      const size_t r0 = (size_t)t * Bt;
-      const bool last = t + 1 == T;
-      const unsigned char* rnext = last ? nullptr : q->reset + r0 + Bt;
-      hipLaunchKernelGGL(seq_ref_cell_bwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g2 + r0 * 4 * H, q->c2 + r0 * H, t ? q->c2 + (r0 - Bt) * H : (const float*)nullptr,
-                         q->reset + r0, q->dh2 + r0 * H, H, last ? (const float*)nullptr : dx2 + H, 2 * H, rnext, dcar2);
-      gemm(Bt, 2 * H, 4 * H, q->g2 + r0 * 4 * H, 4 * H, q->w2, 2 * H, 1, dx2, 2 * H);
-      hipLaunchKernelGGL(seq_ref_cell_bwd_kernel, dim3(nb), dim3(256), 0, s, Bt, H, q->g1 + r0 * 4 * H, q->c1 + r0 * H, t ? q->c1 + (r0 - Bt) * H : (const float*)nullptr,
-                         q->reset + r0, dx2, 2 * H, last ? (const float*)nullptr : dx1h, H, rnext, dcar1);
-      gemm(Bt, H, 4 * H, q->g1 + r0 * 4 * H, 4 * H, q->w1 + Dp, K1, 1, dx1h, H);
-    }
+    lstm_steps_bptt(a, dx2, dx1h, dcar1, dcar2, s, gemm);
   }
   return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence reference launch failed");
 }

@@ -1,5 +1,5 @@
 // The PPO loss head: per-row losses and their gradients wrt the network outputs (reference rl/algos/ppo.py:302-384, FF path,
-// mask = 1).  ONE definition of the arithmetic for its three callers: ppo_loss_kernel (lhw_ppo.hip: a thread per row, outputs
+// mask = 1).  ONE definition of the arithmetic for its three callers: ppo_loss_kernel (lhw_learner.hip: a thread per row, outputs
 // in HBM), mlp_train_strip_kernel (lhw_mlp_strip.hip: the row's outputs and gradients in LDS, between the forward and the backward
 // layers of the same slab) and the thread-per-row kernel of lhw_debug_mlp_train_strip.
 //

@@ -1,4 +1,4 @@
-"""The update path's float32 MFMA GEMM kernel (lhw_debug_gemm -> gemm_f32_kernel, csrc/lhw_ppo.hip) against torch float64 on the
+"""The update path's float32 MFMA GEMM kernel (lhw_debug_gemm -> gemm_f32_kernel, csrc/lhw_gemm.hip) against torch float64 on the
 shapes lhw_ppo_grad issues -- both block-tile sizes, every operand layout, ragged edges (K not a multiple of 16, M / N not a
 multiple of the tile), the fused epilogues (bias + ReLU, ReLU-derivative mask) and the split-K path with the bias gradient's
 column sums taken from the same operand tiles."""
@@ -78,7 +78,7 @@ def test_weight_gradient_split_k_with_fused_bias_gradient(wt, M, N, K, kc):
 
 @pytest.mark.parametrize("K,kc", [(32768, 512), (1000, 512), (4099, 128), (37, 512), (65536, 512)])
 def test_wide_weight_gradient_matches_float64(K, kc):
-    """wgrad_wide_kernel (csrc/lhw_ppo.hip): dW2 = dh2^T h1 and db2 = colsum(dh2) per k slice, operands straight from global memory
+    """wgrad_wide_kernel (csrc/lhw_gemm.hip): dW2 = dh2^T h1 and db2 = colsum(dh2) per k slice, operands straight from global memory
     (reference rl/algos/ppo.py:387-396: the hidden layer's share of loss.backward()), against float64 slice by slice; ragged row
     counts (a last chunk shorter than the 16-row register buffer), run-to-run bitwise determinism."""
     import torch
@@ -150,7 +150,7 @@ def test_fp16_operand_mode_equals_half_rounded_operands(layout, M, N, K):
 
 @pytest.mark.parametrize("R,Dp,O,Op", [(1000, 40, 12, 12), (32768, 40, 12, 12), (4099, 36, 10, 12), (300, 44, 1, 4), (65536, 40, 12, 12)])
 def test_fused_skinny_weight_gradients_match_float64(R, Dp, O, Op):
-    """wgrad_skinny_kernel (csrc/lhw_ppo.hip): dW1 = dh1^T x, db1, dW3 = dy^T h2, db3 of one network in one K-streaming launch
+    """wgrad_skinny_kernel (csrc/lhw_gemm.hip): dW1 = dh1^T x, db1, dW3 = dy^T h2, db3 of one network in one K-streaming launch
     (reference rl/algos/ppo.py:387-396: the first / last layer's share of loss.backward()), against float64; ragged row counts,
     the critic's single output, accumulation into the outputs, run-to-run bitwise determinism."""
     import torch
