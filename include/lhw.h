@@ -434,6 +434,25 @@ typedef struct LhwLstmSeqArgs {
   float* scratch;
 } LhwLstmSeqArgs;
 int lhw_debug_lstm_seq(const LhwLstmSeqArgs* args, int32_t fused, void* stream);
+/* Test hook for lhw_rnn_values' kernel (csrc/lhw_mlp_strip.hip: lstm_seq_value_strip_kernel): ONE network of two stacked cells and a read-out of
+ * one output over a stored rollout of N env rows, on caller-owned device buffers.  Weights as in LhwLstmSeqArgs, wo [H], bo [1]; obs [T + 1][N][D]
+ * and term_obs [T][N][D] RAW observations, obs_mean / obs_std [D]; done [T][N], reset0 [N] (nullable).  The state is kept the way the handle keeps
+ * it: in the recurrent columns of xh1 [N][Dp + H] = [x | h1] and xh2 [N][2H] = [h1 | h2] and in c1 / c2 [N][H]; it is read and left advanced by T
+ * steps.  val [T][N]; vterm [T][N] with term_obs (both or neither); vfinal [N] nullable.  scratch: max((Dp + 3H) * 4H, 6 N H) floats.
+ * fused = 1: one launch (LHW_ERR_UNSUPPORTED outside the LHW_LSTM_SEQ_* bounds; c1 / c2 16-byte aligned); the other columns of xh1 / xh2 are not
+ * touched.  fused = 0: per time slice the launches of lhw_rnn_forward's step with a thread-per-output fmaf-chain kernel for the products -- any
+ * shape, the same arithmetic, bit for bit. */
+typedef struct LhwLstmValuesArgs {
+  int32_t H, D, Dp, T, N;
+  const float *w1, *bi1, *bh1, *w2, *bi2, *bh2, *wo, *bo;
+  const float *obs_mean, *obs_std;
+  const float *obs, *term_obs;
+  const uint8_t *done, *reset0;
+  float *xh1, *xh2, *c1, *c2;
+  float *val, *vterm, *vfinal;
+  float* scratch;
+} LhwLstmValuesArgs;
+int lhw_debug_lstm_values(const LhwLstmValuesArgs* args, int32_t fused, void* stream);
 /* Diagnostic (load balance): the first call arms the recording; later calls return, per env, the shader-clock cycles its
  * wavefront group spent in the most recent control-step launch.  HOST pointer [N] int64, synchronous; humanoid tasks only. */
 int lhw_env_debug_wave_cycles(LhwEnv* env, int64_t* cycles_host);
@@ -566,6 +585,18 @@ int lhw_rnn_layout(const LhwRnn* rnn, int64_t* out19);
 int lhw_rnn_forward(LhwRnn* rnn, const float* theta, const float* obs, int64_t N, const float* obs_mean, const float* obs_std,
                     const uint8_t* reset, uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic, int commit,
                     float* mu, float* act, float* logp, float* value, void* stream);
+/* The critic of theta over a stored rollout: bitwise the values and the critic state that
+ *   for t in 0..T-1: lhw_rnn_forward(obs[t], reset = t ? done[t-1] != 0 : reset0, commit = 1, value = val[t]);
+ *                    lhw_rnn_forward(term_obs[t], commit = 0, value = vterm[t]);
+ *   lhw_rnn_forward(obs[T], commit = 0, value = vfinal)
+ * leave behind, in ONE launch (plus the [in][out] copies of the critic's two weight matrices, made on `stream`); the actor's state is not touched.
+ * obs [T + 1][N][obs_dim], term_obs [T][N][obs_dim] raw observations; done [T][N] LHW_DONE_* flags; reset0 [N] (nullable).  term_obs / vterm
+ * nullable (together), vfinal nullable.  N <= rollout_rows.  term_obs[t] must equal obs[t + 1] on every row whose done[t] is 0 -- what
+ * lhw_env_step / lhw_env_rollout* write -- : where no row of a 32-row slab ended an episode at step t, vterm[t] is taken from val[t + 1].
+ * LHW_ERR_UNSUPPORTED, with nothing written, outside the LHW_LSTM_SEQ_* bounds below: the caller keeps the per-step calls. */
+int lhw_rnn_values(LhwRnn* rnn, const float* theta, const float* obs, const float* term_obs, const uint8_t* done,
+                   const uint8_t* reset0, int32_t T, int32_t N, const float* obs_mean, const float* obs_std,
+                   float* val, float* vterm, float* vfinal, void* stream);
 /* The actor of theta as lhw_env_rollout_lstm reads it: makes the [in][out] copies of the three weight matrices on `stream` (theta is
  * frozen during a rollout: rl/workers/rollout_worker.py:62-77 sync_policy) and fills the view with them, the biases and stds inside
  * theta, the caller's normalisation vectors and the handle's own actor state buffers.  Valid until the next lhw_rnn_apply (or any other

@@ -105,6 +105,12 @@ class LhwLstmSeqArgs(ctypes.Structure):      # include/lhw.h: arguments of the t
                 [(n, ctypes.c_void_p) for n in ("w1", "bi1", "bh1", "w2", "bi2", "bh2", "reset", "dh2", "xh1", "xh2", "g1", "g2", "c1", "c2", "h2", "scratch")])
 
 
+class LhwLstmValuesArgs(ctypes.Structure):      # include/lhw.h: arguments of the test hook lhw_debug_lstm_values
+    _fields_ = ([(n, ctypes.c_int32) for n in ("H", "D", "Dp", "T", "N")] +
+                [(n, ctypes.c_void_p) for n in ("w1", "bi1", "bh1", "w2", "bi2", "bh2", "wo", "bo", "obs_mean", "obs_std", "obs", "term_obs", "done", "reset0",
+                                                "xh1", "xh2", "c1", "c2", "val", "vterm", "vfinal", "scratch")])
+
+
 class LhwRolloutLstmPolicy(ctypes.Structure):      # include/lhw.h: the frozen LSTM actor as lhw_env_rollout_lstm reads it
     _fields_ = [(n, ctypes.c_void_p) for n in ("w1t", "bi1", "bh1", "w2t", "bi2", "bh2", "wot", "bo", "stdv", "obs_mean", "obs_std",
                                                "h1", "h2", "c1", "c2")] + [
@@ -312,6 +318,8 @@ def declare(L):
     sig("lhw_rnn_debug_set_seq_fused", [vp, i32])
     sig("lhw_rnn_debug_last_grad_fused", [vp])
     sig("lhw_debug_lstm_seq", [ctypes.POINTER(LhwLstmSeqArgs), i32, vp])
+    sig("lhw_debug_lstm_values", [ctypes.POINTER(LhwLstmValuesArgs), i32, vp])
+    sig("lhw_rnn_values", [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_debug_step_record", [vp, vp, vp, vp])
     sig("lhw_env_rollout", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_last_rollout_queued", [vp])

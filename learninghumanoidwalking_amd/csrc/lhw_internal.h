@@ -186,3 +186,19 @@ size_t lstm_seq_strip_wt_floats(int H, int Dp);
 void lstm_seq_strip_prepare(const float* w1, const float* w2, int H, int Dp, float* wt, hipStream_t s);   // wt -> w1t, then w2t
 void lstm_seq_strip_forward(const LstmSeqStrip& a, hipStream_t s);
 void lstm_seq_strip_backward(const LstmSeqStrip& a, hipStream_t s);
+
+// The critic of a recurrent rollout in one launch (lhw_mlp_strip.hip: lstm_seq_value_strip_kernel; lhw_rnn_values): one network (two stacked
+// cells, read-out of ONE output) over the stored observations [T + 1][N][D] of N env rows, from and to the state lhw_rnn_forward keeps.
+struct LstmSeqValues {
+  const float *w1t, *w2t;                    // [in][out] copies from lstm_seq_strip_prepare
+  const float *bi1, *bh1, *bi2, *bh2;        // [4H] each
+  const float *wo, *bo;                      // read-out: [H], [1]
+  const float *obs_mean, *obs_std;           // [D]
+  const float *obs, *term_obs;               // RAW observations [T + 1][N][D], terminal observations [T][N][D] (NULL: no vterm)
+  const unsigned char *done, *reset0;        // [T][N] LHW_DONE_* flags; [N] rows that start an episode at step 0 (NULL: none)
+  float *h1; int h1_ld; float *h2; int h2_ld; float *c1, *c2;   // the state: rows of h1_ld / h2_ld / H floats; read, then overwritten
+  float *val, *vterm, *vfinal;               // [T][N], [T][N] (with term_obs), [N] (NULL: not evaluated)
+  int T, N, H, D, Dp;
+};
+bool lstm_seq_values_supported(int H, int Dp);   // the bounds of the other two sequence kernels
+void lstm_seq_strip_values(const LstmSeqValues& a, hipStream_t s);

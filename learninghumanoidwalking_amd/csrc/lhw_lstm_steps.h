@@ -2,6 +2,7 @@
 // lhw_rnn_grad (lhw_rnn.hip, LHW_RNN_SEQ_FUSED=0 and shapes the strip kernels do not take; GEMM = the MFMA launch_gemm) and for the plain
 // reference of lhw_debug_lstm_seq (lhw_mlp_strip.hip, which the SIMT emulator builds; GEMM = a thread per output).  The kernels are static:
 // each of the two translation units carries its own copy of the one definition.
+// Likewise the rollout step of one network (lstm_step_forward): lhw_rnn_forward's body, and the per-step reference of lhw_debug_lstm_values.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,4 +101,46 @@ static void lstm_steps_bptt(const LstmSeqStrip& a, float* dx2, float* dx1h, floa
                        last ? (const float*)nullptr : dx1h, H, rnext, dcar1);
     gemm(Bt, H, 4 * H, a.g1 + r0 * 4 * H, 4 * H, a.w1 + a.Dp, K1, false, dx1h, H);           // d h1_{t-1} = dG1 W1[:, Dp:]
   }
+}
+
+// (obs - mean) / std written into the x part of a concatenated input buffer (row stride ld)
+static __global__ void normalize_ld_kernel(const float* __restrict__ obs, int D, int Dp, size_t R, const float* __restrict__ mean,
+                                           const float* __restrict__ stdv, float* __restrict__ out, int ld) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= R * (size_t)Dp) return;
+  size_t r = i / Dp;
+  int j = (int)(i - r * Dp);
+  out[r * ld + j] = j < D ? (obs[r * D + j] - mean[j]) / stdv[j] : 0.f;
+}
+// zero the hidden / cell state of rows starting an episode
+static __global__ void rnn_reset_kernel(int N, int H, const unsigned char* __restrict__ reset, float* __restrict__ h1, int ld1,
+                                        float* __restrict__ h2, int ld2, float* __restrict__ c1, float* __restrict__ c2) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * H) return;
+  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
+  if (reset[b]) { h1[(size_t)b * ld1 + j] = 0.f; h2[(size_t)b * ld2 + j] = 0.f; c1[i] = 0.f; c2[i] = 0.f; }
+}
+
+// One network's rollout step on N rows, up to the top hidden state h2_out [N][H] (the read-out is the caller's).  The state between steps
+// lives in the recurrent columns of the concatenated step inputs xh1 [N][Dp + H] = [x | h1], xh2 [N][2H] = [h1 | h2] and in c1 / c2 [N][H].
+// reset ([N], may be NULL): rows that start an episode with this observation.  commit: the state advances; else it is only read (the new
+// cell states go to cs [N][H]).  g: [N][4H] scratch.
+struct LstmStepNet {
+  const float *w1, *bi1, *bh1, *w2, *bi2, *bh2;   // theta's own [4H][Dp + H], [4H][2H], biases [4H]
+  int D, Dp, H;
+};
+template <class Gemm>
+static void lstm_step_forward(const LstmStepNet& n, float* xh1, float* xh2, float* c1, float* c2, float* g, float* h2_out, float* cs, const float* obs, int N,
+                              const float* obs_mean, const float* obs_std, const unsigned char* reset, bool commit, hipStream_t s, Gemm gemm) {
+  const int H = n.H, Dp = n.Dp, K1 = Dp + H;
+  const int nb = (int)(((size_t)N * H + 255) / 256);
+  if (reset && commit) hipLaunchKernelGGL(rnn_reset_kernel, dim3(nb), dim3(256), 0, s, N, H, reset, xh1 + Dp, K1, xh2 + H, 2 * H, c1, c2);
+  const size_t nn = (size_t)N * Dp;
+  hipLaunchKernelGGL(normalize_ld_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, obs, n.D, Dp, (size_t)N, obs_mean, obs_std, xh1, K1);
+  gemm(N, 4 * H, K1, xh1, K1, n.w1, K1, true, g, 4 * H);
+  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, N, H, g, n.bi1, n.bh1, (const float*)c1, (const unsigned char*)nullptr, commit ? c1 : cs,
+                     xh2, 2 * H, commit ? xh1 + Dp : (float*)nullptr, K1, (const unsigned char*)nullptr);
+  gemm(N, 4 * H, 2 * H, xh2, 2 * H, n.w2, 2 * H, true, g, 4 * H);
+  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, N, H, g, n.bi2, n.bh2, (const float*)c2, (const unsigned char*)nullptr, commit ? c2 : cs,
+                     h2_out, H, commit ? xh2 + H : (float*)nullptr, 2 * H, (const unsigned char*)nullptr);
 }

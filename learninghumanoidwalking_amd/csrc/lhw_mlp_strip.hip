@@ -857,10 +857,13 @@ __device__ __forceinline__ void seq_st4(float* __restrict__ p, const float (&v)[
 // and dest_b (the next step's recurrent slot, zeroed where that step starts an episode; NULL at the last step), for live rows; h k-major into
 // the slabs sa (NULL: not needed) and sb (with dest_b's zeroing).  row: this lane's row r of the step's [Bt][.] blocks.  bi / bh: the bias vectors
 // in LDS (read from global memory they are loop-invariant loads, which the compiler hoists out of the time loop -- 256 values per lane: 79 spilled VGPRs)
+// WS = false (lstm_seq_value_strip_kernel): nothing goes to HBM, only the slabs are written; keep: c stays as it is (an evaluation that does
+// not advance the state).
+template <bool WS = true>
 __device__ __forceinline__ void seq_cell_fwd(const f32x16 (&acc)[4], float (&c)[16], const float* bi, const float* bh, const int H,
                                              const bool first, const bool rst, const bool rnext, const bool live, const size_t row,
                                              float* __restrict__ G, float* __restrict__ C, float* __restrict__ dest_a, const int lda,
-                                             float* __restrict__ dest_b, const int ldb, float (*sa)[32], float (*sb)[32]) {
+                                             float* __restrict__ dest_b, const int ldb, float (*sa)[32], float (*sb)[32], const bool keep = false) {
   const int lane = threadIdx.x & 63, wave = SEQ_WAVE(), l31 = lane & 31, kh = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; g++) {
@@ -874,14 +877,15 @@ __device__ __forceinline__ void seq_cell_fwd(const f32x16 (&acc)[4], float (&c)[
       const float b_ih[4] = {b_i[0][e], b_i[1][e], b_i[2][e], b_i[3][e]}, b_hh[4] = {b_h[0][e], b_h[1][e], b_h[2][e], b_h[3][e]};
       float gq[4], cn;
       hv[e] = lhw_lstm_cell(acc[0][r], acc[1][r], acc[2][r], acc[3][r], b_ih, b_hh, (first || rst) ? 0.f : c[r], gq, &cn);
-      c[r] = cn; cv[e] = cn;
+      if (!keep) c[r] = cn;
+      cv[e] = cn;
       hz[e] = rnext ? 0.f : hv[e];
       gt[0][e] = gq[0]; gt[1][e] = gq[1]; gt[2][e] = gq[2]; gt[3][e] = gq[3];
       if (sa) sa[j0 + e][l31] = hv[e];
       if (sb) sb[j0 + e][l31] = hz[e];
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (live) {
+    if (WS && live) {
 #pragma unroll
       for (int q = 0; q < 4; q++) seq_st4(G + row * 4 * H + q * H + j0, gt[q]);
       seq_st4(C + row * H + j0, cv);
@@ -939,6 +943,155 @@ __global__ void __launch_bounds__(2 * QH) lstm_seq_fwd_strip_kernel(LstmSeqStrip
     __syncthreads();   // every wave is done with [h1_t | h2_{t-1}]
     seq_cell_fwd(acc, c2, L.B[2], L.B[3], H, t == 0, rst, rnext, live, row, a.g2, a.c2, a.h2, H, last ? (float*)nullptr : a.xh2 + (size_t)Bt * 2 * H + H, 2 * H,
                  (float (*)[32])nullptr, last ? (float (*)[32])nullptr : &L.S2[H]);
+  }
+}
+
+// The critic of a stored recurrent rollout (lhw_rnn_values): the forward kernel's decomposition -- its slabs, seq_mma<4> and seq_cell_fwd -- on RAW
+// observations, from the state lhw_rnn_forward keeps between calls and back into it, with the read-out (ONE output) in the kernel; nothing of
+// size T N H reaches HBM.  Per step t the values are, bit for bit, those of
+//   lhw_rnn_forward(obs[t], reset = t ? done[t-1] != 0 : reset0, commit = 1) -> val[t];  lhw_rnn_forward(term_obs[t], commit = 0) -> vterm[t]
+// and, behind the last step, lhw_rnn_forward(obs[T], commit = 0) -> vfinal.
+//   state     S1[Dp ..) and S2[H ..) hold h1_{t-1} / h2_{t-1} NOT yet zeroed for the episode starts of step t, and c1 / c2 (registers) likewise:
+//             an evaluation that does not advance (vterm[t], vfinal) needs the state as step t left it.  The zeroing for step t + 1 is a pass
+//             of its own behind those evaluations, run only where a live row of the slab has done[t] set (c: seq_cell_fwd's rst).
+//   side      the evaluation that does not advance: cell 1 on [x' | h1_t] with c1 kept, h1' into S2[0 .. H) -- h1_t there is dead once the
+//             main cell-2 product is through, its live copy is S1[Dp ..) -- cell 2 on [h1' | h2_t] with c2 kept, h2' into S2[0 .. H) again
+//             (h1' is dead behind the product), read-out from there.  No LDS beyond the forward slabs.
+//   vterm     the env writes a terminal observation that differs from the next observation only where the episode ended.  In a slab-step in
+//             which no live row has done[t] set, V(term_obs[t]) from the state after step t IS the main evaluation of step t + 1 (same
+//             input, no reset): vterm[t] = val[t + 1], resp. vfinal behind the last step, and the side evaluation is skipped.
+//   read-out  gemm_f32_kernel's chain for N = 1: fmaf over ascending k of h2 from +0, then the bias; lane r < 32 of wave 0 owns row r.
+// Rows beyond N in the last slab load nothing and store nothing.
+struct SeqValLds { SeqFwdLds F; float nm[2][QDP]; float wo[QH]; };   // nm: obs_mean, obs_std (loop-invariant, like the biases)
+
+__global__ void __launch_bounds__(2 * QH) lstm_seq_value_strip_kernel(LstmSeqValues a) {
+  __shared__ SeqValLds L;
+  LHW_LDS_POISON(L);
+  const int tid = threadIdx.x, lane = tid & 63, wave = SEQ_WAVE(), l31 = lane & 31, kh = lane >> 5, nthr = (int)blockDim.x;
+  const int H = a.H, D = a.D, Dp = a.Dp, K1 = Dp + H, N = a.N, T = a.T;
+  const int b0 = (int)blockIdx.x * 32, b = b0 + l31;
+  const bool live = b < N;
+  // one time slice of raw observations [N][D], normalised (normalize_ld_kernel's expression), k-major; zeros in the padded columns and dead rows
+  auto stage_x = [&](const float* __restrict__ x) {
+    for (int i = tid; i < 32 * Dp; i += nthr) {
+      const int row = i / Dp, k = i - row * Dp;
+      L.F.S1[k][row] = (b0 + row < N && k < D) ? (x[(size_t)(b0 + row) * D + k] - L.nm[0][k]) / L.nm[1][k] : 0.f;
+    }
+  };
+  // the value of this lane's row from h2 in S[0 .. H) (tid < 32)
+  auto readout = [&](const float (*S)[32]) {
+    float s = 0.f;
+    for (int k = 0; k < H; k++) s = fmaf(S[k][l31], L.wo[k], s);
+    return s + a.bo[0];
+  };
+  for (int i = tid; i < 4 * H; i += nthr) { L.F.B[0][i] = a.bi1[i]; L.F.B[1][i] = a.bh1[i]; L.F.B[2][i] = a.bi2[i]; L.F.B[3][i] = a.bh2[i]; }
+  for (int i = tid; i < D; i += nthr) { L.nm[0][i] = a.obs_mean[i]; L.nm[1][i] = a.obs_std[i]; }
+  for (int i = tid; i < H; i += nthr) L.wo[i] = a.wo[i];
+  // the state the last call left, zero for the rows that start an episode now
+  for (int i = tid; i < 32 * H; i += nthr) {
+    const int row = i / H, k = i - row * H;
+    const bool keep = b0 + row < N && !(a.reset0 && a.reset0[b0 + row]);
+    L.F.S1[Dp + k][row] = keep ? a.h1[(size_t)(b0 + row) * a.h1_ld + k] : 0.f;
+    L.F.S2[H + k][row] = keep ? a.h2[(size_t)(b0 + row) * a.h2_ld + k] : 0.f;
+  }
+  float c1[16], c2[16];
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const int j0 = 32 * wave + 8 * g + 4 * kh;
+    float u[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) { seq_ld4(u, a.c1 + (size_t)b * H + j0); seq_ld4(v, a.c2 + (size_t)b * H + j0); }
+#pragma unroll
+    for (int e = 0; e < 4; e++) { c1[4 * g + e] = u[e]; c2[4 * g + e] = v[e]; }
+  }
+  __syncthreads();   // mean / std are in LDS
+  stage_x(a.obs);
+  __syncthreads();
+  const int n0[4] = {32 * wave, H + 32 * wave, 2 * H + 32 * wave, 3 * H + 32 * wave};
+  float (*const none)[32] = nullptr;
+  bool fill_prev = false;   // vterm[t - 1] takes val[t]: step t - 1 skipped its side evaluation
+  for (int t = 0; t < T; t++) {
+    const bool last = t + 1 == T;
+    const bool rst = live && (t ? a.done[(size_t)(t - 1) * N + b] != 0 : (a.reset0 && a.reset0[b] != 0));
+    const bool any_done = __any(live && a.done[(size_t)t * N + b] != 0) != 0;   // the same in every wave: each holds all 32 rows
+    const bool fin = last && a.vfinal;
+    const bool side_t = a.vterm && (any_done || (last && !fin));
+    const float* xnext = a.obs + (size_t)(t + 1) * N * D;   // obs[t + 1]: the next step's input, or vfinal's
+    f32x16 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+    seq_mma<4>(L.F.S1, K1, a.w1t, 4 * H, n0, acc);
+    __syncthreads();   // every wave is done with [x_t | h1_{t-1}]
+    seq_cell_fwd<false>(acc, c1, L.F.B[0], L.F.B[1], H, false, rst, false, live, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, L.F.S2, &L.F.S1[Dp]);
+    if (side_t) stage_x(a.term_obs + (size_t)t * N * D);
+    else if (!last || fin) stage_x(xnext);
+    __syncthreads();   // h1_t is in both slabs
+#pragma unroll
+    for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+    seq_mma<4>(L.F.S2, 2 * H, a.w2t, 4 * H, n0, acc);
+    __syncthreads();   // every wave is done with [h1_t | h2_{t-1}]
+    seq_cell_fwd<false>(acc, c2, L.F.B[2], L.F.B[3], H, false, rst, false, live, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, none, &L.F.S2[H]);
+    __syncthreads();   // h2_t is complete
+    if (tid < 32) {
+      const float v = readout(&L.F.S2[H]);
+      if (live) {
+        a.val[(size_t)t * N + b] = v;
+        if (fill_prev) a.vterm[(size_t)(t - 1) * N + b] = v;
+      }
+    }
+    // the evaluations that do not advance the state: V(term_obs[t]), and behind the last step V(obs[T])
+    const int nside = (side_t ? 1 : 0) + (fin ? 1 : 0);
+    for (int e = 0; e < nside; e++) {
+      const bool is_term = side_t && e == 0;
+#pragma unroll
+      for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+      seq_mma<4>(L.F.S1, K1, a.w1t, 4 * H, n0, acc);
+      __syncthreads();   // every wave is done with [x' | h1_t]
+      seq_cell_fwd<false>(acc, c1, L.F.B[0], L.F.B[1], H, false, false, false, live, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, L.F.S2, none, true);
+      if (is_term && (!last || fin)) stage_x(xnext);
+      __syncthreads();   // h1' is in S2[0 .. H)
+#pragma unroll
+      for (int q = 0; q < 4; q++) seq_zero(acc[q]);
+      seq_mma<4>(L.F.S2, 2 * H, a.w2t, 4 * H, n0, acc);
+      __syncthreads();   // every wave is done with [h1' | h2_t]
+      seq_cell_fwd<false>(acc, c2, L.F.B[2], L.F.B[3], H, false, false, false, live, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, L.F.S2, none, true);
+      __syncthreads();   // h2' is in S2[0 .. H)
+      if (tid < 32) {
+        const float v = readout(L.F.S2);
+        if (live) {
+          if (is_term) a.vterm[(size_t)t * N + b] = v;
+          else {
+            a.vfinal[b] = v;
+            if (a.vterm && !side_t) a.vterm[(size_t)t * N + b] = v;
+          }
+        }
+      }
+    }
+    fill_prev = a.vterm && !side_t;
+    if (!last && any_done) {   // the rows whose episode ended start step t + 1 from zero
+      __syncthreads();   // the read-outs are through with the slabs
+      for (int i = tid; i < 32 * H; i += nthr) {
+        const int k = i >> 5, row = i & 31;
+        if (b0 + row < N && a.done[(size_t)t * N + b0 + row] != 0) { L.F.S1[Dp + k][row] = 0.f; L.F.S2[H + k][row] = 0.f; }
+      }
+      __syncthreads();
+    }
+  }
+  // the state behind step T - 1, as lhw_rnn_forward(commit = 1) leaves it (no zeroing for done[T - 1]: that is the next call's reset0)
+  for (int i = tid; i < 32 * H; i += nthr) {
+    const int row = i / H, k = i - row * H;
+    if (b0 + row < N) {
+      a.h1[(size_t)(b0 + row) * a.h1_ld + k] = L.F.S1[Dp + k][row];
+      a.h2[(size_t)(b0 + row) * a.h2_ld + k] = L.F.S2[H + k][row];
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const int j0 = 32 * wave + 8 * g + 4 * kh;
+      const float u[4] = {c1[4 * g], c1[4 * g + 1], c1[4 * g + 2], c1[4 * g + 3]}, v[4] = {c2[4 * g], c2[4 * g + 1], c2[4 * g + 2], c2[4 * g + 3]};
+      seq_st4(a.c1 + (size_t)b * H + j0, u);
+      seq_st4(a.c2 + (size_t)b * H + j0, v);
+    }
   }
 }
 
@@ -1035,16 +1188,22 @@ void lstm_seq_strip_backward(const LstmSeqStrip& a, hipStream_t s) {
   hipLaunchKernelGGL(lstm_seq_bwd_strip_kernel, dim3((a.Bt + 31) / 32), dim3(2 * a.H), 0, s, a);
 }
 
+bool lstm_seq_values_supported(int H, int Dp) { return lstm_seq_strip_supported(H, Dp); }
+void lstm_seq_strip_values(const LstmSeqValues& a, hipStream_t s) {
+  if (a.T <= 0 || a.N <= 0) return;
+  hipLaunchKernelGGL(lstm_seq_value_strip_kernel, dim3((a.N + 31) / 32), dim3(2 * a.H), 0, s, a);
+}
+
 // ---- the plain reference of lhw_debug_lstm_seq: the launch-per-step loops of lhw_rnn_grad (lhw_lstm_steps.h) with a thread per output in place of the MFMA GEMM
-// C [M][N] (ld ldc) = A [M][K] (ld lda) B, B[k][n] at B[k * sk + n * sn]: one fmaf chain over ascending k from +0 per output
+// C [M][N] (ld ldc) = A [M][K] (ld lda) B (+ bias [N] unless NULL), B[k][n] at B[k * sk + n * sn]: one fmaf chain over ascending k from +0 per output
 __global__ void __launch_bounds__(256) seq_ref_gemm_kernel(int M, int N, int K, const float* __restrict__ A, int lda, const float* __restrict__ B, int sk, int sn,
-                                                           float* __restrict__ C, int ldc) {
+                                                           float* __restrict__ C, int ldc, const float* __restrict__ bias) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)M * N) return;
   const int m = (int)(i / N), n = (int)(i - (size_t)m * N);
   float s = 0.f;
   for (int k = 0; k < K; k++) s = fmaf(A[(size_t)m * lda + k], B[(size_t)k * sk + (size_t)n * sn], s);
-  C[(size_t)m * ldc + n] = s;
+  C[(size_t)m * ldc + n] = bias ? s + bias[n] : s;   // (bias: gemm_f32_kernel's epilogue)
 }
 
 extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* stream) {
@@ -1071,7 +1230,7 @@ extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* 
     return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence strip launch failed");
   }
   auto gemm = [&](int M, int N, int K, const float* A, int lda, const float* B, int ldb, bool b_kc, float* C, int ldc) {
-    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, B, b_kc ? 1 : ldb, b_kc ? ldb : 1, C, ldc);
+    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, B, b_kc ? 1 : ldb, b_kc ? ldb : 1, C, ldc, (const float*)nullptr);
   };
   const LstmSeqStrip a{nullptr, nullptr, q->w1, q->w2, q->bi1, q->bh1, q->bi2, q->bh2, q->xh1, q->xh2, q->g1, q->g2, q->c1, q->c2, q->h2, q->dh2, q->reset, T, Bt, H, Dp};
   if (q->passes & 1) lstm_steps_forward(a, s, gemm);
@@ -1080,4 +1239,43 @@ extern "C" int lhw_debug_lstm_seq(const LhwLstmSeqArgs* q, int32_t fused, void* 
     lstm_steps_bptt(a, dx2, dx1h, dcar1, dcar2, s, gemm);
   }
   return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM sequence reference launch failed");
+}
+
+// The critic over a stored rollout outside an LhwRnn (tests, SIMT emulator).  fused = 1: lstm_seq_value_strip_kernel.  fused = 0: the calls it
+// replaces -- lhw_rnn_forward's step (lstm_step_forward, lhw_lstm_steps.h) per time slice with a thread-per-output fmaf chain for the products.
+extern "C" int lhw_debug_lstm_values(const LhwLstmValuesArgs* q, int32_t fused, void* stream) {
+  if (!q || !q->w1 || !q->bi1 || !q->bh1 || !q->w2 || !q->bi2 || !q->bh2 || !q->wo || !q->bo || !q->obs_mean || !q->obs_std || !q->obs || !q->done || !q->xh1 ||
+      !q->xh2 || !q->c1 || !q->c2 || !q->val || !q->scratch || (q->term_obs == nullptr) != (q->vterm == nullptr))
+    return lhw_fail(LHW_ERR_ARG, "null argument");
+  const int H = q->H, D = q->D, Dp = q->Dp, T = q->T, N = q->N, K1 = Dp + H;
+  if (H <= 0 || D <= 0 || Dp < D || (Dp & 3) || T <= 0 || N <= 0) return lhw_fail(LHW_ERR_ARG, "bad shape (H=%d D=%d Dp=%d T=%d N=%d)", H, D, Dp, T, N);
+  hipStream_t s = (hipStream_t)stream;
+  if (fused) {
+    if (!lstm_seq_values_supported(H, Dp))
+      return lhw_fail(LHW_ERR_UNSUPPORTED, "LSTM value strip kernel: hidden width a multiple of 32 in [%d, %d], padded input width <= %d", LHW_LSTM_SEQ_MIN_HIDDEN,
+                      LHW_LSTM_SEQ_MAX_HIDDEN, LHW_LSTM_SEQ_MAX_OBS_PAD);
+    if ((reinterpret_cast<size_t>(q->c1) | reinterpret_cast<size_t>(q->c2)) & 15) return lhw_fail(LHW_ERR_ARG, "c1 / c2 must be 16-byte aligned");
+    float* wt = q->scratch;
+    lstm_seq_strip_prepare(q->w1, q->w2, H, Dp, wt, s);
+    const LstmSeqValues a{wt, wt + (size_t)K1 * 4 * H, q->bi1, q->bh1, q->bi2, q->bh2, q->wo, q->bo, q->obs_mean, q->obs_std, q->obs, q->term_obs, q->done, q->reset0,
+                          q->xh1 + Dp, K1, q->xh2 + H, 2 * H, q->c1, q->c2, q->val, q->vterm, q->vfinal, T, N, H, D, Dp};
+    lstm_seq_strip_values(a, s);
+    return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM value strip launch failed");
+  }
+  auto gemm = [&](int M, int Nn, int K, const float* A, int lda, const float* B, int ldb, bool b_kc, float* C, int ldc) {
+    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)(((size_t)M * Nn + 255) / 256)), dim3(256), 0, s, M, Nn, K, A, lda, B, b_kc ? 1 : ldb, b_kc ? ldb : 1, C, ldc,
+                       (const float*)nullptr);
+  };
+  float *g = q->scratch, *h2o = g + (size_t)N * 4 * H, *cs = h2o + (size_t)N * H;
+  const LstmStepNet net{q->w1, q->bi1, q->bh1, q->w2, q->bi2, q->bh2, D, Dp, H};
+  auto step = [&](const float* obs, const unsigned char* reset, bool commit, float* value) {
+    lstm_step_forward(net, q->xh1, q->xh2, q->c1, q->c2, g, h2o, cs, obs, N, q->obs_mean, q->obs_std, reset, commit, s, gemm);
+    hipLaunchKernelGGL(seq_ref_gemm_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, N, 1, H, (const float*)h2o, H, q->wo, 1, H, value, 1, q->bo);
+  };
+  for (int t = 0; t < T; t++) {
+    step(q->obs + (size_t)t * N * D, t ? q->done + (size_t)(t - 1) * N : q->reset0, true, q->val + (size_t)t * N);
+    if (q->vterm) step(q->term_obs + (size_t)t * N * D, nullptr, false, q->vterm + (size_t)t * N);
+  }
+  if (q->vfinal) step(q->obs + (size_t)T * N * D, nullptr, false, q->vfinal);
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "LSTM value reference launch failed");
 }

@@ -75,23 +75,6 @@ struct LhwRnn : LearnerCore {
   }
 };
 
-// (obs - mean) / std written into the x part of a concatenated input buffer (row stride ld)
-__global__ void normalize_ld_kernel(const float* __restrict__ obs, int D, int Dp, size_t R, const float* __restrict__ mean,
-                                    const float* __restrict__ stdv, float* __restrict__ out, int ld) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= R * (size_t)Dp) return;
-  size_t r = i / Dp;
-  int j = (int)(i - r * Dp);
-  out[r * ld + j] = j < D ? (obs[r * D + j] - mean[j]) / stdv[j] : 0.f;
-}
-// zero the hidden / cell state of rows starting an episode
-__global__ void rnn_reset_kernel(int N, int H, const unsigned char* __restrict__ reset, float* __restrict__ h1, int ld1,
-                                 float* __restrict__ h2, int ld2, float* __restrict__ c1, float* __restrict__ c2) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)N * H) return;
-  const int b = (int)(i / H), j = (int)(i - (size_t)b * H);
-  if (reset[b]) { h1[(size_t)b * ld1 + j] = 0.f; h2[(size_t)b * ld2 + j] = 0.f; c1[i] = 0.f; c2[i] = 0.f; }
-}
 // sequence minibatch gather: columns idx[0..B) of the time-major rollout [T][N] -> rows (t, b) of the workspaces
 __global__ void seq_gather_kernel(const int* __restrict__ idx, int T, int N, int B, int Bt, int Dp, int K1, int A,
                                   const float* __restrict__ xn, const float* __restrict__ xm, const float* __restrict__ act,
@@ -251,26 +234,15 @@ extern "C" int lhw_rnn_forward(LhwRnn* p, const float* theta, const float* obs, 
   if (act && !logp) return lhw_fail(LHW_ERR_ARG, "logp required with act");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
-  const int H = p->H, K1 = p->la.K1, Dp = p->la.Dp;
-  const int nb = (int)(((size_t)N * H + 255) / 256);
+  const int H = p->H, Dp = p->la.Dp;
   const bool want[2] = {act != nullptr || mu != nullptr, value != nullptr};
   const auto gemm = steps_gemm(s);
   for (int n = 0; n < 2; n++) {
     if (!want[n]) continue;
     const LstmLayout& L = n ? p->lc : p->la;
     const float* th = theta + (n ? p->off_critic : p->off_actor);
-    if (reset && commit)
-      hipLaunchKernelGGL(rnn_reset_kernel, dim3(nb), dim3(256), 0, s, (int)N, H, reset, p->rxh1[n] + Dp, K1, p->rxh2[n] + H, 2 * H, p->rc1[n], p->rc2[n]);
-    const size_t nn = (size_t)N * Dp;
-    hipLaunchKernelGGL(normalize_ld_kernel, dim3((nn + 255) / 256), dim3(256), 0, s, obs, p->D, Dp, (size_t)N, obs_mean, obs_std, p->rxh1[n], K1);
-    gemm((int)N, 4 * H, K1, p->rxh1[n], K1, th + L.w1, K1, true, p->rg, 4 * H);
-    hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, (int)N, H, p->rg, th + L.bi1, th + L.bh1, (const float*)p->rc1[n],
-                       (const unsigned char*)nullptr, commit ? p->rc1[n] : p->rcs, p->rxh2[n], 2 * H, commit ? p->rxh1[n] + Dp : (float*)nullptr, K1,
-                       (const unsigned char*)nullptr);
-    gemm((int)N, 4 * H, 2 * H, p->rxh2[n], 2 * H, th + L.w2, 2 * H, true, p->rg, 4 * H);
-    hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(nb), dim3(256), 0, s, (int)N, H, p->rg, th + L.bi2, th + L.bh2, (const float*)p->rc2[n],
-                       (const unsigned char*)nullptr, commit ? p->rc2[n] : p->rcs, p->rh2, H, commit ? p->rxh2[n] + H : (float*)nullptr, 2 * H,
-                       (const unsigned char*)nullptr);
+    const LstmStepNet net{th + L.w1, th + L.bi1, th + L.bh1, th + L.w2, th + L.bi2, th + L.bh2, p->D, Dp, H};
+    lstm_step_forward(net, p->rxh1[n], p->rxh2[n], p->rc1[n], p->rc2[n], p->rg, p->rh2, p->rcs, obs, (int)N, obs_mean, obs_std, reset, commit != 0, s, gemm);
     GemmArgs g{};
     g.A = p->rh2; g.lda = H; g.B = th + L.wo; g.ldb = H; g.C = p->ry; g.ldc = L.Op; g.M = (int)N; g.N = L.O; g.K = H; g.bias = th + L.bo;
     launch_gemm<true, true>(g, s);
@@ -283,6 +255,29 @@ extern "C" int lhw_rnn_forward(LhwRnn* p, const float* theta, const float* obs, 
       HIPCHK(hipMemcpy2DAsync(value, sizeof(float), p->ry, sizeof(float) * L.Op, sizeof(float), N, hipMemcpyDeviceToDevice, s));
     }
   }
+  HIPCHK(hipGetLastError());
+  return LHW_OK;
+}
+
+// The critic over a stored rollout as one launch (lstm_seq_value_strip_kernel, lhw_mlp_strip.hip) in place of 2T + 1 calls of lhw_rnn_forward: same
+// values, same state left in rxh1[1] / rxh2[1] / rc1[1] / rc2[1].  The [in][out] weight copies go to the scratch lhw_rnn_grad's critic strip uses
+// (wt_seq[1]; every user fills it before reading it, in stream order).
+extern "C" int lhw_rnn_values(LhwRnn* p, const float* theta, const float* obs, const float* term_obs, const uint8_t* done, const uint8_t* reset0, int32_t T,
+                              int32_t N, const float* obs_mean, const float* obs_std, float* val, float* vterm, float* vfinal, void* stream) {
+  if (!p || !theta || !obs || !done || !obs_mean || !obs_std || !val || (term_obs == nullptr) != (vterm == nullptr)) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (T <= 0 || N <= 0 || N > p->Nroll) return lhw_fail(LHW_ERR_ARG, "bad argument (T=%d, N=%d, capacity %d)", T, N, p->Nroll);
+  const LstmLayout& L = p->lc;
+  if (!lstm_seq_values_supported(L.H, L.Dp) || !p->wt_seq[1])
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_rnn_values: hidden width a multiple of 32 in [%d, %d] (this critic: %d), padded observation width <= %d",
+                    LHW_LSTM_SEQ_MIN_HIDDEN, LHW_LSTM_SEQ_MAX_HIDDEN, L.H, LHW_LSTM_SEQ_MAX_OBS_PAD);
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t s = (hipStream_t)stream;
+  const float* th = theta + p->off_critic;
+  float* wt = p->wt_seq[1];
+  lstm_seq_strip_prepare(th + L.w1, th + L.w2, L.H, L.Dp, wt, s);
+  const LstmSeqValues a{wt, wt + (size_t)L.K1 * 4 * L.H, th + L.bi1, th + L.bh1, th + L.bi2, th + L.bh2, th + L.wo, th + L.bo, obs_mean, obs_std, obs, term_obs, done, reset0,
+                        p->rxh1[1] + L.Dp, L.K1, p->rxh2[1] + L.H, 2 * L.H, p->rc1[1], p->rc2[1], val, vterm, vfinal, T, N, L.H, p->D, L.Dp};
+  lstm_seq_strip_values(a, s);
   HIPCHK(hipGetLastError());
   return LHW_OK;
 }

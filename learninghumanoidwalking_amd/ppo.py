@@ -410,6 +410,9 @@ class Rollout(_RolloutStorage):
 # DESIGN.md section 1 (profiles/r07_lstm_resident_ab.txt) under the rule of the term-statistics work -- resident by default only if its
 # mean sample time lies below every run of the launch-per-step parent.
 LSTM_RESIDENT_AUTO = False
+# Whether RecurrentRollout evaluates the critic of a rollout in one launch behind it (RnnKernels.values) instead of per control step:
+# LHW_RNN_SEQ_CRITIC = 0 | 1 overrides.  Same bits either way; the A/B of DESIGN.md section 4.2d decides the default under the same rule.
+RNN_SEQ_CRITIC_DEFAULT = False
 
 
 class RecurrentRollout(_RolloutStorage):
@@ -423,7 +426,11 @@ class RecurrentRollout(_RolloutStorage):
     Two ways to collect, bitwise the same buffers (tests/test_rollout_lstm_gpu.py): launch per control step, or the resident rollout
     (BatchedEnv.rollout_lstm: one launch, the actor's two cells evaluated inside the stepper's wavefronts) followed by the critic over
     the stored time slices.  LHW_ROLLOUT_MODE = auto (LSTM_RESIDENT_AUTO decides) | resident (declining raises) | steps; `last_mode`
-    names the path the last collect() took."""
+    names the path the last collect() took.
+
+    The critic: with LHW_RNN_SEQ_CRITIC=1 (read once, here; default RNN_SEQ_CRITIC_DEFAULT) both paths collect with the actor alone and
+    evaluate val / vterm / vfinal of the whole rollout in one launch behind it (RnnKernels.values), where the kernel covers the critic's
+    shape; otherwise per control step (`forward`).  `last_critic_mode` = "sequence" | "steps" names what the last collect() did."""
 
     def __init__(self, env, kernels, T: int, seed: int = 0):
         super().__init__(env, kernels, T, seed)
@@ -434,6 +441,8 @@ class RecurrentRollout(_RolloutStorage):
         self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
         self._tob_all = self._tin_all = None      # [T][N][D] terminal observations / [T][N][176] records: allocated by the first resident rollout
         self.last_mode = None
+        self.seq_critic = os.environ.get("LHW_RNN_SEQ_CRITIC", "1" if RNN_SEQ_CRITIC_DEFAULT else "0") != "0"
+        self.last_critic_mode = None
 
     @property
     def tin_all(self):
@@ -442,16 +451,43 @@ class RecurrentRollout(_RolloutStorage):
 
     def collect(self, deterministic=False):
         self._start()
+        self.last_critic_mode = None      # set by whichever path evaluates val / vterm
+        reset0 = self._rec_reset
         if self._collect_resident(deterministic):
             self.last_mode = "resident"
         else:
             self.last_mode = "steps"
             self._collect_steps(deterministic)
+        if self.last_critic_mode is None:      # the actor alone has run: the critic over the stored slices, in one launch or step by step
+            if self.k.values(self.obs, self._tob_all, self.done, reset0, self.val, self.vterm, self.vfinal):
+                self.last_critic_mode = "sequence"
+                return
+            self._critic_steps(reset0)
         self.k.forward(self.obs[self.T], commit=False, want_actor=False, value=self.vfinal)
+
+    def _critic_steps(self, reset):
+        """V(s_t) advancing the critic's state, V(terminal observation) without, over the stored slices: the calls of the launch-per-step loop"""
+        k = self.k
+        for t in range(self.T):
+            k.forward(self.obs[t], reset=reset, commit=True, want_actor=False, value=self.val[t])
+            k.forward(self._tob_all[t], commit=False, want_actor=False, value=self.vterm[t])
+            reset = (self.done[t] != 0).to(torch.uint8)
+        self.last_critic_mode = "steps"
 
     def _collect_steps(self, deterministic):
         env, k, T = self.env, self.k, self.T
         reset = self._rec_reset
+        if self.seq_critic:      # actor only; the terminal observations are kept for the critic's pass behind the loop
+            if self._tob_all is None:
+                self._tob_all = _lib.empty(T, self.N, env.obs_dim, dtype=torch.float32, device=self.obs.device)
+            for t in range(T):
+                k.forward(self.obs[t], reset=reset, seed=self.seed, env_id_base=self.env_base, counter=self.counter, deterministic=deterministic,
+                          commit=True, want_value=False, mu=self.mu, act=self.act[t], logp=self.logp[t])
+                env.step(self.act[t], obs_out=self.obs[t + 1], term_obs_out=self._tob_all[t], rew_out=self.rew[t], done_out=self.done[t])
+                reset = (self.done[t] != 0).to(torch.uint8)
+                self.counter += 1
+            self._rec_reset = reset
+            return
         for t in range(T):
             k.forward(self.obs[t], reset=reset, seed=self.seed, env_id_base=self.env_base, counter=self.counter,
                       deterministic=deterministic, commit=True, mu=self.mu, act=self.act[t], logp=self.logp[t], value=self.val[t])
@@ -460,6 +496,7 @@ class RecurrentRollout(_RolloutStorage):
             reset = (self.done[t] != 0).to(torch.uint8)
             self.counter += 1
         self._rec_reset = reset
+        self.last_critic_mode = "steps"
 
     def _collect_resident(self, deterministic) -> bool:
         """All T control steps in one launch, then the critic over the stored slices in the order of the launch-per-step loop
@@ -489,12 +526,9 @@ class RecurrentRollout(_RolloutStorage):
                     self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
                 if env.rollout_lstm(pol, T, self.obs, self.act, self.logp, self._tob_all, self.rew, self.done, self._rec_reset,
                                     task_inputs=self._tin_all if self.record_task_inputs else None):
-                    reset = self._rec_reset
-                    for t in range(T):
-                        k.forward(self.obs[t], reset=reset, commit=True, want_actor=False, value=self.val[t])
-                        k.forward(self._tob_all[t], commit=False, want_actor=False, value=self.vterm[t])
-                        reset = (self.done[t] != 0).to(torch.uint8)
-                    self._rec_reset = reset
+                    if not self.seq_critic:
+                        self._critic_steps(self._rec_reset)
+                    self._rec_reset = (self.done[T - 1] != 0).to(torch.uint8)
                     self.counter += T
                     return True
                 why = "the library has no resident LSTM rollout kernel for this env / policy"

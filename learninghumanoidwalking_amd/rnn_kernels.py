@@ -56,6 +56,22 @@ class RnnKernels(_Kernels):
                                            _p(logp) if want_actor else None, _p(value) if want_value else None, self._stream()))
         return mu, act, logp, value
 
+    def values(self, obs, term_obs, done, reset0, val, vterm=None, vfinal=None) -> bool:
+        """The critic over a stored rollout in one launch (lhw_rnn_values): ``obs [T + 1, N, D]`` raw observations, ``term_obs [T, N, D]``,
+        ``done [T, N]`` uint8, ``reset0 [N]`` uint8 or None.  Bitwise what ``forward(obs[t], reset=..., commit=True, want_actor=False)``,
+        ``forward(term_obs[t], commit=False, ...)`` per step and ``forward(obs[T], commit=False, ...)`` write to ``val [T, N]``,
+        ``vterm [T, N]`` (None together with ``term_obs``) and ``vfinal [N]`` (may be None), and the critic state they leave.
+        Returns False, with nothing written, where the kernel does not cover the critic's shape: the caller keeps those calls."""
+        T, N = int(done.shape[0]), int(done.shape[1])
+        assert obs.shape[0] == T + 1 and obs.shape[1] == N and obs.is_contiguous() and done.is_contiguous() and val.is_contiguous()
+        assert (term_obs is None) == (vterm is None) and all(x is None or x.is_contiguous() for x in (term_obs, vterm, vfinal, reset0))
+        rc = self._L.lhw_rnn_values(self._h, _p(self.theta), _p(obs), _p(term_obs), _p(done), _p(reset0), T, N, _p(self.obs_mean), _p(self.obs_std),
+                                    _p(val), _p(vterm), _p(vfinal), self._stream())
+        if rc == -4:      # LHW_ERR_UNSUPPORTED
+            return False
+        _lib.check(rc)
+        return True
+
     def rollout_policy(self, *, seed=0, counter=0, deterministic=False):
         """The frozen LSTM actor as the resident rollout (BatchedEnv.rollout_lstm -> lhw_env_rollout_lstm) evaluates it inside the
         stepper's wavefronts: [in][out] weight copies made on the current stream, and this handle's own actor state buffers -- the ones
