@@ -233,6 +233,22 @@ typedef struct {
 int lhw_env_rollout_lstm(LhwEnv* env, const LhwRolloutLstmPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                          float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, const uint8_t* reset0_dev,
                          double* tin_dev, double* stin_dev, void* stream);
+/* lhw_env_rollout for an env with an OBSERVATION HISTORY (obs_history_len of the reference's YAML configs,
+ * envs/common/base_humanoid_env.py:53,177-197,274: the observation is the last history_len base observations, newest first, flattened; a
+ * reset empties the history and zero-fills it).  obs_dev [T + 1][N][history_len * base] and term_obs_dev [T][N][history_len * base], base =
+ * lhw_env_obs_dim(env); policy->obs_dim must equal history_len * base.  Slice 0 of obs_dev holds the full observations to act on first; per
+ * control step the wavefront that advances an env shifts its row on the device:
+ *   obs[t + 1][n] = [ base observation of step t | done[t][n] ? +0 : obs[t][n] without its last `base` columns ]
+ *   term_obs[t][n] = [ terminal base observation | obs[t][n] without its last `base` columns ]
+ * Nothing of the history is kept in the env handle: obs_dev is the state, slice T the input of the next rollout.  The policy step for rows
+ * wider than 64 columns sums in the order of the per-layer GEMM forward the launch-per-step pipeline runs for such rows (lhw_ppo_forward_at:
+ * every layer one chain over ascending k, the bias behind it); lhw_debug_policy_step is its reference, bit for bit.  tin_dev / stin_dev:
+ * nullable, the records of every control step as in lhw_env_rollout_task_inputs / lhw_env_rollout_step_task_inputs.  history_len == 1
+ * forwards to those entry points and launches their kernels.  LHW_ERR_UNSUPPORTED wherever lhw_env_rollout refuses, and for a padded row
+ * wider than LHW_ROLLOUT_HISTORY_MAX_OBS_PAD (history_len <= 6 on jvrc_walk / jvrc_step, 7 on h1, 5 on h1_walk). */
+int lhw_env_rollout_history(LhwEnv* env, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, int32_t history_len,
+                            float* obs_dev, float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev,
+                            float* rew_terms_dev, double* tin_dev, double* stin_dev, void* stream);
 /* 1 if the most recent lhw_env_rollout of this env drained the job queue (rocprof name humanoid_rollout_kernel<TASK, 64, true>), 0 if
  * every wavefront kept its env group (<.., false>); what bench.py names as the dominant kernel. */
 int lhw_env_last_rollout_queued(LhwEnv* env);
@@ -406,7 +422,9 @@ typedef struct LhwTrainStripArgs {
 int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* args, int32_t fused, void* stream);
 /* Test hook: the rollout's per-control-step policy launch (observation normalisation -> actor -> Gaussian head, one strip launch;
  * what lhw_ppo_forward_at runs when only act / logp are requested) on R raw observation rows [R][obs_dim], from an actor view.
- * y [R][act_pad] receives the means.  The reference of lhw_env_rollout's in-wave policy step (bitwise). */
+ * y [R][act_pad] receives the means.  The reference of lhw_env_rollout's in-wave policy step (bitwise).  obs_pad in (64,
+ * LHW_ROLLOUT_HISTORY_MAX_OBS_PAD] (an observation history): a plain launch, a workgroup per row and a thread per hidden unit, in the
+ * order of the per-layer GEMM forward -- the reference of lhw_env_rollout_history's in-wave step (bitwise). */
 int lhw_debug_policy_step(const LhwRolloutPolicy* policy, const float* obs, int32_t R, uint32_t env_id_base, uint32_t counter, float* y,
                           float* act, float* logp, void* stream);
 /* Test hook: lhw_rnn_forward's actor step (normalisation -> two LSTM cells -> read-out -> Gaussian head, commit = 1) on R raw observation
@@ -507,7 +525,8 @@ int lhw_ppo_begin_rollout(LhwPpo* ppo, const float* theta, void* stream);
 int lhw_ppo_end_rollout(LhwPpo* ppo);
 /* Inside a rollout bracket opened with this theta: the actor of theta as lhw_env_rollout reads it (the bracket's [in][out]
  * weight copies, biases and stds inside theta, the caller's normalisation vectors).  Valid until lhw_ppo_end_rollout /
- * lhw_ppo_apply.  LHW_ERR_UNSUPPORTED outside a bracket or for shapes the strip kernels do not cover.  With fp16 inference selected
+ * lhw_ppo_apply.  LHW_ERR_UNSUPPORTED outside a bracket or for shapes the in-wave steps do not cover (hidden width 256; padded observation
+ * width <= 64, or <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD for lhw_env_rollout_history).  With fp16 inference selected
  * (lhw_ppo_set_inference_dtype) the view asks for fp16 operands: the in-wave policy step then rounds weights and activations to fp16 and
  * accumulates in float32 over ascending k -- the fp16 MFMA of the launch-per-step path adds its 16 products per instruction in its own
  * order, so in THAT mode the two rollouts agree to float32 rounding (1e-6), not bitwise. */
@@ -617,6 +636,9 @@ int lhw_rnn_apply(LhwRnn* rnn, float* theta, float* grad, float* adam_m, float* 
 #define LHW_LSTM_SEQ_MIN_HIDDEN 32
 #define LHW_LSTM_SEQ_MAX_HIDDEN 256
 #define LHW_LSTM_SEQ_MAX_OBS_PAD 128
+/* Padded observation width up to which lhw_env_rollout_history evaluates the feed-forward actor inside the stepper's wavefronts (the rows sit in
+ * the stepper's LDS stage region beside the two hidden layers: two rows of 256 columns still fit the smallest layout, H1's two envs per wave). */
+#define LHW_ROLLOUT_HISTORY_MAX_OBS_PAD 256
 /* debug / A-B: on != 0: lhw_rnn_grad runs each network's forward time loop and its BPTT time loop (rl/algos/ppo.py:512-533) as ONE launch each
  * (the whole-sequence strip kernels, the critic's on a side stream) where the shape is covered; 0: four launches per time step and network.
  * Same bits either way.  A new handle takes the environment's LHW_RNN_SEQ_FUSED (default 1: the A/B of DESIGN.md 4.2c). */

@@ -128,6 +128,7 @@ TASK_INPUT_FIELDS = dict(grf_r=(0, 1), grf_l=(1, 1), contact_z=(2, 1), foot_cont
 
 # include/lhw.h: enum LhwStepTaskInput (the stepping task's second record; offsets into one env's record, length)
 STEP_TASK_INPUT_DIM = 32
+ROLLOUT_HISTORY_MAX_OBS_PAD = 256      # include/lhw.h LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: padded row width of lhw_env_rollout_history's in-wave policy step
 STEP_TASK_INPUT_FIELDS = dict(rsite_xpos=(0, 3), lsite_xpos=(3, 3), target1=(6, 4), target2=(10, 4), reached=(14, 1), frames=(15, 1), t1=(16, 1),
                               t2=(17, 1), nseq=(18, 1), goal=(19, 8), root_xquat=(27, 4))
 
@@ -325,6 +326,7 @@ def declare(L):
     sig("lhw_env_last_rollout_queued", [vp])
     sig("lhw_env_rollout_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_rollout_step_task_inputs", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_env_rollout_history", [vp, ctypes.POINTER(LhwRolloutPolicy), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutPolicy)])
     sig("lhw_debug_policy_step", [ctypes.POINTER(LhwRolloutPolicy), vp, i32, u32, u32, vp, vp, vp, vp])
     sig("lhw_rnn_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutLstmPolicy), vp])

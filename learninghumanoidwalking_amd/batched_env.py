@@ -77,8 +77,9 @@ class BatchedEnv:
         _lib.check(L.lhw_env_create(self._ib.ctypes.data, self._ib.size, self._db.ctypes.data, self._db.size,
                                     ctypes.byref(cfg), ctypes.byref(self._h)))
         self._L = L
-        # obs_history_len > 1 (base_humanoid_env.py:177-197) is kept above the kernels: they emit the base observation, the
-        # history rows are shifted on the device by a few torch ops per step (history_update); obs_dim is the full length
+        # obs_history_len > 1 (base_humanoid_env.py:177-197): obs_dim is the full length.  The resident rollout shifts the history rows
+        # inside the stepper's wavefronts (lhw_env_rollout_history); the launch-per-step calls (step / step_range / reset) get the base
+        # observation from the kernels and shift the rows by a few torch ops per step (history_update) -- the same values
         self.base_obs_dim = L.lhw_env_obs_dim(self._h)
         self.history_len = int(history_len)
         if self.history_len < 1:
@@ -174,10 +175,12 @@ class BatchedEnv:
         term_obs [T, N, D].  `task_inputs` [T, N, TASK_INPUT_DIM] float64 (optional): the sim-facade record of EVERY control step
         (lhw_env_rollout_task_inputs), for reward-only task plug-ins; `step_task_inputs` [T, N, STEP_TASK_INPUT_DIM] float64 (stepping
         task only, together with `task_inputs`): the stepping task's second record of every control step as well
-        (lhw_env_rollout_step_task_inputs).  Returns False (nothing launched) where the library has no resident kernel for this env /
-        policy; a HIP failure raises."""
+        (lhw_env_rollout_step_task_inputs).  An env with an observation history (history_len > 1) goes through
+        lhw_env_rollout_history: the wavefronts shift the history rows themselves, obs[0] is the state they start from, and the env's
+        own copy of the current full observation is set to obs[T] afterwards, so launch-per-step calls may follow.  Returns False
+        (nothing launched) where the library has no resident kernel for this env / policy; a HIP failure raises."""
         N = self.n_envs
-        if self.history_len > 1 or policy is None:
+        if policy is None:
             return False
         assert obs.shape == (T + 1, N, self.obs_dim) and act.shape == (T, N, self.act_dim) and term_obs.shape == (T, N, self.obs_dim)
         assert logp.shape == (T, N) and rew.shape == (T, N) and done.shape == (T, N) and done.dtype == torch.uint8
@@ -191,6 +194,13 @@ class BatchedEnv:
             assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
         if task_inputs is not None:
             assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
+        if self.history_len > 1:
+            rc = self._L.lhw_env_rollout_history(*args[:5], self.history_len, *args[5:], _ptr(task_inputs), _ptr(step_task_inputs),
+                                                 _stream_ptr(self.device))
+            if rc == 0:      # the launch-per-step calls continue from the rollout's last observation (a device copy behind the launch)
+                a, b = int(first), int(first) + (int(N - first) if count is None else int(count))
+                self._full[a:b].copy_(obs[T, a:b])
+        elif task_inputs is not None:
             if step_task_inputs is not None:
                 rc = self._L.lhw_env_rollout_step_task_inputs(*args, _ptr(task_inputs), _ptr(step_task_inputs), _stream_ptr(self.device))
             else:

@@ -248,6 +248,27 @@ extern "C" int lhw_env_rollout_step_task_inputs(LhwEnv* e, const LhwRolloutPolic
   return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
 }
 
+extern "C" int lhw_env_rollout_history(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, int32_t history_len, float* obs_dev,
+                                       float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev,
+                                       double* tin_dev, double* stin_dev, void* stream) {
+  if (history_len < 1) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_history: history_len = %d", history_len);
+  if (stin_dev && (!e || e->task != LHW_TASK_JVRC_STEP)) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: the stepping record needs a stepping-task env");
+  if (stin_dev && !tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_history: the stepping record is exported together with the task-input record");
+  if (history_len == 1)   // no history: the kernels of lhw_env_rollout
+    return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
+  if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: wave-per-env (humanoid) steppers only");
+  HIPCHK(hipSetDevice(e->device));
+  const int rc = humanoid_rollout_history(e->hum, first, count, T, history_len, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev,
+                                          tin_dev, stin_dev, (hipStream_t)stream);
+  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
+  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout_history: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
+  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: needs a float32 actor obs %d x %d (padded <= %d) -> 256 -> 256 -> act %d (<= 12) and a model that "
+                          "fits the task's resident kernel", history_len, e->obs_dim, LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, e->act_dim);
+  HIPCHK(hipGetLastError());
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_rollout_lstm(LhwEnv* e, const LhwRolloutLstmPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                     float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, const uint8_t* reset0_dev,
                                     double* tin_dev, double* stin_dev, void* stream) {

@@ -395,6 +395,8 @@ struct HumanoidEnv {
   bool fast;   // the model fits the two-envs-per-wave kernels (W = 32)
   unsigned* ro_queue = nullptr;   // job counter + per-group progress words of the resident rollout's queue mode (lhw_humanoid_rollout.hip)
   int last_rollout_queued = 0;    // the most recent resident rollout drained the job queue (humanoid_rollout_kernel<.., QUEUE = true>)
+  float *hist_base = nullptr, *hist_tbase = nullptr;   // [n_envs][obs_dim] each: the base observation / terminal observation rows control_step writes
+                                                       // in a rollout with an observation history (lhw_env_rollout_history), one block in `mem`
 };
 
 // ------------------------------------------------------------------------------------------------ LDS working set

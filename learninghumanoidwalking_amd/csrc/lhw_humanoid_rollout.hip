@@ -33,6 +33,7 @@
 #define PKQ 32      // the read-out is summed as PH / PKQ partial products of PKQ k each (SKQ of lhw_mlp_strip.hip)
 #define PXK 64      // capacity of the padded observation row
 #define PO_MAX 16   // action dims the read-out's lane mapping covers (JVRC 12, H1 10): four column groups of four
+#define PXW LHW_ROLLOUT_HISTORY_MAX_OBS_PAD   // capacity of the padded observation row in the history family (policy_step_wide): a multiple of 2 PU
 
 // agent-scope loads / stores of the job queue's progress words (a wave on another XCD wrote them: not through this XCD's L2)
 #if defined(__HIP_EMU__)
@@ -65,15 +66,22 @@ struct HRolloutT {
 };
 // Policy kinds of the resident rollout: the feed-forward 256-256 actor (policy_step) and the two-cell LSTM actor (lstm_policy_step).  The kind
 // is a template parameter of rollout_steps and picks the kernel's argument struct, so a feed-forward kernel holds nothing of the LSTM step.
-enum { POLICY_MLP = 0, POLICY_LSTM = 1 };
+// POLICY_HIST: the feed-forward actor on an observation HISTORY (obs_history_len > 1: rows of history_len x base width, policy_step_wide).
+enum { POLICY_MLP = 0, POLICY_LSTM = 1, POLICY_HIST = 2 };
 struct LstmPolicyArg {
   LhwRolloutLstmPolicy q;
   const unsigned char* reset0;   // [n_total] rows whose episode starts with the rollout's first observation (their state counts as zero)
 };
+struct HistPolicyArg {
+  LhwRolloutPolicy q;    // obs_dim = history_len x the env's base width
+  float *base, *tbase;   // [n_total][base width] each: what control_step writes (observation / terminal observation of the step); history_shift reads them
+};
 typedef HRolloutT<LhwRolloutPolicy> HRollout;
 typedef HRolloutT<LstmPolicyArg> HRolloutLstm;
+typedef HRolloutT<HistPolicyArg> HRolloutHist;
 template <int PK> struct RolloutOf { typedef HRollout type; };
 template <> struct RolloutOf<POLICY_LSTM> { typedef HRolloutLstm type; };
+template <> struct RolloutOf<POLICY_HIST> { typedef HRolloutHist type; };
 
 // One 256-wide ReLU layer for the wave's G rows: hout[r][n] = relu(chain_k fmaf(W^T[k][n], xin[r][k]) + bias[n]), n = 4 wl .. 4 wl + 3.
 // The weight rows of PU consecutive k are requested as one batch of independent 16-byte loads, a batch ahead of the one being
@@ -206,6 +214,94 @@ __device__ __forceinline__ void policy_step(const LhwRolloutPolicy& q, float* sc
     logp_t[env0 + wl] = lp;
   }
   SYNC();
+}
+
+// ------------------------------------------------------------------------------------------------ observation history
+// obs_history_len > 1 (reference envs/common/base_humanoid_env.py:53,177-197,274): the observation is the last H base observations, newest
+// first, H x OBS wide.  Rows wider than the strip kernel's 64 columns go through the per-layer GEMMs in the launch-per-step pipeline
+// (mlp_forward, lhw_ppo.hip), so the in-wave step follows THAT path's order: hidden layers as policy_hidden (one fmaf chain over
+// ascending k from +0, bias, ReLU -- what gemm_f32_kernel computes), the read-out ONE chain over k = 0 .. 255 with the bias after it,
+// as lstm_policy_step's.  LDS: the rows (XK floats each), h1, h2, the Gaussian head's terms -- no partial sums.
+template <int G, int XK> struct PolicyLdsWide { static constexpr int XS = 0, H1 = XS + G * XK, H2 = H1 + G * PH, TM = H2 + G * PH, FLOATS = TM + G * 16; };
+template <int PK, int G> struct PolicyLdsOf { static constexpr int FLOATS = PolicyLds<G>::FLOATS; };
+template <int G> struct PolicyLdsOf<POLICY_HIST, G> { static constexpr int FLOATS = PolicyLdsWide<G, PXW>::FLOATS; };
+
+template <int G, bool HALF, int XK>
+__device__ __forceinline__ void policy_step_wide(const LhwRolloutPolicy& q, float* sc, const float* __restrict__ obs_t, float* __restrict__ act_t,
+                                                 float* __restrict__ logp_t, const int env0, const int nlive, const unsigned genv0, const unsigned counter) {
+  typedef PolicyLdsWide<G, XK> PL;
+  static_assert(XK % (2 * PU) == 0, "policy_hidden multiplies batches of 2 PU rows");
+  const int wl = fresh_wave_lane();
+  const int D = q.obs_dim, O = q.act_dim, Op = q.act_pad;
+  const int KP = (q.obs_pad + 2 * PU - 1) & ~(2 * PU - 1);   // (what policy_hidden's batches read: zero beyond the observation width)
+  float *xs = sc + PL::XS, *h1 = sc + PL::H1, *h2 = sc + PL::H2, *Tm = sc + PL::TM;
+#pragma unroll
+  for (int r = 0; r < G; r++)
+    for (int k = wl; k < KP; k += 64) {      // (the expression of normalize_kernel)
+      float v = 0.f;
+      if (k < D && r < nlive) v = (obs_t[(size_t)(env0 + r) * D + k] - q.obs_mean[k]) / q.obs_std[k];
+      xs[r * XK + k] = HALF ? r16(v) : v;
+    }
+  SYNC();
+  policy_hidden<G, HALF>(q.w1t, q.b1, xs, XK, q.obs_pad, h1, wl);
+  SYNC();
+  policy_hidden<G, HALF>(q.w2t, q.b2, h1, PH, PH, h2, wl);
+  SYNC();
+  // read-out: lane = (row, output unit), one chain over k = 0 .. 255 from +0 and the bias after it, 16 weight loads in flight
+  if (wl < 16 * G) {
+    const int rr = wl >> 4, col = wl & 15;
+    if (col < O && rr < nlive) {
+      const float* w = q.w3t + col;
+      float s = 0.f;
+      for (int k0 = 0; k0 < PH; k0 += 16) {
+        float wv[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) wv[j] = w[(size_t)(k0 + j) * Op];
+#pragma unroll
+        for (int j = 0; j < 16; j++) s = fmaf(h2[rr * PH + k0 + j], HALF ? r16(wv[j]) : wv[j], s);
+      }
+      s += q.b3[col];
+      float term;
+      const float a = lhw_policy_sample(s, q.stdv[col], q.seed, genv0 + (unsigned)rr, counter, col, q.deterministic, &term);
+      act_t[(size_t)(env0 + rr) * O + col] = a;
+      Tm[rr * 16 + col] = term;
+    }
+  }
+  SYNC();
+  if (wl < nlive) {
+    float lp = 0.f;
+    for (int k = 0; k < O; k++) lp += Tm[wl * 16 + k];     // (the order of sample_kernel's sum)
+    logp_t[env0 + wl] = lp;
+  }
+  SYNC();
+}
+
+// The history rows of the wave's live envs behind control step t (batched_env.history_update, base_humanoid_env.py:177-197): the base
+// observation the step returned in front of the previous full observation without its oldest entry -- zeros (+0) instead where the episode
+// ended and the env was reset (the deque is emptied and zero-filled); the terminal row keeps the history the episode ended with.
+//   obs[t+1][env] = [ base      | done ? 0 : obs[t][env][0 : D - OBS] ]
+//   tob[t][env]   = [ term base | obs[t][env][0 : D - OBS] ]
+// Nothing of the history lives in the wave or in the env record: obs[t] is the state, so the job queue needs nothing more.  All 64 lanes.
+__device__ __forceinline__ void history_shift(const HistPolicyArg& hp, const int OBS, const float* obs_t, float* obs_n, float* tob_t, const unsigned char* done_t,
+                                              const int env0, const int nlive) {
+  const int wl = fresh_wave_lane();
+  const int D = hp.q.obs_dim;
+  for (int r = 0; r < nlive; r++) {
+    const size_t env = (size_t)(env0 + r);
+    const bool ended = done_t[env] != 0;
+    for (int i = wl; i < D; i += 64) {
+      float o, tb;
+      if (i < OBS) {
+        o = hp.base[env * OBS + i];
+        tb = hp.tbase[env * OBS + i];
+      } else {
+        tb = obs_t[env * D + i - OBS];
+        o = ended ? 0.f : tb;
+      }
+      obs_n[env * D + i] = o;
+      tob_t[env * D + i] = tb;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ LSTM actor
@@ -399,6 +495,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     // lanes than the ones that read them) is visible
     __threadfence();
     const float* obs_t = ro.obs + (size_t)t * N * OBS;
+    if constexpr (PK == POLICY_HIST) obs_t = ro.obs + (size_t)t * N * (size_t)ro.pol.q.obs_dim;   // (a time slice holds rows of history_len x OBS)
     float* act_t = ro.act + (size_t)t * N * m.nu;
     if constexpr (PK == POLICY_LSTM) {
       // (the flags of the step before: read here, at the start of the policy step, so they also hold where the job queue cut the rollout)
@@ -409,6 +506,13 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
       lstm_policy_step<G>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, rst_t, env0, nlive, p.env_id_base + (unsigned)env0,
                           ro.pol.q.counter + (unsigned)t);
 #endif
+    } else if constexpr (PK == POLICY_HIST) {
+      if (ro.pol.q.fp16_operands)
+        policy_step_wide<G, true, PXW>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+                                       ro.pol.q.counter + (unsigned)t);
+      else
+        policy_step_wide<G, false, PXW>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+                                        ro.pol.q.counter + (unsigned)t);
     } else {
       if (ro.pol.fp16_operands)
         policy_step<G, true>(ro.pol, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
@@ -426,6 +530,10 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     const int g = W == 32 ? (wl >> 5) : 0, lane = wl & (W - 1);
     float* obs_n = ro.obs + (size_t)(t + 1) * N * OBS;
     float* tob_t = ro.tob + (size_t)t * N * OBS;
+    if constexpr (PK == POLICY_HIST) {   // control_step writes rows of OBS floats: the per-env base rows, which history_shift puts in front of the history
+      obs_n = ro.pol.base;
+      tob_t = ro.pol.tbase;
+    }
     float* rew_t = ro.rew + (size_t)t * N;
     unsigned char* done_t = ro.done + (size_t)t * N;
     bool ovf = false;
@@ -450,6 +558,14 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
       }
     }
 #endif
+    if constexpr (PK == POLICY_HIST) {
+      GROUP_SYNC(64);
+      __threadfence();   // the base rows and the flag of this control step (after a W = 64 re-run written by other lanes than the ones that read them)
+      const size_t DH = (size_t)ro.pol.q.obs_dim;
+      history_shift(ro.pol, OBS, obs_t, ro.obs + (size_t)(t + 1) * N * DH, ro.tob + (size_t)t * N * DH, done_t, env0, nlive);
+      // (the rows are published to the next policy step -- in queue mode another wave's -- by the fences that publish obs[t + 1] without a
+      //  history: the one at the top of the loop, and the one behind the chunk in the job loop)
+    }
   }
   if (st.wave_cyc) {
     const int wl = fresh_wave_lane();
@@ -466,7 +582,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 // control steps (control_step reads the HBM record and writes it back), so which wave runs a job does not matter to the bits.
 // A separate instantiation: wrapped into the job loop, the two-envs-per-wave kernels spill 25 more VGPRs and lose 2.8 % (round 5,
 // same box, jvrc_walk @ 4096), and at 8192 envs their waves are within +-2 % of each other anyway (queue +0.1 %).
-// Kernel families from one text (each once more for the LSTM actor, policy kind POLICY_LSTM): humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
+// Kernel families from one text (each once more for the LSTM actor, policy kind POLICY_LSTM, and for the observation history, POLICY_HIST): humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
 // statistics (control_step<.., STATS>) and is launched instead while lhw_env_enable_term_stats is in force.  Generated by a macro and not
 // through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
 #define DEFINE_ROLLOUT_KERNEL(NAME, STATS, PK) \
@@ -477,7 +593,7 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
   constexpr int G = 64 / W;                                                                                                                                         \
   constexpr size_t LDS_BYTES = sizeof(L) * G > sizeof(L1) ? sizeof(L) * G : sizeof(L1);                                                                             \
   static_assert(W == 64 || sizeof(L1) <= sizeof(L) * G, "the one-env-per-wave layout must fit the wave's two-env allocation (8 workgroups per CU)");                \
-  static_assert(L::USIZE_ * 2 - 48 >= PolicyLds<G>::FLOATS, "the policy step's activations must fit the stage region in front of the observation staging");         \
+  static_assert(L::USIZE_ * 2 - 48 >= PolicyLdsOf<PK, G>::FLOATS, "the policy step's activations must fit the stage region in front of the observation staging");         \
   __shared__ __attribute__((aligned(16))) unsigned char SGraw[LDS_BYTES];                                                                                           \
   LHW_LDS_POISON(SGraw);                                                                                                                                            \
   HParamsRef p = *(const HParams LHW_GLOBAL_AS*)pp;                                                                                                                 \
@@ -508,6 +624,9 @@ DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, POLICY_MLP)
 // the same two families with the LSTM actor's in-wave step (lhw_env_rollout_lstm)
 DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, POLICY_LSTM)
 DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, POLICY_LSTM)
+// ... and with the feed-forward actor on an observation history (lhw_env_rollout_history, history_len > 1): rows of up to PXW columns
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, POLICY_HIST)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, POLICY_HIST)
 
 // ------------------------------------------------------------------------------------------------ host side
 // The stepping task's two instantiations live in a translation unit of their own, lhw_humanoid_rollout_step.hip (this file included with
@@ -516,6 +635,7 @@ DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, POLICY_LSTM)
 // halves compile in parallel.
 void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
 void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutLstm ro);
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutHist ro);
 #ifdef LHW_ROLLOUT_STEP_TU
 void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
   // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
@@ -531,6 +651,13 @@ void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_
     else hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
   } else if (queued) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
   else hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+}
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutHist ro) {
+  if (!stats) {
+    if (queued) hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+    else hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  else hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
 }
 #else
 #ifdef LHW_ONLY_WALK
@@ -561,6 +688,15 @@ static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream
   } else {
     if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
     ROLLOUT_OTHER_TASKS(humanoid_rollout_lstm_stats_kernel, 32)
+  }
+}
+static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRolloutHist& ro) {
+  if (!stats) {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_hist_kernel, 32)
+  } else {
+    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+    ROLLOUT_OTHER_TASKS(humanoid_rollout_hist_stats_kernel, 32)
   }
 }
 
@@ -631,6 +767,29 @@ int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRollo
     return -2;
   HRollout ro;
   ro.pol = *pol;
+  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
+}
+
+// the resident rollout of an env with an observation history (lhw_env_rollout_history, history_len > 1): the policy reads rows of history_len
+// base observations; control_step writes the step's base rows to two per-env scratch buffers, allocated by the first such rollout
+int humanoid_rollout_history(HumanoidEnv* h, int first, int count, int T, int history_len, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp,
+                             float* term_obs, float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
+  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0 || history_len < 2) return -1;
+  const int obs_dim = rollout_obs_dim(h);
+  if (pol->hidden != PH || (long long)pol->obs_dim != (long long)history_len * obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) ||
+      pol->act_pad < pol->act_dim || pol->obs_pad < pol->obs_dim || pol->obs_pad > PXW || (pol->obs_pad & 3))
+    return -2;
+  if (!h->fast && h->p.task != TASK_STEP) return -3;   // (as rollout_launch: before anything is allocated)
+  if (!h->hist_base) {
+    float* b = h->mem.get_lazy<float>((size_t)h->p.n_envs * obs_dim * 2);
+    if (!b) return -4;
+    h->hist_base = b;
+    h->hist_tbase = b + (size_t)h->p.n_envs * obs_dim;
+  }
+  HRolloutHist ro;
+  ro.pol.q = *pol;
+  ro.pol.base = h->hist_base;
+  ro.pol.tbase = h->hist_tbase;
   return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
 }
 

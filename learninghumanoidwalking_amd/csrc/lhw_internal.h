@@ -105,6 +105,8 @@ int humanoid_step_range(HumanoidEnv* h, int first, int count, const float* act, 
 int humanoid_last_rollout_queued(const HumanoidEnv* h);
 int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
                      float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // lhw_humanoid_rollout.hip; -1 bad range, -2 / -3 unsupported, -4 HIP error
+int humanoid_rollout_history(HumanoidEnv* h, int first, int count, int T, int history_len, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp,
+                             float* term_obs, float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // history_len > 1; codes as humanoid_rollout
 int humanoid_rollout_lstm(HumanoidEnv* h, int first, int count, int T, const LhwRolloutLstmPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
                           float* rew, uint8_t* done, float* rew_terms, const uint8_t* reset0, double* tin_all, double* stin_all, hipStream_t s);   // same codes
 void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t s);

@@ -686,11 +686,76 @@ extern "C" int lhw_debug_mlp_strip_backward(int32_t H, int32_t O, int32_t Op, co
   return lhw_debug_mlp_strip_backward_bits(H, O, Op, w2, w3, dy, R, h1, h2, dh2, dh1, nullptr, nullptr, stream);
 }
 
+// The feed-forward actor's policy step for rows WIDER than the strip kernels' SXK columns (an observation history, lhw_env_rollout_history) as a
+// plain launch: a workgroup per row, a thread per hidden unit.  For such rows lhw_ppo_forward_at runs one GEMM per layer (mlp_forward, lhw_ppo.hip),
+// so this is that path's order -- every layer ONE fmaf chain over ascending k from +0 (what gemm_f32_kernel's v_mfma_f32_32x32x2_f32 loop computes),
+// then the bias, the read-out included -- and the order of policy_step_wide (lhw_humanoid_rollout.hip).  fp16_operands: as the in-wave step, every
+// weight and activation rounded to fp16 before its product, float32 sums.
+#if defined(__HIP_EMU__)
+__device__ __forceinline__ float ref_r16(float x) { return emu_f16_round(x); }
+#else
+__device__ __forceinline__ float ref_r16(float x) { return (float)(_Float16)x; }
+#endif
+__global__ void __launch_bounds__(SH) mlp_policy_ref_kernel(LhwRolloutPolicy q, const float* __restrict__ obs, int R, unsigned env_base, unsigned counter,
+                                                            float* __restrict__ y, float* __restrict__ act, float* __restrict__ logp) {
+  __shared__ float xs[LHW_ROLLOUT_HISTORY_MAX_OBS_PAD], h1[SH], h2[SH], terms[32];
+  LHW_LDS_POISON(xs);
+  LHW_LDS_POISON(h1);
+  LHW_LDS_POISON(h2);
+  LHW_LDS_POISON(terms);
+  const int row = (int)blockIdx.x, j = (int)threadIdx.x;
+  const int D = q.obs_dim, Dp = q.obs_pad, O = q.act_dim, Op = q.act_pad;
+  const bool half = q.fp16_operands != 0;
+  for (int k = j; k < Dp; k += SH) {
+    const float v = k < D ? (obs[(size_t)row * D + k] - q.obs_mean[k]) / q.obs_std[k] : 0.f;
+    xs[k] = half ? ref_r16(v) : v;
+  }
+  __syncthreads();
+  auto layer = [&](const float* wt, const float* bias, const float* x, int K) {
+    float a = 0.f;
+    for (int k = 0; k < K; k++) {
+      const float w = wt[(size_t)k * SH + j];
+      a = fmaf(half ? ref_r16(w) : w, x[k], a);
+    }
+    const float v = fmaxf(a + bias[j], 0.f);
+    return half ? ref_r16(v) : v;
+  };
+  h1[j] = layer(q.w1t, q.b1, xs, Dp);
+  __syncthreads();
+  h2[j] = layer(q.w2t, q.b2, h1, SH);
+  __syncthreads();
+  if (j < O) {
+    float s = 0.f;
+    for (int k = 0; k < SH; k++) {
+      const float w = q.w3t[(size_t)k * Op + j];
+      s = fmaf(h2[k], half ? ref_r16(w) : w, s);
+    }
+    s += q.b3[j];
+    y[(size_t)row * Op + j] = s;
+    float term;
+    act[(size_t)row * O + j] = lhw_policy_sample(s, q.stdv[j], q.seed, env_base + (unsigned)row, counter, j, q.deterministic, &term);
+    terms[j] = term;
+  }
+  __syncthreads();
+  if (j == 0) {
+    float lp = 0.f;
+    for (int k = 0; k < O; k++) lp += terms[k];     // (the order of sample_kernel's sum)
+    logp[row] = lp;
+  }
+}
+
 // the rollout's fused policy step (normalisation -> three layers -> Gaussian head) on R observation rows, from the actor view the
 // resident rollout reads: the launch lhw_ppo_forward_at issues per control step, reachable without an LhwPpo (tests, SIMT emulator)
 extern "C" int lhw_debug_policy_step(const LhwRolloutPolicy* q, const float* obs, int32_t R, uint32_t env_id_base, uint32_t counter, float* y,
                                      float* act, float* logp, void* stream) {
   if (!q || !obs || !y || !act || !logp || R <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
+  if (q->obs_pad > SXK) {      // an observation history: wider than the strip kernels' slab
+    if (q->hidden != SH || q->obs_pad > LHW_ROLLOUT_HISTORY_MAX_OBS_PAD || (q->obs_pad & 3) || q->obs_pad < q->obs_dim || q->act_dim <= 0 || q->act_dim > 32 ||
+        q->act_pad < q->act_dim)
+      return lhw_fail(LHW_ERR_UNSUPPORTED, "policy step: hidden width 256, padded input width <= %d, outputs <= 32", LHW_ROLLOUT_HISTORY_MAX_OBS_PAD);
+    hipLaunchKernelGGL(mlp_policy_ref_kernel, dim3(R), dim3(SH), 0, (hipStream_t)stream, *q, obs, R, env_id_base, counter, y, act, logp);
+    return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "mlp_policy_ref_kernel launch failed");
+  }
   if (!mlp_strip_supported(q->hidden, q->obs_pad, q->act_dim, q->act_pad)) return lhw_fail(LHW_ERR_UNSUPPORTED, "strip kernels: hidden width 256, padded input width <= 64, outputs <= 32");
   MlpStripFwd a{q->w1t, q->b1, q->w2t, q->b2, q->w3t, q->b3, obs, q->obs_dim, q->obs_pad, q->act_dim, q->act_pad, R, nullptr, nullptr, y};
   a.in_mean = q->obs_mean; a.in_std = q->obs_std; a.in_dim = q->obs_dim;

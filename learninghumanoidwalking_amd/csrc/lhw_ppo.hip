@@ -121,6 +121,12 @@ static int strip_mode() {
   static const int m = getenv("LHW_MLP_STRIP") ? atoi(getenv("LHW_MLP_STRIP")) : 2;
   return m;
 }
+// An actor whose padded observation row is wider than the strip kernels' slab (an observation history) but within the in-wave policy step of
+// lhw_env_rollout_history: its forward runs the per-layer GEMMs below; only the resident rollout reads [in][out] weight copies (LhwPpo::wt_roll)
+static bool rollout_wide_supported(const MlpLayout& L) {
+  return L.H == 256 && !mlp_strip_supported(L.H, L.Dp, L.O, L.Op) && L.Dp > 0 && L.Dp <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD && (L.Dp & 3) == 0 && L.O > 0 && L.O <= 32 &&
+         L.Op >= L.O;
+}
 static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStream_t s, const MlpMode& m) {
   const MlpLayout& L = n.L;
   const int R = r.rows, ldx = n.ldx, half = m.half;
@@ -309,6 +315,8 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
     mem.get(&p->stat_rows, NSTAT * R);
     mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op)));
     mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op));
+  } else if (rollout_wide_supported(p->a.L)) {
+    mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op));   // the actor's copies alone (wt_inf stays NULL: no strip launch reads them)
   }
   bool ok = !mem.failed() && learner_mirror(*p, c);
   p->two_streams = !(getenv("LHW_PPO_TWO_STREAMS") && atoi(getenv("LHW_PPO_TWO_STREAMS")) == 0);
@@ -447,13 +455,14 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
 extern "C" int lhw_ppo_begin_rollout(LhwPpo* p, const float* theta, void* stream) {
   if (!p || !theta) return lhw_fail(LHW_ERR_ARG, "null argument");
   p->roll_theta = nullptr;
-  if (strip_mode() < 2 || !p->wt_roll) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
+  const bool wide = p->wt_roll && !p->wt_inf;   // a wide-row actor: its copies serve lhw_env_rollout_history's in-wave step only
+  if (!p->wt_roll || (!wide && strip_mode() < 2)) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
   const MlpLayout &La = p->a.L, &Lc = p->c.L;
   const float *tha = theta + p->off_actor, *thc = theta + p->off_critic;
   mlp_strip_prepare(tha + La.w1, tha + La.w2, tha + La.w3, La.Dp, La.O, La.Op, p->wt_roll, s);
-  mlp_strip_prepare(thc + Lc.w1, thc + Lc.w2, thc + Lc.w3, Lc.Dp, Lc.O, Lc.Op, p->wt_roll + mlp_strip_wt_floats(La.Dp, La.Op), s);
+  if (!wide) mlp_strip_prepare(thc + Lc.w1, thc + Lc.w2, thc + Lc.w3, Lc.Dp, Lc.O, Lc.Op, p->wt_roll + mlp_strip_wt_floats(La.Dp, La.Op), s);
   HIPCHK(hipGetLastError());
   p->roll_theta = theta;
   return LHW_OK;
@@ -470,8 +479,8 @@ extern "C" int lhw_ppo_rollout_policy(LhwPpo* p, const float* theta, const float
   const MlpLayout& La = p->a.L;
   if (p->roll_theta == nullptr || p->roll_theta != theta || !p->wt_roll)
     return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_ppo_rollout_policy: no rollout bracket open for this theta (lhw_ppo_begin_rollout)");
-  if (!mlp_strip_supported(La.H, La.Dp, La.O, La.Op))
-    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_ppo_rollout_policy: actor with hidden width 256 only");
+  if (!mlp_strip_supported(La.H, La.Dp, La.O, La.Op) && !rollout_wide_supported(La))
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_ppo_rollout_policy: actor with hidden width 256 and a padded observation width <= %d only", LHW_ROLLOUT_HISTORY_MAX_OBS_PAD);
   const float* th = theta + p->off_actor;
   const float* wt = p->wt_roll;
   out->w1t = wt; out->b1 = th + La.b1;

@@ -116,7 +116,7 @@ class HumanoidSpec(BatchedFactory):
             raise ValueError(f"{type(self).__name__}: obs_dim is fixed by the task ({self.base_obs_dim}); got obs_dim={self.obs_dim}")
         c = self.cfg = load_config(self.yaml_path)
         self.sim_dt, self.control_dt = float(c["sim_dt"]), float(c["control_dt"])
-        self.history_len = int(c.get("obs_history_len", 1))     # base_humanoid_env.py:53,177-197 (kept above the kernels: BatchedEnv)
+        self.history_len = int(c.get("obs_history_len", 1))     # base_humanoid_env.py:53,177-197 (BatchedEnv: shifted in-wave by the resident rollout, by torch ops per launched step)
         if self.history_len < 1:
             raise ValueError("obs_history_len must be >= 1")
         self.action_smoothing = float(c["action_smoothing"])

@@ -148,11 +148,12 @@ class Rollout(_RolloutStorage):
         super().__init__(env, kernels, T, seed)
         self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
         self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
-        if task is not None and env.history_len > 1:
-            # (the hooked paths write the reset observation / history rows themselves and know nothing of the env-side history deque)
-            raise NotImplementedError("a plugged-in task with obs_history_len > 1 is not supported")
         # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
         self.reward_only = reward_only_on(task, env.task)
+        if task is not None and env.history_len > 1 and not self.reward_only:
+            # (a task that decides terminations resets through env.reset(mask, obs_out=...), which writes base rows and knows nothing of the
+            #  history; a reward-only task leaves flags, resets and with them the history to the kernels, resident or launch per step)
+            raise NotImplementedError("a plugged-in task that decides terminations itself is not supported with obs_history_len > 1")
         N, D, dev = self.N, env.obs_dim, env.device
         self.tob_all = torch.zeros(T, N, D, dtype=torch.float32, device=dev)      # [T][N][D] terminal observations
         # Number of independent env groups pipelined on separate streams (wave-per-env steppers; LHW_ROLLOUT_GROUPS overrides).
@@ -233,6 +234,8 @@ class Rollout(_RolloutStorage):
         # jvrc_walk @ 4096 +25 % env-steps/s (rollout 0.524 -> 0.397 s), jvrc_step @ 4096 +26 %, h1_walk @ 8192 +9 %, h1 @ 8192 +2 %
         # (twice as many wavefronts as the chip holds and a narrow spread of wave times: there two whole-chip launches in flight
         # already backfill each other's tails).
+        # An env with an observation history goes the same way (lhw_env_rollout_history): jvrc_walk @ 4096 with obs_history_len 3, sampling
+        # 0.47 -> 0.31 s per iteration, resident's mean below every launch-per-step iteration (profiles/r09_history_rollout_ab.txt).
         mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
         if mode not in ("auto", "resident"):
             return False
