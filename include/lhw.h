@@ -383,8 +383,10 @@ int lhw_debug_wgrad_skinny(int32_t H, int32_t Dp, int32_t O, int32_t Op, const f
  * /root/reference/rl/algos/ppo.py:299-406, the actor / critic forward and the activation gradients of loss.backward()):
  * forward  h1 = relu(x W1^T + b1), h2 = relu(h1 W2^T + b2), y = h2 W3^T + b3 for R rows in one launch;
  * backward dh2 = (dy W3) * (h2 > 0), dh1 = (dh2 W2) * (h1 > 0).  Weights in torch Linear layout ([out][in]; W1 row stride Dp,
- * a multiple of 4; W3 [Op][H]); device buffers; H must be 256, Dp <= 64, O <= 32 (LHW_ERR_UNSUPPORTED otherwise).  wt_scratch:
- * (Dp + 256 + Op) * 256 floats for the transposed weight copies the forward kernel reads. */
+ * a multiple of 4; W3 [Op][H]); device buffers; H must be 256, Dp <= LHW_MLP_STRIP_MAX_IN_PAD, O <= 32 (LHW_ERR_UNSUPPORTED otherwise, with
+ * nothing written).  Dp <= 64: the read-out y is the ascending sum of eight 32-k partial chains; Dp > 64 (the wide instantiations): ONE chain over
+ * k with the bias behind it, bitwise the per-layer GEMMs and lhw_debug_policy_step's plain launch.  wt_scratch: (Dp + 256 + Op) * 256 floats for
+ * the transposed weight copies the forward kernel reads. */
 int lhw_debug_mlp_strip_forward(int32_t H, int32_t Dp, int32_t O, int32_t Op, const float* w1, const float* b1, const float* w2,
                                 const float* b2, const float* w3, const float* b3, const float* x, int32_t ldx, int32_t R,
                                 float* h1, float* h2, float* y, float* wt_scratch, void* stream);
@@ -405,7 +407,9 @@ int lhw_debug_mlp_strip_backward_bits(int32_t H, int32_t O, int32_t Op, const fl
  * twins of rows [0, B) (twin0 >= B; act_src / act_sign [O]).  critic = 1: the value head (O = 1, Op = 4; ret [B]).  Outputs, device buffers:
  * h1 / h2 / dh2 / dh1 [rows][256], y / dy [rows][Op], dstd [B][Op] (actor, nullable), stat_rows [6][stat_ld]: every row's terms of the loss
  * scalars in lhw_ppo_grad's order (the actor writes all but term 1, the critic term 1).  fused = 1: one launch.  fused = 0: the forward
- * strip, the head as a thread-per-row kernel on y in HBM, the backward strip -- the same arithmetic, bit for bit. */
+ * strip, the head as a thread-per-row kernel on y in HBM, the backward strip -- the same arithmetic, bit for bit.  Dp in (64,
+ * LHW_MLP_STRIP_MAX_IN_PAD] (the wide instantiation): fused = 0 is instead the per-layer GEMM path that launch takes over, in independent code --
+ * a plain thread-per-output fmaf chain per layer with the GEMM's bias / ReLU / mask epilogue around the same head kernel; bit for bit again. */
 typedef struct LhwTrainStripArgs {
   int32_t H, Dp, O, Op;
   const float *w1, *b1, *w2, *b2, *w3, *b3;   /* torch Linear layout, as lhw_debug_mlp_strip_forward */
@@ -549,6 +553,13 @@ int lhw_ppo_set_update_dtype(LhwPpo* ppo, int fp16);
  * (float32 update, no armed imitation term, hidden width 256); 0: forward strip, ppo_loss_kernel, backward strip.  Same bits either way.
  * A new handle takes the environment's LHW_STRIP_FUSED (default 1). */
 int lhw_ppo_debug_set_strip_fused(LhwPpo* ppo, int32_t on);
+/* debug / A-B: networks whose padded observation row is wider than 64 columns (an observation history; up to LHW_MLP_STRIP_MAX_IN_PAD).  on != 0:
+ * wherever the handle chooses between a strip launch and per-layer GEMMs -- rollout inference, the critic's values behind the resident rollout,
+ * the one-launch policy step of lhw_ppo_forward_at, lhw_ppo_grad's forward / backward strips and train strips -- such shapes take the wide strip
+ * instantiations, under the conditions that hold for narrow shapes (float32; no armed imitation term for the train strips).  0 (a new handle):
+ * they run one GEMM per layer.  Same bits either way: the wide strips compute the GEMM path's chains.  The skinny weight gradients of such
+ * shapes stay split-K GEMMs.  Closes an open rollout bracket (lhw_ppo_begin_rollout makes the critic's weight copies for the path chosen). */
+int lhw_ppo_debug_set_strip_wide(LhwPpo* ppo, int32_t on);
 /* test hook: 1 if the last lhw_ppo_grad of this handle (a captured one included) ran the train strip launches, 0 if the three-launch path */
 int lhw_ppo_debug_last_grad_fused(const LhwPpo* ppo);
 /* time-major [T][N] GAE(lambda); done holds LHW_DONE_* flags, vterm the critic value of the terminal
@@ -639,6 +650,12 @@ int lhw_rnn_apply(LhwRnn* rnn, float* theta, float* grad, float* adam_m, float* 
 /* Padded observation width up to which lhw_env_rollout_history evaluates the feed-forward actor inside the stepper's wavefronts (the rows sit in
  * the stepper's LDS stage region beside the two hidden layers: two rows of 256 columns still fit the smallest layout, H1's two envs per wave). */
 #define LHW_ROLLOUT_HISTORY_MAX_OBS_PAD 256
+/* Padded input width up to which the LDS-resident strip kernels of the feed-forward MLPs run (csrc/lhw_mlp_strip.hip; hidden width 256): up to 64
+ * columns the input slab shares the activation slab with the partial read-out sums (the narrow instantiations); from 68 to this width -- the rows
+ * of an observation history -- the input fills the activation slab [256][rows] by itself and the read-out is one chain over k, the order of the
+ * per-layer GEMMs and of lhw_env_rollout_history's in-wave step (the wide instantiations; lhw_ppo_debug_set_strip_wide).  Equal to
+ * LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: every env that has the resident history rollout can have the strip update. */
+#define LHW_MLP_STRIP_MAX_IN_PAD 256
 /* debug / A-B: on != 0: lhw_rnn_grad runs each network's forward time loop and its BPTT time loop (rl/algos/ppo.py:512-533) as ONE launch each
  * (the whole-sequence strip kernels, the critic's on a side stream) where the shape is covered; 0: four launches per time step and network.
  * Same bits either way.  A new handle takes the environment's LHW_RNN_SEQ_FUSED (default 1: the A/B of DESIGN.md 4.2c). */

@@ -124,7 +124,8 @@ int humanoid_actuator_state(HumanoidEnv* h, double* pos, double* vel, double* tq
 int humanoid_step_record(HumanoidEnv* h, double* seq, double* floor_z, int32_t* istate);
 
 // LDS-resident strip kernels of the 3-layer MLPs (lhw_mlp_strip.hip); hidden width 256 only, callers fall back to the per-layer
-// GEMMs otherwise
+// GEMMs otherwise.  Two sets of instantiations by padded input width Dp, picked by the launchers: narrow (Dp <= 64: mlp_strip_supported) and
+// wide (64 < Dp <= LHW_MLP_STRIP_MAX_IN_PAD: mlp_strip_wide_supported; the read-out is then the GEMM path's single chain)
 struct MlpStripFwd {
   const float *w1t, *b1, *w2t, *b2, *w3t, *b3;   // TRANSPOSED weights ([in][out]: W1^T [Dp][256], W2^T [256][256], W3^T [256][Op]) from mlp_strip_prepare
   const float* x; int ldx;                   // [R][ldx] inputs (Dp used columns)
@@ -159,10 +160,12 @@ struct MlpStripTrain {
   LhwPpoHead head;
   float* stat_rows; int stat_ld;             // [NSTAT][stat_ld]: every live row's terms of the loss scalars (the actor's launch writes all but
 };                                           // term 1, the critic's term 1)
-bool mlp_train_strip_supported(int H, int Dp, int O, int Op, int critic);
+bool mlp_train_strip_supported(int H, int Dp, int O, int Op, int critic);            // the narrow train strip takes this shape
+bool mlp_train_strip_wide_supported(int H, int Dp, int O, int Op, int critic);       // the wide one does
 void mlp_train_strip(const MlpStripTrain& t, hipStream_t s);
 size_t mlp_strip_bits_words(size_t rows);    // words per layer of the mask bits of a launch over `rows` rows (64-row slabs)
-bool mlp_strip_supported(int H, int Dp, int O, int Op);
+bool mlp_strip_supported(int H, int Dp, int O, int Op);        // the narrow forward / backward strips take this shape
+bool mlp_strip_wide_supported(int H, int Dp, int O, int Op);   // the wide forward strip does (the backward strip has no input-width bound)
 size_t mlp_strip_wt_floats(int Dp, int Op);
 // WT [cols][ldt] <- W [rows][ld] for up to three matrices in one launch (mlp_strip_prepare's kernel; rows == 0: no matrix)
 struct LhwTransposeJob { const float* W; float* WT; int rows, cols, ld, ldt; };

@@ -22,6 +22,13 @@
 // Float32 operands and accumulation (the f32-input MFMA is an fmaf chain over ascending k), so the hidden layers are
 // bit-identical to the per-layer GEMM path and the networks keep the reference's float32 semantics; only the read-out's
 // summation order differs.
+//
+// Two sets of instantiations by the capacity XK of the input slab.  NARROW (XK = 64, padded input rows of up to 64 columns): the input slab is the
+// last 64 rows of S and the read-out is the sum of partials described above.  WIDE (XK = 256 = LHW_MLP_STRIP_MAX_IN_PAD: the rows of an observation
+// history, 68 .. 256 columns): the input fills S from row 0 -- it only has to live until the first layer's products are done, the accumulators
+// are in registers and h1 is written behind a barrier -- so the LDS allocation and the two workgroups per CU stay; the read-out is ONE chain
+// over k per row tile (fwd_readout_chain), which makes these instantiations bit-identical to the per-layer GEMM path in EVERY output, and to
+// the in-wave policy step of the history rollout (policy_step_wide).  The launchers pick the instantiation by Dp.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -38,7 +45,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define SH 256          // hidden width the strip kernels are compiled for
 #define SBK 16          // K step (one register buffer of weight operands)
-#define SXK 64          // capacity of the input slab (padded input width of the first layer / output width of the last)
+#define SXK 64          // capacity of the narrow input slab (padded input width of the first layer) and of the dy slab (output width of the last)
+#define SXW LHW_MLP_STRIP_MAX_IN_PAD   // capacity of the WIDE input slab (an observation history): the input fills the whole slab, S from row 0
+static_assert(SXK <= SH && SXW <= SH, "the input slab is a part of the activation slab");
+static_assert(SXW == LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, "every row the in-wave policy step of the history rollout takes has the strip update");
 #define SKQ 32          // the read-out is summed as SH / SKQ partial products of SKQ k each, in ascending order, whatever the shape
 
 // Shape of a workgroup: RT row tiles of 32 slab rows, NW waves, each owning CT column tiles of 32 output units (NW * CT * 32 =
@@ -70,8 +80,8 @@ extern "C" int lhw_debug_strip_clock_read(unsigned long long* host) {
 
 template <class C>
 struct StripLds {
-  float S[SH][C::LD];       // activation slab, k-major (Big: 69 632 B).  The input slab (x / dy, at most SXK columns) occupies
-};                          // its last SXK rows until the first layer's products are done
+  float S[SH][C::LD];       // activation slab, k-major (Big: 69 632 B).  The input slab (x: at most XK columns, XK = SXK or SXW per
+};                          // instantiation; dy: at most SXK) occupies its last XK rows until the first layer's products are done
 
 // Which global rows a slab holds: row tile i = the 32 rows from base[i]; a tile's rows from end[i] on are not live (staged as zeros,
 // never stored).  Consecutive: ROWS rows from row0.  Twins (the update's actor with mirroring): tile 0 = rows [r0, r0 + 32), tile 1 = the
@@ -259,7 +269,7 @@ __device__ __forceinline__ void store_act(StripLds<C>& L, const f32x16 (&acc)[C:
 // stage a [rows][K] row-major slab (row stride ld) k-major into X, zero-padded to a multiple of SBK in k and beyond R in rows
 // (mean / stdv: the input is a raw observation row of in_dim entries, normalised on the way in -- the same expression as
 // normalize_kernel, so the update, which normalises its minibatches there, sees the same bits)
-template <class C>
+template <class C, int XK>
 __device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __restrict__ x, const int ld, const int K, const SlabRows<C>& sr,
                                             const float* __restrict__ mean = nullptr, const float* __restrict__ stdv = nullptr, const int in_dim = 0) {
   const int Kp = (K + SBK - 1) & ~(SBK - 1);
@@ -268,7 +278,7 @@ __device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __re
     // -- as a loop of load -> write round trips (twelve of them, dependent) this stage took 5.4 us of a 64 us forward pass
     // (profiles/r06_strip_clock.txt)
     const int k4 = Kp >> 2;
-    constexpr int NQ = (C::ROWS * (SXK / 4) + C::THR - 1) / C::THR;
+    constexpr int NQ = (C::ROWS * (XK / 4) + C::THR - 1) / C::THR;
     const float rk4 = 1.f / (float)k4;
     float4 v[NQ];
 #pragma unroll
@@ -302,13 +312,14 @@ __device__ __forceinline__ void stage_input(float (*X)[C::LD], const float* __re
 // The phases of the kernels below.  Stamps: forward 0 .. 11, backward from stamp c0.
 // forward, hidden layers: x slab -> h1 -> h2; returns behind the barrier that leaves h2 in the slab.  bits1 / bits2 (HBM) or rb1 / rb2 (the
 // thread's registers, with RB) take the ReLU mask words
-template <class C, bool RB>
+template <class C, bool RB, int XK>
 __device__ __forceinline__ void fwd_hidden(StripLds<C>& L, const MlpStripFwd& a, const SlabRows<C>& sr, unsigned (&rb1)[C::CT], unsigned (&rb2)[C::CT]) {
-  float (*X)[C::LD] = &L.S[SH - SXK];
+  static_assert(XK <= SH && XK % SBK == 0, "the input slab is the last XK rows of the activation slab");
+  float (*X)[C::LD] = &L.S[SH - XK];
   WOp<C> w;
   SCLK(0);
   wload<C>(w, a.w1t, SH, a.Dp, 0);   // (the first weights of a layer are in flight while the slab is staged / the previous epilogue runs)
-  stage_input<C>(X, a.x, a.ldx, a.Dp, sr, a.in_mean, a.in_std, a.in_dim);
+  stage_input<C, XK>(X, a.x, a.ldx, a.Dp, sr, a.in_mean, a.in_std, a.in_dim);
   __syncthreads();
   SCLK(1);
   f32x16 acc[C::RT][C::CT];
@@ -373,6 +384,41 @@ __device__ __forceinline__ float (*fwd_readout_partials(StripLds<C>& L, const Ml
   return P;
 }
 
+// Read-out of the WIDE instantiations (XK > SXK).  For rows wider than SXK columns the path these kernels take over is the per-layer GEMM
+// forward, whose read-out is ONE fmaf chain over k = 0 .. SH - 1 from +0 with the bias behind it -- the order of policy_step_wide
+// (lhw_humanoid_rollout.hip) and of mlp_policy_ref_kernel too -- not the sum of SH / SKQ partial chains.  A chain cannot be cut over k between
+// waves: wave i < RT runs row tile i's, one accumulator through SH / 2 MFMAs, and the other waves wait at the barrier.  Returns like
+// fwd_readout_partials, P[0] [ROWS][32] holding the chains (the caller adds the bias) and no further partial.
+template <class C>
+__device__ __forceinline__ float (*fwd_readout_chain(StripLds<C>& L, const MlpStripFwd& a))[C::ROWS][32] {
+  static_assert(C::RT <= C::NW, "a wave per row tile");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, kh = lane >> 5;
+  f32x16 p;
+#pragma unroll
+  for (int r = 0; r < 16; r++) p[r] = 0.f;
+  if (wave < C::RT) {
+#pragma unroll 8
+    for (int kk = 0; kk < SH / 2; kk++) {
+      const int k = kk * 2 + kh;
+      const float bv = a.w3t[(size_t)k * a.Op + min(l31, a.O - 1)], b = l31 < a.O ? bv : 0.f;
+      p = __builtin_amdgcn_mfma_f32_32x32x2f32(L.S[k][32 * wave + l31], b, p, 0, 0, 0);
+    }
+  }
+  SCLK(10);
+  __syncthreads();   // all waves are done with the slab
+  SCLK(11);
+  float (*P)[C::ROWS][32] = reinterpret_cast<float (*)[C::ROWS][32]>(&L.S[0][0]);
+  if (wave < C::RT) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) P[0][32 * wave + (r & 3) + 8 * (r >> 2) + 4 * kh][l31] = p[r];
+  }
+  __syncthreads();
+  return P;
+}
+// how many partials the read-out of an instantiation with input-slab capacity XK leaves in P: SH / SKQ (fwd_readout_partials), or the one chain
+template <int XK> struct ReadoutParts { static constexpr int N = XK > SXK ? 1 : SH / SKQ; };
+
 // backward layers from the dy slab in X (complete, behind a barrier; `w` holds the first K step of W3): dh2 = (dy W3) * (h2 > 0) ->
 // dh1 = (dh2 W2) * (h1 > 0).  The masks: the activations h1 / h2, or their bits from HBM (bits1 / bits2) or, with RB, registers (rb1 / rb2)
 template <class C, bool RB>
@@ -400,7 +446,8 @@ __device__ __forceinline__ void bwd_layers(StripLds<C>& L, WOp<C>& w, const floa
   SCLK(c0 + 6);
 }
 
-template <class C>
+// XK: capacity of the input slab, SXK or SXW
+template <class C, int XK>
 __global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a) {
   __shared__ StripLds<C> L;
   LHW_LDS_POISON(L);
@@ -408,9 +455,9 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_fwd_strip_kernel(MlpStripFwd a)
   const int row0 = (int)blockIdx.x * C::ROWS;
   const SlabRows<C> sr = SlabRows<C>::consecutive(row0, a.R);
   unsigned rb1[C::CT], rb2[C::CT];   // (RB = 0: never touched; see store_act_t)
-  fwd_hidden<C, false>(L, a, sr, rb1, rb2);
-  float (*P)[C::ROWS][32] = fwd_readout_partials<C>(L, a);
-  constexpr int NQ = SH / SKQ;
+  fwd_hidden<C, false, XK>(L, a, sr, rb1, rb2);
+  float (*P)[C::ROWS][32] = ReadoutParts<XK>::N == 1 ? fwd_readout_chain<C>(L, a) : fwd_readout_partials<C>(L, a);
+  constexpr int NQ = ReadoutParts<XK>::N;
   for (int i = tid; i < C::ROWS * 32; i += C::THR) {
     const int row = i >> 5, col = i & 31;
     if (col < a.O && row0 + row < a.R) {
@@ -447,7 +494,7 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_bwd_strip_kernel(MlpStripBwd a)
   WOp<C> w;
   SCLK(0);
   wload<C>(w, a.w3, SH, a.O, 0);
-  stage_input<C>(X, a.dy, a.Op, a.O, sr);
+  stage_input<C, SXK>(X, a.dy, a.Op, a.O, sr);
   __syncthreads();
   unsigned rb1[C::CT], rb2[C::CT];   // (RB = 0: never touched; see store_act_t)
   bwd_layers<C, false>(L, w, a.w2, a.w3, a.O, sr, a.h1, a.h2, a.dh2, a.dh1, a.bits1, a.bits2, rb1, rb2, 1);
@@ -458,12 +505,14 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_bwd_strip_kernel(MlpStripBwd a)
 // workgroups of a CU), the loss launch and its dependency edges, and the HBM round trips of y, dy and the mask bits.  Every product and
 // every row's arithmetic is the other path's: the same fwd_hidden / fwd_readout_partials / bwd_layers on the same per-row fmaf chains, the same
 // ascending-k sum of the read-out partials, lhw_ppo_head.h's head -- bit-identical h1, h2, y, dy, dh2, dh1.
+// (XK = SXW, the wide instantiation: the other path is the per-layer GEMMs around ppo_loss_kernel's head and the read-out is fwd_readout_chain's single
+// chain; the dy slab stays in the LAST SXK rows of S, so the backward half is the narrow kernel's text.)
 //   read-out sum: y = sum of the partials + b3 -> P[0] in place (each thread its own entries) and, if asked for, HBM
 //   head: a thread per minibatch row reads its y (and its twin's) from P[0], writes dy k-major into the input-slab region X (disjoint from
 //         P[0]), zero-padded as stage_input would, and the row's loss terms / dstd to HBM
 //   dy slab -> HBM once (the weight-gradient kernels read it), then bwd_layers with the mask words still in registers
 // Stamps: forward 0 .. 11, 12 read-out sum done, 13 head done (behind the barrier), backward 14 .. 20.
-template <class C, int CRITIC>
+template <class C, int CRITIC, int XK>
 __global__ void __launch_bounds__(C::THR, 2) mlp_train_strip_kernel(MlpStripTrain t) {
   static_assert(C::RT == 2, "a twin slab is two row tiles");
   __shared__ StripLds<C> L;
@@ -473,9 +522,9 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_train_strip_kernel(MlpStripTrai
   const int nrow = t.twin0 > 0 ? 32 : C::ROWS;   // minibatch rows per slab
   const SlabRows<C> sr = t.twin0 > 0 ? SlabRows<C>::twins((int)blockIdx.x * 32, a.R, t.twin0) : SlabRows<C>::consecutive((int)blockIdx.x * C::ROWS, a.R);
   unsigned rb1[C::CT], rb2[C::CT];
-  fwd_hidden<C, true>(L, a, sr, rb1, rb2);
-  float (*P)[C::ROWS][32] = fwd_readout_partials<C>(L, a);
-  constexpr int NQ = SH / SKQ;
+  fwd_hidden<C, true, XK>(L, a, sr, rb1, rb2);
+  float (*P)[C::ROWS][32] = ReadoutParts<XK>::N == 1 ? fwd_readout_chain<C>(L, a) : fwd_readout_partials<C>(L, a);
+  constexpr int NQ = ReadoutParts<XK>::N;
   for (int i = tid; i < C::ROWS * 32; i += C::THR) {
     const int row = i >> 5, col = i & 31;
     if (col < a.O) {
@@ -491,7 +540,7 @@ __global__ void __launch_bounds__(C::THR, 2) mlp_train_strip_kernel(MlpStripTrai
   WOp<C> w;
   wload<C>(w, t.w3, SH, a.O, 0);
   __syncthreads();   // y is complete in P[0]; the other partials are spent
-  float (*X)[C::LD] = &L.S[SH - SXK];
+  float (*X)[C::LD] = &L.S[SH - SXK];   // (the dy slab: the last SXK rows whatever XK, disjoint from P[0])
   const int Kp = (a.O + SBK - 1) & ~(SBK - 1), Kz = max(Kp, a.Op);
   if (tid < nrow) {
     const int m = (int)blockIdx.x * nrow + tid;
@@ -584,17 +633,23 @@ void lhw_transpose3(const LhwTransposeJob (&jobs)[3], hipStream_t s) {
 
 size_t mlp_strip_bits_words(size_t rows) { return (rows + StripBig::ROWS - 1) / StripBig::ROWS * StripBig::THR * StripBig::CT; }
 
+// the narrow instantiations (input slab of SXK columns; read-out as partial sums) ...
 bool mlp_strip_supported(int H, int Dp, int O, int Op) { return H == SH && Dp > 0 && Dp <= SXK && (Dp & 3) == 0 && O > 0 && O <= 32 && Op >= O; }
+// ... and the wide ones (rows of an observation history: the input fills the slab; read-out as the GEMM path's single chain)
+bool mlp_strip_wide_supported(int H, int Dp, int O, int Op) { return H == SH && Dp > SXK && Dp <= SXW && (Dp & 3) == 0 && O > 0 && O <= 32 && Op >= O; }
 
 // Rows up to which the small shape is used: below it the slabs of the big shape would not even fill the CUs once, and the call
 // is latency-bound (rollout inference); above it the big shape's operand reuse wins (the update's minibatches).
 #define STRIP_SMALL_ROWS 16384
 void mlp_strip_forward(const MlpStripFwd& a, hipStream_t s, int shape /* 0: by row count, 1: small, 2: big */) {
   if (a.R <= 0) return;
-  if ((shape == 1 || (shape == 0 && a.R <= STRIP_SMALL_ROWS)) && !a.bits1 && !a.bits2)   // (mask bits: the backward kernel's shape)
-    hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripSmall>), dim3((a.R + StripSmall::ROWS - 1) / StripSmall::ROWS), dim3(StripSmall::THR), 0, s, a);
-  else
-    hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripBig>), dim3((a.R + StripBig::ROWS - 1) / StripBig::ROWS), dim3(StripBig::THR), 0, s, a);
+  const bool small = (shape == 1 || (shape == 0 && a.R <= STRIP_SMALL_ROWS)) && !a.bits1 && !a.bits2;   // (mask bits: the backward kernel's shape)
+  const bool wide = a.Dp > SXK;                                                                         // (the instantiation by input width)
+  const dim3 grid(small ? (a.R + StripSmall::ROWS - 1) / StripSmall::ROWS : (a.R + StripBig::ROWS - 1) / StripBig::ROWS), block(small ? StripSmall::THR : StripBig::THR);
+  if (small && !wide) hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripSmall, SXK>), grid, block, 0, s, a);
+  else if (small) hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripSmall, SXW>), grid, block, 0, s, a);
+  else if (!wide) hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripBig, SXK>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((mlp_fwd_strip_kernel<StripBig, SXW>), grid, block, 0, s, a);
 }
 
 void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s) {
@@ -606,13 +661,36 @@ void mlp_strip_backward(const MlpStripBwd& a, hipStream_t s) {
 bool mlp_train_strip_supported(int H, int Dp, int O, int Op, int critic) {
   return mlp_strip_supported(H, Dp, O, Op) && Op <= SXK && (!critic || (O == 1 && Op == 4));
 }
+bool mlp_train_strip_wide_supported(int H, int Dp, int O, int Op, int critic) {
+  return mlp_strip_wide_supported(H, Dp, O, Op) && Op <= SXK && (!critic || (O == 1 && Op == 4));
+}
 
 void mlp_train_strip(const MlpStripTrain& t, hipStream_t s) {
   if (t.f.R <= 0) return;
   const int nrow = t.twin0 > 0 ? 32 : StripBig::ROWS;
   const dim3 grid((t.f.R + nrow - 1) / nrow), block(StripBig::THR);
-  if (t.critic) hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 1>), grid, block, 0, s, t);
-  else hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 0>), grid, block, 0, s, t);
+  const bool wide = t.f.Dp > SXK;
+  if (t.critic && !wide) hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 1, SXK>), grid, block, 0, s, t);
+  else if (t.critic) hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 1, SXW>), grid, block, 0, s, t);
+  else if (!wide) hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 0, SXK>), grid, block, 0, s, t);
+  else hipLaunchKernelGGL((mlp_train_strip_kernel<StripBig, 0, SXW>), grid, block, 0, s, t);
+}
+
+// C [M][ldc] = epilogue(A [M][lda] B): a thread per output, ONE fmaf chain over ascending k from +0 -- what gemm_f32_kernel's MFMA loop computes --
+// then its epilogue: + bias[n], ReLU, zero where mask[m][n] <= 0.  B[k][n] = Bm[k * sk + n * sn].  The per-layer GEMM path in independent code
+// (this file is built without lhw_gemm.hip on the SIMT emulator): the reference of the wide train strip (lhw_debug_mlp_train_strip, fused = 0).
+__global__ void __launch_bounds__(256) mlp_ref_layer_kernel(int M, int N, int K, const float* __restrict__ A, int lda, const float* __restrict__ Bm, int sk, int sn,
+                                                            float* __restrict__ C, int ldc, const float* __restrict__ bias, int relu,
+                                                            const float* __restrict__ mask, int ldmask) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)M * N) return;
+  const int m = (int)(i / N), n = (int)(i - (size_t)m * N);
+  float v = 0.f;
+  for (int k = 0; k < K; k++) v = fmaf(A[(size_t)m * lda + k], Bm[(size_t)k * sk + (size_t)n * sn], v);
+  if (bias) v += bias[n];
+  if (relu) v = fmaxf(v, 0.f);
+  if (mask && !(mask[(size_t)m * ldmask + n] > 0.f)) v = 0.f;
+  C[(size_t)m * ldc + n] = v;
 }
 
 // One network's forward + head + backward over a minibatch, outside an LhwPpo (tests, SIMT emulator).  fused = 1: mlp_train_strip_kernel.
@@ -622,8 +700,9 @@ extern "C" int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* q, int32_t fus
   if (!q || !q->w1 || !q->b1 || !q->w2 || !q->b2 || !q->w3 || !q->b3 || !q->x || !q->h1 || !q->h2 || !q->y || !q->dy || !q->dh2 || !q->dh1 ||
       !q->stat_rows || !q->wt_scratch || (q->critic ? !q->ret : (!q->act || !q->old_logp || !q->adv || !q->stdv)))
     return lhw_fail(LHW_ERR_ARG, "null argument");
-  if (!mlp_train_strip_supported(q->H, q->Dp, q->O, q->Op, q->critic) || q->ldx < q->Dp || (q->ldx & 3))
-    return lhw_fail(LHW_ERR_UNSUPPORTED, "train strip kernel: hidden width 256, padded input width <= 64, outputs <= 32 in rows of <= 64, critic 1 in 4");
+  const bool wide = mlp_train_strip_wide_supported(q->H, q->Dp, q->O, q->Op, q->critic);
+  if ((!wide && !mlp_train_strip_supported(q->H, q->Dp, q->O, q->Op, q->critic)) || q->ldx < q->Dp || (q->ldx & 3))
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "train strip kernel: hidden width 256, padded input width <= %d (a multiple of 4), outputs <= 32 in rows of <= 64, critic 1 in 4", SXW);
   const int mir = !q->critic && q->twin0 > 0;
   if (q->B <= 0 || q->stat_ld < q->B || (mir && (q->twin0 < q->B || !q->act_src || !q->act_sign))) return lhw_fail(LHW_ERR_ARG, "bad row counts / mirror tables");
   hipStream_t s = (hipStream_t)stream;
@@ -636,6 +715,24 @@ extern "C" int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* q, int32_t fus
     MlpStripTrain t{MlpStripFwd{w1t, q->b1, w2t, q->b2, w3t, q->b3, q->x, q->ldx, Dp, O, Op, B, q->h1, q->h2, q->y}, q->w2, q->w3, q->dy, q->dh2, q->dh1,
                     mir ? q->twin0 : 0, q->critic, h, q->stat_rows, q->stat_ld};
     mlp_train_strip(t, s);
+  } else if (wide) {
+    // the path the wide train strip takes over: one GEMM per layer (mlp_forward / mlp_backward of lhw_ppo.hip without strips), here as plain chains
+    auto layer = [&](int M, int N, int K, const float* A, int lda, const float* Bm, int sk, int sn, float* C, int ldc, const float* bias, int relu, const float* mask) {
+      hipLaunchKernelGGL(mlp_ref_layer_kernel, dim3((unsigned)(((size_t)M * N + 255) / 256)), dim3(256), 0, s, M, N, K, A, lda, Bm, sk, sn, C, ldc, bias, relu, mask, SH);
+    };
+    for (int pass = 0; pass <= mir; pass++) {
+      const size_t r0 = pass ? (size_t)q->twin0 : 0;
+      layer(B, SH, Dp, q->x + r0 * q->ldx, q->ldx, q->w1, 1, Dp, q->h1 + r0 * SH, SH, q->b1, 1, nullptr);   // (weights in torch layout: B[k][n] = W[n][k])
+      layer(B, SH, SH, q->h1 + r0 * SH, SH, q->w2, 1, SH, q->h2 + r0 * SH, SH, q->b2, 1, nullptr);
+      layer(B, O, SH, q->h2 + r0 * SH, SH, q->w3, 1, SH, q->y + r0 * Op, Op, q->b3, 0, nullptr);
+    }
+    if (q->critic) hipLaunchKernelGGL(ppo_head_rows_kernel<1>, dim3((B + 255) / 256), dim3(256), 0, s, h, q->y, Op, 0, q->dy, q->stat_rows, q->stat_ld);
+    else hipLaunchKernelGGL(ppo_head_rows_kernel<0>, dim3((B + 255) / 256), dim3(256), 0, s, h, q->y, Op, q->twin0, q->dy, q->stat_rows, q->stat_ld);
+    for (int pass = 0; pass <= mir; pass++) {
+      const size_t r0 = pass ? (size_t)q->twin0 : 0;
+      layer(B, SH, O, q->dy + r0 * Op, Op, q->w3, SH, 1, q->dh2 + r0 * SH, SH, nullptr, 0, q->h2 + r0 * SH);   // dh2 = (dy W3) * (h2 > 0): B[k = o][n] = W3[o][n]
+      layer(B, SH, SH, q->dh2 + r0 * SH, SH, q->w2, SH, 1, q->dh1 + r0 * SH, SH, nullptr, 0, q->h1 + r0 * SH);  // dh1 = (dh2 W2) * (h1 > 0)
+    }
   } else {
     for (int pass = 0; pass <= mir; pass++) {
       const size_t r0 = pass ? (size_t)q->twin0 : 0;
@@ -657,7 +754,8 @@ extern "C" int lhw_debug_mlp_strip_forward_bits(int32_t H, int32_t Dp, int32_t O
                                                 const float* b2, const float* w3, const float* b3, const float* x, int32_t ldx, int32_t R,
                                                 float* h1, float* h2, float* y, float* wt_scratch, uint32_t* bits1, uint32_t* bits2, void* stream) {
   if (!wt_scratch || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !x || !h1 || !h2 || !y) return lhw_fail(LHW_ERR_ARG, "null argument");
-  if (!mlp_strip_supported(H, Dp, O, Op) || ldx < Dp) return lhw_fail(LHW_ERR_UNSUPPORTED, "strip kernels: hidden width 256, padded input width <= 64, outputs <= 32");
+  if ((!mlp_strip_supported(H, Dp, O, Op) && !mlp_strip_wide_supported(H, Dp, O, Op)) || ldx < Dp)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "strip kernels: hidden width 256, padded input width <= %d (a multiple of 4), outputs <= 32", SXW);
   mlp_strip_prepare(w1, w2, w3, Dp, O, Op, wt_scratch, (hipStream_t)stream);
   MlpStripFwd a{wt_scratch, b1, wt_scratch + (size_t)Dp * SH, b2, wt_scratch + (size_t)Dp * SH + (size_t)SH * SH, b3, x, ldx, Dp, O, Op, R, h1, h2, y};
   a.bits1 = bits1; a.bits2 = bits2;

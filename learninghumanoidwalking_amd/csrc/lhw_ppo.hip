@@ -43,7 +43,7 @@ struct MlpNet {
   const float* x = nullptr; int ldx = 0;                  // gathered minibatch inputs [rows][ldx]: one buffer for both networks
   float *h1 = nullptr, *h2 = nullptr, *y = nullptr;       // activations [rows][H] x 2, read-out [rows][Op]
   float *dy = nullptr, *dh2 = nullptr, *dh1 = nullptr;    // d loss / d them
-  float* wt = nullptr;                                    // [in][out] weight copies for the strip kernels (hidden width 256 only)
+  float* wt = nullptr;                                    // [in][out] weight copies for the strip kernels (shapes they take, narrow or wide)
   unsigned *bits1 = nullptr, *bits2 = nullptr;            // ReLU masks of h1 / h2 as bits, forward strip -> backward strip: a launch whose first row is
                                                           // r uses the words from mlp_strip_bits_words(r) on; NULL: max_rows % 64 != 0
   const _Float16* x_h = nullptr; int ldxh = 0;            // fp16 storage: inputs [rows][ldxh], ldxh = Dp rounded up to 8 (16-byte rows), pad columns zero
@@ -58,6 +58,7 @@ struct MlpMode {
   bool wt_ready;   // forward strip: the weight copies are already made
   bool infer;      // forward: h1 / h2 are not kept (in the strip kernel they never leave LDS) and no mask bits are written
   bool have_dh;    // backward: dh2 / dh1 are already there (train strip launch): the weight gradients only
+  bool wide;       // the strip kernels may run for rows wider than 64 columns too (LhwPpo::strip_wide)
 };
 
 struct LhwPpo : LearnerCore {
@@ -92,6 +93,9 @@ struct LhwPpo : LearnerCore {
   int strip_fused = 1;
   float* stat_rows = nullptr;   // [NSTAT][max_rows]: the rows' loss terms the train strip launches leave for ppo_stats_rows_kernel
   int last_grad_fused = 0;      // which path the last lhw_ppo_grad took (lhw_ppo_debug_last_grad_fused)
+  // rows wider than 64 columns (an observation history) through the wide strip instantiations instead of one GEMM per layer, wherever the
+  // handle chooses between the two (lhw_ppo_debug_set_strip_wide; the Python layer sets it from LHW_STRIP_WIDE)
+  int strip_wide = 0;
   // lhw_ppo_step: one optimiser step (lhw_ppo_grad + lhw_ppo_apply) captured once per (buffers, minibatch size, grad_scale) as a hipGraph
   // and replayed; the two things that change from step to step -- the minibatch's index pointer (gather_kernel) and Adam's bias
   // corrections (adam2_kernel) -- are patched into the executable graph's kernel nodes before each launch.  grad_scale is part of the key
@@ -100,7 +104,7 @@ struct LhwPpo : LearnerCore {
   hipGraphExec_t step_exec = nullptr;
   hipGraphNode_t node_gather = nullptr, node_adam = nullptr;
   const void* step_key[12] = {nullptr};
-  int step_key_b = 0, step_key_half = 0, step_key_fused = 0;
+  int step_key_b = 0, step_key_half = 0, step_key_fused = 0, step_key_wide = 0;
   uint32_t step_key_gs = 0;
   ~LhwPpo() {
     (void)hipSetDevice(device);
@@ -121,11 +125,18 @@ static int strip_mode() {
   static const int m = getenv("LHW_MLP_STRIP") ? atoi(getenv("LHW_MLP_STRIP")) : 2;
   return m;
 }
-// An actor whose padded observation row is wider than the strip kernels' slab (an observation history) but within the in-wave policy step of
-// lhw_env_rollout_history: its forward runs the per-layer GEMMs below; only the resident rollout reads [in][out] weight copies (LhwPpo::wt_roll)
+// An actor whose padded observation row is wider than the narrow strips' 64 columns (an observation history) but within the in-wave policy step
+// of lhw_env_rollout_history, which reads [in][out] weight copies (LhwPpo::wt_roll) whatever path the handle's own launches take.  Stated from
+// the shape alone; the same shapes as the wide strip instantiations (LHW_MLP_STRIP_MAX_IN_PAD == LHW_ROLLOUT_HISTORY_MAX_OBS_PAD)
 static bool rollout_wide_supported(const MlpLayout& L) {
-  return L.H == 256 && !mlp_strip_supported(L.H, L.Dp, L.O, L.Op) && L.Dp > 0 && L.Dp <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD && (L.Dp & 3) == 0 && L.O > 0 && L.O <= 32 &&
-         L.Op >= L.O;
+  return L.H == 256 && L.Dp > 64 && L.Dp <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD && (L.Dp & 3) == 0 && L.O > 0 && L.O <= 32 && L.Op >= L.O;
+}
+// the strip kernels take this network: a narrow shape, or a wide one with the switch on
+static bool strip_shape(const MlpLayout& L, bool wide_on) {
+  return mlp_strip_supported(L.H, L.Dp, L.O, L.Op) || (wide_on && mlp_strip_wide_supported(L.H, L.Dp, L.O, L.Op));
+}
+static bool train_strip_shape(const MlpLayout& L, int critic, bool wide_on) {
+  return mlp_train_strip_supported(L.H, L.Dp, L.O, L.Op, critic) || (wide_on && mlp_train_strip_wide_supported(L.H, L.Dp, L.O, L.Op, critic));
 }
 static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStream_t s, const MlpMode& m) {
   const MlpLayout& L = n.L;
@@ -133,7 +144,7 @@ static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStrea
   const size_t H = L.H, r0 = r.first;
   const float* x = n.x + r0 * ldx;
   float *h1 = n.h1 + r0 * H, *h2 = n.h2 + r0 * H, *y = n.y + r0 * L.Op;
-  if (m.strip && n.wt && !half && mlp_strip_supported(L.H, L.Dp, L.O, L.Op)) {   // one launch, h1 / h2 stay in LDS between the layers
+  if (m.strip && n.wt && !half && strip_shape(L, m.wide)) {   // one launch, h1 / h2 stay in LDS between the layers
     if (!m.wt_ready) mlp_strip_prepare(theta + L.w1, theta + L.w2, theta + L.w3, L.Dp, L.O, L.Op, n.wt, s);   // [in][out] copies of the weights
     MlpStripFwd a{n.wt, theta + L.b1, n.wt + (size_t)L.Dp * L.H, theta + L.b2, n.wt + (size_t)L.Dp * L.H + (size_t)L.H * L.H,
                   theta + L.b3, x, ldx, L.Dp, L.O, L.Op, R, m.infer ? nullptr : h1, m.infer ? nullptr : h2, y};
@@ -197,7 +208,7 @@ static void mlp_backward(const MlpNet& n, const float* theta, RowSpan r, const B
   GemmArgs g{};
   // (have_dh: a train strip launch has taken the strip launch's place, so neither it nor the GEMMs below compute dh2 / dh1 again.  Only where
   // the strip path would have made them: float32, a shape the strips take)
-  const bool strip = m.have_dh || (m.strip && !half && mlp_strip_supported(L.H, L.Dp, L.O, L.Op));
+  const bool strip = m.have_dh || (m.strip && !half && strip_shape(L, m.wide));
   if (strip && !m.have_dh) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
     MlpStripBwd a{theta + L.w2, theta + L.w3, dy, h1, h2, L.O, L.Op, R, dh2, dh1};
     if (n.bits1) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
@@ -303,8 +314,9 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
   mem.get(&p->part, std::max<size_t>((size_t)p->max_slices * H * std::max<size_t>(H, Dp), (size_t)COLSUM_CHUNKS * H));
   mem.get(&p->bwd_part, bwd_parts_floats(p->a.L, R, 2) + bwd_parts_floats(p->c.L, R, 1));
   a.x = cr.x = p->xb; a.ldx = cr.ldx = (int)Dp;
-  if (mlp_strip_supported(a.L.H, a.L.Dp, a.L.O, a.L.Op)) mem.get(&a.wt, mlp_strip_wt_floats(a.L.Dp, a.L.Op));
-  if (mlp_strip_supported(cr.L.H, cr.L.Dp, cr.L.O, cr.L.Op)) mem.get(&cr.wt, mlp_strip_wt_floats(cr.L.Dp, cr.L.Op));
+  // (the strip kernels' scratch for every shape they take, narrow or wide: whether a wide shape USES it is the switch's business, strip_wide)
+  if (strip_shape(a.L, true)) mem.get(&a.wt, mlp_strip_wt_floats(a.L.Dp, a.L.Op));
+  if (strip_shape(cr.L, true)) mem.get(&cr.wt, mlp_strip_wt_floats(cr.L.Dp, cr.L.Op));
   if (a.wt && cr.wt && R % 64 == 0 && !(getenv("LHW_STRIP_BITS") && atoi(getenv("LHW_STRIP_BITS")) == 0)) {
     const size_t bw = mlp_strip_bits_words(R);   // per layer: 2 bw words for the actor's 2R rows, bw for the critic's
     mem.get(&a.bits1, 4 * bw); mem.get(&cr.bits1, 2 * bw);
@@ -315,8 +327,6 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
     mem.get(&p->stat_rows, NSTAT * R);
     mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op)));
     mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op));
-  } else if (rollout_wide_supported(p->a.L)) {
-    mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op));   // the actor's copies alone (wt_inf stays NULL: no strip launch reads them)
   }
   bool ok = !mem.failed() && learner_mirror(*p, c);
   p->two_streams = !(getenv("LHW_PPO_TWO_STREAMS") && atoi(getenv("LHW_PPO_TWO_STREAMS")) == 0);
@@ -370,6 +380,13 @@ extern "C" int lhw_ppo_debug_set_strip_fused(LhwPpo* p, int32_t on) {
   return LHW_OK;
 }
 
+extern "C" int lhw_ppo_debug_set_strip_wide(LhwPpo* p, int32_t on) {
+  if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
+  p->strip_wide = on ? 1 : 0;
+  p->roll_theta = nullptr;   // (an open bracket has the critic's weight copies of the other choice)
+  return LHW_OK;
+}
+
 extern "C" int lhw_ppo_debug_last_grad_fused(const LhwPpo* p) { return p ? p->last_grad_fused : LHW_ERR_ARG; }
 
 extern "C" int64_t lhw_ppo_param_count(const LhwPpo* p) { return p ? (int64_t)p->n_params : LHW_ERR_ARG; }
@@ -407,7 +424,7 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
   size_t n = (size_t)N * Dp;
   float *wta = nullptr, *wtc = nullptr;   // this call's weight copies for the strip kernel
   const bool wt_ready = p->roll_theta != nullptr && p->roll_theta == theta;   // inside a rollout bracket: made once by lhw_ppo_begin_rollout
-  if (strip_mode() >= 2 && p->wt_inf) {
+  if (strip_mode() >= 2 && p->wt_inf && strip_shape(p->a.L, p->strip_wide) && strip_shape(p->c.L, p->strip_wide)) {
     const size_t fa = mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op), fc = mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op);
     wta = wt_ready ? p->wt_roll : p->wt_inf + (size_t)(ws_row * WT_SLOTS / p->max_rows) * (fa + fc);
     wtc = wta + fa;
@@ -416,7 +433,7 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
   // slab, the three layers, the Gaussian head on the read-out -- instead of normalise / forward / sample launches
   // (the fused staging reads RAW observation rows of width obs_dim: without the normalisation vectors it would have to copy rows
   // of width Dp, which the caller's buffer does not have -- those calls take the three-launch path)
-  const bool fused = act && logp && !mu && !value && wta && obs_mean && obs_std && !p->infer_half && mlp_strip_supported(p->a.L.H, p->a.L.Dp, p->a.L.O, p->a.L.Op);
+  const bool fused = act && logp && !mu && !value && wta && obs_mean && obs_std && !p->infer_half;   // (wta: a shape the strips take, see above)
   if (fused) {
     const MlpLayout& La = p->a.L;
     const float* th = theta + p->off_actor;
@@ -432,7 +449,7 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
   }
   hipLaunchKernelGGL(normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, s, obs, p->D, p->a.L.Dp, (size_t)N, obs_mean, obs_std,
                      xb, (float*)nullptr, (const int*)nullptr, (const float*)nullptr);
-  const MlpMode infer{p->infer_half, false, true, wt_ready, true, false};
+  const MlpMode infer{p->infer_half, false, true, wt_ready, true, false, p->strip_wide != 0};
   MlpNet na = p->a, nc = p->c;   // with this call's weight copies
   na.wt = wta; nc.wt = wtc;
   if (act || mu) {
@@ -455,14 +472,17 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
 extern "C" int lhw_ppo_begin_rollout(LhwPpo* p, const float* theta, void* stream) {
   if (!p || !theta) return lhw_fail(LHW_ERR_ARG, "null argument");
   p->roll_theta = nullptr;
-  const bool wide = p->wt_roll && !p->wt_inf;   // a wide-row actor: its copies serve lhw_env_rollout_history's in-wave step only
-  if (!p->wt_roll || (!wide && strip_mode() < 2)) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
+  // a wide-row actor: its copies serve lhw_env_rollout_history's in-wave step, whatever the handle's own launches run; the critic's are made
+  // only where strip launches will read them (the switch on)
+  const bool wide = rollout_wide_supported(p->a.L);
+  const bool strips = strip_mode() >= 2 && (!wide || p->strip_wide);
+  if (!p->wt_roll || (!wide && !strips)) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
   const MlpLayout &La = p->a.L, &Lc = p->c.L;
   const float *tha = theta + p->off_actor, *thc = theta + p->off_critic;
   mlp_strip_prepare(tha + La.w1, tha + La.w2, tha + La.w3, La.Dp, La.O, La.Op, p->wt_roll, s);
-  if (!wide) mlp_strip_prepare(thc + Lc.w1, thc + Lc.w2, thc + Lc.w3, Lc.Dp, Lc.O, Lc.Op, p->wt_roll + mlp_strip_wt_floats(La.Dp, La.Op), s);
+  if (strips) mlp_strip_prepare(thc + Lc.w1, thc + Lc.w2, thc + Lc.w3, Lc.Dp, Lc.O, Lc.Op, p->wt_roll + mlp_strip_wt_floats(La.Dp, La.Op), s);
   HIPCHK(hipGetLastError());
   p->roll_theta = theta;
   return LHW_OK;
@@ -550,8 +570,8 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   // ---- prologue
   // the [in][out] weight copies of the forward strips are made on the side stream while the minibatch is gathered (round 6: the two
   // 9 us transposes were the first links of the step's chain)
-  const bool strips = strip_mode() >= 1 && !p->update_half && na.wt && nc.wt && mlp_strip_supported(La.H, La.Dp, La.O, La.Op) &&
-                      mlp_strip_supported(Lc.H, Lc.Dp, Lc.O, Lc.Op);
+  const bool wide_on = p->strip_wide != 0;
+  const bool strips = strip_mode() >= 1 && !p->update_half && na.wt && nc.wt && strip_shape(La, wide_on) && strip_shape(Lc, wide_on);
   if (strips) {
     sp.fork();
     mlp_strip_prepare(th_a + La.w1, th_a + La.w2, th_a + La.w3, La.Dp, La.O, La.Op, na.wt, sc);
@@ -573,10 +593,9 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   // between the passes, no loss launch, no mask bits; the weight-gradient kernels follow as on the other path.  With mirroring a slab pairs
   // 32 rows with their twins, whatever B (a ragged last slab has dead rows in both tiles).  Not for an armed imitation term, --fp16, or
   // shapes the strips reject: those run forward strip (or GEMMs), ppo_loss_kernel, backward.
-  const bool fused = strips && p->strip_fused && !p->imit_target && p->stat_rows && mlp_train_strip_supported(La.H, La.Dp, La.O, La.Op, 0) &&
-                     mlp_train_strip_supported(Lc.H, Lc.Dp, Lc.O, Lc.Op, 1);
+  const bool fused = strips && p->strip_fused && !p->imit_target && p->stat_rows && train_strip_shape(La, 0, wide_on) && train_strip_shape(Lc, 1, wide_on);
   p->last_grad_fused = fused ? 1 : 0;
-  const MlpMode mode{p->update_half, hstore, strip_mode() >= 1, strips, false, fused};
+  const MlpMode mode{p->update_half, hstore, strip_mode() >= 1, strips, false, fused, wide_on};
   const int nblk = (B + 255) / 256;
   // fp16 update: the back-propagated gradients are rounded to fp16 per GEMM, and d loss / d output carries 1 / B -- at B = 32768
   // most of it would fall into the fp16 subnormal range.  Loss scaling by a power of two (exact in float32): the read-out
@@ -675,7 +694,8 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
   HIPCHK(hipSetDevice(p->device));
   const void* key[12] = {theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream};
   uint32_t gs_key; memcpy(&gs_key, &grad_scale, sizeof gs_key);
-  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_fused == p->strip_fused && p->step_key_gs == gs_key;
+  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_fused == p->strip_fused && p->step_key_wide == p->strip_wide &&
+              p->step_key_gs == gs_key;
   for (int i = 0; same && i < 12; i++) same = p->step_key[i] == key[i];
   if (!same) {
     if (p->step_exec) { (void)hipGraphExecDestroy(p->step_exec); p->step_exec = nullptr; }
@@ -704,7 +724,7 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
     if (!p->node_gather || !p->node_adam) return lhw_fail(LHW_ERR_HIP, "lhw_ppo_step: gather / Adam nodes not found in the captured graph (%zu nodes)", nn);
     HIPCHK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
     for (int i = 0; i < 12; i++) p->step_key[i] = key[i];
-    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_fused = p->strip_fused; p->step_key_gs = gs_key;
+    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_fused = p->strip_fused; p->step_key_wide = p->strip_wide; p->step_key_gs = gs_key;
   }
   // patch the two nodes: each kernel's one argument, built by the function that builds it for the launch
   GatherArgs ga = gather_args(p, xn, xm, act, old_logp, adv, ret, idx, B);

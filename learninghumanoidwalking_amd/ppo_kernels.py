@@ -6,6 +6,7 @@ storage"); every arithmetic step of the learner runs in liblhw.so.
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -147,6 +148,13 @@ class _Kernels:
         return float(out[0]), float(out[1])
 
 
+# Observation rows wider than 64 padded columns (obs_history_len > 1) through the wide instantiations of the LDS-resident strip kernels --
+# inference, the critic's values behind the resident rollout and the update's forward / loss / backward launches -- instead of one GEMM per
+# layer (lhw_ppo_debug_set_strip_wide).  LHW_STRIP_WIDE = 0 | 1 overrides; read once per handle.  Same bits either way; the default follows
+# the project's A/B rule: True only once every run with the strips lies below every run without them.
+STRIP_WIDE_DEFAULT = False
+
+
 class PpoKernels(_Kernels):
     """Flat-parameter actor/critic (D -> H -> H -> A | 1, ReLU) living on one GPU."""
 
@@ -164,6 +172,13 @@ class PpoKernels(_Kernels):
             return {f"{p}_w1": (o[f"{p}_w1"], H, Dp, 0, D), f"{p}_b1": (o[f"{p}_b1"], H), f"{p}_w2": (o[f"{p}_w2"], H, H, 0, H),
                     f"{p}_b2": (o[f"{p}_b2"], H), f"{p}_w3": (o[f"{p}_w3"], rows, H, 0, H), f"{p}_b3": (o[f"{p}_b3"], rows)}
         self._specs = {**net("a", A), "stds": (o["stds"], A), **net("c", 1)}
+        self.strip_wide = os.environ.get("LHW_STRIP_WIDE", "1" if STRIP_WIDE_DEFAULT else "0") != "0"
+        _lib.check(self._L.lhw_ppo_debug_set_strip_wide(self._h, int(self.strip_wide)))
+
+    @property
+    def last_grad_fused(self):
+        """1 if the last grad_minibatch / step_minibatch ran the train strip launches, 0 if forward, loss kernel and backward."""
+        return int(self._L.lhw_ppo_debug_last_grad_fused(self._h))
 
     def set_tensors(self, tensors: dict):
         # theta changes: a rollout bracket opened on the old weights (its [in][out] copies, the resident rollout's actor view) is void
