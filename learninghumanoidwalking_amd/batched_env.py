@@ -179,35 +179,46 @@ class BatchedEnv:
         lhw_env_rollout_history: the wavefronts shift the history rows themselves, obs[0] is the state they start from, and the env's
         own copy of the current full observation is set to obs[T] afterwards, so launch-per-step calls may follow.  Returns False
         (nothing launched) where the library has no resident kernel for this env / policy; a HIP failure raises."""
-        N = self.n_envs
         if policy is None:
             return False
+        L, bufs, head = self._L, (obs, act, logp, term_obs, rew, done), ()
+        if self.history_len > 1:
+            fn, records, head = L.lhw_env_rollout_history, 2, (self.history_len,)
+        elif step_task_inputs is not None:
+            fn, records = L.lhw_env_rollout_step_task_inputs, 2
+        elif task_inputs is not None:
+            fn, records = L.lhw_env_rollout_task_inputs, 1
+        else:
+            fn, records = L.lhw_env_rollout, 0
+        ok = self._resident(fn, policy, T, bufs, first, count, task_inputs, step_task_inputs, records, head=head)
+        if ok and self.history_len > 1:      # the launch-per-step calls continue from the rollout's last observation (a device copy behind the launch)
+            a, b = int(first), int(first) + (int(self.n_envs - first) if count is None else int(count))
+            self._full[a:b].copy_(obs[T, a:b])
+        return ok
+
+    def _resident(self, fn, policy, T, bufs, first, count, task_inputs, step_task_inputs, records, head=(), flags=()) -> bool:
+        """What the resident-rollout entry points share: the checks of the buffers (obs, act, logp, term_obs, rew, done), of `flags` ([N] uint8
+        each) and of the task-input records, the call, and its result: False where the library declines (LHW_ERR_UNSUPPORTED: the caller keeps
+        the launch-per-step pipeline), anything else -- LHW_ERR_HIP ... -- raises.  What `fn` takes besides the common arguments: `head`
+        (integers) behind T, the flags behind rew_terms, then the first `records` of (task_inputs, step_task_inputs)."""
+        N = self.n_envs
+        obs, act, logp, term_obs, rew, done = bufs
         assert obs.shape == (T + 1, N, self.obs_dim) and act.shape == (T, N, self.act_dim) and term_obs.shape == (T, N, self.obs_dim)
         assert logp.shape == (T, N) and rew.shape == (T, N) and done.shape == (T, N) and done.dtype == torch.uint8
-        for x in (obs, act, logp, term_obs, rew, done):
+        for x in flags:
+            assert x.shape == (N,) and x.dtype == torch.uint8
+        for x in bufs + tuple(flags):
             assert x.is_cuda and x.is_contiguous()
-        args = (self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), _ptr(obs),
-                _ptr(act), _ptr(logp), _ptr(term_obs), _ptr(rew), _ptr(done), _ptr(self.rew_terms))
         if step_task_inputs is not None:
             assert task_inputs is not None, "the stepping record is exported together with the LhwTaskInput one"
             assert step_task_inputs.shape == (T, N, _lib.STEP_TASK_INPUT_DIM) and step_task_inputs.dtype == torch.float64
             assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
         if task_inputs is not None:
             assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
-        if self.history_len > 1:
-            rc = self._L.lhw_env_rollout_history(*args[:5], self.history_len, *args[5:], _ptr(task_inputs), _ptr(step_task_inputs),
-                                                 _stream_ptr(self.device))
-            if rc == 0:      # the launch-per-step calls continue from the rollout's last observation (a device copy behind the launch)
-                a, b = int(first), int(first) + (int(N - first) if count is None else int(count))
-                self._full[a:b].copy_(obs[T, a:b])
-        elif task_inputs is not None:
-            if step_task_inputs is not None:
-                rc = self._L.lhw_env_rollout_step_task_inputs(*args, _ptr(task_inputs), _ptr(step_task_inputs), _stream_ptr(self.device))
-            else:
-                rc = self._L.lhw_env_rollout_task_inputs(*args, _ptr(task_inputs), _stream_ptr(self.device))
-        else:
-            rc = self._L.lhw_env_rollout(*args, _stream_ptr(self.device))
-        if rc == -4:      # LHW_ERR_UNSUPPORTED: the caller keeps the launch-per-step pipeline (anything else -- LHW_ERR_HIP ... -- raises)
+        tail = tuple(flags) + (task_inputs, step_task_inputs)[:records]
+        rc = fn(self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), *head, *(_ptr(x) for x in bufs),
+                _ptr(self.rew_terms), *(_ptr(x) for x in tail), _stream_ptr(self.device))
+        if rc == -4:
             return False
         _lib.check(rc)
         return True
@@ -219,27 +230,10 @@ class BatchedEnv:
         whose state buffers the launch reads and writes -- and `reset0` [N] uint8: the envs whose episode starts with obs[0] (their state
         counts as zero; afterwards the state is zeroed wherever the previous step's done flag is set: reference
         rl/workers/rollout_worker.py:130-190).  Returns False (nothing launched) where the library has no such kernel for this env / policy."""
-        N = self.n_envs
         if self.history_len > 1 or policy is None:
             return False
-        assert obs.shape == (T + 1, N, self.obs_dim) and act.shape == (T, N, self.act_dim) and term_obs.shape == (T, N, self.obs_dim)
-        assert logp.shape == (T, N) and rew.shape == (T, N) and done.shape == (T, N) and done.dtype == torch.uint8
-        assert reset0.shape == (N,) and reset0.dtype == torch.uint8
-        for x in (obs, act, logp, term_obs, rew, done, reset0):
-            assert x.is_cuda and x.is_contiguous()
-        if step_task_inputs is not None:
-            assert task_inputs is not None, "the stepping record is exported together with the LhwTaskInput one"
-            assert step_task_inputs.shape == (T, N, _lib.STEP_TASK_INPUT_DIM) and step_task_inputs.dtype == torch.float64
-            assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
-        if task_inputs is not None:
-            assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
-        rc = self._L.lhw_env_rollout_lstm(self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), _ptr(obs),
-                                          _ptr(act), _ptr(logp), _ptr(term_obs), _ptr(rew), _ptr(done), _ptr(self.rew_terms), _ptr(reset0),
-                                          _ptr(task_inputs), _ptr(step_task_inputs), _stream_ptr(self.device))
-        if rc == -4:      # LHW_ERR_UNSUPPORTED
-            return False
-        _lib.check(rc)
-        return True
+        return self._resident(self._L.lhw_env_rollout_lstm, policy, T, (obs, act, logp, term_obs, rew, done), first, count, task_inputs, step_task_inputs, 2,
+                              flags=(reset0,))
 
     def last_rollout_queued(self) -> bool:
         """the most recent resident rollout drained the job queue (stepping task with more envs than wave slots)"""

@@ -216,75 +216,81 @@ extern "C" int lhw_env_step_range(LhwEnv* e, int32_t first, int32_t count, const
   return LHW_OK;
 }
 
-static int env_rollout_impl(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
-                            float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, double* tin_dev, double* stin_dev,
-                            void* stream) {
-  if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
-  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout: wave-per-env (humanoid) steppers only");
+// What the five resident-rollout entry points share, once: the argument checks, the launch (humanoid_rollout) and its codes.  `name`: the entry
+// point that was called.
+static int env_rollout(const char* name, LhwEnv* e, const HumanoidRollout& rq, void* stream) {
+  if (!e || (!rq.mlp && !rq.lstm) || !rq.obs || !rq.act || !rq.logp || !rq.term_obs || !rq.rew || !rq.done ||
+      (rq.kind == POLICY_LSTM && !rq.reset0))
+    return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: wave-per-env (humanoid) steppers only", name);
+  if (rq.stin_all && e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: the stepping record needs a stepping-task env", name);
+  if (rq.stin_all && !rq.tin_all) return lhw_fail(LHW_ERR_ARG, "%s: the stepping record is exported together with the task-input record", name);
   HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_rollout(e->hum, first, count, T, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, (hipStream_t)stream);
-  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
-  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
-  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout: needs a float32 actor obs %d -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's resident kernel",
-                          e->obs_dim, e->act_dim);
+  const int rc = humanoid_rollout(e->hum, rq, (hipStream_t)stream);
+  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", rq.first, rq.first + rq.count, rq.T);
+  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "%s: a HIP call failed while preparing the launch (%s)", name, hipGetErrorString(hipGetLastError()));
+  if (rc && rq.kind == POLICY_MLP)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: needs a float32 actor obs %d -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's resident kernel", name,
+                    e->obs_dim, e->act_dim);
+  if (rc && rq.kind == POLICY_HIST)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: needs a float32 actor obs %d x %d (padded <= %d) -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's "
+                    "resident kernel", name, rq.history_len, e->obs_dim, LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, e->act_dim);
+  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: needs a float32 LSTM actor obs %d -> 256 -> 256 -> act %d (<= 12) with a state row per env and a model that fits "
+                          "the task's resident kernel", name, e->obs_dim, e->act_dim);
   HIPCHK(hipGetLastError());
   return LHW_OK;
 }
+// the arguments the five entry points share, in the ABI's order, as a request of a feed-forward policy without a history; the entry point names the rest
+static HumanoidRollout rollout_request(int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev,
+                                       uint8_t* done_dev, float* rew_terms_dev, double* tin_dev, double* stin_dev) {
+  HumanoidRollout rq;
+  rq.first = first; rq.count = count; rq.T = T;
+  rq.obs = obs_dev; rq.act = act_dev; rq.logp = logp_dev; rq.term_obs = term_obs_dev; rq.rew = rew_dev; rq.done = done_dev; rq.rew_terms = rew_terms_dev;
+  rq.tin_all = tin_dev; rq.stin_all = stin_dev;
+  return rq;
+}
 extern "C" int lhw_env_rollout(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, void* stream) {
-  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, nullptr, nullptr, stream);
+  HumanoidRollout rq = rollout_request(first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, nullptr, nullptr);
+  rq.mlp = policy;
+  return env_rollout("lhw_env_rollout", e, rq, stream);
 }
 extern "C" int lhw_env_rollout_task_inputs(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                            float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, double* tin_dev,
                                            void* stream) {
   if (!tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_task_inputs: null task-input buffer");
-  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, nullptr, stream);
+  HumanoidRollout rq = rollout_request(first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, nullptr);
+  rq.mlp = policy;
+  return env_rollout("lhw_env_rollout_task_inputs", e, rq, stream);
 }
 extern "C" int lhw_env_rollout_step_task_inputs(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev,
                                                 float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev,
                                                 float* rew_terms_dev, double* tin_dev, double* stin_dev, void* stream) {
-  if (!e || e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_step_task_inputs: stepping-task envs only");
   if (!tin_dev || !stin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_step_task_inputs: null task-input buffer");
-  return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
+  HumanoidRollout rq = rollout_request(first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev);
+  rq.mlp = policy;
+  return env_rollout("lhw_env_rollout_step_task_inputs", e, rq, stream);
 }
 
 extern "C" int lhw_env_rollout_history(LhwEnv* e, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, int32_t history_len, float* obs_dev,
                                        float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev,
                                        double* tin_dev, double* stin_dev, void* stream) {
   if (history_len < 1) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_history: history_len = %d", history_len);
-  if (stin_dev && (!e || e->task != LHW_TASK_JVRC_STEP)) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: the stepping record needs a stepping-task env");
-  if (stin_dev && !tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_history: the stepping record is exported together with the task-input record");
-  if (history_len == 1)   // no history: the kernels of lhw_env_rollout
-    return env_rollout_impl(e, policy, first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev, stream);
-  if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
-  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: wave-per-env (humanoid) steppers only");
-  HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_rollout_history(e->hum, first, count, T, history_len, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev,
-                                          tin_dev, stin_dev, (hipStream_t)stream);
-  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
-  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout_history: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
-  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_history: needs a float32 actor obs %d x %d (padded <= %d) -> 256 -> 256 -> act %d (<= 12) and a model that "
-                          "fits the task's resident kernel", history_len, e->obs_dim, LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, e->act_dim);
-  HIPCHK(hipGetLastError());
-  return LHW_OK;
+  HumanoidRollout rq = rollout_request(first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev);
+  rq.mlp = policy;
+  rq.history_len = history_len;
+  if (history_len > 1) rq.kind = POLICY_HIST;   // (history_len = 1, no history: the kernels of lhw_env_rollout)
+  return env_rollout("lhw_env_rollout_history", e, rq, stream);
 }
 
 extern "C" int lhw_env_rollout_lstm(LhwEnv* e, const LhwRolloutLstmPolicy* policy, int32_t first, int32_t count, int32_t T, float* obs_dev, float* act_dev,
                                     float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev, float* rew_terms_dev, const uint8_t* reset0_dev,
                                     double* tin_dev, double* stin_dev, void* stream) {
-  if (!e || !policy || !obs_dev || !act_dev || !logp_dev || !term_obs_dev || !rew_dev || !done_dev || !reset0_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
-  if (e->task == LHW_TASK_CARTPOLE) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: wave-per-env (humanoid) steppers only");
-  if (stin_dev && e->task != LHW_TASK_JVRC_STEP) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: the stepping record needs a stepping-task env");
-  if (stin_dev && !tin_dev) return lhw_fail(LHW_ERR_ARG, "lhw_env_rollout_lstm: the stepping record is exported together with the task-input record");
-  HIPCHK(hipSetDevice(e->device));
-  const int rc = humanoid_rollout_lstm(e->hum, first, count, T, policy, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, reset0_dev, tin_dev,
-                                       stin_dev, (hipStream_t)stream);
-  if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", first, first + count, T);
-  if (rc == -4) return lhw_fail(LHW_ERR_HIP, "lhw_env_rollout_lstm: a HIP call failed while preparing the launch (%s)", hipGetErrorString(hipGetLastError()));
-  if (rc) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_rollout_lstm: needs a float32 LSTM actor obs %d -> 256 -> 256 -> act %d (<= 12) with a state row per env and a model "
-                          "that fits the task's resident kernel", e->obs_dim, e->act_dim);
-  HIPCHK(hipGetLastError());
-  return LHW_OK;
+  HumanoidRollout rq = rollout_request(first, count, T, obs_dev, act_dev, logp_dev, term_obs_dev, rew_dev, done_dev, rew_terms_dev, tin_dev, stin_dev);
+  rq.kind = POLICY_LSTM;
+  rq.lstm = policy;
+  rq.reset0 = reset0_dev;
+  return env_rollout("lhw_env_rollout_lstm", e, rq, stream);
 }
 
 extern "C" int lhw_env_last_rollout_queued(LhwEnv* e) {

@@ -67,7 +67,7 @@ struct HRolloutT {
 // Policy kinds of the resident rollout: the feed-forward 256-256 actor (policy_step) and the two-cell LSTM actor (lstm_policy_step).  The kind
 // is a template parameter of rollout_steps and picks the kernel's argument struct, so a feed-forward kernel holds nothing of the LSTM step.
 // POLICY_HIST: the feed-forward actor on an observation HISTORY (obs_history_len > 1: rows of history_len x base width, policy_step_wide).
-enum { POLICY_MLP = 0, POLICY_LSTM = 1, POLICY_HIST = 2 };
+// (the enum is lhw_internal.h's: the API layer names the kind of a request)
 struct LstmPolicyArg {
   LhwRolloutLstmPolicy q;
   const unsigned char* reset0;   // [n_total] rows whose episode starts with the rollout's first observation (their state counts as zero)
@@ -479,7 +479,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
   const int eidx0 = grp * G;
   const int nlive = min(G, lz.env_count - eidx0);
   const int env0 = lz.env_first + eidx0;
-  const int OBS = TASK == TASK_WALK ? 37 : (TASK == TASK_STEP ? 39 : (TASK == TASK_H1WALK ? 43 : 35));
+  const int OBS = humanoid_base_obs_dim(TASK);
   const size_t N = (size_t)ro.n_total;
   // (diagnostic, lhw_env_debug_wave_cycles: shader-clock cycles the group's control steps took, summed over the rollout's chunks;
   //  control_step leaves the last step's own figure in the same word, so the running sum is picked up before the chunk's first step)
@@ -629,95 +629,74 @@ DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, POLICY_HIST)
 DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, POLICY_HIST)
 
 // ------------------------------------------------------------------------------------------------ host side
+// A policy kind's two kernel families, plain and with the term statistics: the one place that names them.  The launch tables below are
+// built from it, so a kernel is instantiated where a table names it and nowhere else.
+template <int PK> using RolloutFn = void (*)(const HModel*, const HParams*, HLaunch, HState, typename RolloutOf<PK>::type);
+template <int PK, bool STATS, int TASK, int W, bool QUEUE>
+constexpr RolloutFn<PK> rollout_kernel() {
+#if defined(LHW_ONLY_WALK) && !defined(LHW_ROLLOUT_STEP_TU)   // (development builds: this unit compiles the jvrc_walk kernels only, the other tasks' cells stay empty)
+  if constexpr (TASK != TASK_WALK) return nullptr; else
+#endif
+  if constexpr (PK == POLICY_LSTM) {
+    if constexpr (STATS) return humanoid_rollout_lstm_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_lstm_kernel<TASK, W, QUEUE>;
+  } else if constexpr (PK == POLICY_HIST) {
+    if constexpr (STATS) return humanoid_rollout_hist_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_hist_kernel<TASK, W, QUEUE>;
+  } else {
+    if constexpr (STATS) return humanoid_rollout_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_kernel<TASK, W, QUEUE>;
+  }
+}
+
 // The stepping task's two instantiations live in a translation unit of their own, lhw_humanoid_rollout_step.hip (this file included with
 // LHW_ROLLOUT_STEP_TU defined): it is compiled with LLVM's iterative ILP scheduling strategy, which makes the one-env-per-wave kernels 3 % faster
 // (the two-envs-per-wave kernels are built with iterative-maxocc instead: _lib.EXTRA_FLAGS, profiles/r06_stepper_compiler_flags.txt) -- and the two
 // halves compile in parallel.
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro);
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutLstm ro);
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutHist ro);
+template <int PK>
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st,
+                                  const typename RolloutOf<PK>::type& ro);
 #ifdef LHW_ROLLOUT_STEP_TU
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRollout ro) {
-  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
-  if (!stats) {
-    if (queued) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-    else hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  else hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+template <int PK>
+void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st,
+                                  const typename RolloutOf<PK>::type& ro) {
+  // [stats][not queued].  The plain family is named first, and the kinds are instantiated below in the order MLP, LSTM, HIST: the compiler
+  // emits kernels in the order it meets them, and theirs is then the order without the feature
+  static constexpr RolloutFn<PK> table[2][2] = {{rollout_kernel<PK, false, TASK_STEP, 64, true>(), rollout_kernel<PK, false, TASK_STEP, 64, false>()},
+                                                {rollout_kernel<PK, true, TASK_STEP, 64, true>(), rollout_kernel<PK, true, TASK_STEP, 64, false>()}};
+  hipLaunchKernelGGL(table[stats][!queued], grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
 }
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutLstm ro) {
-  if (!stats) {
-    if (queued) hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-    else hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  else hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-}
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st, HRolloutHist ro) {
-  if (!stats) {
-    if (queued) hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-    else hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  } else if (queued) hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_STEP, 64, true>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-  else hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_STEP, 64, false>), grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
-}
+#define ROLLOUT_STEP_KIND(PK) \
+  template void humanoid_rollout_launch_step<PK>(bool, bool, dim3, hipStream_t, const HModel*, const HParams*, HLaunch, HState, const typename RolloutOf<PK>::type&);
+ROLLOUT_STEP_KIND(POLICY_MLP) ROLLOUT_STEP_KIND(POLICY_LSTM) ROLLOUT_STEP_KIND(POLICY_HIST)
 #else
-#ifdef LHW_ONLY_WALK
-#define ROLLOUT_OTHER_TASKS(KERNEL, WIDTH)
-#else
-#define ROLLOUT_OTHER_TASKS(KERNEL, WIDTH)                                                                                                                      \
-  else if (h->p.task == TASK_H1WALK) hipLaunchKernelGGL((KERNEL<TASK_H1WALK, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro); \
-  else hipLaunchKernelGGL((KERNEL<TASK_STAND, WIDTH, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-#endif
-
 int humanoid_last_rollout_queued(const HumanoidEnv* h) { return h->last_rollout_queued; }
 
 // the two-envs-per-wave launches of one policy kind
-static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRollout& ro) {
-  // (the plain family is named first: the compiler emits kernels in the order it meets them, and theirs is then the order without the feature)
-  if (!stats) {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_kernel, 32)
-  } else {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_stats_kernel, 32)
-  }
-}
-static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRolloutLstm& ro) {
-  if (!stats) {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_lstm_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_lstm_kernel, 32)
-  } else {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_lstm_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_lstm_stats_kernel, 32)
-  }
-}
-static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const HRolloutHist& ro) {
-  if (!stats) {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_hist_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_hist_kernel, 32)
-  } else {
-    if (h->p.task == TASK_WALK) hipLaunchKernelGGL((humanoid_rollout_hist_stats_kernel<TASK_WALK, 32, false>), grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
-    ROLLOUT_OTHER_TASKS(humanoid_rollout_hist_stats_kernel, 32)
-  }
+template <int PK>
+static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro) {
+  // [stats][task: walk, h1_walk, stand].  The plain family is named first: the compiler emits kernels in the order it meets them, and
+  // theirs is then the order without the feature
+  static constexpr RolloutFn<PK> table[2][3] = {
+      {rollout_kernel<PK, false, TASK_WALK, 32, false>(), rollout_kernel<PK, false, TASK_H1WALK, 32, false>(), rollout_kernel<PK, false, TASK_STAND, 32, false>()},
+      {rollout_kernel<PK, true, TASK_WALK, 32, false>(), rollout_kernel<PK, true, TASK_H1WALK, 32, false>(), rollout_kernel<PK, true, TASK_STAND, 32, false>()}};
+  const RolloutFn<PK> k = table[stats][h->p.task == TASK_WALK ? 0 : (h->p.task == TASK_H1WALK ? 1 : 2)];
+  if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
 }
 
-// everything of a resident rollout but the policy view (ro.pol, filled by the caller); -1 bad range, -3 unsupported, -4 HIP error
-template <class RO>
-static int rollout_launch(HumanoidEnv* h, RO& ro, int first, int count, int T, float* obs, float* act, float* logp, float* term_obs, float* rew, uint8_t* done,
-                          float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
+// everything of a resident rollout but the policy view (ro.pol, filled by the caller) and the checks (humanoid_rollout); -4 HIP error
+template <int PK>
+static int rollout_launch(HumanoidEnv* h, typename RolloutOf<PK>::type& ro, const HumanoidRollout& rq, hipStream_t s) {
+  const int first = rq.first, count = rq.count, T = rq.T;
   ro.T = T; ro.n_total = h->p.n_envs;
-  ro.obs = obs; ro.act = act; ro.logp = logp; ro.tob = term_obs; ro.rew = rew; ro.done = done; ro.rew_terms = rew_terms;
+  ro.obs = rq.obs; ro.act = rq.act; ro.logp = rq.logp; ro.tob = rq.term_obs; ro.rew = rq.rew; ro.done = rq.done; ro.rew_terms = rq.rew_terms;
   ro.queue = nullptr; ro.chunk = 0;
-  ro.tin_step = tin_all ? (long long)h->p.n_envs * LHW_TASK_INPUT_DIM : 0;
+  ro.tin_step = rq.tin_all ? (long long)h->p.n_envs * LHW_TASK_INPUT_DIM : 0;
   HState st = h->st;
-  if (tin_all) st.tin = tin_all;   // [T][n_envs][LHW_TASK_INPUT_DIM]: every control step's record instead of the last one's
-  if (stin_all) {                  // [T][n_envs][LHW_STEP_TASK_INPUT_DIM] (stepping task, exported together with tin_all: its slice offset follows tin_off)
-    if (!tin_all || h->p.task != TASK_STEP) return -1;
-    st.stin = stin_all;
-  } else if (tin_all) {
-    st.stin = nullptr;             // (an armed per-launch stepping record is [n_envs] long: not written at the time slices of tin_all)
+  if (rq.tin_all) {
+    st.tin = rq.tin_all;       // [T][n_envs][LHW_TASK_INPUT_DIM]: every control step's record instead of the last one's
+    // [T][n_envs][LHW_STEP_TASK_INPUT_DIM] (stepping task, exported together with tin_all: its slice offset follows tin_off), or none
+    // (an armed per-launch stepping record is [n_envs] long: not written at the time slices of tin_all)
+    st.stin = rq.stin_all;
   }
   const HLaunch lz{first, count, 0, h->iteration, 0};
-  if (!h->fast && h->p.task != TASK_STEP) return -3;   // a walking / standing model that does not fit the two-envs-per-wave layout (or LHW_ONE_ENV_PER_WAVE): launch-per-step only
   // Stepping task with more env groups than wave slots: the resident waves share a job queue of `chunk`-step pieces instead of a
   // group each (humanoid_rollout_kernel<.., QUEUE = true>).  LHW_ROLLOUT_CHUNK: control steps per job (default 10; 0 = one wave per
   // group whatever the batch).  LHW_ROLLOUT_SLOTS: tests only,
@@ -749,62 +728,60 @@ static int rollout_launch(HumanoidEnv* h, RO& ro, int first, int count, int T, f
   const dim3 grid(grid_n);
   h->last_rollout_queued = ro.queue != nullptr;
   const bool stats = h->p.tstat != nullptr;   // per-term episode statistics armed: the kernels that keep them
-  if (h->fast) rollout_launch_fast(h, stats, grid, s, lz, st, ro);
+  if (h->fast) rollout_launch_fast<PK>(h, stats, grid, s, lz, st, ro);
 #ifndef LHW_ONLY_WALK
-  else humanoid_rollout_launch_step(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+  else humanoid_rollout_launch_step<PK>(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
 #endif
   return 0;
 }
 
-static int rollout_obs_dim(const HumanoidEnv* h) { return h->p.task == TASK_STEP ? 39 : (h->p.task == TASK_WALK ? 37 : (h->p.task == TASK_H1WALK ? 43 : 35)); }
+// (instantiated here, in the order of the kinds, and not where humanoid_rollout happens to name them first: this line decides the order
+//  in which the compiler emits the two-envs-per-wave kernels, the one they have had so far)
+#define ROLLOUT_KIND(PK) template int rollout_launch<PK>(HumanoidEnv*, typename RolloutOf<PK>::type&, const HumanoidRollout&, hipStream_t);
+ROLLOUT_KIND(POLICY_MLP) ROLLOUT_KIND(POLICY_LSTM) ROLLOUT_KIND(POLICY_HIST)
 
-int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
-  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
-  const int obs_dim = rollout_obs_dim(h);
-  if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
-      pol->obs_pad < obs_dim || pol->obs_pad > PXK || (pol->obs_pad & 3))
-    return -2;
-  HRollout ro;
-  ro.pol = *pol;
-  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
+// the shape clauses the in-wave policy steps share: the width of the env's rows, the capacity of the step's padded observation row (PXK / PXW)
+template <class POL>
+static bool policy_fits(const POL* q, const HumanoidEnv* h, long long obs_dim, int obs_cap) {
+  return q->hidden == PH && q->obs_dim == obs_dim && q->act_dim == h->m.nu && q->act_pad <= PO_MAX && !(q->act_pad & 3) && q->act_pad >= q->act_dim &&
+         q->obs_pad >= obs_dim && q->obs_pad <= obs_cap && !(q->obs_pad & 3);
 }
 
-// the resident rollout of an env with an observation history (lhw_env_rollout_history, history_len > 1): the policy reads rows of history_len
-// base observations; control_step writes the step's base rows to two per-env scratch buffers, allocated by the first such rollout
-int humanoid_rollout_history(HumanoidEnv* h, int first, int count, int T, int history_len, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp,
-                             float* term_obs, float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s) {
-  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0 || history_len < 2) return -1;
-  const int obs_dim = rollout_obs_dim(h);
-  if (pol->hidden != PH || (long long)pol->obs_dim != (long long)history_len * obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) ||
-      pol->act_pad < pol->act_dim || pol->obs_pad < pol->obs_dim || pol->obs_pad > PXW || (pol->obs_pad & 3))
+int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s) {
+  if (rq.first < 0 || rq.count <= 0 || rq.first + rq.count > h->p.n_envs || rq.T <= 0 || rq.history_len < 1) return -1;
+  if (rq.stin_all && (!rq.tin_all || h->p.task != TASK_STEP)) return -1;
+  const int base = humanoid_base_obs_dim(h->p.task);
+  const long long obs_dim = (long long)rq.history_len * base;
+  if (rq.kind == POLICY_LSTM) {   // ... and the policy's state buffers must hold a row per env of the batch
+    const LhwRolloutLstmPolicy* q = rq.lstm;
+    if (!policy_fits(q, h, obs_dim, PXK) || q->state_rows < h->p.n_envs || (q->h1_ld & 3) || (q->h2_ld & 3) || q->h1_ld < PH || q->h2_ld < PH) return -2;
+  } else if (!policy_fits(rq.mlp, h, obs_dim, rq.kind == POLICY_HIST ? PXW : PXK)) {
     return -2;
-  if (!h->fast && h->p.task != TASK_STEP) return -3;   // (as rollout_launch: before anything is allocated)
+  }
+  if (!h->fast && h->p.task != TASK_STEP) return -3;   // a walking / standing model that does not fit the two-envs-per-wave layout (or LHW_ONE_ENV_PER_WAVE): launch-per-step only
+  if (rq.kind == POLICY_MLP) {
+    HRollout ro;
+    ro.pol = *rq.mlp;
+    return rollout_launch<POLICY_MLP>(h, ro, rq, s);
+  }
+  if (rq.kind == POLICY_LSTM) {
+    HRolloutLstm ro;
+    ro.pol.q = *rq.lstm;
+    ro.pol.reset0 = rq.reset0;
+    return rollout_launch<POLICY_LSTM>(h, ro, rq, s);
+  }
+  // the policy reads rows of history_len base observations; control_step writes the step's base rows to two per-env scratch buffers,
+  // allocated by the first such rollout
   if (!h->hist_base) {
-    float* b = h->mem.get_lazy<float>((size_t)h->p.n_envs * obs_dim * 2);
+    float* b = h->mem.get_lazy<float>((size_t)h->p.n_envs * base * 2);
     if (!b) return -4;
     h->hist_base = b;
-    h->hist_tbase = b + (size_t)h->p.n_envs * obs_dim;
+    h->hist_tbase = b + (size_t)h->p.n_envs * base;
   }
   HRolloutHist ro;
-  ro.pol.q = *pol;
+  ro.pol.q = *rq.mlp;
   ro.pol.base = h->hist_base;
   ro.pol.tbase = h->hist_tbase;
-  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
-}
-
-// the LSTM actor's resident rollout (lhw_env_rollout_lstm); the policy's state buffers must hold a row per env of the batch
-int humanoid_rollout_lstm(HumanoidEnv* h, int first, int count, int T, const LhwRolloutLstmPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                          float* rew, uint8_t* done, float* rew_terms, const uint8_t* reset0, double* tin_all, double* stin_all, hipStream_t s) {
-  if (first < 0 || count <= 0 || first + count > h->p.n_envs || T <= 0) return -1;
-  const int obs_dim = rollout_obs_dim(h);
-  if (pol->hidden != PH || pol->obs_dim != obs_dim || pol->act_dim != h->m.nu || pol->act_pad > PO_MAX || (pol->act_pad & 3) || pol->act_pad < pol->act_dim ||
-      pol->obs_pad < obs_dim || pol->obs_pad > PXK || (pol->obs_pad & 3) || pol->state_rows < h->p.n_envs || (pol->h1_ld & 3) || (pol->h2_ld & 3) ||
-      pol->h1_ld < PH || pol->h2_ld < PH)
-    return -2;
-  HRolloutLstm ro;
-  ro.pol.q = *pol;
-  ro.pol.reset0 = reset0;
-  return rollout_launch(h, ro, first, count, T, obs, act, logp, term_obs, rew, done, rew_terms, tin_all, stin_all, s);
+  return rollout_launch<POLICY_HIST>(h, ro, rq, s);
 }
 #endif   // LHW_ROLLOUT_STEP_TU

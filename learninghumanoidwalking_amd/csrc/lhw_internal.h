@@ -103,12 +103,26 @@ void humanoid_step(HumanoidEnv* h, const float* act, float* obs, float* term_obs
 int humanoid_step_range(HumanoidEnv* h, int first, int count, const float* act, float* obs, float* term_obs, float* rew, uint8_t* done,
                         float* rew_terms, hipStream_t s);
 int humanoid_last_rollout_queued(const HumanoidEnv* h);
-int humanoid_rollout(HumanoidEnv* h, int first, int count, int T, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                     float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // lhw_humanoid_rollout.hip; -1 bad range, -2 / -3 unsupported, -4 HIP error
-int humanoid_rollout_history(HumanoidEnv* h, int first, int count, int T, int history_len, const LhwRolloutPolicy* pol, float* obs, float* act, float* logp,
-                             float* term_obs, float* rew, uint8_t* done, float* rew_terms, double* tin_all, double* stin_all, hipStream_t s);   // history_len > 1; codes as humanoid_rollout
-int humanoid_rollout_lstm(HumanoidEnv* h, int first, int count, int T, const LhwRolloutLstmPolicy* pol, float* obs, float* act, float* logp, float* term_obs,
-                          float* rew, uint8_t* done, float* rew_terms, const uint8_t* reset0, double* tin_all, double* stin_all, hipStream_t s);   // same codes
+// One resident rollout, whatever the policy kind, as the API layer hands it to lhw_humanoid_rollout.hip.  Policy kinds: the feed-forward actor,
+// the LSTM actor, the feed-forward actor on an observation history (rows of history_len x the env's base width).
+enum { POLICY_MLP = 0, POLICY_LSTM = 1, POLICY_HIST = 2 };
+struct HumanoidRollout {
+  int first, count, T;
+  float *obs, *act, *logp, *term_obs, *rew;
+  uint8_t* done;
+  float* rew_terms;                             // nullable
+  double *tin_all, *stin_all;                   // nullable: the task-input record(s) of every control step
+  int kind = POLICY_MLP;
+  const LhwRolloutPolicy* mlp = nullptr;        // the view of POLICY_MLP and POLICY_HIST
+  const LhwRolloutLstmPolicy* lstm = nullptr;   // ... of POLICY_LSTM
+  const uint8_t* reset0 = nullptr;              // POLICY_LSTM
+  int history_len = 1;                          // > 1: POLICY_HIST
+};
+int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s);   // -1 bad range, -2 / -3 unsupported, -4 HIP error
+// width of a task's base observation (the kernels' TASK_* ids are the ABI's LHW_TASK_* values: lhw_humanoid.hip)
+constexpr int humanoid_base_obs_dim(int task) {
+  return task == LHW_TASK_JVRC_WALK ? 37 : (task == LHW_TASK_JVRC_STEP ? 39 : (task == LHW_TASK_H1_WALK ? 43 : 35));
+}
 void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t s);
 void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, hipStream_t s);
 double* humanoid_ep_stats(HumanoidEnv* h);

@@ -136,6 +136,18 @@ class _RolloutStorage:
         """(sum of finished-episode returns, sum of their lengths, their number) since the last call: the env's own counters."""
         return self.env.pop_episode_stats()
 
+    @staticmethod
+    def _rollout_mode():
+        """LHW_ROLLOUT_MODE: auto | resident (declining raises) | steps (and anything else)"""
+        return os.environ.get("LHW_ROLLOUT_MODE", "auto")
+
+    @staticmethod
+    def _declined(mode, why) -> bool:
+        """The resident rollout is not to be had, because `why`: False -- the launch-per-step pipeline runs -- unless the mode insists on it."""
+        if mode == "resident":
+            raise _lib.LhwError(-4, f"LHW_ROLLOUT_MODE=resident, but {why}")
+        return False
+
 
 class Rollout(_RolloutStorage):
     """Feed-forward policies: the resident rollout where the library has it, else one policy and one env launch per control step.
@@ -236,29 +248,25 @@ class Rollout(_RolloutStorage):
         # already backfill each other's tails).
         # An env with an observation history goes the same way (lhw_env_rollout_history): jvrc_walk @ 4096 with obs_history_len 3, sampling
         # 0.47 -> 0.31 s per iteration, resident's mean below every launch-per-step iteration (profiles/r09_history_rollout_ab.txt).
-        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
+        mode = self._rollout_mode()
         if mode not in ("auto", "resident"):
             return False
         env, T = self.env, self.T
         pol = self.k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
         if pol is None:
-            why = "the kernels have no in-wave policy step for this actor"
-        elif env.env_id_base != self.env_base:
+            return self._declined(mode, "the kernels have no in-wave policy step for this actor")
+        if env.env_id_base != self.env_base:
             # (the in-wave policy step keys its noise by the env's own global ids; the per-step calls pass self.env_base + row)
-            why = "the env's env_id_base is not the rollout's"
-        else:
-            if task_inputs and self._tin_all is None:
-                self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-                if env.task == TASK_JVRC_STEP:
-                    self._stin_all = _lib.empty(T, self.N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-            if env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done,
+            return self._declined(mode, "the env's env_id_base is not the rollout's")
+        if task_inputs and self._tin_all is None:
+            self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+            if env.task == TASK_JVRC_STEP:
+                self._stin_all = _lib.empty(T, self.N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+        if not env.rollout(pol, T, self.obs, self.act, self.logp, self.tob_all, self.rew, self.done,
                            task_inputs=self._tin_all if task_inputs else None, step_task_inputs=self._stin_all if task_inputs else None):
-                self.counter += T
-                return True
-            why = "the library has no resident rollout kernel for this env / policy"
-        if mode == "resident":
-            raise _lib.LhwError(-4, f"LHW_ROLLOUT_MODE=resident, but {why}")
-        return False
+            return self._declined(mode, "the library has no resident rollout kernel for this env / policy")
+        self.counter += T
+        return True
 
     def _collect_steps(self, deterministic, rew, done, after_step=None):
         """Launch per control step: the actor, then the env step writing its reward and flags to rew[t] / done[t], then
@@ -506,38 +514,33 @@ class RecurrentRollout(_RolloutStorage):
         (V(s_t) advancing the critic's state, V(terminal observation) without): the same calls on the same values, so not a bit of
         `val` / `vterm` changes, and the critic no longer sits between two control steps.  The means of the last step (`self.mu`) are
         not produced here: nothing reads them.  Returns False where the launch-per-step loop is to run instead."""
-        mode = os.environ.get("LHW_ROLLOUT_MODE", "auto")
+        mode = self._rollout_mode()
         if mode not in ("auto", "resident") or (mode == "auto" and not (LSTM_RESIDENT_AUTO or self.record_task_inputs)):
             return False      # (the per-step record exists only on the resident path: asking for it selects that path)
         env, k, T = self.env, self.k, self.T
         if env.task == 0:
-            why = "the cartpole env has no wave-per-env stepper to host a policy step"
-        elif k.hidden != 256:
-            why = f"the in-wave LSTM step covers hidden width 256 only (this actor: {k.hidden})"
-        elif env.env_id_base != self.env_base:
-            why = "the env's env_id_base is not the rollout's"
-        elif env.history_len > 1:
-            why = "the env keeps an observation history above the kernels"
-        else:
-            pol = k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
-            if pol is None:
-                why = "the kernels have no in-wave policy step for this actor"
-            else:
-                if self._tob_all is None:
-                    self._tob_all = _lib.empty(T, self.N, env.obs_dim, dtype=torch.float32, device=self.obs.device)
-                if self.record_task_inputs and self._tin_all is None:
-                    self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
-                if env.rollout_lstm(pol, T, self.obs, self.act, self.logp, self._tob_all, self.rew, self.done, self._rec_reset,
-                                    task_inputs=self._tin_all if self.record_task_inputs else None):
-                    if not self.seq_critic:
-                        self._critic_steps(self._rec_reset)
-                    self._rec_reset = (self.done[T - 1] != 0).to(torch.uint8)
-                    self.counter += T
-                    return True
-                why = "the library has no resident LSTM rollout kernel for this env / policy"
-        if mode == "resident":
-            raise _lib.LhwError(-4, f"LHW_ROLLOUT_MODE=resident, but {why}")
-        return False
+            return self._declined(mode, "the cartpole env has no wave-per-env stepper to host a policy step")
+        if k.hidden != 256:
+            return self._declined(mode, f"the in-wave LSTM step covers hidden width 256 only (this actor: {k.hidden})")
+        if env.env_id_base != self.env_base:
+            return self._declined(mode, "the env's env_id_base is not the rollout's")
+        if env.history_len > 1:
+            return self._declined(mode, "the env keeps an observation history above the kernels")
+        pol = k.rollout_policy(seed=self.seed, counter=self.counter, deterministic=deterministic)
+        if pol is None:
+            return self._declined(mode, "the kernels have no in-wave policy step for this actor")
+        if self._tob_all is None:
+            self._tob_all = _lib.empty(T, self.N, env.obs_dim, dtype=torch.float32, device=self.obs.device)
+        if self.record_task_inputs and self._tin_all is None:
+            self._tin_all = _lib.empty(T, self.N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+        if not env.rollout_lstm(pol, T, self.obs, self.act, self.logp, self._tob_all, self.rew, self.done, self._rec_reset,
+                                task_inputs=self._tin_all if self.record_task_inputs else None):
+            return self._declined(mode, "the library has no resident LSTM rollout kernel for this env / policy")
+        if not self.seq_critic:
+            self._critic_steps(self._rec_reset)
+        self._rec_reset = (self.done[T - 1] != 0).to(torch.uint8)
+        self.counter += T
+        return True
 
 
 # Whether a PPO learner arms the per-term episode statistics of its env unless told otherwise (PPO(term_stats=...), --term-stats /

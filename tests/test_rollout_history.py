@@ -166,6 +166,37 @@ def test_history_rollout_through_the_job_queue(monkeypatch):
     assert envs[0].pop_episode_stats() == envs[1].pop_episode_stats()
 
 
+@pytest.mark.parametrize("name,stats", [("h1_walk", False), ("jvrc_step", False), ("jvrc_walk", True), ("h1", True), ("h1_walk", True), ("jvrc_step", True),
+                                        ("jvrc_step_queued", True)])
+def test_history_rollout_other_kernels(name, stats, monkeypatch):
+    """the history kernels no test above launches: the remaining tasks against the launch-per-step loop, and the kernels that keep the
+    per-term episode statistics (lhw_env_enable_term_stats) against their plain twins -- the same bits; one auto-reset (on the last step) inside"""
+    from tests.test_rollout_lstm import _spec
+    queued = name.endswith("_queued")
+    spec = _spec(name[:-7] if queued else name)
+    N, T, H = 3, 2, 2
+    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=2) for _ in range(2)]
+    pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
+    obs0 = [_first_full(e.reset(), H) for e in envs]
+    L = emu.lib()
+    if stats:
+        assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
+    if queued:      # every (group, control step) a job of one resident wave
+        monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
+        monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
+    a = _resident(envs[0], pol, T, obs0[0], H) if stats else _reference(envs[0], pol, T, obs0[0], H)
+    b = _resident(envs[1], pol, T, obs0[1], H)
+    _same(a, b)
+    assert L.lhw_env_last_rollout_queued(envs[1]._h) == int(queued)
+    assert (a["done"] != 0).any()
+    _same_state(*envs)
+    if stats:
+        terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
+        ep = ctypes.c_int64()
+        assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), None, None) == 0
+        assert ep.value == int((a["done"] != 0).sum())
+
+
 def test_history_entry_point_bounds_and_history_one():
     from learninghumanoidwalking_amd import _lib as product
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec

@@ -219,11 +219,15 @@ def test_lstm_resident_rollout_through_the_job_queue_is_bitwise_the_same(monkeyp
     _same_state(pols[0], pols[2])
 
 
-@pytest.mark.parametrize("name", ["jvrc_walk", "jvrc_step"])
-def test_lstm_resident_rollout_with_armed_term_statistics_gives_the_same_bits(name):
-    spec = _spec(name)
-    N, T = 3, 5
-    envs, pols = _pair(spec, N, 6, 4, max_traj_len=3)
+@pytest.mark.parametrize("name", ["jvrc_walk", "jvrc_step", "h1", "h1_walk", "jvrc_step_queued"])
+def test_lstm_resident_rollout_with_armed_term_statistics_gives_the_same_bits(name, monkeypatch):
+    queued = name.endswith("_queued")
+    spec = _spec(name[:-7] if queued else name)
+    N, T, traj = (3, 5, 3) if name in ("jvrc_walk", "jvrc_step") else (3, 2, 2)      # (the later cases: one auto-reset, on the last step)
+    if queued:      # every (group, control step) a job of one resident wave
+        monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
+        monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
+    envs, pols = _pair(spec, N, 6, 4, max_traj_len=traj)
     L = emu.lib()
     assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
     obs0 = [e.reset().copy() for e in envs]
@@ -232,6 +236,7 @@ def test_lstm_resident_rollout_with_armed_term_statistics_gives_the_same_bits(na
     b = _resident(envs[1], pols[1], T, obs0[1], reset0)
     _same(a, b)
     _same_state(pols[0], pols[1])
+    assert all(L.lhw_env_last_rollout_queued(e._h) == int(queued) for e in envs)
     terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
     ep, te, tr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr)) == 0

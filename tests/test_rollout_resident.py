@@ -167,6 +167,32 @@ def test_resident_rollout_other_tasks(name):
         np.testing.assert_array_equal(x, y)
 
 
+@pytest.mark.parametrize("name", ["h1", "h1_walk", "jvrc_step", "jvrc_step_queued"])
+def test_resident_rollout_with_armed_term_statistics_gives_the_same_bits(name, monkeypatch):
+    """the kernels that keep the per-term episode statistics (lhw_env_enable_term_stats) for the tasks tests/test_term_stats.py does not
+    run: the rollout of their plain twins bit for bit, one auto-reset (on the last step) inside"""
+    from tests.test_rollout_lstm import _spec
+    queued = name.endswith("_queued")
+    spec = _spec(name[:-7] if queued else name)
+    N, T = 3, 2
+    if queued:      # every (group, control step) a job of one resident wave
+        monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
+        monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
+    envs = [emu.make_emulated(spec, N, seed=2, max_traj_len=2) for _ in range(2)]
+    L = emu.lib()
+    assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
+    pol = NumpyActor(spec.obs_dim, spec.act_dim, seed=9)
+    a, b = (_resident(e, pol, T, e.reset().copy()) for e in envs)
+    _same(a, b)
+    assert all(L.lhw_env_last_rollout_queued(e._h) == int(queued) for e in envs)
+    for x, y in zip(envs[0].get_state(), envs[1].get_state()):
+        np.testing.assert_array_equal(x, y)
+    terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
+    ep = ctypes.c_int64()
+    assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), None, None) == 0
+    assert ep.value == int((a["done"] != 0).sum()) > 0
+
+
 def test_resident_rollout_through_the_job_queue_is_bitwise_the_same(monkeypatch):
     """Stepping task with more env groups than wave slots (jvrc_step @ 4096 on the chip; forced here by LHW_ROLLOUT_SLOTS): the
     resident waves pop (group, chunk of control steps) jobs from a queue, so a group's chunks run on whichever wave is free and a
