@@ -562,6 +562,13 @@ int lhw_ppo_debug_set_strip_fused(LhwPpo* ppo, int32_t on);
 int lhw_ppo_debug_set_strip_wide(LhwPpo* ppo, int32_t on);
 /* test hook: 1 if the last lhw_ppo_grad of this handle (a captured one included) ran the train strip launches, 0 if the three-launch path */
 int lhw_ppo_debug_last_grad_fused(const LhwPpo* ppo);
+/* test hook: which kernels the handle's calls launch, as the handle itself decides it -- once per call, from its switches (read from the LHW_*
+ * environment when it was created; the two debug setters above), the update dtype, the network shape and the row capacity.
+ * out13[0..8): the plan of an lhw_ppo_grad call on a minibatch of B rows (imitation != 0: with an imitation term armed) -- fp16 operands,
+ * fp16 storage, forward strips, backward strips (masks: 1 actor | 2 critic), train strips, mask bits, wide instantiations, streams (1 | 2).
+ * out13[8..13): lhw_ppo_forward[_at] and the rollout bracket -- fp16 operands, forward launches run the strips, the one-launch policy step is
+ * available, lhw_ppo_begin_rollout makes the critic's weight copies, ... the actor's (the bracket opens). */
+int lhw_ppo_debug_plan(const LhwPpo* ppo, int32_t B, int32_t imitation, int32_t* out13);
 /* time-major [T][N] GAE(lambda); done holds LHW_DONE_* flags, vterm the critic value of the terminal
  * observation, vfinal [N] the value of the observation after the last step */
 int lhw_gae(int32_t T, int32_t N, const float* rew, const float* val, const uint8_t* done, const float* vterm,

@@ -284,6 +284,7 @@ def declare(L):
     sig("lhw_ppo_debug_set_strip_fused", [vp, i32])
     sig("lhw_ppo_debug_set_strip_wide", [vp, i32])
     sig("lhw_ppo_debug_last_grad_fused", [vp])
+    sig("lhw_ppo_debug_plan", [vp, i32, i32, ctypes.POINTER(i32)])
     sig("lhw_debug_wgrad_wide", [vp, vp, i32, i32, vp, vp, vp])
     sig("lhw_debug_wgrad_skinny", [i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_phase_cycles", [vp, ctypes.c_int, vp])

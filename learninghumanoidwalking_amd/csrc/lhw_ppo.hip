@@ -35,6 +35,14 @@ static MlpLayout mlp_layout(int D, int H, int O) {
   L.total = o;
   return L;
 }
+// The [in][out] weight copies the strip kernels multiply by (mlp_strip_wt_floats floats: W1^T, W2^T, W3^T) -- this pair owns their layout:
+// the six weight / bias pointers of MlpStripFwd / LhwRolloutPolicy for the copies wt of the network at th, and making wt from th
+struct StripWeights { const float *w1t, *b1, *w2t, *b2, *w3t, *b3; };
+static StripWeights strip_weights(const MlpLayout& L, const float* wt, const float* th) {
+  const float* w2t = wt + (size_t)L.Dp * L.H;
+  return {wt, th + L.b1, w2t, th + L.b2, w2t + (size_t)L.H * L.H, th + L.b3};
+}
+static void strip_prepare(const MlpLayout& L, const float* th, float* wt, hipStream_t s) { mlp_strip_prepare(th + L.w1, th + L.w2, th + L.w3, L.Dp, L.O, L.Op, wt, s); }
 // One network as the passes below see it: its layout, its rows of the minibatch workspace, the strip kernels' weight copies and mask
 // bits, and the fp16 copies of the --fp16 update.  Built once by lhw_ppo_create (the fp16 part by lhw_ppo_set_update_dtype).  The actor's
 // buffers hold 2 R rows (normal rows, from row R the mirrored rows), the critic's R; a pass takes a RowSpan of them.
@@ -50,36 +58,63 @@ struct MlpNet {
   _Float16 *h1_h = nullptr, *h2_h = nullptr, *dh2_h = nullptr, *dh1_h = nullptr;   // [rows][H]
 };
 struct RowSpan { size_t first; int rows; };
-// How a pass runs; one value per call of the update, one per inference call
-struct MlpMode {
-  int half;        // fp16 operands (gemm_h_kernel) ...
-  bool hstore;     // ... that live as fp16 in the net's *_h buffers (update); else float32 storage, rounded while staged
-  bool strip;      // the strip kernels may run (forward: if the net has weight copies)
-  bool wt_ready;   // forward strip: the weight copies are already made
-  bool infer;      // forward: h1 / h2 are not kept (in the strip kernel they never leave LDS) and no mask bits are written
-  bool have_dh;    // backward: dh2 / dh1 are already there (train strip launch): the weight gradients only
-  bool wide;       // the strip kernels may run for rows wider than 64 columns too (LhwPpo::strip_wide)
+// The handle's switches: every LHW_* variable this file reads, read once, by lhw_ppo_create -- a handle sees the environment it was created
+// in (DESIGN.md section 4.2 has the table).  lhw_ppo_debug_set_strip_fused / _wide write the same record.
+struct Switches {
+  int mlp_strip;                  // LHW_MLP_STRIP: 0 = per-layer GEMMs everywhere, 1 = LDS-resident strip kernels in the update, 2 = in rollout inference
+                                  // as well (default: the rollout and the update then evaluate the networks with the same kernel, bit for bit)
+  int strip_bits, strip_fused;    // LHW_STRIP_BITS: ReLU masks go from forward to backward strip as bits; LHW_STRIP_FUSED: train strips where the step allows
+  int strip_wide;                 // rows wider than 64 columns (an observation history) take the wide strip instantiations (Python layer: LHW_STRIP_WIDE)
+  int two_streams, graph, fp16_storage;   // LHW_PPO_TWO_STREAMS: the update's critic chain on its own stream; LHW_PPO_GRAPH: lhw_ppo_step captures and
+};                                        // replays; LHW_FP16_STORAGE: the --fp16 update keeps its activations as fp16 in HBM (0: rounded per GEMM)
+static Switches read_switches() {
+  auto on = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+  return {on("LHW_MLP_STRIP", 2), on("LHW_STRIP_BITS", 1) != 0, on("LHW_STRIP_FUSED", 1) != 0, 0, on("LHW_PPO_TWO_STREAMS", 1) != 0,
+          on("LHW_PPO_GRAPH", 1) != 0, on("LHW_FP16_STORAGE", 1) != 0};
+}
+// Which kernels one lhw_ppo_grad call launches (update_plan).  The call and the two passes below read it, and the key of a captured step holds
+// it by value: whatever decides a launch is in that key.  fwd_strip / bwd_strip are masks: bit 0 the actor, bit 1 the critic.
+struct UpdatePlan {
+  int32_t half, hstore;           // fp16 operands (gemm_h_kernel); ... that live as fp16 in the nets' *_h buffers (else rounded while staged)
+  int32_t fwd_strip, bwd_strip;   // forward layers as one forward strip launch; activation gradients as one backward strip launch (else GEMMs)
+  int32_t train;                  // train strips: ONE launch per network runs forward, loss head and backward layers (no fwd / bwd strip then)
+  int32_t bits, wide;             // the forward strips leave the ReLU masks as bits for the backward strips; the strip launches are the wide instantiations
+  int32_t streams;                // 2: the critic's chain runs on the side stream
 };
+// ... and what lhw_ppo_forward[_at] and the rollout bracket do (infer_plan)
+struct InferPlan {
+  int32_t half, strips, policy_step;     // fp16 operands (per-layer GEMMs); forward launches run the forward strip; the one-launch policy step is available
+  int32_t critic_copies, actor_copies;   // lhw_ppo_begin_rollout makes the critic's [in][out] copies (forward launches read them); the actor's: the bracket opens
+};
+// How one network's forward or backward pass runs: named fields, filled from the call's plan
+struct MlpPass {
+  int half = 0; bool hstore = false;               // as UpdatePlan's
+  const float* wt = nullptr;                       // forward: the network's READY [in][out] copies, the forward strip runs; NULL: one GEMM per layer
+  bool keep = false, bits = false;                 // forward strip: h1 / h2 are kept for a backward pass (else they never leave LDS), their masks as bits too
+  bool bwd_strip = false, have_dh = false;         // backward: dh2 / dh1 by one backward strip launch; they are already there (train strip launch)
+};
+// What a captured step was captured for: buffers and stream, minibatch size, the bits of grad_scale, the plan
+struct StepKey {
+  const void* ptr[12]; int32_t B; uint32_t gs; UpdatePlan plan;
+  bool operator==(const StepKey& o) const { return memcmp(this, &o, sizeof o) == 0; }
+};
+static_assert(std::has_unique_object_representations_v<StepKey>, "StepKey is compared as bytes");
 
 struct LhwPpo : LearnerCore {
   int max_rows;  // capacity of the minibatch workspace (rows per net)
-  _Float16* xb_h = nullptr;   // --fp16 update: fp16 copy of xb [2R][ldxh] (the nets' x_h)
-  int ldxh = 0;
-  int infer_half = 0;     // rollout inference with fp16 operands (lhw_ppo_set_inference_dtype)
-  int update_half = 0;    // every GEMM of the update with fp16 operands (lhw_ppo_set_update_dtype)
+  _Float16* xb_h = nullptr; int ldxh = 0;   // --fp16 update: fp16 copy of xb [2R][ldxh] (the nets' x_h)
+  int infer_half = 0, update_half = 0;      // fp16 operands in rollout inference (lhw_ppo_set_inference_dtype) / in every GEMM of the update (lhw_ppo_set_update_dtype)
   MlpNet a, c;            // actor (2R rows), critic (R rows; read-out [R][4])
   // workspace
   float *xb = nullptr;   // [2R][Dp] gathered minibatch inputs (normal rows, then mirrored rows)
   float *mb_act = nullptr, *mb_logp = nullptr, *mb_adv = nullptr, *mb_ret = nullptr;
   float *part = nullptr;       // split-K partial tiles [max slices][H*H]
   float *dstd = nullptr;       // per-row d loss / d std [R][Op]
-  float *wt_inf = nullptr;                  // [in][out] weight copies for the strip kernels beside the update's (a.wt, c.wt): WT_SLOTS pairs
-                                            // (actor, critic) for rollout inference, one per eighth of the
-                                            // forward workspace, so that concurrent calls (disjoint row ranges, different streams) do not share one
+  float *wt_inf = nullptr;                  // [in][out] weight copies for the strip kernels beside the update's (a.wt, c.wt): WT_SLOTS pairs (actor, critic) for rollout
+                                            // inference, one per eighth of the forward workspace, so that concurrent calls (disjoint row ranges, different streams) do not share one
   float *wt_roll = nullptr;                 // ... and the pair made once per rollout by lhw_ppo_begin_rollout (read-only until end_rollout / apply)
   const float* roll_theta = nullptr;        // theta the wt_roll copies were made from (NULL: no rollout bracket open)
-  const float* imit_target = nullptr;          // imitation term of the NEXT lhw_ppo_grad call (lhw_ppo_set_imitation)
-  const unsigned char* imit_mask = nullptr;
+  const float* imit_target = nullptr; const unsigned char* imit_mask = nullptr;   // imitation term of the NEXT lhw_ppo_grad call (lhw_ppo_set_imitation)
   float imit_coeff = 0.f, imit_inv_count = 0.f;
   float *bwd_part = nullptr;   // split-K partials of the weight / bias gradients: actor (two passes), then critic
   int max_slices = 0;
@@ -87,44 +122,21 @@ struct LhwPpo : LearnerCore {
   // the loss kernel): the load / multiply / store phases of one network's GEMMs overlap the other's
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_head = nullptr;
-  int two_streams = 1;
-  // each network's forward, loss head and backward layers as one train strip launch (lhw_mlp_strip.hip) where the step allows it;
-  // LHW_STRIP_FUSED=0 / lhw_ppo_debug_set_strip_fused: forward strip, ppo_loss_kernel, backward strip
-  int strip_fused = 1;
+  Switches sw{};
   float* stat_rows = nullptr;   // [NSTAT][max_rows]: the rows' loss terms the train strip launches leave for ppo_stats_rows_kernel
-  int last_grad_fused = 0;      // which path the last lhw_ppo_grad took (lhw_ppo_debug_last_grad_fused)
-  // rows wider than 64 columns (an observation history) through the wide strip instantiations instead of one GEMM per layer, wherever the
-  // handle chooses between the two (lhw_ppo_debug_set_strip_wide; the Python layer sets it from LHW_STRIP_WIDE)
-  int strip_wide = 0;
-  // lhw_ppo_step: one optimiser step (lhw_ppo_grad + lhw_ppo_apply) captured once per (buffers, minibatch size, grad_scale) as a hipGraph
-  // and replayed; the two things that change from step to step -- the minibatch's index pointer (gather_kernel) and Adam's bias
-  // corrections (adam2_kernel) -- are patched into the executable graph's kernel nodes before each launch.  grad_scale is part of the key
-  // (its bits): sumsq2_kernel's node keeps the scale it was captured with, so a new scale recaptures instead of clipping with a stale norm
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  hipGraphNode_t node_gather = nullptr, node_adam = nullptr;
-  const void* step_key[12] = {nullptr};
-  int step_key_b = 0, step_key_half = 0, step_key_fused = 0, step_key_wide = 0;
-  uint32_t step_key_gs = 0;
+  UpdatePlan last_plan{};       // the plan of the last lhw_ppo_grad (lhw_ppo_debug_last_grad_fused: its train bit)
+  // lhw_ppo_step: the captured optimiser step, the two kernel nodes patched before each launch, and what it was captured for
+  hipGraph_t step_graph = nullptr; hipGraphExec_t step_exec = nullptr; hipGraphNode_t node_gather = nullptr, node_adam = nullptr;
+  StepKey step_key{};
   ~LhwPpo() {
     (void)hipSetDevice(device);
     if (step_exec) (void)hipGraphExecDestroy(step_exec);
     if (step_graph) (void)hipGraphDestroy(step_graph);
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (ev_head) (void)hipEventDestroy(ev_head);
+    for (hipEvent_t e : {ev_fork, ev_join, ev_head}) if (e) (void)hipEventDestroy(e);
   }
 };
-// y = mlp(x) for the rows of r; keeps h1 / h2 for the backward pass unless m.infer
-// LHW_MLP_STRIP (tuning aid): 0 = per-layer GEMMs everywhere, 1 = LDS-resident strip kernels for the update's forward and
-// activation-gradient passes, 2 = for the rollout inference as well (default: the rollout and the update then evaluate the
-// networks with the same kernel, bit for bit)
 #define WT_SLOTS 8
-static int strip_mode() {
-  static const int m = getenv("LHW_MLP_STRIP") ? atoi(getenv("LHW_MLP_STRIP")) : 2;
-  return m;
-}
 // An actor whose padded observation row is wider than the narrow strips' 64 columns (an observation history) but within the in-wave policy step
 // of lhw_env_rollout_history, which reads [in][out] weight copies (LhwPpo::wt_roll) whatever path the handle's own launches take.  Stated from
 // the shape alone; the same shapes as the wide strip instantiations (LHW_MLP_STRIP_MAX_IN_PAD == LHW_ROLLOUT_HISTORY_MAX_OBS_PAD)
@@ -138,22 +150,45 @@ static bool strip_shape(const MlpLayout& L, bool wide_on) {
 static bool train_strip_shape(const MlpLayout& L, int critic, bool wide_on) {
   return mlp_train_strip_supported(L.H, L.Dp, L.O, L.Op, critic) || (wide_on && mlp_train_strip_wide_supported(L.H, L.Dp, L.O, L.Op, critic));
 }
-static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStream_t s, const MlpMode& m) {
+// The two plans.  (lhw_ppo_create has allocated what a shape the strips take, narrow or wide, needs: the nets' wt, stat_rows, wt_inf / wt_roll.)  The
+// strips are not for --fp16 or shapes they reject (per network), train strips not for an armed imitation term either: forward strip (or GEMMs), ppo_loss_kernel, backward
+static UpdatePlan update_plan(const LhwPpo* p, bool imitation) {
+  const Switches& w = p->sw;
+  UpdatePlan u{};
+  u.half = p->update_half; u.hstore = u.half && p->xb_h != nullptr;
+  const int nets = w.mlp_strip >= 1 && !u.half ? (strip_shape(p->a.L, w.strip_wide) ? 1 : 0) | (strip_shape(p->c.L, w.strip_wide) ? 2 : 0) : 0;
+  u.train = nets == 3 && w.strip_fused && !imitation && train_strip_shape(p->a.L, 0, w.strip_wide) && train_strip_shape(p->c.L, 1, w.strip_wide);
+  u.fwd_strip = u.bwd_strip = u.train ? 0 : nets;
+  u.bits = u.fwd_strip && p->a.bits1 != nullptr;
+  u.wide = nets && !strip_shape(p->c.L, false);
+  u.streams = w.two_streams ? 2 : 1;
+  return u;
+}
+static InferPlan infer_plan(const LhwPpo* p) {
+  InferPlan i{};
+  i.half = p->infer_half;
+  i.critic_copies = p->sw.mlp_strip >= 2 && p->wt_roll && strip_shape(p->a.L, p->sw.strip_wide) && strip_shape(p->c.L, p->sw.strip_wide);
+  i.strips = i.policy_step = i.critic_copies && !i.half;
+  // (a wide-row actor's copies serve lhw_env_rollout_history's in-wave step, whatever the handle's own launches run)
+  i.actor_copies = i.critic_copies || (p->wt_roll && rollout_wide_supported(p->a.L));
+  return i;
+}
+// y = mlp(x) for the rows of r
+static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStream_t s, const MlpPass& m) {
   const MlpLayout& L = n.L;
   const int R = r.rows, ldx = n.ldx, half = m.half;
   const size_t H = L.H, r0 = r.first;
   const float* x = n.x + r0 * ldx;
   float *h1 = n.h1 + r0 * H, *h2 = n.h2 + r0 * H, *y = n.y + r0 * L.Op;
-  if (m.strip && n.wt && !half && strip_shape(L, m.wide)) {   // one launch, h1 / h2 stay in LDS between the layers
-    if (!m.wt_ready) mlp_strip_prepare(theta + L.w1, theta + L.w2, theta + L.w3, L.Dp, L.O, L.Op, n.wt, s);   // [in][out] copies of the weights
-    MlpStripFwd a{n.wt, theta + L.b1, n.wt + (size_t)L.Dp * L.H, theta + L.b2, n.wt + (size_t)L.Dp * L.H + (size_t)L.H * L.H,
-                  theta + L.b3, x, ldx, L.Dp, L.O, L.Op, R, m.infer ? nullptr : h1, m.infer ? nullptr : h2, y};
-    if (!m.infer && n.bits1) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
+  if (m.wt) {   // one launch, h1 / h2 stay in LDS between the layers
+    const StripWeights w = strip_weights(L, m.wt, theta);
+    MlpStripFwd a{w.w1t, w.b1, w.w2t, w.b2, w.w3t, w.b3, x, ldx, L.Dp, L.O, L.Op, R, m.keep ? h1 : nullptr, m.keep ? h2 : nullptr, y};
+    if (m.bits) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
     mlp_strip_forward(a, s);
     return;
   }
+  const bool hs = m.hstore;
   // one GEMM per layer.  hs (--fp16 update): x / h1 / h2 live in fp16, the weights are rounded while staged, y stays float32 for the loss
-  const bool hs = m.hstore && half;
   auto F = [](const _Float16* q) { return reinterpret_cast<const float*>(q); };
   const float* in[3] = {hs ? F(n.x_h + r0 * n.ldxh) : x, hs ? F(n.h1_h + r0 * H) : h1, hs ? F(n.h2_h + r0 * H) : h2};
   float* out[3] = {hs ? reinterpret_cast<float*>(n.h1_h + r0 * H) : h1, hs ? reinterpret_cast<float*>(n.h2_h + r0 * H) : h2, y};
@@ -194,24 +229,23 @@ static BwdParts bwd_parts_carve(const MlpLayout& L, size_t rows, int passes, flo
 // -- and, from the same operand tiles, the bias gradients' partial column sums -- in P behind the z slices an earlier pass
 // wrote; mlp_backward_segments then lists them for the ordered reduction into grad.  Every reduction runs in a fixed order
 // (same seed -> bitwise identical weights, the property the reference's tests/test_determinism.py checks).
-static void mlp_backward(const MlpNet& n, const float* theta, RowSpan r, const BwdParts& P, BwdSlices& z, hipStream_t s, const MlpMode& m) {
+static void mlp_backward(const MlpNet& n, const float* theta, RowSpan r, const BwdParts& P, BwdSlices& z, hipStream_t s, const MlpPass& m) {
   const MlpLayout& L = n.L;
   const int R = r.rows, half = m.half;
   const size_t H = L.H, r0 = r.first;
   const float* dy = n.dy + r0 * L.Op;
+  const bool hs = m.hstore;
   // hs (--fp16 update with fp16 storage): the same five GEMMs on the fp16 copies (dy and the weights are float32)
-  const bool hs = m.hstore && half;
   auto F = [](const _Float16* q) { return reinterpret_cast<const float*>(q); };
   const float *x = hs ? F(n.x_h + r0 * n.ldxh) : n.x + r0 * n.ldx, *h1 = hs ? F(n.h1_h + r0 * H) : n.h1 + r0 * H, *h2 = hs ? F(n.h2_h + r0 * H) : n.h2 + r0 * H;
   float *dh2 = hs ? reinterpret_cast<float*>(n.dh2_h + r0 * H) : n.dh2 + r0 * H, *dh1 = hs ? reinterpret_cast<float*>(n.dh1_h + r0 * H) : n.dh1 + r0 * H;
   const int ldx = hs ? n.ldxh : n.ldx;
   GemmArgs g{};
-  // (have_dh: a train strip launch has taken the strip launch's place, so neither it nor the GEMMs below compute dh2 / dh1 again.  Only where
-  // the strip path would have made them: float32, a shape the strips take)
-  const bool strip = m.have_dh || (m.strip && !half && strip_shape(L, m.wide));
-  if (strip && !m.have_dh) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
+  // (have_dh: a train strip launch has taken the strip launch's place, so neither it nor the GEMMs below compute dh2 / dh1 again)
+  const bool strip = m.have_dh || m.bwd_strip;
+  if (m.bwd_strip) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
     MlpStripBwd a{theta + L.w2, theta + L.w3, dy, h1, h2, L.O, L.Op, R, dh2, dh1};
-    if (n.bits1) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
+    if (m.bits) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
     mlp_strip_backward(a, s);
   }
   // The skinny weight gradients dW1 / db1 / dW3 / db3: one K-streaming launch behind the activation gradients (wgrad_skinny_kernel; its
@@ -297,7 +331,7 @@ __global__ void gather_kernel(GatherArgs a) {
 extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
   if (const int rc = learner_check(c, (void**)out, c && c->max_rows > 0)) return rc;
   std::unique_ptr<LhwPpo> p(new LhwPpo());
-  p->max_rows = c->max_rows;
+  p->max_rows = c->max_rows; p->sw = read_switches();
   MlpNet &a = p->a, &cr = p->c;
   a.L = mlp_layout(c->obs_dim, c->hidden, c->act_dim);
   cr.L = mlp_layout(c->obs_dim, c->hidden, 1);
@@ -317,32 +351,25 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
   // (the strip kernels' scratch for every shape they take, narrow or wide: whether a wide shape USES it is the switch's business, strip_wide)
   if (strip_shape(a.L, true)) mem.get(&a.wt, mlp_strip_wt_floats(a.L.Dp, a.L.Op));
   if (strip_shape(cr.L, true)) mem.get(&cr.wt, mlp_strip_wt_floats(cr.L.Dp, cr.L.Op));
-  if (a.wt && cr.wt && R % 64 == 0 && !(getenv("LHW_STRIP_BITS") && atoi(getenv("LHW_STRIP_BITS")) == 0)) {
+  if (a.wt && cr.wt && R % 64 == 0 && p->sw.strip_bits) {
     const size_t bw = mlp_strip_bits_words(R);   // per layer: 2 bw words for the actor's 2R rows, bw for the critic's
     mem.get(&a.bits1, 4 * bw); mem.get(&cr.bits1, 2 * bw);
     if (a.bits1 && cr.bits1) { a.bits2 = a.bits1 + 2 * bw; cr.bits2 = cr.bits1 + bw; }
   }
-  p->strip_fused = !(getenv("LHW_STRIP_FUSED") && atoi(getenv("LHW_STRIP_FUSED")) == 0);
   if (a.wt && cr.wt) {
     mem.get(&p->stat_rows, NSTAT * R);
     mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op)));
     mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op));
   }
-  bool ok = !mem.failed() && learner_mirror(*p, c);
-  p->two_streams = !(getenv("LHW_PPO_TWO_STREAMS") && atoi(getenv("LHW_PPO_TWO_STREAMS")) == 0);
-  ok = ok && hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess &&
-       hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&p->ev_head, hipEventDisableTiming) == hipSuccess;
+  const bool ok = !mem.failed() && learner_mirror(*p, c) && hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess &&
+                  hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreateWithFlags(&p->ev_head, hipEventDisableTiming) == hipSuccess;
   if (!ok) return lhw_fail(LHW_ERR_HIP, "PPO workspace allocation failed (max_rows=%d) or bad mirror table", c->max_rows);
   *out = p.release();
   return LHW_OK;
 }
 
-extern "C" int lhw_ppo_destroy(LhwPpo* p) {
-  delete p;   // (~LhwPpo: step graph, side stream, events; then the memory owner)
-  return LHW_OK;
-}
+extern "C" int lhw_ppo_destroy(LhwPpo* p) { delete p; return LHW_OK; }   // (~LhwPpo: step graph, side stream, events; then the memory owner)
 
 extern "C" int lhw_ppo_set_inference_dtype(LhwPpo* p, int fp16) {
   if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
@@ -352,7 +379,7 @@ extern "C" int lhw_ppo_set_inference_dtype(LhwPpo* p, int fp16) {
 
 extern "C" int lhw_ppo_set_update_dtype(LhwPpo* p, int fp16) {
   if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
-  if (fp16 && !p->xb_h && !(getenv("LHW_FP16_STORAGE") && atoi(getenv("LHW_FP16_STORAGE")) == 0)) {
+  if (fp16 && !p->xb_h && p->sw.fp16_storage) {
     // fp16 HBM storage of the minibatch activations (round 6; LHW_FP16_STORAGE=0: float32 storage rounded per GEMM, as through round 5)
     // All or nothing: the handle's pointers are set once all nine blocks exist; a failure frees those obtained and leaves it as it was.
     HIPCHK(hipSetDevice(p->device));
@@ -376,19 +403,26 @@ extern "C" int lhw_ppo_set_update_dtype(LhwPpo* p, int fp16) {
 
 extern "C" int lhw_ppo_debug_set_strip_fused(LhwPpo* p, int32_t on) {
   if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
-  p->strip_fused = on ? 1 : 0;
+  p->sw.strip_fused = on ? 1 : 0;
   return LHW_OK;
 }
 
 extern "C" int lhw_ppo_debug_set_strip_wide(LhwPpo* p, int32_t on) {
   if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
-  p->strip_wide = on ? 1 : 0;
+  p->sw.strip_wide = on ? 1 : 0;
   p->roll_theta = nullptr;   // (an open bracket has the critic's weight copies of the other choice)
   return LHW_OK;
 }
 
-extern "C" int lhw_ppo_debug_last_grad_fused(const LhwPpo* p) { return p ? p->last_grad_fused : LHW_ERR_ARG; }
-
+extern "C" int lhw_ppo_debug_last_grad_fused(const LhwPpo* p) { return p ? p->last_plan.train : LHW_ERR_ARG; }
+// out13: UpdatePlan's eight fields for a minibatch of B rows (imitation != 0: with an imitation term armed), then InferPlan's five
+extern "C" int lhw_ppo_debug_plan(const LhwPpo* p, int32_t B, int32_t imitation, int32_t* out13) {
+  if (!p || !out13 || B <= 0 || B > p->max_rows) return lhw_fail(LHW_ERR_ARG, "bad argument (B = %d, capacity %d)", B, p ? p->max_rows : 0);
+  const UpdatePlan u = update_plan(p, imitation != 0);
+  const InferPlan i = infer_plan(p);
+  memcpy(out13, &u, sizeof u); memcpy(out13 + sizeof u / sizeof(int32_t), &i, sizeof i);
+  return LHW_OK;
+}
 extern "C" int64_t lhw_ppo_param_count(const LhwPpo* p) { return p ? (int64_t)p->n_params : LHW_ERR_ARG; }
 
 // offsets (in floats) of each tensor inside the flat parameter vector:
@@ -396,24 +430,22 @@ extern "C" int64_t lhw_ppo_param_count(const LhwPpo* p) { return p ? (int64_t)p-
 extern "C" int lhw_ppo_layout(const LhwPpo* p, int64_t* out15) {
   if (!p || !out15) return lhw_fail(LHW_ERR_ARG, "null argument");
   const MlpLayout &a = p->a.L, &c = p->c.L;
-  int64_t v[15] = {(int64_t)(p->off_actor + a.w1), (int64_t)(p->off_actor + a.b1), (int64_t)(p->off_actor + a.w2),
-                   (int64_t)(p->off_actor + a.b2), (int64_t)(p->off_actor + a.w3), (int64_t)(p->off_actor + a.b3),
-                   (int64_t)p->off_std,
-                   (int64_t)(p->off_critic + c.w1), (int64_t)(p->off_critic + c.b1), (int64_t)(p->off_critic + c.w2),
-                   (int64_t)(p->off_critic + c.b2), (int64_t)(p->off_critic + c.w3), (int64_t)(p->off_critic + c.b3),
-                   (int64_t)a.Dp, (int64_t)a.Op};
-  memcpy(out15, v, sizeof v);
+  const size_t oa = p->off_actor, oc = p->off_critic;
+  const size_t v[15] = {oa + a.w1, oa + a.b1, oa + a.w2, oa + a.b2, oa + a.w3, oa + a.b3, p->off_std,
+                        oc + c.w1, oc + c.b1, oc + c.w2, oc + c.b2, oc + c.w3, oc + c.b3, (size_t)a.Dp, (size_t)a.Op};
+  for (int i = 0; i < 15; i++) out15[i] = (int64_t)v[i];
   return LHW_OK;
 }
-extern "C" int lhw_ppo_normalize(LhwPpo* p, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
-                                 float* xm, void* stream) {
+extern "C" int lhw_ppo_normalize(LhwPpo* p, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn, float* xm, void* stream) {
   return learner_normalize(p, obs, R, obs_mean, obs_std, xn, xm, stream);
 }
 
+// Rollout inference for N rows (N <= max_rows): normalise, actor + critic forward, sample.
+//   act/logp/mu may be NULL to run the critic only; value may be NULL to run the actor only.
 // ws_row: first row of the forward workspace to use (concurrent calls on different streams must use disjoint row ranges)
-static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int64_t N, const float* obs_mean, const float* obs_std,
-                            uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic, int64_t ws_row, float* mu,
-                            float* act, float* logp, float* value, void* stream) {
+extern "C" int lhw_ppo_forward_at(LhwPpo* p, const float* theta, const float* obs, int64_t N, const float* obs_mean, const float* obs_std,
+                                  uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic, int64_t ws_row, float* mu,
+                                  float* act, float* logp, float* value, void* stream) {
   if (!p || !theta || !obs || N <= 0 || ws_row < 0 || ws_row + N > p->max_rows)
     return lhw_fail(LHW_ERR_ARG, "bad argument (rows [%lld, %lld), capacity %d)", (long long)ws_row, (long long)(ws_row + N), p ? p->max_rows : 0);
   HIPCHK(hipSetDevice(p->device));
@@ -421,10 +453,11 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
   const size_t Dp = p->a.L.Dp, Op = p->a.L.Op, r0 = (size_t)ws_row;
   float *xb = p->xb + r0 * Dp, *ya = p->a.y + r0 * Op, *yc = p->c.y + r0 * 4;
   const RowSpan rows{r0, (int)N};
-  size_t n = (size_t)N * Dp;
+  const InferPlan ip = infer_plan(p);
+  const float *tha = theta + p->off_actor, *thc = theta + p->off_critic;
   float *wta = nullptr, *wtc = nullptr;   // this call's weight copies for the strip kernel
   const bool wt_ready = p->roll_theta != nullptr && p->roll_theta == theta;   // inside a rollout bracket: made once by lhw_ppo_begin_rollout
-  if (strip_mode() >= 2 && p->wt_inf && strip_shape(p->a.L, p->strip_wide) && strip_shape(p->c.L, p->strip_wide)) {
+  if (ip.strips) {
     const size_t fa = mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op), fc = mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op);
     wta = wt_ready ? p->wt_roll : p->wt_inf + (size_t)(ws_row * WT_SLOTS / p->max_rows) * (fa + fc);
     wtc = wta + fa;
@@ -433,13 +466,11 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
   // slab, the three layers, the Gaussian head on the read-out -- instead of normalise / forward / sample launches
   // (the fused staging reads RAW observation rows of width obs_dim: without the normalisation vectors it would have to copy rows
   // of width Dp, which the caller's buffer does not have -- those calls take the three-launch path)
-  const bool fused = act && logp && !mu && !value && wta && obs_mean && obs_std && !p->infer_half;   // (wta: a shape the strips take, see above)
-  if (fused) {
+  if (ip.policy_step && act && logp && !mu && !value && obs_mean && obs_std) {
     const MlpLayout& La = p->a.L;
-    const float* th = theta + p->off_actor;
-    if (!wt_ready) mlp_strip_prepare(th + La.w1, th + La.w2, th + La.w3, La.Dp, La.O, La.Op, wta, s);
-    MlpStripFwd a{wta, th + La.b1, wta + (size_t)La.Dp * La.H, th + La.b2, wta + (size_t)La.Dp * La.H + (size_t)La.H * La.H, th + La.b3,
-                  obs, p->D, La.Dp, La.O, La.Op, (int)N, nullptr, nullptr, ya};
+    if (!wt_ready) strip_prepare(La, tha, wta, s);
+    const StripWeights w = strip_weights(La, wta, tha);
+    MlpStripFwd a{w.w1t, w.b1, w.w2t, w.b2, w.w3t, w.b3, obs, p->D, La.Dp, La.O, La.Op, (int)N, nullptr, nullptr, ya};
     a.in_mean = obs_mean; a.in_std = obs_std; a.in_dim = p->D;
     a.stdv = theta + p->off_std; a.act = act; a.logp = logp;
     a.seed = seed; a.env_base = env_id_base; a.counter = counter; a.deterministic = deterministic;
@@ -447,22 +478,23 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
     HIPCHK(hipGetLastError());
     return LHW_OK;
   }
-  hipLaunchKernelGGL(normalize_kernel, dim3((n + 255) / 256), dim3(256), 0, s, obs, p->D, p->a.L.Dp, (size_t)N, obs_mean, obs_std,
+  hipLaunchKernelGGL(normalize_kernel, dim3(((size_t)N * Dp + 255) / 256), dim3(256), 0, s, obs, p->D, p->a.L.Dp, (size_t)N, obs_mean, obs_std,
                      xb, (float*)nullptr, (const int*)nullptr, (const float*)nullptr);
-  const MlpMode infer{p->infer_half, false, true, wt_ready, true, false, p->strip_wide != 0};
-  MlpNet na = p->a, nc = p->c;   // with this call's weight copies
-  na.wt = wta; nc.wt = wtc;
+  MlpPass m; m.half = ip.half;   // (h1 / h2 are not kept, no mask bits)
   if (act || mu) {
-    mlp_forward(na, theta + p->off_actor, rows, s, infer);
+    if (wta && !wt_ready) strip_prepare(p->a.L, tha, wta, s);
+    m.wt = wta;
+    mlp_forward(p->a, tha, rows, s, m);
     if (mu) HIPCHK(hipMemcpy2DAsync(mu, sizeof(float) * p->A, ya, sizeof(float) * p->a.L.Op, sizeof(float) * p->A, N, hipMemcpyDeviceToDevice, s));
     if (act) {
       if (!logp) return lhw_fail(LHW_ERR_ARG, "logp required with act");
-      hipLaunchKernelGGL(sample_kernel, dim3((N + 7) / 8), dim3(256), 0, s, ya, p->a.L.Op, p->A, (int)N, theta + p->off_std,
-                         seed, env_id_base, counter, deterministic, act, logp);
+      hipLaunchKernelGGL(sample_kernel, dim3((N + 7) / 8), dim3(256), 0, s, ya, p->a.L.Op, p->A, (int)N, theta + p->off_std, seed, env_id_base, counter, deterministic, act, logp);
     }
   }
   if (value) {
-    mlp_forward(nc, theta + p->off_critic, rows, s, infer);
+    if (wtc && !wt_ready) strip_prepare(p->c.L, thc, wtc, s);
+    m.wt = wtc;
+    mlp_forward(p->c, thc, rows, s, m);
     HIPCHK(hipMemcpy2DAsync(value, sizeof(float), yc, sizeof(float) * 4, sizeof(float), N, hipMemcpyDeviceToDevice, s));
   }
   HIPCHK(hipGetLastError());
@@ -472,17 +504,12 @@ static int ppo_forward_impl(LhwPpo* p, const float* theta, const float* obs, int
 extern "C" int lhw_ppo_begin_rollout(LhwPpo* p, const float* theta, void* stream) {
   if (!p || !theta) return lhw_fail(LHW_ERR_ARG, "null argument");
   p->roll_theta = nullptr;
-  // a wide-row actor: its copies serve lhw_env_rollout_history's in-wave step, whatever the handle's own launches run; the critic's are made
-  // only where strip launches will read them (the switch on)
-  const bool wide = rollout_wide_supported(p->a.L);
-  const bool strips = strip_mode() >= 2 && (!wide || p->strip_wide);
-  if (!p->wt_roll || (!wide && !strips)) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
+  const InferPlan ip = infer_plan(p);
+  if (!ip.actor_copies) return LHW_OK;   // per-layer GEMM inference reads theta itself: nothing to prepare
   HIPCHK(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
-  const MlpLayout &La = p->a.L, &Lc = p->c.L;
-  const float *tha = theta + p->off_actor, *thc = theta + p->off_critic;
-  mlp_strip_prepare(tha + La.w1, tha + La.w2, tha + La.w3, La.Dp, La.O, La.Op, p->wt_roll, s);
-  if (strips) mlp_strip_prepare(thc + Lc.w1, thc + Lc.w2, thc + Lc.w3, Lc.Dp, Lc.O, Lc.Op, p->wt_roll + mlp_strip_wt_floats(La.Dp, La.Op), s);
+  strip_prepare(p->a.L, theta + p->off_actor, p->wt_roll, s);   // (the critic's only where forward launches will read them)
+  if (ip.critic_copies) strip_prepare(p->c.L, theta + p->off_critic, p->wt_roll + mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op), s);
   HIPCHK(hipGetLastError());
   p->roll_theta = theta;
   return LHW_OK;
@@ -497,33 +524,21 @@ extern "C" int lhw_ppo_rollout_policy(LhwPpo* p, const float* theta, const float
                                       uint32_t counter, int deterministic, LhwRolloutPolicy* out) {
   if (!p || !theta || !obs_mean || !obs_std || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
   const MlpLayout& La = p->a.L;
-  if (p->roll_theta == nullptr || p->roll_theta != theta || !p->wt_roll)
+  const InferPlan ip = infer_plan(p);
+  if (p->roll_theta != theta || !ip.actor_copies)
     return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_ppo_rollout_policy: no rollout bracket open for this theta (lhw_ppo_begin_rollout)");
-  if (!mlp_strip_supported(La.H, La.Dp, La.O, La.Op) && !rollout_wide_supported(La))
-    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_ppo_rollout_policy: actor with hidden width 256 and a padded observation width <= %d only", LHW_ROLLOUT_HISTORY_MAX_OBS_PAD);
-  const float* th = theta + p->off_actor;
-  const float* wt = p->wt_roll;
-  out->w1t = wt; out->b1 = th + La.b1;
-  out->w2t = wt + (size_t)La.Dp * La.H; out->b2 = th + La.b2;
-  out->w3t = wt + (size_t)La.Dp * La.H + (size_t)La.H * La.H; out->b3 = th + La.b3;
+  const StripWeights w = strip_weights(La, p->wt_roll, theta + p->off_actor);
+  out->w1t = w.w1t; out->b1 = w.b1; out->w2t = w.w2t; out->b2 = w.b2; out->w3t = w.w3t; out->b3 = w.b3;
   out->stdv = theta + p->off_std; out->obs_mean = obs_mean; out->obs_std = obs_std;
   out->obs_dim = p->D; out->obs_pad = La.Dp; out->act_dim = La.O; out->act_pad = La.Op; out->hidden = La.H;
   out->deterministic = deterministic; out->seed = seed; out->counter = counter;
-  out->fp16_operands = p->infer_half ? 1 : 0;
+  out->fp16_operands = ip.half ? 1 : 0;
   return LHW_OK;
 }
 
-// Rollout inference for N rows (N <= max_rows): normalise, actor + critic forward, sample.
-//   act/logp/mu may be NULL to run the critic only; value may be NULL to run the actor only.
-extern "C" int lhw_ppo_forward(LhwPpo* p, const float* theta, const float* obs, int64_t N, const float* obs_mean,
-                               const float* obs_std, uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic,
-                               float* mu, float* act, float* logp, float* value, void* stream) {
-  return ppo_forward_impl(p, theta, obs, N, obs_mean, obs_std, seed, env_id_base, counter, deterministic, 0, mu, act, logp, value, stream);
-}
-extern "C" int lhw_ppo_forward_at(LhwPpo* p, const float* theta, const float* obs, int64_t N, const float* obs_mean,
-                                  const float* obs_std, uint64_t seed, uint32_t env_id_base, uint32_t counter, int deterministic,
-                                  int64_t ws_row, float* mu, float* act, float* logp, float* value, void* stream) {
-  return ppo_forward_impl(p, theta, obs, N, obs_mean, obs_std, seed, env_id_base, counter, deterministic, ws_row, mu, act, logp, value, stream);
+extern "C" int lhw_ppo_forward(LhwPpo* p, const float* theta, const float* obs, int64_t N, const float* obs_mean, const float* obs_std, uint64_t seed,
+                               uint32_t env_id_base, uint32_t counter, int deterministic, float* mu, float* act, float* logp, float* value, void* stream) {
+  return lhw_ppo_forward_at(p, theta, obs, N, obs_mean, obs_std, seed, env_id_base, counter, deterministic, 0, mu, act, logp, value, stream);
 }
 // the spans of the actor's rows one pass covers for a minibatch of B rows in a workspace of R: the mirrored rows start at row R, so they
 // follow the normal ones without a gap when B == R
@@ -533,8 +548,7 @@ static RowSpans actor_spans(int mir, int B, int R) {
   return {{{0, B}, {(size_t)R, B}}, mir ? 2 : 1};
 }
 // gather_kernel's argument for a minibatch, for its launch and for the patch of its captured launch (lhw_ppo_step)
-static GatherArgs gather_args(const LhwPpo* p, const float* xn, const float* xm, const float* act, const float* old_logp, const float* adv, const float* ret,
-                              const int32_t* idx, int32_t B) {
+static GatherArgs gather_args(const LhwPpo* p, const float* xn, const float* xm, const float* act, const float* old_logp, const float* adv, const float* ret, const int32_t* idx, int32_t B) {
   return GatherArgs{idx, B, p->max_rows, p->a.L.Dp, p->A, xn, p->use_mirror ? xm : nullptr, act, old_logp, adv, ret, p->xb, p->mb_act, p->mb_logp, p->mb_adv, p->mb_ret};
 }
 
@@ -550,9 +564,8 @@ extern "C" int lhw_ppo_set_imitation(LhwPpo* p, const float* target, const uint8
 // One minibatch: gather rows idx[0..B) from the iteration's buffers, forward (policy on obs and on mirrored
 // obs, critic), losses, backward.  Gradients are ACCUMULATED into grad (flat, same layout as theta);
 // stats_dev[0..4] += actor_loss, critic_loss, mirror_loss, approx_kl, clip_fraction of this minibatch.
-extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const float* xn, const float* xm, const float* act,
-                            const float* old_logp, const float* adv, const float* ret, const int32_t* idx, int32_t B,
-                            float* stats_dev, void* stream) {
+extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const float* xn, const float* xm, const float* act, const float* old_logp,
+                            const float* adv, const float* ret, const int32_t* idx, int32_t B, float* stats_dev, void* stream) {
   if (!p || !theta || !grad || !xn || !act || !old_logp || !adv || !ret || !idx || !stats_dev) return lhw_fail(LHW_ERR_ARG, "null argument");
   if (B <= 0 || B > p->max_rows) return lhw_fail(LHW_ERR_ARG, "minibatch %d exceeds workspace capacity %d", B, p->max_rows);
   const int mir = p->use_mirror && xm != nullptr;
@@ -561,27 +574,22 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   const MlpNet &na = p->a, &nc = p->c;
   const MlpLayout &La = na.L, &Lc = nc.L;
   const int R = p->max_rows, Dp = La.Dp, Op = La.Op;
-  const float* th_a = theta + p->off_actor;
-  const float* th_c = theta + p->off_critic;
-  const StreamPair sp{s, p->two_streams ? p->side : s, p->ev_fork, p->ev_join};
+  const float *th_a = theta + p->off_actor, *th_c = theta + p->off_critic;
+  const UpdatePlan u = p->last_plan = update_plan(p, p->imit_target != nullptr);
+  const StreamPair sp{s, u.streams == 2 ? p->side : s, p->ev_fork, p->ev_join};
   hipStream_t sc = sp.sc;   // the critic's chain
-  const RowSpans spans = actor_spans(mir, B, R);
-  const RowSpan rows_c{0, B};
+  const RowSpans spans = actor_spans(mir, B, R); const RowSpan rows_c{0, B};
   // ---- prologue
   // the [in][out] weight copies of the forward strips are made on the side stream while the minibatch is gathered (round 6: the two
   // 9 us transposes were the first links of the step's chain)
-  const bool wide_on = p->strip_wide != 0;
-  const bool strips = strip_mode() >= 1 && !p->update_half && na.wt && nc.wt && strip_shape(La, wide_on) && strip_shape(Lc, wide_on);
-  if (strips) {
-    sp.fork();
-    mlp_strip_prepare(th_a + La.w1, th_a + La.w2, th_a + La.w3, La.Dp, La.O, La.Op, na.wt, sc);
-    mlp_strip_prepare(th_c + Lc.w1, th_c + Lc.w2, th_c + Lc.w3, Lc.Dp, Lc.O, Lc.Op, nc.wt, sc);
-  }
+  const int strips = u.train ? 3 : u.fwd_strip;   // the networks whose copies a launch of this step reads
+  if (strips) sp.fork();
+  if (strips & 1) strip_prepare(La, th_a, na.wt, sc);
+  if (strips & 2) strip_prepare(Lc, th_c, nc.wt, sc);
   hipLaunchKernelGGL(gather_kernel, dim3(((size_t)B * Dp + 255) / 256), dim3(256), 0, s, gather_args(p, xn, xm, act, old_logp, adv, ret, idx, B));
   if (strips) sp.join();
   // --fp16 update with fp16 storage: fp16 copies of the gathered rows; every activation the GEMMs exchange stays fp16 in HBM
-  const bool hstore = p->update_half && p->xb_h != nullptr;
-  for (int i = 0; hstore && i < spans.n; i++) {
+  for (int i = 0; u.hstore && i < spans.n; i++) {
     const RowSpan r = spans.v[i];
     const size_t nn = (size_t)r.rows * p->ldxh;
     hipLaunchKernelGGL(rows_to_half_kernel, dim3((nn + 255) / 256), dim3(256), 0, s, p->xb + r.first * Dp, Dp, Dp, (size_t)r.rows, p->xb_h + r.first * p->ldxh, p->ldxh);
@@ -591,30 +599,33 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   BwdSlices za, zc;
   // Train strips: per network ONE launch runs the forward layers, the loss head and the backward layers (mlp_train_strip_kernel) -- no join
   // between the passes, no loss launch, no mask bits; the weight-gradient kernels follow as on the other path.  With mirroring a slab pairs
-  // 32 rows with their twins, whatever B (a ragged last slab has dead rows in both tiles).  Not for an armed imitation term, --fp16, or
-  // shapes the strips reject: those run forward strip (or GEMMs), ppo_loss_kernel, backward.
-  const bool fused = strips && p->strip_fused && !p->imit_target && p->stat_rows && train_strip_shape(La, 0, wide_on) && train_strip_shape(Lc, 1, wide_on);
-  p->last_grad_fused = fused ? 1 : 0;
-  const MlpMode mode{p->update_half, hstore, strip_mode() >= 1, strips, false, fused, wide_on};
+  // 32 rows with their twins, whatever B (a ragged last slab has dead rows in both tiles).  Where the plan has none: forward strip (or GEMMs),
+  // ppo_loss_kernel, backward.
+  const bool fused = u.train != 0;
+  MlpPass ma;
+  ma.half = u.half; ma.hstore = u.hstore; ma.keep = true; ma.bits = u.bits; ma.have_dh = fused;
+  MlpPass mc = ma;
+  ma.wt = u.fwd_strip & 1 ? na.wt : nullptr; ma.bwd_strip = u.bwd_strip & 1;
+  mc.wt = u.fwd_strip & 2 ? nc.wt : nullptr; mc.bwd_strip = u.bwd_strip & 2;
   const int nblk = (B + 255) / 256;
   // fp16 update: the back-propagated gradients are rounded to fp16 per GEMM, and d loss / d output carries 1 / B -- at B = 32768
   // most of it would fall into the fp16 subnormal range.  Loss scaling by a power of two (exact in float32): the read-out
   // gradients are multiplied by 2^ceil(log2 B) by the loss kernel and the weight-gradient totals divided by it in the final ordered reduction.
-  const float lscale = p->update_half ? exp2f(ceilf(log2f((float)B))) : 1.f;
+  const float lscale = u.half ? exp2f(ceilf(log2f((float)B))) : 1.f;
   // ---- forward and loss; on the fused path the critic's backward too (its launches sit between the two train strips' on the side stream)
   if (fused) {
     const LhwPpoHead head{B, p->A, Op, p->mb_act, p->mb_logp, p->mb_adv, p->mb_ret, theta + p->off_std, p->clip, p->mirror_coeff, mir, p->d_act_src,
                           p->d_act_sign, p->learn_std ? p->dstd : (float*)nullptr, nullptr, nullptr, 0.f, 0.f, 1.f};
     auto train = [&](const MlpNet& n, const float* th, int twin0, int critic, hipStream_t st) {
       const MlpLayout& L = n.L;
-      MlpStripTrain t{MlpStripFwd{n.wt, th + L.b1, n.wt + (size_t)L.Dp * L.H, th + L.b2, n.wt + (size_t)L.Dp * L.H + (size_t)L.H * L.H, th + L.b3, p->xb, Dp, L.Dp, L.O, L.Op,
-                                  B, n.h1, n.h2, nullptr},
+      const StripWeights w = strip_weights(L, n.wt, th);
+      MlpStripTrain t{MlpStripFwd{w.w1t, w.b1, w.w2t, w.b2, w.w3t, w.b3, p->xb, Dp, L.Dp, L.O, L.Op, B, n.h1, n.h2, nullptr},
                       th + L.w2, th + L.w3, n.dy, n.dh2, n.dh1, twin0, critic, head, p->stat_rows, R};
       mlp_train_strip(t, st);
     };
     sp.fork();
     train(nc, th_c, 0, 1, sc);
-    mlp_backward(nc, th_c, rows_c, Pc, zc, sc, mode);
+    mlp_backward(nc, th_c, rows_c, Pc, zc, sc, mc);
     train(na, th_a, mir ? R : 0, 0, s);
     // (the step's loss statistics -- logging only -- are summed at the tail of the side stream, off both chains, once the actor's rows are there)
     if (sc != s) { (void)hipEventRecord(p->ev_head, s); (void)hipStreamWaitEvent(sc, p->ev_head, 0); }
@@ -622,8 +633,8 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, sc, p->stats_part, nblk, NSTAT, stats_dev);
   } else {
     sp.fork();
-    mlp_forward(nc, th_c, rows_c, sc, mode);
-    for (int i = 0; i < spans.n; i++) mlp_forward(na, th_a, spans.v[i], s, mode);
+    mlp_forward(nc, th_c, rows_c, sc, mc);
+    for (int i = 0; i < spans.n; i++) mlp_forward(na, th_a, spans.v[i], s, ma);
     sp.join();
     hipLaunchKernelGGL(ppo_loss_kernel, dim3(nblk), dim3(256), 0, s, B, R, p->A, Op, na.y, nc.y, p->mb_act, p->mb_logp,
                        p->mb_adv, p->mb_ret, theta + p->off_std, p->clip, p->mirror_coeff, mir, p->d_act_src, p->d_act_sign, na.dy,
@@ -640,12 +651,11 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
     sp.fork();
     // (the step's loss statistics -- logging only -- are summed at the head of the side stream, off the actor's chain)
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(64), 0, sc, p->stats_part, nblk, NSTAT, stats_dev);
-    mlp_backward(nc, th_c, rows_c, Pc, zc, sc, mode);
+    mlp_backward(nc, th_c, rows_c, Pc, zc, sc, mc);
   }
-  for (int i = 0; i < spans.n; i++) mlp_backward(na, th_a, spans.v[i], Pa, za, s, mode);
+  for (int i = 0; i < spans.n; i++) mlp_backward(na, th_a, spans.v[i], Pa, za, s, ma);
   sp.join();
-  SegList S;
-  S.n = 0; S.scale = 1.f / lscale;
+  SegList S; S.n = 0; S.scale = 1.f / lscale;
   mlp_backward_segments(S, La, grad + p->off_actor, Pa, za);
   mlp_backward_segments(S, Lc, grad + p->off_critic, Pc, zc);
   launch_reduce_segments(S, s);
@@ -653,21 +663,18 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   return LHW_OK;
 }
 
-extern "C" int lhw_ppo_apply(LhwPpo* p, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale,
-                             void* stream) {
+extern "C" int lhw_ppo_apply(LhwPpo* p, float* theta, float* grad, float* adam_m, float* adam_v, int64_t step, float grad_scale, void* stream) {
   if (p) p->roll_theta = nullptr;   // theta changes: the weight copies of an open rollout bracket are stale
   return learner_apply(p, theta, grad, adam_m, adam_v, step, grad_scale, stream);
 }
 extern "C" int lhw_ppo_debug_grad_sqnorms(LhwPpo* p, float* out2_host) { return learner_grad_sqnorms(p, out2_host); }
-// One optimiser step as ONE graph launch (round 6).  lhw_ppo_grad + lhw_ppo_apply are some forty launches on two streams, a dozen of
-// them small (gather, loss, ordered reductions, transposes, clip, Adam: 5-20 us of work each behind a launch gap of the same order);
-// captured once per (buffers, minibatch size, grad_scale) as a hipGraph they replay with one host call and the runtime's graph scheduling
-// between the nodes.  Same kernels, same order, same arithmetic: bitwise the weights of the two-call path (tests/test_iteration_gpu.py,
-// tests/test_optimizer_gpu.py).  What changes from step to step is patched into the executable graph: the minibatch's index pointer
-// (in gather_kernel's argument) and Adam's bias corrections (in adam2_kernel's).  A different grad_scale recaptures: it is also
-// an argument of sumsq2_kernel, whose node is not patched.  Single process only -- with data parallelism the gradient all-reduce sits
-// between the two halves (the Python layer then keeps lhw_ppo_grad / all-reduce / lhw_ppo_apply).  LHW_PPO_GRAPH=0 turns it off (the two
-// calls, eagerly).
+// One optimiser step as ONE graph launch.  lhw_ppo_grad + lhw_ppo_apply are some forty launches on two streams, a dozen of them small (gather,
+// loss, ordered reductions, transposes, clip, Adam: 5-20 us of work each behind a launch gap of the same order); captured once per StepKey as a
+// hipGraph they replay with one host call and the runtime's graph scheduling between the nodes.  Same kernels, same order, same arithmetic: bitwise
+// the weights of the two-call path (tests/test_iteration_gpu.py, tests/test_optimizer_gpu.py).  What changes from step to step is patched into the
+// executable graph: the minibatch's index pointer (in gather_kernel's argument) and Adam's bias corrections (in adam2_kernel's).  A different
+// grad_scale recaptures: it is also an argument of sumsq2_kernel, whose node is not patched.  Single process only -- with data parallelism the gradient
+// all-reduce sits between the two halves (the Python layer then keeps lhw_ppo_grad / all-reduce / lhw_ppo_apply).  LHW_PPO_GRAPH=0: the two calls, eagerly.
 // replaces the argument of a captured launch of a kernel whose one parameter is a by-value struct
 static int patch_kernel_arg(hipGraphExec_t exec, hipGraphNode_t node, void* arg) {
   void* args[1] = {arg};
@@ -677,27 +684,20 @@ static int patch_kernel_arg(hipGraphExec_t exec, hipGraphNode_t node, void* arg)
   HIPCHK(hipGraphExecKernelNodeSetParams(exec, node, &kp));
   return LHW_OK;
 }
-static bool ppo_graph_on() {
-  static const bool on = !(getenv("LHW_PPO_GRAPH") && atoi(getenv("LHW_PPO_GRAPH")) == 0);
-  return on;
-}
 extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m, float* adam_v, const float* xn, const float* xm, const float* act,
                             const float* old_logp, const float* adv, const float* ret, const int32_t* idx, int32_t B, float* stats_dev,
                             int64_t step, float grad_scale, void* stream) {
   if (!p || !theta || !grad || !adam_m || !adam_v || !idx || step <= 0) return lhw_fail(LHW_ERR_ARG, "bad argument");
   hipStream_t s = (hipStream_t)stream;
   // (an armed imitation term is a one-shot argument of the next lhw_ppo_grad: not captured; the legacy default stream cannot be captured)
-  if (!ppo_graph_on() || p->imit_target != nullptr || s == nullptr) {
+  if (!p->sw.graph || p->imit_target != nullptr || s == nullptr) {
     const int rc = lhw_ppo_grad(p, theta, grad, xn, xm, act, old_logp, adv, ret, idx, B, stats_dev, stream);
     return rc ? rc : lhw_ppo_apply(p, theta, grad, adam_m, adam_v, step, grad_scale, stream);
   }
   HIPCHK(hipSetDevice(p->device));
-  const void* key[12] = {theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream};
-  uint32_t gs_key; memcpy(&gs_key, &grad_scale, sizeof gs_key);
-  bool same = p->step_exec != nullptr && p->step_key_b == B && p->step_key_half == p->update_half && p->step_key_fused == p->strip_fused && p->step_key_wide == p->strip_wide &&
-              p->step_key_gs == gs_key;
-  for (int i = 0; same && i < 12; i++) same = p->step_key[i] == key[i];
-  if (!same) {
+  StepKey key{{theta, grad, adam_m, adam_v, xn, xm, act, old_logp, adv, ret, stats_dev, stream}, B, 0, update_plan(p, false)};
+  memcpy(&key.gs, &grad_scale, sizeof key.gs);
+  if (!p->step_exec || !(p->step_key == key)) {
     if (p->step_exec) { (void)hipGraphExecDestroy(p->step_exec); p->step_exec = nullptr; }
     if (p->step_graph) { (void)hipGraphDestroy(p->step_graph); p->step_graph = nullptr; }
     p->node_gather = p->node_adam = nullptr;
@@ -723,8 +723,7 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
     }
     if (!p->node_gather || !p->node_adam) return lhw_fail(LHW_ERR_HIP, "lhw_ppo_step: gather / Adam nodes not found in the captured graph (%zu nodes)", nn);
     HIPCHK(hipGraphInstantiate(&p->step_exec, g, nullptr, nullptr, 0));
-    for (int i = 0; i < 12; i++) p->step_key[i] = key[i];
-    p->step_key_b = B; p->step_key_half = p->update_half; p->step_key_fused = p->strip_fused; p->step_key_wide = p->strip_wide; p->step_key_gs = gs_key;
+    p->step_key = key;
   }
   // patch the two nodes: each kernel's one argument, built by the function that builds it for the launch
   GatherArgs ga = gather_args(p, xn, xm, act, old_logp, adv, ret, idx, B);
@@ -735,4 +734,3 @@ extern "C" int lhw_ppo_step(LhwPpo* p, float* theta, float* grad, float* adam_m,
   HIPCHK(hipGraphLaunch(p->step_exec, s));
   return LHW_OK;
 }
-

@@ -180,6 +180,16 @@ class PpoKernels(_Kernels):
         """1 if the last grad_minibatch / step_minibatch ran the train strip launches, 0 if forward, loss kernel and backward."""
         return int(self._L.lhw_ppo_debug_last_grad_fused(self._h))
 
+    PLAN_FIELDS = ("fp16_operands", "fp16_storage", "fwd_strip", "bwd_strip", "train_strip", "mask_bits", "wide", "streams",
+                   "infer_fp16_operands", "infer_strips", "policy_step", "critic_copies", "actor_copies")
+
+    def plan(self, B=None, imitation=False):
+        """Which kernels the handle's calls launch (lhw_ppo_debug_plan): the plan of a grad_minibatch on B rows (default max_rows), with an
+        imitation term armed or not, then that of ``forward`` and the rollout bracket.  fwd_strip / bwd_strip: 1 actor | 2 critic."""
+        out = (ctypes.c_int32 * len(self.PLAN_FIELDS))()
+        _lib.check(self._L.lhw_ppo_debug_plan(self._h, int(self.max_rows if B is None else B), int(bool(imitation)), out))
+        return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
+
     def set_tensors(self, tensors: dict):
         # theta changes: a rollout bracket opened on the old weights (its [in][out] copies, the resident rollout's actor view) is void
         self.end_rollout()

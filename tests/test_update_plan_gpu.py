@@ -1,0 +1,121 @@
+"""Which kernels a feed-forward handle's calls launch is decided once per call, by one plan (lhw_ppo_debug_plan): the plan a handle reports for
+each setting of its switches, dtypes, shape and row capacity, and -- where a minibatch runs -- lhw_ppo_debug_last_grad_fused agreeing with it.
+Tiny handles (obs 37 -> 40 padded columns, 12 actions, 64 rows unless the case says otherwise); the switches are set in the environment before
+the handle is created, which is when it reads them."""
+import numpy as np
+import pytest
+import torch
+
+from tests.test_optimizer_gpu import _ppo_batch
+
+pytestmark = pytest.mark.gpu
+
+SWITCHES = ("LHW_MLP_STRIP", "LHW_STRIP_BITS", "LHW_STRIP_FUSED", "LHW_STRIP_WIDE", "LHW_PPO_TWO_STREAMS", "LHW_PPO_GRAPH", "LHW_FP16_STORAGE")
+UPDATE = ("fp16_operands", "fp16_storage", "fwd_strip", "bwd_strip", "train_strip", "mask_bits", "wide", "streams")
+INFER = ("infer_fp16_operands", "infer_strips", "policy_step", "critic_copies", "actor_copies")
+BOTH = 3      # fwd_strip / bwd_strip: 1 actor | 2 critic
+
+# the update: train strips / forward strip, loss kernel, backward strip / one GEMM per layer
+U_TRAIN = dict(fp16_operands=0, fp16_storage=0, fwd_strip=0, bwd_strip=0, train_strip=1, mask_bits=0, wide=0, streams=2)
+U_STRIPS = dict(U_TRAIN, fwd_strip=BOTH, bwd_strip=BOTH, train_strip=0, mask_bits=1)
+U_GEMM = dict(U_TRAIN, train_strip=0)
+# forward launches and the rollout bracket: strips and the one-launch policy step, both networks' copies / GEMMs, no bracket
+I_STRIPS = dict(infer_fp16_operands=0, infer_strips=1, policy_step=1, critic_copies=1, actor_copies=1)
+I_GEMM = dict(infer_fp16_operands=0, infer_strips=0, policy_step=0, critic_copies=0, actor_copies=0)
+
+# id: (environment, handle arguments, calls on the new handle, imitation armed, expected update plan, expected inference plan)
+CASES = {
+    "default": ({}, {}, [], False, U_TRAIN, I_STRIPS),
+    "fused-off": ({}, {}, [("fused", 0)], False, U_STRIPS, I_STRIPS),
+    "fused-off-48-rows": ({}, dict(max_rows=48), [("fused", 0)], False, dict(U_STRIPS, mask_bits=0), I_STRIPS),      # capacity not a multiple of 64
+    "bits-off": (dict(LHW_STRIP_BITS="0"), {}, [("fused", 0)], False, dict(U_STRIPS, mask_bits=0), I_STRIPS),
+    "imitation-armed": ({}, {}, [], True, U_STRIPS, I_STRIPS),
+    "update-fp16": ({}, {}, [("update_fp16", 1)], False, dict(U_GEMM, fp16_operands=1, fp16_storage=1), I_STRIPS),
+    "update-fp16-f32-storage": (dict(LHW_FP16_STORAGE="0"), {}, [("update_fp16", 1)], False, dict(U_GEMM, fp16_operands=1), I_STRIPS),
+    "inference-fp16": ({}, {}, [("inference_fp16", 1)], False, U_TRAIN,
+                       dict(I_STRIPS, infer_fp16_operands=1, infer_strips=0, policy_step=0)),      # copies made, the view asks for fp16 operands
+    "mlp-strip-1": (dict(LHW_MLP_STRIP="1"), {}, [], False, U_TRAIN, I_GEMM),
+    "mlp-strip-0": (dict(LHW_MLP_STRIP="0"), {}, [], False, U_GEMM, I_GEMM),
+    "obs-111-wide-off": ({}, dict(obs_dim=111), [], False, U_GEMM, dict(I_GEMM, actor_copies=1)),      # the actor's copies serve the history rollout
+    "obs-111-wide-on": ({}, dict(obs_dim=111), [("wide", 1)], False, dict(U_TRAIN, wide=1), I_STRIPS),
+    "hidden-64": ({}, dict(hidden=64), [], False, U_GEMM, I_GEMM),
+    "one-stream": (dict(LHW_PPO_TWO_STREAMS="0"), {}, [], False, dict(U_TRAIN, streams=1), I_STRIPS),
+}
+
+
+def _handle(monkeypatch, env=None, obs_dim=37, hidden=256, max_rows=64):
+    from learninghumanoidwalking_amd.ppo_kernels import PpoKernels, reference_init
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in (env or {}).items():
+        monkeypatch.setenv(name, value)
+    k = PpoKernels(obs_dim, 12, hidden=hidden, max_rows=max_rows, lr=1e-3)
+    k.set_tensors(reference_init(obs_dim, 12, hidden, 0.223, generator_seed=7))
+    return k
+
+
+def _call(k, what, on):
+    from learninghumanoidwalking_amd import _lib
+    if what == "fused":
+        _lib.check(k._L.lhw_ppo_debug_set_strip_fused(k._h, on))
+    elif what == "wide":
+        _lib.check(k._L.lhw_ppo_debug_set_strip_wide(k._h, on))
+    elif what == "update_fp16":
+        k.set_update_fp16(bool(on))
+    else:
+        k.set_inference_fp16(bool(on))
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_plan_follows_switches_dtypes_shape_and_capacity(case, monkeypatch):
+    env, handle_kw, calls, imitation, update, infer = CASES[case]
+    k = _handle(monkeypatch, env, **handle_kw)
+    for what, on in calls:
+        _call(k, what, on)
+    B = k.max_rows
+    plan = k.plan(B, imitation)
+    print(case, plan)
+    assert {f: plan[f] for f in UPDATE} == update
+    assert {f: plan[f] for f in INFER} == infer
+    # the rollout bracket opens, and has a view to give, exactly where the plan makes the actor's copies
+    k.begin_rollout()
+    view = k.rollout_policy()
+    k.end_rollout()
+    assert (view is not None) == bool(infer["actor_copies"])
+    if view is not None:
+        assert view.fp16_operands == infer["infer_fp16_operands"]
+    # one minibatch: the path that ran is the plan's
+    rs = np.random.default_rng(3)
+    xn, xm, act, logp, adv, ret, idx = _ppo_batch(k, rs, 2 * B, 1, B)
+    imit = None
+    if imitation:
+        mask = torch.tensor(rs.integers(0, 2, size=(B, 12)).astype(np.uint8)).cuda()
+        imit = (0.5, torch.zeros(B, 12, device="cuda"), mask, max(int(mask.sum()), 1))
+    k.grad_minibatch(xn, None, act, logp, adv, ret, idx[0], imitation=imit)
+    torch.cuda.synchronize()
+    assert k.last_grad_fused == update["train_strip"]
+    assert torch.isfinite(k.grad).all() and k.grad.abs().sum() > 0
+    assert k.plan(B) == k.plan(B, False), "the imitation term was armed for one call"
+
+
+def test_a_toggled_switch_recaptures_the_step(monkeypatch):
+    """The captured step's key holds the plan: lhw_ppo_step after lhw_ppo_debug_set_strip_fused(0) runs the other path, and the weights are those of
+    a second handle that made the same calls eagerly."""
+    B = 64
+    graph, eager = _handle(monkeypatch), _handle(monkeypatch)
+    rs = np.random.default_rng(5)
+    stream = torch.cuda.Stream()      # not the legacy default stream: that one cannot be captured
+    with torch.cuda.stream(stream):
+        xn, xm, act, logp, adv, ret, idx = _ppo_batch(graph, rs, 256, 2, B)
+        for t, on in enumerate((1, 0)):
+            for k in (graph, eager):
+                _call(k, "fused", on)
+            graph.step_minibatch(xn, None, act, logp, adv, ret, idx[t])
+            eager.grad_minibatch(xn, None, act, logp, adv, ret, idx[t])
+            eager.apply()
+            stream.synchronize()
+            for k in (graph, eager):
+                assert k.plan(B)["train_strip"] == on and k.last_grad_fused == on, "the step was captured again for the new plan"
+    for name in ("theta", "adam_m", "adam_v"):
+        assert torch.equal(getattr(graph, name), getattr(eager, name)), name
+    assert torch.equal(graph.stats[:6], eager.stats[:6])
