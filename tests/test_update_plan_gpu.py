@@ -43,14 +43,14 @@ CASES = {
 }
 
 
-def _handle(monkeypatch, env=None, obs_dim=37, hidden=256, max_rows=64):
+def _handle(monkeypatch, env=None, obs_dim=37, hidden=256, max_rows=64, act_dim=12, **kw):
     from learninghumanoidwalking_amd.ppo_kernels import PpoKernels, reference_init
     for name in SWITCHES:
         monkeypatch.delenv(name, raising=False)
     for name, value in (env or {}).items():
         monkeypatch.setenv(name, value)
-    k = PpoKernels(obs_dim, 12, hidden=hidden, max_rows=max_rows, lr=1e-3)
-    k.set_tensors(reference_init(obs_dim, 12, hidden, 0.223, generator_seed=7))
+    k = PpoKernels(obs_dim, act_dim, hidden=hidden, max_rows=max_rows, **{"lr": 1e-3, **kw})
+    k.set_tensors(reference_init(obs_dim, act_dim, hidden, 0.223, generator_seed=7))
     return k
 
 
