@@ -401,6 +401,18 @@ int lhw_debug_mlp_strip_forward_bits(int32_t H, int32_t Dp, int32_t O, int32_t O
 int lhw_debug_mlp_strip_backward_bits(int32_t H, int32_t O, int32_t Op, const float* w2, const float* w3, const float* dy, int32_t R,
                                       const float* h1, const float* h2, float* dh2, float* dh1, const uint32_t* bits1, const uint32_t* bits2,
                                       void* stream);
+/* Test hooks for the fp16 strip kernels (csrc/lhw_mlp_strip_h.hip; the --fp16 update and fp16 inference behind lhw_ppo_debug_set_strip_fp16): the
+ * same two passes with fp16 operands on v_mfma_f32_32x32x16_f16, float32 accumulation, the activations between the layers in LDS as fp16 -- bit
+ * for bit three / two lhw_debug_gemm launches in the fp16-operand, fp16-storage modes (wt = 16 + bits).  Weights float32 in torch Linear layout;
+ * the entry makes the kernels' fp16 copies of them in wh_scratch (163840 halves, 16-byte aligned) first.  forward: x is float32 [R][ldx] (x_half = 0: rounded while staged) or fp16 [R][ldx] (x_half != 0; ldx counts halves);
+ * h1_h / h2_h fp16 [R][256], written once (both may be NULL: they never leave LDS); y float32 [R][Op], columns < O written.  backward: dy float32
+ * [R][Op]; h1_h / h2_h the stored fp16 activations (the masks, > 0); dh2_h / dh1_h fp16 [R][256].  fp16 buffers 16-byte aligned.
+ * Shapes: H = 256, Dp <= 64 (a multiple of 4), O <= 32, Op >= O; others return LHW_ERR_UNSUPPORTED with nothing written. */
+int lhw_debug_mlp_strip_forward_h(int32_t H, int32_t Dp, int32_t O, int32_t Op, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* w3, const float* b3, const void* x, int32_t ldx, int32_t x_half, int32_t R,
+                                  void* h1_h, void* h2_h, float* y, void* wh_scratch, void* stream);
+int lhw_debug_mlp_strip_backward_h(int32_t H, int32_t O, int32_t Op, const float* w2, const float* w3, const float* dy, int32_t R,
+                                   const void* h1_h, const void* h2_h, void* dh2_h, void* dh1_h, void* wh_scratch, void* stream);
 /* Test hook for the update's train strip kernel (csrc/lhw_mlp_strip.hip: forward layers, PPO head, backward layers of one network on slabs
  * that stay in LDS): one network's pass over a minibatch of B rows.  critic = 0: the actor (O = act_dim outputs in rows of Op <= 64; act [B][O],
  * old_logp / adv [B], stdv [O]); twin0 > 0 adds the mirror term: rows [twin0, twin0 + B) of x / h1 / h2 / y / dy / dh2 / dh1 are the mirrored
@@ -560,10 +572,19 @@ int lhw_ppo_debug_set_strip_fused(LhwPpo* ppo, int32_t on);
  * they run one GEMM per layer.  Same bits either way: the wide strips compute the GEMM path's chains.  The skinny weight gradients of such
  * shapes stay split-K GEMMs.  Closes an open rollout bracket (lhw_ppo_begin_rollout makes the critic's weight copies for the path chosen). */
 int lhw_ppo_debug_set_strip_wide(LhwPpo* ppo, int32_t on);
+/* debug / A-B: the fp16 strip kernels (csrc/lhw_mlp_strip_h.hip) for narrow shapes (hidden 256, padded observation row <= 64 columns).  on != 0:
+ * a --fp16 update with fp16 storage (lhw_ppo_set_update_dtype; not LHW_FP16_STORAGE=0) runs each network's forward layers as one forward strip
+ * launch and its activation gradients as one backward strip launch (LHW_MLP_STRIP >= 1; the plan reports fwd_strip = bwd_strip = 3, no train
+ * strips, no mask bits; the weight gradients stay split-K fp16 GEMMs), and fp16 inference (lhw_ppo_set_inference_dtype) runs the forward strip in
+ * lhw_ppo_forward[_at] (LHW_MLP_STRIP >= 2; infer_strips = 1; the one-launch policy step stays float32-only).  0 (a new handle): one fp16 GEMM per
+ * layer.  Same bits either way: the strips compute the GEMM path's chains on the same MFMA.  The first call with on != 0 allocates the kernels'
+ * fp16 weight copies (6.5 MB; LHW_ERR_HIP if that fails, the handle unchanged); every call closes an open rollout bracket.  The Python layer
+ * passes LHW_STRIP_FP16 on. */
+int lhw_ppo_debug_set_strip_fp16(LhwPpo* ppo, int32_t on);
 /* test hook: 1 if the last lhw_ppo_grad of this handle (a captured one included) ran the train strip launches, 0 if the three-launch path */
 int lhw_ppo_debug_last_grad_fused(const LhwPpo* ppo);
 /* test hook: which kernels the handle's calls launch, as the handle itself decides it -- once per call, from its switches (read from the LHW_*
- * environment when it was created; the two debug setters above), the update dtype, the network shape and the row capacity.
+ * environment when it was created; the three debug setters above), the update dtype, the network shape and the row capacity.
  * out13[0..8): the plan of an lhw_ppo_grad call on a minibatch of B rows (imitation != 0: with an imitation term armed) -- fp16 operands,
  * fp16 storage, forward strips, backward strips (masks: 1 actor | 2 critic), train strips, mask bits, wide instantiations, streams (1 | 2).
  * out13[8..13): lhw_ppo_forward[_at] and the rollout bracket -- fp16 operands, forward launches run the strips, the one-launch policy step is

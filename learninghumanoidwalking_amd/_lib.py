@@ -283,6 +283,9 @@ def declare(L):
     sig("lhw_debug_mlp_train_strip", [ctypes.POINTER(LhwTrainStripArgs), i32, vp])
     sig("lhw_ppo_debug_set_strip_fused", [vp, i32])
     sig("lhw_ppo_debug_set_strip_wide", [vp, i32])
+    sig("lhw_ppo_debug_set_strip_fp16", [vp, i32])
+    sig("lhw_debug_mlp_strip_forward_h", [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp])
+    sig("lhw_debug_mlp_strip_backward_h", [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_debug_last_grad_fused", [vp])
     sig("lhw_ppo_debug_plan", [vp, i32, i32, ctypes.POINTER(i32)])
     sig("lhw_debug_wgrad_wide", [vp, vp, i32, i32, vp, vp, vp])

@@ -13,6 +13,7 @@
 
 #include "lhw_gemm.h"
 #include "lhw_learner.h"
+#include "lhw_mlp_strip_h.h"
 
 // ------------------------------------------------------------------------------------------- MLP plumbing
 // Internal parameter layout of one 3-layer MLP (in D -> H -> H -> O), all float32:
@@ -42,6 +43,7 @@ static StripWeights strip_weights(const MlpLayout& L, const float* wt, const flo
   const float* w2t = wt + (size_t)L.Dp * L.H;
   return {wt, th + L.b1, w2t, th + L.b2, w2t + (size_t)L.H * L.H, th + L.b3};
 }
+static void strip_h_prepare(const MlpLayout& L, const float* th, _Float16* wh, hipStream_t s) { mlp_strip_h_prepare(th + L.w1, th + L.w2, th + L.w3, L.Dp, L.O, wh, s); }
 static void strip_prepare(const MlpLayout& L, const float* th, float* wt, hipStream_t s) { mlp_strip_prepare(th + L.w1, th + L.w2, th + L.w3, L.Dp, L.O, L.Op, wt, s); }
 // One network as the passes below see it: its layout, its rows of the minibatch workspace, the strip kernels' weight copies and mask
 // bits, and the fp16 copies of the --fp16 update.  Built once by lhw_ppo_create (the fp16 part by lhw_ppo_set_update_dtype).  The actor's
@@ -56,21 +58,24 @@ struct MlpNet {
                                                           // r uses the words from mlp_strip_bits_words(r) on; NULL: max_rows % 64 != 0
   const _Float16* x_h = nullptr; int ldxh = 0;            // fp16 storage: inputs [rows][ldxh], ldxh = Dp rounded up to 8 (16-byte rows), pad columns zero
   _Float16 *h1_h = nullptr, *h2_h = nullptr, *dh2_h = nullptr, *dh1_h = nullptr;   // [rows][H]
+  _Float16* wh = nullptr;                                 // the fp16 strip kernels' weight copies for the update (lhw_ppo_debug_set_strip_fp16 allocates them)
 };
 struct RowSpan { size_t first; int rows; };
 // The handle's switches: every LHW_* variable this file reads, read once, by lhw_ppo_create -- a handle sees the environment it was created
-// in (DESIGN.md section 4.2 has the table).  lhw_ppo_debug_set_strip_fused / _wide write the same record.
+// in (DESIGN.md section 4.2 has the table).  lhw_ppo_debug_set_strip_fused / _wide / _fp16 write the same record.
 struct Switches {
   int mlp_strip;                  // LHW_MLP_STRIP: 0 = per-layer GEMMs everywhere, 1 = LDS-resident strip kernels in the update, 2 = in rollout inference
                                   // as well (default: the rollout and the update then evaluate the networks with the same kernel, bit for bit)
   int strip_bits, strip_fused;    // LHW_STRIP_BITS: ReLU masks go from forward to backward strip as bits; LHW_STRIP_FUSED: train strips where the step allows
   int strip_wide;                 // rows wider than 64 columns (an observation history) take the wide strip instantiations (Python layer: LHW_STRIP_WIDE)
   int two_streams, graph, fp16_storage;   // LHW_PPO_TWO_STREAMS: the update's critic chain on its own stream; LHW_PPO_GRAPH: lhw_ppo_step captures and
-};                                        // replays; LHW_FP16_STORAGE: the --fp16 update keeps its activations as fp16 in HBM (0: rounded per GEMM)
+                                          // replays; LHW_FP16_STORAGE: the --fp16 update keeps its activations as fp16 in HBM (0: rounded per GEMM)
+  int strip_fp16;                 // fp16 operands take the fp16 strip kernels where float32 operands take the narrow strips (Python layer: LHW_STRIP_FP16)
+};
 static Switches read_switches() {
   auto on = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
   return {on("LHW_MLP_STRIP", 2), on("LHW_STRIP_BITS", 1) != 0, on("LHW_STRIP_FUSED", 1) != 0, 0, on("LHW_PPO_TWO_STREAMS", 1) != 0,
-          on("LHW_PPO_GRAPH", 1) != 0, on("LHW_FP16_STORAGE", 1) != 0};
+          on("LHW_PPO_GRAPH", 1) != 0, on("LHW_FP16_STORAGE", 1) != 0, 0};
 }
 // Which kernels one lhw_ppo_grad call launches (update_plan).  The call and the two passes below read it, and the key of a captured step holds
 // it by value: whatever decides a launch is in that key.  fwd_strip / bwd_strip are masks: bit 0 the actor, bit 1 the critic.
@@ -83,15 +88,16 @@ struct UpdatePlan {
 };
 // ... and what lhw_ppo_forward[_at] and the rollout bracket do (infer_plan)
 struct InferPlan {
-  int32_t half, strips, policy_step;     // fp16 operands (per-layer GEMMs); forward launches run the forward strip; the one-launch policy step is available
+  int32_t half, strips, policy_step;     // fp16 operands; forward launches run the forward strip (with half: the fp16 one, else per-layer GEMMs); the one-launch policy step is available
   int32_t critic_copies, actor_copies;   // lhw_ppo_begin_rollout makes the critic's [in][out] copies (forward launches read them); the actor's: the bracket opens
 };
 // How one network's forward or backward pass runs: named fields, filled from the call's plan
 struct MlpPass {
   int half = 0; bool hstore = false;               // as UpdatePlan's
   const float* wt = nullptr;                       // forward: the network's READY [in][out] copies, the forward strip runs; NULL: one GEMM per layer
+  const _Float16* wh = nullptr;                    // with half: the network's READY fp16 copies, the fp16 forward strip runs / the fp16 backward strip reads them
   bool keep = false, bits = false;                 // forward strip: h1 / h2 are kept for a backward pass (else they never leave LDS), their masks as bits too
-  bool bwd_strip = false, have_dh = false;         // backward: dh2 / dh1 by one backward strip launch; they are already there (train strip launch)
+  bool bwd_strip = false, have_dh = false;         // backward: dh2 / dh1 by one backward strip launch (with half: the fp16 one); they are already there (train strip launch)
 };
 // What a captured step was captured for: buffers and stream, minibatch size, the bits of grad_scale, the plan
 struct StepKey {
@@ -113,7 +119,8 @@ struct LhwPpo : LearnerCore {
   float *wt_inf = nullptr;                  // [in][out] weight copies for the strip kernels beside the update's (a.wt, c.wt): WT_SLOTS pairs (actor, critic) for rollout
                                             // inference, one per eighth of the forward workspace, so that concurrent calls (disjoint row ranges, different streams) do not share one
   float *wt_roll = nullptr;                 // ... and the pair made once per rollout by lhw_ppo_begin_rollout (read-only until end_rollout / apply)
-  const float* roll_theta = nullptr;        // theta the wt_roll copies were made from (NULL: no rollout bracket open)
+  _Float16 *wh_inf = nullptr, *wh_roll = nullptr;   // the same two sets for the fp16 forward strip (with the nets' wh: one block, lhw_ppo_debug_set_strip_fp16)
+  const float* roll_theta = nullptr;        // theta the wt_roll (and wh_roll) copies were made from (NULL: no rollout bracket open)
   const float* imit_target = nullptr; const unsigned char* imit_mask = nullptr;   // imitation term of the NEXT lhw_ppo_grad call (lhw_ppo_set_imitation)
   float imit_coeff = 0.f, imit_inv_count = 0.f;
   float *bwd_part = nullptr;   // split-K partials of the weight / bias gradients: actor (two passes), then critic
@@ -147,19 +154,22 @@ static bool rollout_wide_supported(const MlpLayout& L) {
 static bool strip_shape(const MlpLayout& L, bool wide_on) {
   return mlp_strip_supported(L.H, L.Dp, L.O, L.Op) || (wide_on && mlp_strip_wide_supported(L.H, L.Dp, L.O, L.Op));
 }
+static bool strip_h_shape(const MlpLayout& L) { return mlp_strip_h_supported(L.H, L.Dp, L.O, L.Op); }   // the fp16 strip kernels do (narrow only)
 static bool train_strip_shape(const MlpLayout& L, int critic, bool wide_on) {
   return mlp_train_strip_supported(L.H, L.Dp, L.O, L.Op, critic) || (wide_on && mlp_train_strip_wide_supported(L.H, L.Dp, L.O, L.Op, critic));
 }
 // The two plans.  (lhw_ppo_create has allocated what a shape the strips take, narrow or wide, needs: the nets' wt, stat_rows, wt_inf / wt_roll.)  The
-// strips are not for --fp16 or shapes they reject (per network), train strips not for an armed imitation term either: forward strip (or GEMMs), ppo_loss_kernel, backward
+// strips are not for shapes they reject (per network), nor for --fp16 unless the fp16 strips are switched on (fp16 storage, narrow shapes: forward and backward
+// strip, never train strips or mask bits); train strips not for an armed imitation term either: forward strip (or GEMMs), ppo_loss_kernel, backward
 static UpdatePlan update_plan(const LhwPpo* p, bool imitation) {
   const Switches& w = p->sw;
   UpdatePlan u{};
   u.half = p->update_half; u.hstore = u.half && p->xb_h != nullptr;
-  const int nets = w.mlp_strip >= 1 && !u.half ? (strip_shape(p->a.L, w.strip_wide) ? 1 : 0) | (strip_shape(p->c.L, w.strip_wide) ? 2 : 0) : 0;
-  u.train = nets == 3 && w.strip_fused && !imitation && train_strip_shape(p->a.L, 0, w.strip_wide) && train_strip_shape(p->c.L, 1, w.strip_wide);
+  auto takes = [&](const MlpLayout& L) { return u.half ? strip_h_shape(L) : strip_shape(L, w.strip_wide); };
+  const int nets = w.mlp_strip >= 1 && (!u.half || (u.hstore && w.strip_fp16 && p->a.wh)) ? (takes(p->a.L) ? 1 : 0) | (takes(p->c.L) ? 2 : 0) : 0;
+  u.train = nets == 3 && !u.half && w.strip_fused && !imitation && train_strip_shape(p->a.L, 0, w.strip_wide) && train_strip_shape(p->c.L, 1, w.strip_wide);
   u.fwd_strip = u.bwd_strip = u.train ? 0 : nets;
-  u.bits = u.fwd_strip && p->a.bits1 != nullptr;
+  u.bits = u.fwd_strip && !u.half && p->a.bits1 != nullptr;
   u.wide = nets && !strip_shape(p->c.L, false);
   u.streams = w.two_streams ? 2 : 1;
   return u;
@@ -168,7 +178,8 @@ static InferPlan infer_plan(const LhwPpo* p) {
   InferPlan i{};
   i.half = p->infer_half;
   i.critic_copies = p->sw.mlp_strip >= 2 && p->wt_roll && strip_shape(p->a.L, p->sw.strip_wide) && strip_shape(p->c.L, p->sw.strip_wide);
-  i.strips = i.policy_step = i.critic_copies && !i.half;
+  i.policy_step = i.critic_copies && !i.half;
+  i.strips = i.policy_step || (i.critic_copies && p->sw.strip_fp16 && p->a.wh && strip_h_shape(p->a.L) && strip_h_shape(p->c.L));   // (fp16: the fp16 forward strip)
   // (a wide-row actor's copies serve lhw_env_rollout_history's in-wave step, whatever the handle's own launches run)
   i.actor_copies = i.critic_copies || (p->wt_roll && rollout_wide_supported(p->a.L));
   return i;
@@ -188,6 +199,13 @@ static void mlp_forward(const MlpNet& n, const float* theta, RowSpan r, hipStrea
     return;
   }
   const bool hs = m.hstore;
+  if (m.wh) {   // fp16 operands, one launch: the update's fp16 rows (h1 / h2 kept as fp16) or inference's float32 rows (nothing kept)
+    const MlpStripFwdH a{m.wh, theta + L.b1, theta + L.b2, theta + L.b3, hs ? nullptr : x, ldx,
+                         hs ? n.x_h + r0 * n.ldxh : nullptr, n.ldxh, L.Dp, L.O, L.Op, R, hs && m.keep ? n.h1_h + r0 * H : nullptr,
+                         hs && m.keep ? n.h2_h + r0 * H : nullptr, y};
+    mlp_strip_forward_h(a, s);
+    return;
+  }
   // one GEMM per layer.  hs (--fp16 update): x / h1 / h2 live in fp16, the weights are rounded while staged, y stays float32 for the loss
   auto F = [](const _Float16* q) { return reinterpret_cast<const float*>(q); };
   const float* in[3] = {hs ? F(n.x_h + r0 * n.ldxh) : x, hs ? F(n.h1_h + r0 * H) : h1, hs ? F(n.h2_h + r0 * H) : h2};
@@ -243,14 +261,17 @@ static void mlp_backward(const MlpNet& n, const float* theta, RowSpan r, const B
   GemmArgs g{};
   // (have_dh: a train strip launch has taken the strip launch's place, so neither it nor the GEMMs below compute dh2 / dh1 again)
   const bool strip = m.have_dh || m.bwd_strip;
-  if (m.bwd_strip) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
+  if (m.bwd_strip && half) {   // the same launch with fp16 operands, on the fp16 copies (the plan: only with fp16 storage)
+    const MlpStripBwdH a{m.wh, dy, n.h1_h + r0 * H, n.h2_h + r0 * H, L.O, L.Op, R, n.dh2_h + r0 * H, n.dh1_h + r0 * H};
+    mlp_strip_backward_h(a, s);
+  } else if (m.bwd_strip) {   // dh2 = (dy W3) * (h2 > 0) and dh1 = (dh2 W2) * (h1 > 0) in one launch, the dh2 slab staying in LDS
     MlpStripBwd a{theta + L.w2, theta + L.w3, dy, h1, h2, L.O, L.Op, R, dh2, dh1};
     if (m.bits) { a.bits1 = n.bits1 + mlp_strip_bits_words(r0); a.bits2 = n.bits2 + mlp_strip_bits_words(r0); }
     mlp_strip_backward(a, s);
   }
   // The skinny weight gradients dW1 / db1 / dW3 / db3: one K-streaming launch behind the activation gradients (wgrad_skinny_kernel; its
-  // slices are at least KC_SKINNY rows, so they fit the partial regions), or two split-K GEMMs (other widths, fp16 operands)
-  const bool fused_skinny = strip && z.w1 == z.w3 && wgrad_skinny_supported(L.H, L.Dp, L.O, L.Op) && ldx >= L.Dp && !(ldx & 3) && fused_skinny_on();
+  // slices are at least KC_SKINNY rows, so they fit the partial regions; it reads float32), or two split-K GEMMs (other widths, fp16 operands)
+  const bool fused_skinny = strip && !half && z.w1 == z.w3 && wgrad_skinny_supported(L.H, L.Dp, L.O, L.Op) && ldx >= L.Dp && !(ldx & 3) && fused_skinny_on();
   // dW3 [O][H] = dy^T h2 ; db3 = colsum(dy)
   g.A = dy; g.lda = L.Op; g.B = h2; g.ldb = L.H; g.b_half = hs; g.M = L.O; g.N = L.H; g.K = R;
   g.part = P.w3 + (size_t)z.w3 * L.O * L.H; g.colsum = P.b3 + (size_t)z.w3 * L.O; g.k_chunk = KC_SKINNY;
@@ -414,6 +435,20 @@ extern "C" int lhw_ppo_debug_set_strip_wide(LhwPpo* p, int32_t on) {
   return LHW_OK;
 }
 
+extern "C" int lhw_ppo_debug_set_strip_fp16(LhwPpo* p, int32_t on) {
+  if (!p) return lhw_fail(LHW_ERR_ARG, "null ppo");
+  if (on && !p->a.wh && strip_h_shape(p->a.L) && strip_h_shape(p->c.L)) {
+    // the kernels' fp16 weight copies, one block: the update's pair, the rollout bracket's, WT_SLOTS pairs for forward calls outside a bracket
+    HIPCHK(hipSetDevice(p->device));
+    _Float16* wh = p->mem.get_lazy<_Float16>((size_t)(4 + 2 * WT_SLOTS) * MLP_STRIP_H_WH_HALVES, LhwDevMem::RAW);
+    if (!wh) return lhw_fail(LHW_ERR_HIP, "fp16 strip weight copies: allocation failed");
+    p->a.wh = wh; p->c.wh = wh + MLP_STRIP_H_WH_HALVES; p->wh_roll = wh + 2 * MLP_STRIP_H_WH_HALVES; p->wh_inf = wh + 4 * MLP_STRIP_H_WH_HALVES;
+  }
+  p->sw.strip_fp16 = on ? 1 : 0;
+  p->roll_theta = nullptr;   // (an open bracket may not have the fp16 copies)
+  return LHW_OK;
+}
+
 extern "C" int lhw_ppo_debug_last_grad_fused(const LhwPpo* p) { return p ? p->last_plan.train : LHW_ERR_ARG; }
 // out13: UpdatePlan's eight fields for a minibatch of B rows (imitation != 0: with an imitation term armed), then InferPlan's five
 extern "C" int lhw_ppo_debug_plan(const LhwPpo* p, int32_t B, int32_t imitation, int32_t* out13) {
@@ -457,10 +492,14 @@ extern "C" int lhw_ppo_forward_at(LhwPpo* p, const float* theta, const float* ob
   const float *tha = theta + p->off_actor, *thc = theta + p->off_critic;
   float *wta = nullptr, *wtc = nullptr;   // this call's weight copies for the strip kernel
   const bool wt_ready = p->roll_theta != nullptr && p->roll_theta == theta;   // inside a rollout bracket: made once by lhw_ppo_begin_rollout
-  if (ip.strips) {
+  _Float16 *wha = nullptr, *whc = nullptr;   // ... for the fp16 forward strip
+  if (ip.strips && !ip.half) {
     const size_t fa = mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op), fc = mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op);
     wta = wt_ready ? p->wt_roll : p->wt_inf + (size_t)(ws_row * WT_SLOTS / p->max_rows) * (fa + fc);
     wtc = wta + fa;
+  } else if (ip.strips) {
+    wha = wt_ready ? p->wh_roll : p->wh_inf + (size_t)(ws_row * WT_SLOTS / p->max_rows) * 2 * MLP_STRIP_H_WH_HALVES;
+    whc = wha + MLP_STRIP_H_WH_HALVES;
   }
   // the rollout's policy step (actions + log-densities only) as ONE strip launch: observation normalisation on the way into the
   // slab, the three layers, the Gaussian head on the read-out -- instead of normalise / forward / sample launches
@@ -483,7 +522,8 @@ extern "C" int lhw_ppo_forward_at(LhwPpo* p, const float* theta, const float* ob
   MlpPass m; m.half = ip.half;   // (h1 / h2 are not kept, no mask bits)
   if (act || mu) {
     if (wta && !wt_ready) strip_prepare(p->a.L, tha, wta, s);
-    m.wt = wta;
+    if (wha && !wt_ready) strip_h_prepare(p->a.L, tha, wha, s);
+    m.wt = wta; m.wh = wha;
     mlp_forward(p->a, tha, rows, s, m);
     if (mu) HIPCHK(hipMemcpy2DAsync(mu, sizeof(float) * p->A, ya, sizeof(float) * p->a.L.Op, sizeof(float) * p->A, N, hipMemcpyDeviceToDevice, s));
     if (act) {
@@ -493,7 +533,8 @@ extern "C" int lhw_ppo_forward_at(LhwPpo* p, const float* theta, const float* ob
   }
   if (value) {
     if (wtc && !wt_ready) strip_prepare(p->c.L, thc, wtc, s);
-    m.wt = wtc;
+    if (whc && !wt_ready) strip_h_prepare(p->c.L, thc, whc, s);
+    m.wt = wtc; m.wh = whc;
     mlp_forward(p->c, thc, rows, s, m);
     HIPCHK(hipMemcpy2DAsync(value, sizeof(float), yc, sizeof(float) * 4, sizeof(float), N, hipMemcpyDeviceToDevice, s));
   }
@@ -510,6 +551,10 @@ extern "C" int lhw_ppo_begin_rollout(LhwPpo* p, const float* theta, void* stream
   hipStream_t s = (hipStream_t)stream;
   strip_prepare(p->a.L, theta + p->off_actor, p->wt_roll, s);   // (the critic's only where forward launches will read them)
   if (ip.critic_copies) strip_prepare(p->c.L, theta + p->off_critic, p->wt_roll + mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op), s);
+  if (ip.critic_copies && p->sw.strip_fp16 && p->a.wh) {   // the fp16 forward strip's copies of both networks, whichever dtype is selected right now
+    strip_h_prepare(p->a.L, theta + p->off_actor, p->wh_roll, s);
+    strip_h_prepare(p->c.L, theta + p->off_critic, p->wh_roll + MLP_STRIP_H_WH_HALVES, s);
+  }
   HIPCHK(hipGetLastError());
   p->roll_theta = theta;
   return LHW_OK;
@@ -582,10 +627,10 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   // ---- prologue
   // the [in][out] weight copies of the forward strips are made on the side stream while the minibatch is gathered (round 6: the two
   // 9 us transposes were the first links of the step's chain)
-  const int strips = u.train ? 3 : u.fwd_strip;   // the networks whose copies a launch of this step reads
+  const int strips = u.train ? 3 : u.fwd_strip;   // the networks whose copies a launch of this step reads (fp16 operands: the fp16 copies)
   if (strips) sp.fork();
-  if (strips & 1) strip_prepare(La, th_a, na.wt, sc);
-  if (strips & 2) strip_prepare(Lc, th_c, nc.wt, sc);
+  if (strips & 1) { if (u.half) strip_h_prepare(La, th_a, na.wh, sc); else strip_prepare(La, th_a, na.wt, sc); }
+  if (strips & 2) { if (u.half) strip_h_prepare(Lc, th_c, nc.wh, sc); else strip_prepare(Lc, th_c, nc.wt, sc); }
   hipLaunchKernelGGL(gather_kernel, dim3(((size_t)B * Dp + 255) / 256), dim3(256), 0, s, gather_args(p, xn, xm, act, old_logp, adv, ret, idx, B));
   if (strips) sp.join();
   // --fp16 update with fp16 storage: fp16 copies of the gathered rows; every activation the GEMMs exchange stays fp16 in HBM
@@ -605,8 +650,8 @@ extern "C" int lhw_ppo_grad(LhwPpo* p, const float* theta, float* grad, const fl
   MlpPass ma;
   ma.half = u.half; ma.hstore = u.hstore; ma.keep = true; ma.bits = u.bits; ma.have_dh = fused;
   MlpPass mc = ma;
-  ma.wt = u.fwd_strip & 1 ? na.wt : nullptr; ma.bwd_strip = u.bwd_strip & 1;
-  mc.wt = u.fwd_strip & 2 ? nc.wt : nullptr; mc.bwd_strip = u.bwd_strip & 2;
+  ma.wt = !u.half && (u.fwd_strip & 1) ? na.wt : nullptr; ma.wh = u.half && (u.fwd_strip & 1) ? na.wh : nullptr; ma.bwd_strip = u.bwd_strip & 1;
+  mc.wt = !u.half && (u.fwd_strip & 2) ? nc.wt : nullptr; mc.wh = u.half && (u.fwd_strip & 2) ? nc.wh : nullptr; mc.bwd_strip = u.bwd_strip & 2;
   const int nblk = (B + 255) / 256;
   // fp16 update: the back-propagated gradients are rounded to fp16 per GEMM, and d loss / d output carries 1 / B -- at B = 32768
   // most of it would fall into the fp16 subnormal range.  Loss scaling by a power of two (exact in float32): the read-out

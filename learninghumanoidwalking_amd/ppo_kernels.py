@@ -153,6 +153,10 @@ class _Kernels:
 # layer (lhw_ppo_debug_set_strip_wide).  LHW_STRIP_WIDE = 0 | 1 overrides; read once per handle.  Same bits either way; the default follows
 # the project's A/B rule: True only once every run with the strips lies below every run without them.
 STRIP_WIDE_DEFAULT = False
+# fp16 operands (--fp16, --infer-fp16) through the fp16 strip kernels -- one forward and one backward launch per network in the update, one forward
+# launch in inference -- instead of one fp16 GEMM per layer (lhw_ppo_debug_set_strip_fp16; narrow shapes, fp16 storage).  LHW_STRIP_FP16 = 0 | 1
+# overrides; read once per handle.  Same bits either way; the default follows the same A/B rule.
+STRIP_FP16_DEFAULT = False
 
 
 class PpoKernels(_Kernels):
@@ -174,6 +178,12 @@ class PpoKernels(_Kernels):
         self._specs = {**net("a", A), "stds": (o["stds"], A), **net("c", 1)}
         self.strip_wide = os.environ.get("LHW_STRIP_WIDE", "1" if STRIP_WIDE_DEFAULT else "0") != "0"
         _lib.check(self._L.lhw_ppo_debug_set_strip_wide(self._h, int(self.strip_wide)))
+        self.set_strip_fp16(os.environ.get("LHW_STRIP_FP16", "1" if STRIP_FP16_DEFAULT else "0") != "0")
+
+    def set_strip_fp16(self, on=True):
+        """fp16 operands run the fp16 strip kernels where the plan allows (lhw_ppo_debug_set_strip_fp16); same bits as the per-layer fp16 GEMMs."""
+        _lib.check(self._L.lhw_ppo_debug_set_strip_fp16(self._h, int(bool(on))))
+        self.strip_fp16 = bool(on)
 
     @property
     def last_grad_fused(self):

@@ -30,7 +30,7 @@ CASES = {
     "hidden-64": ({}, dict(hidden=64), [], False),
     "one-stream": (dict(LHW_PPO_TWO_STREAMS="0"), {}, [], False),
 }
-SWITCHES = ("LHW_MLP_STRIP", "LHW_STRIP_BITS", "LHW_STRIP_FUSED", "LHW_STRIP_WIDE", "LHW_PPO_TWO_STREAMS", "LHW_PPO_GRAPH", "LHW_FP16_STORAGE")
+SWITCHES = ("LHW_MLP_STRIP", "LHW_STRIP_BITS", "LHW_STRIP_FUSED", "LHW_STRIP_WIDE", "LHW_STRIP_FP16", "LHW_PPO_TWO_STREAMS", "LHW_PPO_GRAPH", "LHW_FP16_STORAGE")
 ACT = 12
 
 
