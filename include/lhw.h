@@ -245,7 +245,9 @@ int lhw_env_rollout_lstm(LhwEnv* env, const LhwRolloutLstmPolicy* policy, int32_
  * every layer one chain over ascending k, the bias behind it); lhw_debug_policy_step is its reference, bit for bit.  tin_dev / stin_dev:
  * nullable, the records of every control step as in lhw_env_rollout_task_inputs / lhw_env_rollout_step_task_inputs.  history_len == 1
  * forwards to those entry points and launches their kernels.  LHW_ERR_UNSUPPORTED wherever lhw_env_rollout refuses, and for a padded row
- * wider than LHW_ROLLOUT_HISTORY_MAX_OBS_PAD (history_len <= 6 on jvrc_walk / jvrc_step, 7 on h1, 5 on h1_walk). */
+ * wider than LHW_ROLLOUT_HISTORY_MAX_OBS_PAD (history_len <= 27 on jvrc_walk, 26 on jvrc_step, 29 on h1, 23 on h1_walk).  Rows wider than
+ * 256 columns pass through the wave's LDS in pieces of 256; the first layer's chain of a hidden unit runs on from piece to piece, so it is
+ * the same chain at every width. */
 int lhw_env_rollout_history(LhwEnv* env, const LhwRolloutPolicy* policy, int32_t first, int32_t count, int32_t T, int32_t history_len,
                             float* obs_dev, float* act_dev, float* logp_dev, float* term_obs_dev, float* rew_dev, uint8_t* done_dev,
                             float* rew_terms_dev, double* tin_dev, double* stin_dev, void* stream);
@@ -440,7 +442,7 @@ int lhw_debug_mlp_train_strip(const LhwTrainStripArgs* args, int32_t fused, void
  * what lhw_ppo_forward_at runs when only act / logp are requested) on R raw observation rows [R][obs_dim], from an actor view.
  * y [R][act_pad] receives the means.  The reference of lhw_env_rollout's in-wave policy step (bitwise).  obs_pad in (64,
  * LHW_ROLLOUT_HISTORY_MAX_OBS_PAD] (an observation history): a plain launch, a workgroup per row and a thread per hidden unit, in the
- * order of the per-layer GEMM forward -- the reference of lhw_env_rollout_history's in-wave step (bitwise). */
+ * order of the per-layer GEMM forward -- the reference of lhw_env_rollout_history's in-wave step (bitwise) at every width it accepts. */
 int lhw_debug_policy_step(const LhwRolloutPolicy* policy, const float* obs, int32_t R, uint32_t env_id_base, uint32_t counter, float* y,
                           float* act, float* logp, void* stream);
 /* Test hook: lhw_rnn_forward's actor step (normalisation -> two LSTM cells -> read-out -> Gaussian head, commit = 1) on R raw observation
@@ -675,14 +677,18 @@ int lhw_rnn_apply(LhwRnn* rnn, float* theta, float* grad, float* adam_m, float* 
 #define LHW_LSTM_SEQ_MIN_HIDDEN 32
 #define LHW_LSTM_SEQ_MAX_HIDDEN 256
 #define LHW_LSTM_SEQ_MAX_OBS_PAD 128
-/* Padded observation width up to which lhw_env_rollout_history evaluates the feed-forward actor inside the stepper's wavefronts (the rows sit in
- * the stepper's LDS stage region beside the two hidden layers: two rows of 256 columns still fit the smallest layout, H1's two envs per wave). */
-#define LHW_ROLLOUT_HISTORY_MAX_OBS_PAD 256
+/* Padded observation width up to which lhw_env_rollout_history evaluates the feed-forward actor inside the stepper's wavefronts.  A validated
+ * limit, not an LDS size: the rows pass through the stepper's LDS stage region 256 columns at a time (two such pieces still fit the smallest
+ * layout beside the two hidden layers, H1's two envs per wave) and the first layer's chains run on from piece to piece, so this is four pieces:
+ * history_len <= 27 on jvrc_walk, 26 on jvrc_step, 29 on h1, 23 on h1_walk.  The rollout buffers grow with the row: obs_dev is
+ * (T + 1) * N * history_len * base floats and term_obs_dev T * N * history_len * base. */
+#define LHW_ROLLOUT_HISTORY_MAX_OBS_PAD 1024
 /* Padded input width up to which the LDS-resident strip kernels of the feed-forward MLPs run (csrc/lhw_mlp_strip.hip; hidden width 256): up to 64
  * columns the input slab shares the activation slab with the partial read-out sums (the narrow instantiations); from 68 to this width -- the rows
  * of an observation history -- the input fills the activation slab [256][rows] by itself and the read-out is one chain over k, the order of the
- * per-layer GEMMs and of lhw_env_rollout_history's in-wave step (the wide instantiations; lhw_ppo_debug_set_strip_wide).  Equal to
- * LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: every env that has the resident history rollout can have the strip update. */
+ * per-layer GEMMs and of lhw_env_rollout_history's in-wave step (the wide instantiations; lhw_ppo_debug_set_strip_wide).  A capacity of
+ * its own, below LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: wider rows have the resident history rollout, and per-layer GEMMs in the update, in rollout
+ * inference and in the critic's values, whatever the switch says. */
 #define LHW_MLP_STRIP_MAX_IN_PAD 256
 /* debug / A-B: on != 0: lhw_rnn_grad runs each network's forward time loop and its BPTT time loop (rl/algos/ppo.py:512-533) as ONE launch each
  * (the whole-sequence strip kernels, the critic's on a side stream) where the shape is covered; 0: four launches per time step and network.

@@ -128,7 +128,7 @@ TASK_INPUT_FIELDS = dict(grf_r=(0, 1), grf_l=(1, 1), contact_z=(2, 1), foot_cont
 
 # include/lhw.h: enum LhwStepTaskInput (the stepping task's second record; offsets into one env's record, length)
 STEP_TASK_INPUT_DIM = 32
-ROLLOUT_HISTORY_MAX_OBS_PAD = 256      # include/lhw.h LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: padded row width of lhw_env_rollout_history's in-wave policy step
+ROLLOUT_HISTORY_MAX_OBS_PAD = 1024     # include/lhw.h LHW_ROLLOUT_HISTORY_MAX_OBS_PAD: widest padded row lhw_env_rollout_history's in-wave policy step takes
 STEP_TASK_INPUT_FIELDS = dict(rsite_xpos=(0, 3), lsite_xpos=(3, 3), target1=(6, 4), target2=(10, 4), reached=(14, 1), frames=(15, 1), t1=(16, 1),
                               t2=(17, 1), nseq=(18, 1), goal=(19, 8), root_xquat=(27, 4))
 

@@ -33,7 +33,8 @@
 #define PKQ 32      // the read-out is summed as PH / PKQ partial products of PKQ k each (SKQ of lhw_mlp_strip.hip)
 #define PXK 64      // capacity of the padded observation row
 #define PO_MAX 16   // action dims the read-out's lane mapping covers (JVRC 12, H1 10): four column groups of four
-#define PXW LHW_ROLLOUT_HISTORY_MAX_OBS_PAD   // capacity of the padded observation row in the history family (policy_step_wide): a multiple of 2 PU
+#define PXC 256     // columns of the padded observation row the history family's step holds in LDS at a time (policy_step_wide's chunk): a multiple of 2 PU
+#define PXW LHW_ROLLOUT_HISTORY_MAX_OBS_PAD   // widest padded observation row the history family takes: a validated limit (PXW / PXC chunks), not an LDS size
 
 // agent-scope loads / stores of the job queue's progress words (a wave on another XCD wrote them: not through this XCD's L2)
 #if defined(__HIP_EMU__)
@@ -224,7 +225,54 @@ __device__ __forceinline__ void policy_step(const LhwRolloutPolicy& q, float* sc
 // as lstm_policy_step's.  LDS: the rows (XK floats each), h1, h2, the Gaussian head's terms -- no partial sums.
 template <int G, int XK> struct PolicyLdsWide { static constexpr int XS = 0, H1 = XS + G * XK, H2 = H1 + G * PH, TM = H2 + G * PH, FLOATS = TM + G * 16; };
 template <int PK, int G> struct PolicyLdsOf { static constexpr int FLOATS = PolicyLds<G>::FLOATS; };
-template <int G> struct PolicyLdsOf<POLICY_HIST, G> { static constexpr int FLOATS = PolicyLdsWide<G, PXW>::FLOATS; };
+template <int G> struct PolicyLdsOf<POLICY_HIST, G> { static constexpr int FLOATS = PolicyLdsWide<G, PXC>::FLOATS; };
+
+// policy_hidden in two parts, so that a unit's chain can run over more than one piece of a row: policy_hidden_acc continues the lane's chains
+// (acc) over rows 0 .. K - 1 of wt and the K values of each xin row -- the load batches, the clamped rows past K and the order of policy_hidden --
+// and policy_hidden_out adds the bias, applies the ReLU and stores.  acc from +0, one policy_hidden_acc, policy_hidden_out IS policy_hidden.
+// A restatement beside it and not its new body: built from these two parts, policy_hidden compiled to other code in the kernels of the plain
+// family (118 instructions more in the two-envs-per-wave kernels, the same resource figures), which are to stay the kernels without the feature.
+template <int G, bool HALF>
+__device__ __forceinline__ void policy_hidden_acc(float (&acc)[G][4], const float* __restrict__ wt, const float* xin, const int ldx, const int K, const int wl) {
+  const float4* w4 = reinterpret_cast<const float4*>(wt) + wl;
+  float4 wa[PU], wb[PU];
+  auto load = [&](float4 (&w)[PU], const int k0) {
+#pragma unroll
+    for (int j = 0; j < PU; j++) w[j] = w4[(size_t)min(k0 + j, K - 1) * (PH / 4)];
+  };
+  auto mul = [&](const float4 (&w)[PU], const int k0) {
+#pragma unroll
+    for (int j = 0; j < PU; j++)
+#pragma unroll
+      for (int r = 0; r < G; r++) {
+        const float x = xin[r * ldx + k0 + j];   // (HALF: rounded when it was stored)
+        const float w0 = HALF ? r16(w[j].x) : w[j].x, w1 = HALF ? r16(w[j].y) : w[j].y, w2 = HALF ? r16(w[j].z) : w[j].z, w3 = HALF ? r16(w[j].w) : w[j].w;
+        acc[r][0] = fmaf(w0, x, acc[r][0]); acc[r][1] = fmaf(w1, x, acc[r][1]);
+        acc[r][2] = fmaf(w2, x, acc[r][2]); acc[r][3] = fmaf(w3, x, acc[r][3]);
+      }
+  };
+  load(wa, 0);
+  for (int k0 = 0; k0 < K; k0 += 2 * PU) {
+    load(wb, k0 + PU);
+    __builtin_amdgcn_sched_barrier(0);
+    mul(wa, k0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(wa, k0 + 2 * PU);
+    __builtin_amdgcn_sched_barrier(0);
+    if (k0 + PU < K) mul(wb, k0 + PU);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+template <int G, bool HALF>
+__device__ __forceinline__ void policy_hidden_out(const float (&acc)[G][4], const float* __restrict__ bias, float* hout, const int wl) {
+  const float4 b = reinterpret_cast<const float4*>(bias)[wl];
+#pragma unroll
+  for (int r = 0; r < G; r++) {
+    float4 v = make_float4(fmaxf(acc[r][0] + b.x, 0.f), fmaxf(acc[r][1] + b.y, 0.f), fmaxf(acc[r][2] + b.z, 0.f), fmaxf(acc[r][3] + b.w, 0.f));
+    if (HALF) v = make_float4(r16(v.x), r16(v.y), r16(v.z), r16(v.w));   // the next layer's operand
+    *reinterpret_cast<float4*>(hout + r * PH + 4 * wl) = v;
+  }
+}
 
 template <int G, bool HALF, int XK>
 __device__ __forceinline__ void policy_step_wide(const LhwRolloutPolicy& q, float* sc, const float* __restrict__ obs_t, float* __restrict__ act_t,
@@ -233,17 +281,30 @@ __device__ __forceinline__ void policy_step_wide(const LhwRolloutPolicy& q, floa
   static_assert(XK % (2 * PU) == 0, "policy_hidden multiplies batches of 2 PU rows");
   const int wl = fresh_wave_lane();
   const int D = q.obs_dim, O = q.act_dim, Op = q.act_pad;
-  const int KP = (q.obs_pad + 2 * PU - 1) & ~(2 * PU - 1);   // (what policy_hidden's batches read: zero beyond the observation width)
   float *xs = sc + PL::XS, *h1 = sc + PL::H1, *h2 = sc + PL::H2, *Tm = sc + PL::TM;
+  // Layer 1 over the row in chunks of XK columns: xs holds one chunk at a time, the lane's chains (acc) run on from chunk to chunk -- for
+  // every width the one ascending-k chain from +0 -- and the bias and the ReLU come behind the last one.  A row of up to XK columns is one trip.
+  float acc[G][4];
 #pragma unroll
   for (int r = 0; r < G; r++)
-    for (int k = wl; k < KP; k += 64) {      // (the expression of normalize_kernel)
-      float v = 0.f;
-      if (k < D && r < nlive) v = (obs_t[(size_t)(env0 + r) * D + k] - q.obs_mean[k]) / q.obs_std[k];
-      xs[r * XK + k] = HALF ? r16(v) : v;
-    }
-  SYNC();
-  policy_hidden<G, HALF>(q.w1t, q.b1, xs, XK, q.obs_pad, h1, wl);
+#pragma unroll
+    for (int c = 0; c < 4; c++) acc[r][c] = 0.f;
+  for (int c0 = 0; c0 < q.obs_pad; c0 += XK) {
+    const int kc = min(XK, q.obs_pad - c0);                // columns of this chunk
+    const int KP = (kc + 2 * PU - 1) & ~(2 * PU - 1);      // (what policy_hidden_acc's batches read: zero beyond the observation width)
+#pragma unroll
+    for (int r = 0; r < G; r++)
+      for (int k = wl; k < KP; k += 64) {      // (the expression of normalize_kernel)
+        const int col = c0 + k;
+        float v = 0.f;
+        if (col < D && r < nlive) v = (obs_t[(size_t)(env0 + r) * D + col] - q.obs_mean[col]) / q.obs_std[col];
+        xs[r * XK + k] = HALF ? r16(v) : v;
+      }
+    SYNC();
+    policy_hidden_acc<G, HALF>(acc, q.w1t + (size_t)c0 * PH, xs, XK, kc, wl);
+    if (c0 + XK < q.obs_pad) SYNC();      // every lane has read this chunk before the next one takes its place
+  }
+  policy_hidden_out<G, HALF>(acc, q.b1, h1, wl);
   SYNC();
   policy_hidden<G, HALF>(q.w2t, q.b2, h1, PH, PH, h2, wl);
   SYNC();
@@ -508,10 +569,10 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 #endif
     } else if constexpr (PK == POLICY_HIST) {
       if (ro.pol.q.fp16_operands)
-        policy_step_wide<G, true, PXW>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+        policy_step_wide<G, true, PXC>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
                                        ro.pol.q.counter + (unsigned)t);
       else
-        policy_step_wide<G, false, PXW>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
+        policy_step_wide<G, false, PXC>(ro.pol.q, reinterpret_cast<float*>(SG[0].U), obs_t, act_t, ro.logp + (size_t)t * N, env0, nlive, p.env_id_base + (unsigned)env0,
                                         ro.pol.q.counter + (unsigned)t);
     } else {
       if (ro.pol.fp16_operands)

@@ -48,7 +48,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SXK 64          // capacity of the narrow input slab (padded input width of the first layer) and of the dy slab (output width of the last)
 #define SXW LHW_MLP_STRIP_MAX_IN_PAD   // capacity of the WIDE input slab (an observation history): the input fills the whole slab, S from row 0
 static_assert(SXK <= SH && SXW <= SH, "the input slab is a part of the activation slab");
-static_assert(SXW == LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, "every row the in-wave policy step of the history rollout takes has the strip update");
+static_assert(SXW <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD, "every row the wide strips take has the resident history rollout (wider rows have it too: per-layer GEMMs)");
 #define SKQ 32          // the read-out is summed as SH / SKQ partial products of SKQ k each, in ascending order, whatever the shape
 
 // Shape of a workgroup: RT row tiles of 32 slab rows, NW waves, each owning CT column tiles of 32 output units (NW * CT * 32 =
@@ -796,7 +796,7 @@ __device__ __forceinline__ float ref_r16(float x) { return (float)(_Float16)x; }
 #endif
 __global__ void __launch_bounds__(SH) mlp_policy_ref_kernel(LhwRolloutPolicy q, const float* __restrict__ obs, int R, unsigned env_base, unsigned counter,
                                                             float* __restrict__ y, float* __restrict__ act, float* __restrict__ logp) {
-  __shared__ float xs[LHW_ROLLOUT_HISTORY_MAX_OBS_PAD], h1[SH], h2[SH], terms[32];
+  __shared__ float xs[LHW_ROLLOUT_HISTORY_MAX_OBS_PAD], h1[SH], h2[SH], terms[32];   // (the whole row, at every width the launcher accepts: 6 KB with h1 / h2)
   LHW_LDS_POISON(xs);
   LHW_LDS_POISON(h1);
   LHW_LDS_POISON(h2);

@@ -146,7 +146,8 @@ struct LhwPpo : LearnerCore {
 #define WT_SLOTS 8
 // An actor whose padded observation row is wider than the narrow strips' 64 columns (an observation history) but within the in-wave policy step
 // of lhw_env_rollout_history, which reads [in][out] weight copies (LhwPpo::wt_roll) whatever path the handle's own launches take.  Stated from
-// the shape alone; the same shapes as the wide strip instantiations (LHW_MLP_STRIP_MAX_IN_PAD == LHW_ROLLOUT_HISTORY_MAX_OBS_PAD)
+// the shape alone.  More shapes than the wide strip instantiations take (LHW_MLP_STRIP_MAX_IN_PAD < LHW_ROLLOUT_HISTORY_MAX_OBS_PAD): past the strips'
+// capacity the handle's own launches are per-layer GEMMs whatever the switch says, and only the actor's copy is made
 static bool rollout_wide_supported(const MlpLayout& L) {
   return L.H == 256 && L.Dp > 64 && L.Dp <= LHW_ROLLOUT_HISTORY_MAX_OBS_PAD && (L.Dp & 3) == 0 && L.O > 0 && L.O <= 32 && L.Op >= L.O;
 }
@@ -381,6 +382,8 @@ extern "C" int lhw_ppo_create(const LhwPpoConfig* c, LhwPpo** out) {
     mem.get(&p->stat_rows, NSTAT * R);
     mem.get(&p->wt_inf, WT_SLOTS * (mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op)));
     mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op) + mlp_strip_wt_floats(p->c.L.Dp, p->c.L.Op));
+  } else if (rollout_wide_supported(a.L)) {   // rows past the strips' capacity: the actor's copy for the in-wave step, nothing else reads one
+    mem.get(&p->wt_roll, mlp_strip_wt_floats(p->a.L.Dp, p->a.L.Op));
   }
   const bool ok = !mem.failed() && learner_mirror(*p, c) && hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess &&

@@ -248,6 +248,8 @@ class Rollout(_RolloutStorage):
         # already backfill each other's tails).
         # An env with an observation history goes the same way (lhw_env_rollout_history): jvrc_walk @ 4096 with obs_history_len 3, sampling
         # 0.47 -> 0.31 s per iteration, resident's mean below every launch-per-step iteration (profiles/r09_history_rollout_ab.txt).
+        # Rows past 256 padded columns (up to 1024: the in-wave step takes them in chunks) too: obs_history_len 12, 448 columns, 0.49 - 0.50 ->
+        # 0.32 s, by the same rule (profiles/r16_history_long_ab.txt) -- so nothing here asks for the row's width.
         mode = self._rollout_mode()
         if mode not in ("auto", "resident"):
             return False

@@ -1,0 +1,152 @@
+"""The resident rollout of an env with a LONG observation history (lhw_env_rollout_history with padded rows past 256 columns) on the
+SIMT emulator.  The in-wave policy step holds 256 columns of a row in LDS at a time and carries the first layer's chains from one such
+chunk to the next, so for every width a hidden unit's sum is still the one fmaf chain over ascending k from +0 that the reference launch
+computes.  Against a loop of { lhw_debug_policy_step on the H x base wide rows ; env.step ; the history rule in numpy }: every buffer
+BITWISE the same -- observations, actions, log-densities, rewards, done flags, the terminal rows where an episode ended -- and the env
+state afterwards.  N = 3 throughout: one two-env wavefront and one half-filled one.  The widths are the ones at which the chunk loop
+takes another shape: a second chunk of four columns (260), exactly two full chunks (508 -> 512 as the batches read it), a third chunk of
+eight columns (520), and the capacity (1000 of 1024).  CPU twin of tests/test_rollout_history_long_gpu.py."""
+import numpy as np
+import pytest
+
+from tests import emu
+from tests.test_rollout_history import UNSUPPORTED, _first_full, _reference, _resident, _same, _same_state
+from tests.test_rollout_resident import NumpyActor, _fallen_states
+
+N = 3
+
+
+def _twins(spec, seed, max_traj_len):
+    return [emu.make_emulated(spec, N, seed=seed, max_traj_len=max_traj_len) for _ in range(2)]
+
+
+def test_second_chunk_of_four_columns_with_a_truncation_inside():
+    """jvrc_walk, H = 7: 259 -> 260 columns, the smallest row with a second chunk.  Episodes are truncated at 3 control steps of 5: the
+    history is zero-filled inside the rollout, and the terminal rows keep theirs"""
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    spec = JvrcWalkSpec()
+    T, H = 5, 7
+    envs = _twins(spec, 3, 3)
+    pol = NumpyActor(H * 37, 12, seed=5, scale=2.0)
+    assert pol.view.obs_pad == 260
+    obs0 = [_first_full(e.reset(), H) for e in envs]
+    a = _reference(envs[0], pol, T, obs0[0], H)
+    b = _resident(envs[1], pol, T, obs0[1], H)
+    _same(a, b)
+    assert (a["done"] & 2).any(), "no truncation / auto-reset inside the rollout"
+    for t in range(T):
+        np.testing.assert_array_equal((b["obs"][t + 1][:, 37:] == 0).all(axis=1), b["done"][t] != 0)
+        assert not np.signbit(b["obs"][t + 1][b["done"][t] != 0][:, 37:]).any()      # +0
+    ended = b["done"] != 0
+    assert b["tob"][ended][:, 37:74].any(), "a terminal row lost the history its episode ended with"
+    _same_state(*envs)
+    assert envs[0].pop_episode_stats() == envs[1].pop_episode_stats()
+
+
+def test_two_full_chunks_one_wave_per_group_and_through_the_job_queue(monkeypatch):
+    """jvrc_step (one env per wave), H = 13: 507 -> 508 columns, which the step's batches of 16 read as exactly two chunks of 256"""
+    from learninghumanoidwalking_amd.envs.jvrc_step import JvrcStepSpec
+    spec = JvrcStepSpec()
+    T, H = 3, 13
+    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=2) for _ in range(3)]
+    pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
+    assert pol.view.obs_pad == 508
+    obs0 = [_first_full(e.reset(), H) for e in envs]
+    a = _reference(envs[0], pol, T, obs0[0], H)
+    L = emu.lib()
+    monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "0")      # one wave per group whatever the batch
+    b = _resident(envs[1], pol, T, obs0[1], H)
+    assert L.lhw_env_last_rollout_queued(envs[1]._h) == 0
+    monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "2")      # a chunk of control steps that does not divide T
+    monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")      # one resident wave drains every (group, chunk) job
+    c = _resident(envs[2], pol, T, obs0[2], H)
+    assert L.lhw_env_last_rollout_queued(envs[2]._h) == 1
+    _same(a, b)
+    _same(a, c)
+    assert (a["done"] != 0).any()
+    _same_state(envs[0], envs[1])
+    _same_state(envs[0], envs[2])
+
+
+@pytest.mark.parametrize("half", [0, 1])
+def test_three_chunks_the_last_eight_columns_wide(half):
+    """jvrc_walk, H = 14: 518 -> 520 columns, with float32 and with fp16 operands; the history is full before the first step"""
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    spec = JvrcWalkSpec()
+    T, H = 2, 14
+    envs = _twins(spec, 7, 0)
+    pol = NumpyActor(H * 37, 12, seed=13, scale=1.5)
+    assert pol.view.obs_pad == 520
+    pol.view.fp16_operands = half
+    full = [_first_full(e.reset(), H) for e in envs]
+    full[0][:, 37:] = full[1][:, 37:] = np.random.default_rng(3).normal(size=(N, (H - 1) * 37)).astype(np.float32)
+    _same(_reference(envs[0], pol, T, full[0], H), _resident(envs[1], pol, T, full[1], H))
+    _same_state(*envs)
+
+
+def test_in_wave_rerun_of_an_overflowing_env_with_a_long_row():
+    """envs 0 and 2 lie on the floor with more than the two-envs-per-wave layout's 8 contacts: the wave repeats their control step with the
+    one-env-per-wave layout, re-interpreting the LDS the policy step's chunks went through, and shifts the rows afterwards"""
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    spec = JvrcWalkSpec()
+    T, H = 3, 7
+    envs = _twins(spec, 11, 50)
+    pol = NumpyActor(H * 37, 12, seed=8)
+    q, v = _fallen_states(spec, 4, seed=21)
+    q, v = q[[0, 1, 3]], v[[0, 1, 3]]      # (the fallen poses: one in the full wavefront, one in the half-filled one)
+    for e in envs:
+        e.reset()
+        e.set_state(q, v)
+    obs0 = _first_full(envs[0].obs, H)      # (the observation still describes the reset pose: the same stale input for both paths)
+    a = _reference(envs[0], pol, T, obs0, H)
+    b = _resident(envs[1], pol, T, obs0, H)
+    _same(a, b)
+    ra, rb = envs[0].pop_rerun_count(), envs[1].pop_rerun_count()
+    assert ra > 0 and ra == rb, (ra, rb)
+    assert envs[0].pop_fault_stats() == envs[1].pop_fault_stats() == (0, 0)
+    _same_state(*envs)
+
+
+def test_sub_range_with_a_long_row_leaves_env_0_alone():
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    spec = JvrcWalkSpec()
+    T, H = 2, 7
+    envs = _twins(spec, 4, 50)
+    pol = NumpyActor(H * 37, 12, seed=6, deterministic=True)
+    obs0 = [_first_full(e.reset(), H) for e in envs]
+    before = [x.copy() for x in envs[1].get_state()]
+    a = _reference(envs[0], pol, T, obs0[0], H)
+    b = _resident(envs[1], pol, T, obs0[1], H, first=1, count=2)      # envs 1, 2: the range starts inside a wavefront pair
+    _same(a, b, rows=slice(1, 3))
+    for k in ("act", "logp", "tob", "rew", "done"):
+        assert not b[k][:, 0].any(), k
+    assert not b["obs"][1:, 0].any()
+    np.testing.assert_array_equal(b["obs"][0], obs0[1])
+    after = envs[1].get_state()
+    for x, y, z in zip(before, after, envs[0].get_state()):
+        np.testing.assert_array_equal(x[0], y[0])      # env 0's record: where the reset left it
+        np.testing.assert_array_equal(y[1:], z[1:])
+        assert not np.array_equal(y[0], z[0])
+
+
+def test_capacity():
+    """jvrc_walk: H = 27 (999 -> 1000 columns, four chunks) is the reference launch bit for bit; H = 28 (1036 columns) is refused and
+    nothing is written"""
+    from learninghumanoidwalking_amd import _lib as product
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    spec = JvrcWalkSpec()
+    assert product.ROLLOUT_HISTORY_MAX_OBS_PAD == 1024
+    H = 27
+    envs = _twins(spec, 6, 0)
+    pol = NumpyActor(H * 37, 12, seed=1, scale=1.5)
+    assert pol.view.obs_pad == 1000
+    full = [_first_full(e.reset(), H) for e in envs]
+    full[0][:, 37:] = full[1][:, 37:] = np.random.default_rng(4).normal(size=(N, (H - 1) * 37)).astype(np.float32)
+    _same(_reference(envs[0], pol, 1, full[0], H), _resident(envs[1], pol, 1, full[1], H))
+    _same_state(*envs)
+    env = envs[1]
+    b = _resident(env, NumpyActor((H + 1) * 37, 12, seed=1), 1, _first_full(env.obs, H + 1), H + 1, expect=UNSUPPORTED)
+    for k in ("act", "logp", "tob", "rew", "done"):
+        assert not b[k].any(), k
+    assert not b["obs"][1:].any()
+    _same_state(*envs)
