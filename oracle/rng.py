@@ -12,7 +12,7 @@ def splitmix64(x: int) -> int:
 
 
 def bits(seed: int, env: int, stream: int, counter: int, slot: int) -> int:
-    k = splitmix64((seed ^ (0xD1342543DE82EF95 * (env + 1))) & _M)
+    k = splitmix64((seed ^ (0xD1342543DE82EF95 * ((env + 1) & 0xFFFFFFFF))) & _M)      # (the header forms env + 1 in uint32_t)
     return splitmix64(k ^ (stream << 56) ^ (counter << 16) ^ slot)
 
 
