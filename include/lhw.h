@@ -352,6 +352,20 @@ int lhw_env_enable_term_stats(LhwEnv* env, int enable);
  * finished-episode sums only -- episodes still running keep their partial sums): term_sum [lhw_env_num_reward_terms] = sum over the finished episodes of the episode's sum of each
  * term, in the reference's dict order (the order of rew_terms_dev); episodes = terminated + truncated.  LHW_ERR_ARG while disabled. */
 int lhw_env_pop_term_stats(LhwEnv* env, double* term_sum, int64_t* episodes, int64_t* terminated, int64_t* truncated);
+/* Task shaping: the leading weight of every reward term and the termination bounds of the fused humanoid tasks, which the reference
+ * keeps as literals in tasks/walking_task.py, stepping_task.py and standing_task.py (calc_reward / done).  An env starts with the
+ * reference's values; the setter replaces them for the whole batch from the next launch on, in every way a control step is executed
+ * (launch per step, resident rollouts of every policy kind), with rew_terms and the per-term statistics reporting the weighted terms.
+ * term_weights [n_weights = lhw_env_num_reward_terms], in the order of rew_terms_dev; finite, negative allowed (a penalty).
+ * term_limits [n_limits = LHW_TERM_LIMIT_COUNT]: walking / standing terminate on root z < [0] or root z > [1]; the stepping task on
+ * (root z - lower foot site z) < [0], and its [1] must be +inf.  No NaN, [0] < [1]; -inf / +inf switch a bound off.  The inner
+ * constants of the terms and the self-collision rule are not settings.  HOST pointers; either may be NULL, which leaves that half as it
+ * is.  Synchronises the device (as lhw_env_set_state).  Episodes in flight continue under the new values: their return, and their
+ * running per-term sums, simply carry on -- a curriculum that changes weights between iterations mixes both in the episodes that span
+ * the change.  LHW_ERR_ARG (nothing changed) for a wrong count or value, LHW_ERR_UNSUPPORTED for cartpole. */
+#define LHW_TERM_LIMIT_COUNT 2   /* [0] lower bound, [1] upper bound (stepping task: must be +inf, it has none) */
+int lhw_env_set_task_shaping(LhwEnv* env, const double* term_weights, int32_t n_weights, const double* term_limits, int32_t n_limits);
+int lhw_env_get_task_shaping(const LhwEnv* env, double* term_weights /*[lhw_env_num_reward_terms]*/, double* term_limits /*[2]*/);
 /* Fault counters since the last call (host pointers, synchronous, resets them): control steps in which contacts were
  * dropped because more than the compiled-in cap were active (16 per env; the stepping task, whose feet rest on the floor AND on
  * the terrain boxes under them, merges identical contacts and holds 192 found / 64 distinct ones per sub-step), and control steps in which an env's state became

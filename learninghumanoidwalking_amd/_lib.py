@@ -37,6 +37,37 @@ class LhwEnvConfig(ctypes.Structure):
 
 TASK_CARTPOLE, TASK_JVRC_WALK, TASK_H1_STAND, TASK_JVRC_STEP, TASK_H1_WALK = 0, 1, 2, 3, 4      # include/lhw.h: LhwEnvConfig.task
 
+# The reward dictionary of each task in the reference's dict order -- the order of rew_terms, of lhw_env_pop_term_stats and of
+# lhw_env_set_task_shaping (cartpole_env.py:182-187, walking_task.py:131-146, standing_task.py:99-106, stepping_task.py:109-122)
+_WALK_TERMS = ("foot_frc_score", "foot_vel_score", "root_accel", "height_error", "com_vel_error", "yaw_vel_error", "upper_body_reward",
+               "posture_error", "torque_penalty", "action_penalty")
+REWARD_TERMS = {TASK_CARTPOLE: ("upright", "center", "velocity", "action"), TASK_JVRC_WALK: _WALK_TERMS, TASK_H1_WALK: _WALK_TERMS,
+                TASK_H1_STAND: ("com_vel_error", "yaw_vel_error", "height", "upperbody", "joint_torque_reward", "posture"),
+                TASK_JVRC_STEP: ("foot_frc_score", "foot_vel_score", "orient_cost", "height_error", "step_reward", "upper_body_reward")}
+# Task shaping an env starts with -- the reference's literals, as humanoid_create fills them (lhw_env_get_task_shaping on a fresh env
+# returns these; tests/test_task_shaping.py holds the two tables together): term weights in REWARD_TERMS order, and the termination
+# bounds (lo, hi) on the root height (stepping task: on the root height above the lower foot site, no upper bound)
+_WALK_WEIGHTS = (0.225, 0.225, 0.050, 0.050, 0.150, 0.150, 0.050, 0.050, 0.025, 0.025)
+DEFAULT_REWARD_WEIGHTS = {TASK_JVRC_WALK: _WALK_WEIGHTS, TASK_H1_WALK: _WALK_WEIGHTS, TASK_H1_STAND: (0.3, 0.3, 0.1, 0.1, 0.1, 0.1),
+                          TASK_JVRC_STEP: (0.150, 0.150, 0.050, 0.050, 0.450, 0.050)}
+DEFAULT_TERMINATION = {TASK_JVRC_WALK: (0.6, 1.4), TASK_H1_WALK: (0.6, 1.4), TASK_H1_STAND: (0.9, 1.4), TASK_JVRC_STEP: (0.6, float("inf"))}
+
+
+def shaping_weights(task, reward_weights, current):
+    """Term weights in REWARD_TERMS[task] order from `reward_weights` -- a dict by term name (partial: the other terms keep `current`) or a
+    full sequence.  An unknown name raises KeyError naming the valid ones."""
+    names = REWARD_TERMS[task]
+    if isinstance(reward_weights, dict):
+        unknown = [k for k in reward_weights if k not in names]
+        if unknown:
+            raise KeyError(f"unknown reward terms {sorted(unknown)}: this task's terms are {list(names)}")
+        w = [float(reward_weights.get(k, c)) for k, c in zip(names, current)]
+    else:
+        w = [float(x) for x in reward_weights]
+        if len(w) != len(names):
+            raise ValueError(f"{len(w)} reward weights for the {len(names)} terms {list(names)}")
+    return np.array(w, dtype=np.float64)
+
 
 def env_config(task, n_envs, *, frame_skip, kp, kd, seed=0, device=0, max_traj_len=0, env_id_base=0, action_smoothing=1.0,
                nominal_qpos=None, action_offset=None, task_params=None, task_iparams=None, clock_lut=None, init_noise=0.0,
@@ -264,6 +295,8 @@ def declare(L):
     sig("lhw_env_pop_episode_stats", [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)])
     sig("lhw_env_enable_term_stats", [vp, i32])
     sig("lhw_env_pop_term_stats", [vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)])
+    sig("lhw_env_set_task_shaping", [vp, vp, i32, vp, i32])
+    sig("lhw_env_get_task_shaping", [vp, vp, vp])
     sig("lhw_env_set_iteration", [vp, i64])
     sig("lhw_env_pop_fault_stats", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_pop_rerun_count", [vp, ctypes.POINTER(i64)])

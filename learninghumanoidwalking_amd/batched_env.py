@@ -12,17 +12,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import TASK_CARTPOLE, TASK_H1_STAND, TASK_H1_WALK, TASK_JVRC_STEP, TASK_JVRC_WALK  # noqa: F401
+from ._lib import REWARD_TERMS, TASK_CARTPOLE, TASK_H1_STAND, TASK_H1_WALK, TASK_JVRC_STEP, TASK_JVRC_WALK  # noqa: F401
 from .model import Model
 
 DONE_TERMINATED, DONE_TRUNCATED = 1, 2
-# The reward dictionary of each task in the reference's dict order -- the order of rew_terms and of lhw_env_pop_term_stats
-# (cartpole_env.py:182-187, walking_task.py:131-146, standing_task.py:99-106, stepping_task.py:109-122)
-_WALK_TERMS = ("foot_frc_score", "foot_vel_score", "root_accel", "height_error", "com_vel_error", "yaw_vel_error", "upper_body_reward",
-               "posture_error", "torque_penalty", "action_penalty")
-REWARD_TERMS = {TASK_CARTPOLE: ("upright", "center", "velocity", "action"), TASK_JVRC_WALK: _WALK_TERMS, TASK_H1_WALK: _WALK_TERMS,
-                TASK_H1_STAND: ("com_vel_error", "yaw_vel_error", "height", "upperbody", "joint_torque_reward", "posture"),
-                TASK_JVRC_STEP: ("foot_frc_score", "foot_vel_score", "orient_cost", "height_error", "step_reward", "upper_body_reward")}
 
 
 def term_stats_dict(term_sum, terminated: int, truncated: int, names) -> dict:
@@ -249,6 +242,27 @@ class BatchedEnv:
         qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(self.n_envs, self.nq)
         qvel = np.ascontiguousarray(qvel, dtype=np.float64).reshape(self.n_envs, self.nv)
         _lib.check(self._L.lhw_env_set_state(self._h, qpos.ctypes.data, qvel.ctypes.data))
+
+    def task_shaping(self):
+        """({term name: weight} in the order of rew_terms, (lo, hi)): the reward-term weights and termination bounds this env's kernels
+        apply, read back from the library (lhw_env_get_task_shaping; humanoid tasks only)."""
+        w, lim = np.zeros(self.n_terms), np.zeros(2)
+        _lib.check(self._L.lhw_env_get_task_shaping(self._h, w.ctypes.data, lim.ctypes.data))
+        return dict(zip(REWARD_TERMS[self.task], w.tolist())), (float(lim[0]), float(lim[1]))
+
+    def set_task_shaping(self, reward_weights=None, termination=None):
+        """Reward-term weights and / or termination bounds of the fused task, for the whole batch from the next launch on
+        (lhw_env_set_task_shaping: synchronises the device; episodes in flight carry on under the new values -- a reward curriculum may
+        call this between iterations).  `reward_weights`: a dict by the names of REWARD_TERMS[task] (partial: the other terms keep their
+        current weight; an unknown name raises KeyError) or a full sequence in that order.  `termination`: (lo, hi) on the root height
+        (stepping task: on the root height above the lower foot site, hi must stay +inf); +-inf switch a bound off."""
+        w = lim = None
+        if reward_weights is not None:
+            w = _lib.shaping_weights(self.task, reward_weights, self.task_shaping()[0].values())
+        if termination is not None:
+            lim = np.array([float(x) for x in termination], dtype=np.float64)
+        _lib.check(self._L.lhw_env_set_task_shaping(self._h, w.ctypes.data if w is not None else None, 0 if w is None else w.size,
+                                                    lim.ctypes.data if lim is not None else None, 0 if lim is None else lim.size))
 
     def pop_episode_stats(self):
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()

@@ -323,6 +323,37 @@ extern "C" int lhw_env_set_state(LhwEnv* e, const double* qpos_host, const doubl
   return LHW_OK;
 }
 
+extern "C" int lhw_env_get_task_shaping(const LhwEnv* e, double* term_weights, double* term_limits) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  if (!e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "task shaping exists for the humanoid tasks only");
+  double w[LHW_MAX_REWARD_TERMS];
+  humanoid_get_task_shaping(e->hum, w, term_limits);
+  for (int k = 0; term_weights && k < e->n_terms; k++) term_weights[k] = w[k];
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_set_task_shaping(LhwEnv* e, const double* term_weights, int32_t n_weights, const double* term_limits, int32_t n_limits) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  if (!e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "task shaping exists for the humanoid tasks only");
+  if (term_weights) {
+    if (n_weights != e->n_terms) return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: n_weights = %d, this task has %d reward terms", (int)n_weights, e->n_terms);
+    for (int k = 0; k < n_weights; k++)
+      if (!std::isfinite(term_weights[k])) return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: weight %d is not finite", k);
+  }
+  if (term_limits) {
+    if (n_limits != LHW_TERM_LIMIT_COUNT) return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: n_limits = %d, must be %d (lower, upper)", (int)n_limits, LHW_TERM_LIMIT_COUNT);
+    if (std::isnan(term_limits[0]) || std::isnan(term_limits[1])) return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: a termination limit is NaN");
+    if (!(term_limits[0] < term_limits[1]))
+      return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: lower limit %g is not below upper limit %g", term_limits[0], term_limits[1]);
+    if (e->task == LHW_TASK_JVRC_STEP && term_limits[1] != (double)INFINITY)
+      return lhw_fail(LHW_ERR_ARG, "lhw_env_set_task_shaping: the stepping task has no upper limit (pass +inf, got %g)", term_limits[1]);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (humanoid_set_task_shaping(e->hum, term_weights, n_weights, term_limits)) return lhw_fail(LHW_ERR_HIP, "task shaping: parameter upload failed");
+  return LHW_OK;
+}
+
 // ep_stats[first .. first + count) -> host after a device synchronise, then cleared on the device
 static int pop_stats(LhwEnv* e, int first, int count, double* out) {
   HIPCHK(hipSetDevice(e->device));

@@ -269,8 +269,13 @@ struct HParams {
   double kp[NU], kd[NU], nominal_qpos[NQ], action_offset[NU], neutral_pose[NU], obs_noise[36];   // (members, like the model tables)
   double* tstat;                        // per-term episode statistics (lhw_env_enable_term_stats; layout: lhw_internal.h LHW_TS_*): the running episode's sum
                                         // of every reward term per env, then the sums over each env's finished episodes -- a side array, not part of the
-                                        // env record.  Read by the STATS instantiations of the kernels only (launched while it is non-NULL); last member,
-                                        // so every other field sits where it sat
+                                        // env record.  Read by the STATS instantiations of the kernels only (launched while it is non-NULL); added
+                                        // behind every earlier member, so every other field sits where it sat
+  double rew_w[10];                     // task shaping (lhw_env_set_task_shaping): the leading weight of every reward term, in the order of rew_terms
+                                        // (humanoid_create: the reference's tasks/*_task.py values; the 6-term tasks leave [6..9] at 0) ...
+  double term_lim[2];                   // ... and the termination bounds: root z outside [lo, hi] (walking, standing), root z above the lower foot
+                                        // site below lo (stepping: hi is +inf, it has none).  Uniform across the batch: scalar loads of p.  Added
+                                        // behind tstat by the same rule
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const HModel LHW_GLOBAL_AS& HModelRef;
@@ -3576,26 +3581,26 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
           const double PI4 = 3.141592653589793 / 4;
           const double maxf = m.totalmass * 9.8 * 0.5;
           const double nl = fmin(grf_l, maxf) / maxf * 2 - 1, nr = fmin(grf_r, maxf) / maxf * 2 - 1;
-          terms[0] = 0.225 * ((tan(PI4 * lf * nl) + tan(PI4 * rf * nr)) / 2);
+          terms[0] = p.rew_w[0] * ((tan(PI4 * lf * nl) + tan(PI4 * rf * nr)) / 2);
           const double nlv = fmin(sqrt(dot3(lv, lv)), 0.2) / 0.2 * 2 - 1, nrv = fmin(sqrt(dot3(rv, rv)), 0.2) / 0.2 * 2 - 1;
-          terms[1] = 0.225 * ((tan(PI4 * lvc * nlv) + tan(PI4 * rvc * nrv)) / 2);
-          terms[2] = 0.050 * exp(-0.25 * s_rootacc);
+          terms[1] = p.rew_w[1] * ((tan(PI4 * lvc * nlv) + tan(PI4 * rvc * nrv)) / 2);
+          terms[2] = p.rew_w[2] * exp(-0.25 * s_rootacc);
           double herr = fabs(S.xpos[3 * p.root_body + 2] - cz - p.goal_height);
           if (herr < 0.01 + 0.05 * gs) herr = 0;
-          terms[3] = 0.050 * exp(-40 * herr * herr);
+          terms[3] = p.rew_w[3] * exp(-40 * herr * herr);
           const double ex = vloc[0] - vx, ey = vloc[1] - vy, en = sqrt(ex * ex + ey * ey);
-          terms[4] = 0.150 * exp(-10 * (en * en));
+          terms[4] = p.rew_w[4] * exp(-10 * (en * en));
           const double ye = fabs(S.qvel[5] - yaw_ref);
-          terms[5] = 0.150 * exp(-10 * (ye * ye * ye));
+          terms[5] = p.rew_w[5] * exp(-10 * (ye * ye * ye));
           const double hx = S.xpos[3 * p.head_body] - S.xpos[3 * p.root_body], hy = S.xpos[3 * p.head_body + 1] - S.xpos[3 * p.root_body + 1];
-          terms[6] = 0.050 * exp(-10 * sqrt(hx * hx + hy * hy));
-          terms[7] = 0.050 * exp(-sqrt(s_posture));
-          terms[8] = 0.025 * exp(-0.25 * (s_tq / (double)m.nu));
-          terms[9] = 0.025 * exp(-5 * s_act / (double)m.nu);
+          terms[6] = p.rew_w[6] * exp(-10 * sqrt(hx * hx + hy * hy));
+          terms[7] = p.rew_w[7] * exp(-sqrt(s_posture));
+          terms[8] = p.rew_w[8] * exp(-0.25 * (s_tq / (double)m.nu));
+          terms[9] = p.rew_w[9] * exp(-5 * s_act / (double)m.nu);
           for (int k = 0; k < 10; k++) r_sum += terms[k];  // python sum() over the dict, left to right
         }
           const double z = S.qpos[2];
-          terminated = z < 0.6 || z > 1.4 || self_collision;  // walking_task.py:184-192
+          terminated = z < p.term_lim[0] || z > p.term_lim[1] || self_collision;  // walking_task.py:184-192
         } else if (TASK == TASK_STEP) {
           // ---- SteppingTask.step (stepping_task.py:211-243) on the stale site / body frames
           phase += 1;
@@ -3640,26 +3645,26 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
             const double PI4 = 3.141592653589793 / 4;
             const double maxf = m.totalmass * 9.8 * 0.5;
             const double nl = fmin(grf_l, maxf) / maxf * 2 - 1, nr = fmin(grf_r, maxf) / maxf * 2 - 1;
-            terms[0] = 0.150 * ((tan(PI4 * lf * nl) + tan(PI4 * rf * nr)) / 2);
+            terms[0] = p.rew_w[0] * ((tan(PI4 * lf * nl) + tan(PI4 * rf * nr)) / 2);
             const double nlv = fmin(sqrt(dot3(lv, lv)), 0.2) / 0.2 * 2 - 1, nrv = fmin(sqrt(dot3(rv, rv)), 0.2) / 0.2 * 2 - 1;
-            terms[1] = 0.150 * ((tan(PI4 * lvc * nlv) + tan(PI4 * rvc * nrv)) / 2);
+            terms[1] = p.rew_w[1] * ((tan(PI4 * lvc * nlv) + tan(PI4 * rvc * nrv)) / 2);
             const double inner = cos(0.5 * tg[3]) * S.rootquat[0] + sin(0.5 * tg[3]) * S.rootquat[3];
-            terms[2] = 0.050 * exp(-(10 * (1 - inner * inner)));
+            terms[2] = p.rew_w[2] * exp(-(10 * (1 - inner * inner)));
             double herr = fabs(rootp[2] - cz - p.goal_height);
             if (herr < 0.01) herr = 0;
-            terms[3] = 0.050 * exp(-40 * herr * herr);
+            terms[3] = p.rew_w[3] * exp(-40 * herr * herr);
             const double dl = sqrt((lp[0] - tg[0]) * (lp[0] - tg[0]) + (lp[1] - tg[1]) * (lp[1] - tg[1]) + (lp[2] - tg[2]) * (lp[2] - tg[2]));
             const double dr = sqrt((rp[0] - tg[0]) * (rp[0] - tg[0]) + (rp[1] - tg[1]) * (rp[1] - tg[1]) + (rp[2] - tg[2]) * (rp[2] - tg[2]));
             const double hit = reached ? exp(-fmin(dl, dr) / 0.25) : 0.0;
             const double mx = (tg[0] + tg2[0]) / 2, my = (tg[1] + tg2[1]) / 2;
             const double progress = exp(-sqrt((rootp[0] - mx) * (rootp[0] - mx) + (rootp[1] - my) * (rootp[1] - my)) / 2);
-            terms[4] = 0.450 * (0.8 * hit + 0.2 * progress);
+            terms[4] = p.rew_w[4] * (0.8 * hit + 0.2 * progress);
             const double hx = S.xpos[3 * p.head_body] - rootp[0], hy = S.xpos[3 * p.head_body + 1] - rootp[1], hn = sqrt(hx * hx + hy * hy);
-            terms[5] = 0.050 * exp(-10 * (hn * hn));
+            terms[5] = p.rew_w[5] * exp(-10 * (hn * hn));
             for (int k = 0; k < 6; k++) r_sum += terms[k];
             for (int k = 6; k < 10; k++) terms[k] = 0;
           }
-          terminated = (rootp[2] - fmin(lp[2], rp[2])) < 0.6 || self_collision;  // stepping_task.py:247-259
+          terminated = (rootp[2] - fmin(lp[2], rp[2])) < p.term_lim[0] || self_collision;  // stepping_task.py:247-259
         } else {
           // ---- StandingTask.calc_reward / done (standing_task.py:49-131) on the fields of the last forward pass
           double s_posture = 0, s_tau = 0;
@@ -3677,16 +3682,16 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
           const double fwd = sqrt(vloc[0] * vloc[0] + vloc[1] * vloc[1]), yaw = fabs(S.qvel[5]);
           const double herr = fabs(S.xpos[3 * p.root_body + 2] - p.goal_height);
           const double uerr = sqrt(hloc[0] * hloc[0] + hloc[1] * hloc[1]);
-          terms[0] = 0.3 * exp(-4 * (fwd * fwd));
-          terms[1] = 0.3 * exp(-4 * (yaw * yaw));
-          terms[2] = 0.1 * exp(-0.5 * (herr * herr));
-          terms[3] = 0.1 * exp(-40 * (uerr * uerr));
-          terms[4] = 0.1 * exp(-5e-5 * s_tau);
-          terms[5] = 0.1 * exp(-1 * s_posture);
+          terms[0] = p.rew_w[0] * exp(-4 * (fwd * fwd));
+          terms[1] = p.rew_w[1] * exp(-4 * (yaw * yaw));
+          terms[2] = p.rew_w[2] * exp(-0.5 * (herr * herr));
+          terms[3] = p.rew_w[3] * exp(-40 * (uerr * uerr));
+          terms[4] = p.rew_w[4] * exp(-5e-5 * s_tau);
+          terms[5] = p.rew_w[5] * exp(-1 * s_posture);
           for (int k = 0; k < 6; k++) r_sum += terms[k];
           for (int k = 6; k < 10; k++) terms[k] = 0;
           const double z = S.qpos[2];
-          terminated = z < 0.9 || z > 1.4 || self_collision;  // standing_task.py:111-131
+          terminated = z < p.term_lim[0] || z > p.term_lim[1] || self_collision;  // standing_task.py:111-131
         }
         if (st.tin) {   // the batched sim facade (include/lhw.h: LhwTaskInput)
           double* ti = st.tin + lz.tin_off + (size_t)env * LHW_TASK_INPUT_DIM;

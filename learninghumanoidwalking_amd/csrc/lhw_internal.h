@@ -128,6 +128,10 @@ void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, 
 double* humanoid_ep_stats(HumanoidEnv* h);
 double* humanoid_term_stats(HumanoidEnv* h);                   // the term-statistics block the kernels write (NULL = off)
 int humanoid_set_term_stats(HumanoidEnv* h, double* block);    // hands it to the kernels (NULL stops them); -1 HIP error
+// task shaping (lhw_env_set_task_shaping): weights [LHW_MAX_REWARD_TERMS] / limits [LHW_TERM_LIMIT_COUNT] of the host mirror; the setter
+// takes validated values (either half may be NULL), uploads the parameters and returns -1 on a HIP error
+void humanoid_get_task_shaping(const HumanoidEnv* h, double* weights, double* limits);
+int humanoid_set_task_shaping(HumanoidEnv* h, const double* weights, int n_weights, const double* limits);
 void humanoid_set_iteration(HumanoidEnv* h, int64_t it);
 int humanoid_occupancy();
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);

@@ -90,7 +90,14 @@ class BatchedFactory:
         if cls is None:
             from ..batched_env import BatchedEnv as cls
         model, task, kw = self.env_args()
-        return cls(model, task, n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base, **kw)
+        env = cls(model, task, n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base, **kw)
+        shaping = self.task_shaping()
+        if shaping is not None:      # (only then: a substituted backend without the method serves every config that does not shape the task)
+            env.set_task_shaping(reward_weights=shaping[0], termination=shaping[1])
+        return env
+
+    def task_shaping(self):
+        return None     # (the humanoid specs read it from the YAML)
 
 
 @dataclass
@@ -125,6 +132,9 @@ class HumanoidSpec(BatchedFactory):
         self.perturb_interval = int(pc["interval"] / self.control_dt) if pc.get("enable") else 0
         self.perturb_bodies = list(pc.get("bodies", []))
         self.force_magnitude, self.torque_magnitude = float(pc.get("force_magnitude", 0)), float(pc.get("torque_magnitude", 0))
+        # task shaping, no reference counterpart in the YAML (there: literals of tasks/*_task.py): `reward_weights: {term: weight}` (partial,
+        # by the names of REWARD_TERMS) and `termination: {min_height:, max_height:}`; checked here, applied by make_batched
+        self._shaping = self._read_task_shaping(c)
         self._model = None
         self._configure(c)
         # jvrc_walk.py:62-63, h1_env.py:54-55: np.tile over the history
@@ -156,6 +166,33 @@ class HumanoidSpec(BatchedFactory):
             return None
         m = self.model()
         return dict(interval=self.perturb_interval, bodies=[m.body_id(b) for b in self.perturb_bodies], force=self.force_magnitude, torque=self.torque_magnitude)
+
+    def _read_task_shaping(self, c):
+        from .._lib import DEFAULT_REWARD_WEIGHTS, DEFAULT_TERMINATION, TASK_JVRC_STEP, shaping_weights
+        rw, term = c.get("reward_weights"), c.get("termination")
+        if rw is None and term is None:
+            return None
+        weights = shaping_weights(self.task_code, dict(rw or {}), DEFAULT_REWARD_WEIGHTS[self.task_code])
+        if not np.isfinite(weights).all():
+            raise ValueError(f"reward_weights of {self.yaml_path} must be finite: {rw}")
+        term = dict(term or {})
+        unknown = set(term) - {"min_height", "max_height"}
+        if unknown:
+            raise KeyError(f"unknown termination keys {sorted(unknown)} in {self.yaml_path}: min_height, max_height")
+        if self.task_code == TASK_JVRC_STEP and "max_height" in term:
+            raise ValueError(f"termination.max_height in {self.yaml_path}: the stepping task ends an episode on the root height above the "
+                             "lower foot only (min_height); it has no upper bound")
+        lo, hi = DEFAULT_TERMINATION[self.task_code]
+        lo, hi = float(term.get("min_height", lo)), float(term.get("max_height", hi))
+        if not lo < hi:      # (NaN fails it too)
+            raise ValueError(f"termination of {self.yaml_path}: min_height {lo} must lie below max_height {hi}")
+        return weights, (lo, hi)
+
+    def task_shaping(self):
+        """None for a YAML with neither `reward_weights:` nor `termination:` (every config of the reference), else
+        (term weights [n_terms] float64 in REWARD_TERMS order -- the YAML's over the reference's --, (lo, hi)): what make_batched hands to
+        BatchedEnv.set_task_shaping.  Not part of env_args(): the weights are a run-time setting of the env, not of its creation."""
+        return self._shaping
 
     def clock_lut(self):
         return None     # (a task with a gait clock mixes in WalkingTask)

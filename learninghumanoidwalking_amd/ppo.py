@@ -161,7 +161,9 @@ class Rollout(_RolloutStorage):
         self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
         self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
         # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
-        self.reward_only = reward_only_on(task, env.task)
+        # ... against the bounds the env is configured with (a stand-in env without task_shaping: the reference's)
+        shaping = getattr(env, "task_shaping", None) if task is not None else None
+        self.reward_only = reward_only_on(task, env.task, shaping()[1] if shaping is not None else None)
         if task is not None and env.history_len > 1 and not self.reward_only:
             # (a task that decides terminations resets through env.reset(mask, obs_out=...), which writes base rows and knows nothing of the
             #  history; a reward-only task leaves flags, resets and with them the history to the kernels, resident or launch per step)
@@ -657,8 +659,10 @@ class PPO:
         self.task = task(spec, self.device) if task is not None else None
         # A task that decides terminations itself is consulted after every control step and the env never ends an episode by itself:
         # the rollout truncates and resets (Rollout._task_step).  A reward-only task leaves all that to the kernel.
-        # (reward_only counts only where the task declares this env's fused termination as its own: task_hook.reward_only_on)
-        own_done = self.task is not None and not reward_only_on(self.task, getattr(spec, "task_code", None))
+        # (reward_only counts only where the task declares this env's fused termination as its own: task_hook.reward_only_on,
+        #  and its bounds are the ones this env will be configured with: the YAML's `termination:`, else the reference's)
+        shaping = getattr(spec, "task_shaping", lambda: None)()
+        own_done = self.task is not None and not reward_only_on(self.task, getattr(spec, "task_code", None), shaping[1] if shaping else None)
         self.env = spec.make_batched(self.n_proc, seed=env_seed, device=self.device, max_traj_len=0 if own_done else self.max_traj_len,
                                      env_id_base=dist_utils.shard_env_ids(self.n_proc, self.rank))
         self.env.env_id_base = dist_utils.shard_env_ids(self.n_proc, self.rank)

@@ -22,6 +22,15 @@ the host through ``lhw_env_reset(mask)``, which runs the same reset code with th
 The per-term episode statistics of the kernels (``BatchedEnv.enable_term_stats``, ``PPO(term_stats=True)``) describe the FUSED reward:
 with a task plugged in the reward does not come from the kernel, so ``PPO.term_stats`` is None and no reward_terms.csv is written
 (a plug-in keeps its own terms in ``last_terms``).
+
+Changing a term's WEIGHT or a termination HEIGHT needs no plug-in: they are settings of the fused tasks (``reward_weights:`` /
+``termination:`` in the env's YAML, ``BatchedEnv.set_task_shaping``; include/lhw.h: lhw_env_set_task_shaping), at full speed on every
+rollout path and policy kind, with the term statistics intact.  What a plug-in costs instead: a reward-only one makes the resident
+rollout export ``[T][N][176]`` float64 (2.3 GB at 4096 x 400, 1.4 KB written per env-step) and recompute the reward in torch; one with
+its own termination rule leaves the resident kernel for a launch, a torch evaluation and a reset launch per control step, and is refused
+with ``obs_history_len > 1`` and ``--recurrent``.  A shipped plug-in whose bounds equal the bounds the ENV is configured with (not only the
+reference's literals) still counts as reward-only (``reward_only_on``): plug-ins are for what the settings do not reach -- the inner
+constants of a term, new terms, another termination rule.
 """
 from __future__ import annotations
 
@@ -96,15 +105,24 @@ def device_task_inputs(env) -> TaskInputs:
     return view
 
 
-def reward_only_on(task, env_task) -> bool:
+def reward_only_on(task, env_task, env_limits=None) -> bool:
     """Whether a plugged-in task runs as a reward-only plug-in on an env of kernel task `env_task` (batched_env.TASK_*): the kernel
     then keeps its own termination, so the task's `reward_only = True` is honoured only where its `done()` IS that env's fused
     termination.  A task names the envs for which that holds in `fused_tasks`; a task without that declaration (a user's) is taken at
-    its word.  PPO (the env's max_traj_len) and Rollout (which collection path) both decide with this predicate."""
-    if task is None or not getattr(task, "reward_only", False):
+    its word.  `env_limits`: the termination bounds the env is configured with (BatchedEnv.task_shaping()[1]); a shipped task, which
+    states its own bounds (`termination_limits()`), is then reward-only where those equal the ENV's bounds -- a run whose YAML sets
+    `termination:` and whose plug-in is given the same limits stays resident.  Without `env_limits` (or with the bounds a fresh env has)
+    the bounds compared against are the reference's literals, as ever.  PPO (the env's max_traj_len) and Rollout (which collection path)
+    both decide with this predicate."""
+    if task is None:
         return False
     fused = getattr(task, "fused_tasks", None)
-    return fused is None or env_task in fused
+    own = getattr(task, "termination_limits", None)
+    declared = getattr(task, "reward_only", False)
+    if env_limits is not None and own is not None and (declared or getattr(task, "_own_limits", False)):
+        # (_own_limits: the constructor cleared reward_only because the bounds are not the reference's; what counts is whether they are the env's)
+        declared = tuple(float(x) for x in own()) == tuple(float(x) for x in env_limits)
+    return bool(declared) and (fused is None or env_task in fused)
 
 
 class VectorTask:
@@ -142,7 +160,8 @@ class VectorWalkingTask(VectorTask):
 
     def __init__(self, spec, device, weights: dict | None = None, height_limits=(0.6, 1.4)):
         if tuple(height_limits) != (0.6, 1.4):
-            self.reward_only = False      # another termination rule than the fused one: consulted step by step
+            self.reward_only = False      # another termination rule than the fused one's default: consulted step by step, unless the env
+            self._own_limits = True       # is configured with the same bounds (reward_only_on(..., env_limits))
         self.w = dict(self.WEIGHTS, **(weights or {}))
         unknown = set(self.w) - set(self.TERMS)
         if unknown:
@@ -153,6 +172,9 @@ class VectorWalkingTask(VectorTask):
         self.neutral = torch.as_tensor(np.asarray(spec.half_sitting_pose, dtype=np.float64), device=device)
         self.zlim = height_limits
         self.last_terms = None
+
+    def termination_limits(self):
+        return tuple(self.zlim)
 
     @staticmethod
     def _clock(a, b, ca, cb, cap):
@@ -206,6 +228,7 @@ class VectorStandingTask(VectorTask):
     def __init__(self, spec, device, weights: dict | None = None, height_limits=(0.9, 1.4)):
         if tuple(height_limits) != (0.9, 1.4):
             self.reward_only = False
+            self._own_limits = True
         self.w = dict(self.WEIGHTS, **(weights or {}))
         unknown = set(self.w) - set(self.TERMS)
         if unknown:
@@ -214,6 +237,9 @@ class VectorStandingTask(VectorTask):
         self.neutral = torch.as_tensor(np.asarray(spec.action_offset(), dtype=np.float64), device=device)   # standing_task.py:33 (the nominal leg pose)
         self.zlim = height_limits
         self.last_terms = None
+
+    def termination_limits(self):
+        return tuple(self.zlim)
 
     def evaluate(self, ti: TaskInputs):
         R = ti.root_xmat.reshape(-1, 3, 3)
@@ -248,7 +274,8 @@ class VectorSteppingTask(VectorTask):
 
     def __init__(self, spec, device, weights: dict | None = None, min_root_height: float = 0.6):
         if float(min_root_height) != 0.6:
-            self.reward_only = False      # another termination rule than the fused one: consulted step by step
+            self.reward_only = False      # another termination rule than the fused one's default: consulted step by step, unless the env
+            self._own_limits = True       # is configured with the same bound (reward_only_on(..., env_limits))
         self.w = dict(self.WEIGHTS, **(weights or {}))
         unknown = set(self.w) - set(self.TERMS)
         if unknown:
@@ -258,6 +285,9 @@ class VectorSteppingTask(VectorTask):
         self.goal_height = float(spec.goal_height)
         self.min_root_height = float(min_root_height)
         self.last_terms = None
+
+    def termination_limits(self):
+        return (self.min_root_height, float("inf"))
 
     def evaluate(self, ti: TaskInputs):
         ph = ti.phase.long()

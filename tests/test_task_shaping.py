@@ -1,0 +1,132 @@
+"""Task shaping -- the reward-term weights and termination bounds of the fused humanoid tasks as run-time settings
+(lhw_env_set_task_shaping / lhw_env_get_task_shaping, include/lhw.h; `reward_weights:` / `termination:` in an env's YAML) -- on the
+SIMT emulator, plus the host-only parts (YAML -> spec -> make_batched, reward_only_on against the env's bounds).  The reference has
+these numbers as literals of /root/reference/tasks/walking_task.py:131-146,184-192, stepping_task.py:109-122,247-259 and
+standing_task.py:99-106,111-131; what other values must give is stated by the shipped plug-ins (tests/task_shaping_checks.py).
+CPU twin of tests/test_task_shaping_gpu.py."""
+import numpy as np
+import pytest
+
+from tests import task_shaping_checks as C
+
+BACKEND = C.EmuBackend()
+
+
+def test_fresh_env_reports_the_reference_values():
+    C.check_defaults(BACKEND)
+
+
+def test_setting_the_values_an_env_has_changes_no_bit():
+    C.check_neutrality(BACKEND)
+
+
+@pytest.mark.parametrize("name", C.ENVS)
+def test_reward_terms_follow_the_weights(name):
+    C.check_weights(BACKEND, name)
+
+
+@pytest.mark.parametrize("name", C.ENVS)
+def test_termination_follows_the_limits(name):
+    C.check_limits(BACKEND, name)
+
+
+def test_resident_rollout_is_bitwise_the_launch_per_step_loop_under_shaping():
+    C.check_resident_equals_steps(BACKEND)
+
+
+def test_setter_between_two_resident_rollouts():
+    C.check_setter_mid_run(BACKEND)
+
+
+def test_refused_calls_name_their_cause_and_change_nothing():
+    C.check_errors(BACKEND)
+
+
+# ---------------------------------------------------------------------------------------------------------------- spec / YAML (no library)
+def _yaml(tmp_path, name, text):
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS
+    base = ENVIRONMENTS[name]().yaml_path
+    path = tmp_path / f"{name}_shaped.yaml"
+    path.write_text(f"inherits: {base}\n" + text)      # (load_config: the child's keys win; an absolute parent path is taken as it is)
+    return ENVIRONMENTS[name](yaml_path=str(path))
+
+
+def test_yaml_keys_give_weights_in_term_order_and_limits(tmp_path):
+    from learninghumanoidwalking_amd import _lib
+    spec = _yaml(tmp_path, "jvrc_walk", "reward_weights: {com_vel_error: 0.30, torque_penalty: 0.0}\ntermination: {min_height: 0.5, max_height: 1.5}\n")
+    w, lim = spec.task_shaping()
+    want = dict(zip(_lib.REWARD_TERMS[_lib.TASK_JVRC_WALK], _lib.DEFAULT_REWARD_WEIGHTS[_lib.TASK_JVRC_WALK]), com_vel_error=0.30, torque_penalty=0.0)
+    assert list(w) == [want[k] for k in _lib.REWARD_TERMS[_lib.TASK_JVRC_WALK]] and w.dtype == np.float64
+    assert lim == (0.5, 1.5)
+    assert "reward_weights" not in spec.env_args()[2] and "termination" not in spec.env_args()[2]      # (a setting of the env, not of its creation)
+    # one key alone: the other half keeps the reference's values
+    w, lim = _yaml(tmp_path, "h1", "termination: {min_height: 0.8}\n").task_shaping()
+    assert list(w) == list(_lib.DEFAULT_REWARD_WEIGHTS[_lib.TASK_H1_STAND]) and lim == (0.8, 1.4)
+    w, lim = _yaml(tmp_path, "jvrc_step", "reward_weights: {step_reward: 0.6}\ntermination: {min_height: 0.55}\n").task_shaping()
+    assert list(w) == [0.150, 0.150, 0.050, 0.050, 0.6, 0.050] and lim == (0.55, float("inf"))
+
+
+def test_yaml_mistakes_are_refused(tmp_path):
+    with pytest.raises(KeyError) as e:
+        _yaml(tmp_path, "jvrc_walk", "reward_weights: {com_vel: 0.3}\n")
+    assert "com_vel_error" in str(e.value) and "action_penalty" in str(e.value)      # (names the valid terms)
+    with pytest.raises(ValueError):
+        _yaml(tmp_path, "jvrc_step", "termination: {min_height: 0.5, max_height: 1.5}\n")
+    with pytest.raises(ValueError):
+        _yaml(tmp_path, "jvrc_walk", "termination: {min_height: 1.5}\n")      # above the (default) upper bound
+    with pytest.raises(KeyError):
+        _yaml(tmp_path, "jvrc_walk", "termination: {min_hight: 0.5}\n")
+
+
+def test_configs_without_the_keys_do_not_touch_the_backend(tmp_path, monkeypatch):
+    """every shipped config: task_shaping() is None and make_batched serves a backend that has no set_task_shaping (the substitution seam
+    envs.humanoid.BatchedEnv); a shaped config calls it, after the constructor, with the spec's arrays"""
+    from learninghumanoidwalking_amd.envs import ENVIRONMENTS, humanoid
+
+    class Plain:
+        def __init__(self, model, task, n_envs, **kw):
+            self.kw = kw
+
+    class Shaped(Plain):
+        def set_task_shaping(self, reward_weights=None, termination=None):
+            self.shaping = (reward_weights, termination)
+
+    for name in C.ENVS + ("cartpole",):
+        spec = ENVIRONMENTS[name]()
+        assert spec.task_shaping() is None
+        monkeypatch.setattr(humanoid, "BatchedEnv", Plain)
+        env = spec.make_batched(3, seed=1)
+        assert isinstance(env, Plain) and env.kw["seed"] == 1
+    spec = _yaml(tmp_path, "jvrc_walk", "reward_weights: {root_accel: 0.1}\n")
+    monkeypatch.setattr(humanoid, "BatchedEnv", Shaped)
+    env = spec.make_batched(3)
+    assert list(env.shaping[0]) == list(spec.task_shaping()[0]) and env.shaping[1] == (0.6, 1.4)
+    monkeypatch.setattr(humanoid, "BatchedEnv", Plain)
+    with pytest.raises(AttributeError):
+        spec.make_batched(3)      # (a shaped config needs a backend that can shape: no silent default)
+
+
+def test_reward_only_is_decided_against_the_bounds_the_env_is_configured_with():
+    from learninghumanoidwalking_amd import batched_env as be
+    from learninghumanoidwalking_amd.envs.jvrc_step import JvrcStepSpec
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    from learninghumanoidwalking_amd.task_hook import VectorSteppingTask, VectorTask, VectorWalkingTask, reward_only_on
+    inf = float("inf")
+    plain, own = VectorWalkingTask(JvrcWalkSpec(), "cpu"), VectorWalkingTask(JvrcWalkSpec(), "cpu", height_limits=(0.5, 1.5))
+    # a default env: exactly the two-argument decision
+    assert reward_only_on(plain, be.TASK_JVRC_WALK, (0.6, 1.4)) and reward_only_on(plain, be.TASK_JVRC_WALK)
+    assert not reward_only_on(own, be.TASK_JVRC_WALK, (0.6, 1.4)) and not reward_only_on(own, be.TASK_JVRC_WALK)
+    # an env configured with other bounds: the plug-in with the SAME bounds restates its termination, the plain one no longer does
+    assert reward_only_on(own, be.TASK_JVRC_WALK, (0.5, 1.5)) and reward_only_on(own, be.TASK_H1_WALK, (0.5, 1.5))
+    assert not reward_only_on(plain, be.TASK_JVRC_WALK, (0.5, 1.5)) and not reward_only_on(own, be.TASK_JVRC_WALK, (0.5, 1.4))
+    assert not reward_only_on(own, be.TASK_JVRC_STEP, (0.5, 1.5))      # (still only on the envs whose rule it restates)
+    step = VectorSteppingTask(JvrcStepSpec(), "cpu", min_root_height=0.55)
+    assert reward_only_on(step, be.TASK_JVRC_STEP, (0.55, inf)) and not reward_only_on(step, be.TASK_JVRC_STEP, (0.6, inf))
+    assert not reward_only_on(step, be.TASK_JVRC_STEP)
+
+    class Mine(VectorTask):      # a user's task states no bounds: taken at its word, as ever
+        reward_only = True
+    assert reward_only_on(Mine(), be.TASK_JVRC_WALK, (0.5, 1.5)) and not reward_only_on(None, be.TASK_JVRC_WALK, (0.5, 1.5))
+    off = VectorWalkingTask(JvrcWalkSpec(), "cpu")
+    off.reward_only = False      # a user who wants the shipped task consulted step by step keeps that
+    assert not reward_only_on(off, be.TASK_JVRC_WALK, (0.6, 1.4))

@@ -1,0 +1,112 @@
+"""Task shaping -- the reward-term weights and termination bounds of the fused humanoid tasks as run-time settings
+(lhw_env_set_task_shaping / lhw_env_get_task_shaping, include/lhw.h; `reward_weights:` / `termination:` in an env's YAML) -- on the GPU
+through the product BatchedEnv: the checks of tests/test_task_shaping.py (tests/task_shaping_checks.py), plus one learner-level check:
+a shaped YAML keeps the resident rollout, the per-term statistics and exports no record, and computes what the plug-in route computes.
+The reference has these numbers as literals of /root/reference/tasks/walking_task.py:131-146,184-192, stepping_task.py:109-122,247-259
+and standing_task.py:99-106,111-131."""
+from functools import partial
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from tests import task_shaping_checks as C
+
+pytestmark = pytest.mark.gpu
+
+BACKEND = C.GpuBackend()
+
+
+def test_fresh_env_reports_the_reference_values():
+    C.check_defaults(BACKEND)
+
+
+def test_setting_the_values_an_env_has_changes_no_bit():
+    C.check_neutrality(BACKEND)
+
+
+@pytest.mark.parametrize("name", C.ENVS)
+def test_reward_terms_follow_the_weights(name):
+    C.check_weights(BACKEND, name)
+
+
+@pytest.mark.parametrize("name", C.ENVS)
+def test_termination_follows_the_limits(name):
+    C.check_limits(BACKEND, name)
+
+
+def test_resident_rollout_is_bitwise_the_launch_per_step_loop_under_shaping():
+    C.check_resident_equals_steps(BACKEND)
+
+
+def test_setter_between_two_resident_rollouts():
+    C.check_setter_mid_run(BACKEND)
+
+
+def test_refused_calls_name_their_cause_and_change_nothing():
+    C.check_errors(BACKEND)
+
+
+def test_batched_env_methods_take_names_and_read_back():
+    from learninghumanoidwalking_amd.batched_env import REWARD_TERMS
+    spec = C.spec_of("jvrc_walk")
+    env = spec.make_batched(2, seed=1, device=0)
+    w, lim = env.task_shaping()
+    assert tuple(w) == REWARD_TERMS[env.task] and w["com_vel_error"] == 0.150 and lim == (0.6, 1.4)
+    env.set_task_shaping(reward_weights=dict(com_vel_error=0.30, torque_penalty=0.0))      # partial, by name, over the current values
+    env.set_task_shaping(termination=(0.5, 1.5))
+    w2, lim2 = env.task_shaping()
+    assert w2 == dict(w, com_vel_error=0.30, torque_penalty=0.0) and lim2 == (0.5, 1.5)
+    env.set_task_shaping(reward_weights=list(C.shaped_weights(10)))                         # a full sequence
+    np.testing.assert_array_equal(list(env.task_shaping()[0].values()), C.shaped_weights(10))
+    with pytest.raises(KeyError) as e:
+        env.set_task_shaping(reward_weights=dict(com_vel=0.3))
+    assert "com_vel_error" in str(e.value)
+    env.close()
+
+
+def _args(N, T):
+    return SimpleNamespace(gamma=0.99, lam=0.95, lr=3e-4, eps=1e-5, entropy_coeff=0.0, clip=0.2, minibatch_size=512, epochs=1,
+                           max_traj_len=T, num_procs=N, num_envs=N, max_grad_norm=0.5, mirror_coeff=0.4, eval_freq=10**9,
+                           recurrent=False, imitate=None, learn_std=False, std_dev=0.4, no_mirror=True, continued=None,
+                           logdir="/tmp/lhw_test_task_shaping", device_index=0)
+
+
+def test_a_shaped_yaml_keeps_the_resident_rollout_and_the_term_statistics(tmp_path):
+    """jvrc_walk, 64 envs, T = 8, no mirror loss.  Learner A: YAML with `reward_weights:` and `termination:`.  Learner B: the plug-in route --
+    VectorWalkingTask(weights=same, height_limits=same) on an env whose YAML sets the same `termination:` (make_batched hands it to
+    env.set_task_shaping(termination=...), so that the fused flags the resident rollout keeps are the plug-in's done(); its fused weights
+    stay the reference's, the reward is the plug-in's).  Same seeds: rewards within 1e-6 (float32 fused terms against the float64 plug-in:
+    REW_ATOL), flags identical, both resident."""
+    from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
+    from learninghumanoidwalking_amd.ppo import PPO
+    from learninghumanoidwalking_amd.task_hook import VectorWalkingTask
+    N, T = 64, 8
+    weights = dict(zip(VectorWalkingTask.TERMS, (float(x) for x in C.shaped_weights(10))))
+    limits = (0.79, 1.2)
+    base = f"inherits: {JvrcWalkSpec().yaml_path}\n"      # (load_config: the child's keys win)
+    term = f"termination: {{min_height: {limits[0]}, max_height: {limits[1]}}}\n"
+    rw = "reward_weights: {" + ", ".join(f"{k}: {v!r}" for k, v in weights.items()) + "}\n"
+    (tmp_path / "shaped.yaml").write_text(base + rw + term)
+    (tmp_path / "limits.yaml").write_text(base + term)
+
+    a = PPO(partial(JvrcWalkSpec, yaml_path=str(tmp_path / "shaped.yaml")), _args(N, T), seed=9, term_stats=True)
+    a.sample_parallel_with_workers()
+    assert a.rollout.last_mode == "resident"
+    assert isinstance(a.term_stats, dict) and list(a.term_stats["terms"]) == list(VectorWalkingTask.TERMS)
+    assert a.rollout._tin_all is None and a.rollout.tin_all is None      # no task-input record was allocated
+    got_w, got_lim = a.env.task_shaping()
+    assert got_w == weights and got_lim == limits
+
+    b = PPO(partial(JvrcWalkSpec, yaml_path=str(tmp_path / "limits.yaml")), _args(N, T), seed=9,
+            task=partial(VectorWalkingTask, weights=weights, height_limits=limits))
+    assert b.env.task_shaping()[1] == limits and list(b.env.task_shaping()[0].values()) == list(VectorWalkingTask.WEIGHTS.values())
+    b.sample_parallel_with_workers()
+    assert b.rollout.last_mode == "resident" and b.rollout.reward_only      # (reward_only_on against the env's configured bounds)
+    assert b.term_stats is None and b.rollout._tin_all is not None         # what the plug-in route costs
+    ra, rb = a.rollout.rew.cpu().numpy(), b.rollout.rew.cpu().numpy()
+    print("fused under the YAML's weights vs plug-in: max |d reward|", np.abs(ra - rb).max(), "episodes ended", int((a.rollout.done != 0).sum()))
+    np.testing.assert_array_equal(a.rollout.done.cpu().numpy(), b.rollout.done.cpu().numpy())
+    np.testing.assert_allclose(ra, rb, rtol=0, atol=C.REW_ATOL)
+    assert ((a.rollout.done & 1) != 0).any(), "the tightened bounds must end episodes"
+    np.testing.assert_array_equal(a.rollout.act.cpu().numpy(), b.rollout.act.cpu().numpy())
