@@ -503,8 +503,20 @@ typedef struct LhwLstmValuesArgs {
   float* scratch;
 } LhwLstmValuesArgs;
 int lhw_debug_lstm_values(const LhwLstmValuesArgs* args, int32_t fused, void* stream);
+/* The two diagnostic clocks of the humanoid steppers, lhw_env_debug_wave_cycles (wave clock) and lhw_env_phase_cycles (phase clock).
+ * The kernels the product runs carry neither clock.  Once a clock of an env is armed (it stays armed for the env's life), the env's control
+ * steps run a second set of kernels that do: every launch-per-step control step (lhw_env_step / lhw_env_step_range, all tasks) and the
+ * resident rollout of a feed-forward policy without an observation history (lhw_env_rollout and its *_task_inputs forms, all tasks, the
+ * job queue of the stepping task included).  Every value a step stores is the same, bit for bit, with and without the clocks.
+ * What has no kernels with clocks never runs with a clock armed, so that no call records nothing without saying so:
+ *  - lhw_env_rollout_lstm and lhw_env_rollout_history on an env with an armed clock fail with LHW_ERR_UNSUPPORTED before anything is
+ *    launched -- the code with which a resident rollout is declined for any other reason; the caller steps the env launch by launch
+ *    (BatchedEnv.rollout returns False), and those steps record.
+ *  - The clocks and the per-term episode statistics exclude each other: arming a clock while lhw_env_enable_term_stats is in force, and
+ *    lhw_env_enable_term_stats(env, 1) on an env with an armed clock, fail with LHW_ERR_UNSUPPORTED and change nothing. */
 /* Diagnostic (load balance): the first call arms the recording; later calls return, per env, the shader-clock cycles its
- * wavefront group spent in the most recent control-step launch.  HOST pointer [N] int64, synchronous; humanoid tasks only. */
+ * wavefront group spent in the most recent control-step launch (after a resident rollout: in all control steps of the rollout).
+ * HOST pointer [N] int64, synchronous; humanoid tasks only. */
 int lhw_env_debug_wave_cycles(LhwEnv* env, int64_t* cycles_host);
 int lhw_env_set_iteration(LhwEnv* env, int64_t iteration);
 /* Diagnostic: shader-clock cycles env 0 spent in each phase of the wave-per-env stepper since the last call

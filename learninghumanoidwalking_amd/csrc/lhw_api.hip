@@ -229,6 +229,9 @@ static int env_rollout(const char* name, LhwEnv* e, const HumanoidRollout& rq, v
   const int rc = humanoid_rollout(e->hum, rq, (hipStream_t)stream);
   if (rc == -1) return lhw_fail(LHW_ERR_ARG, "env range [%d, %d) outside the batch, or T = %d", rq.first, rq.first + rq.count, rq.T);
   if (rc == -4) return lhw_fail(LHW_ERR_HIP, "%s: a HIP call failed while preparing the launch (%s)", name, hipGetErrorString(hipGetLastError()));
+  if (rc == -5)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: a diagnostic clock of this env is armed (lhw_env_phase_cycles / lhw_env_debug_wave_cycles) and only the plain feed-forward "
+                                         "rollout kernels carry the clocks: step this env launch by launch (lhw_env_step)", name);
   if (rc && rq.kind == POLICY_MLP)
     return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: needs a float32 actor obs %d -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's resident kernel", name,
                     e->obs_dim, e->act_dim);
@@ -378,7 +381,11 @@ extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len
 static double* term_stats_block(LhwEnv* e) { return e->task == LHW_TASK_CARTPOLE ? e->cps.tstat : humanoid_term_stats(e->hum); }
 static int set_term_stats_block(LhwEnv* e, double* block) {
   if (e->task == LHW_TASK_CARTPOLE) { e->cps.tstat = block; return LHW_OK; }
-  return humanoid_set_term_stats(e->hum, block) ? lhw_fail(LHW_ERR_HIP, "term statistics: parameter upload failed") : LHW_OK;
+  const int rc = humanoid_set_term_stats(e->hum, block);
+  if (rc == -2)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_enable_term_stats: a diagnostic clock of this env is armed (lhw_env_phase_cycles / lhw_env_debug_wave_cycles) and "
+                                         "the kernels that keep the statistics carry no clocks");
+  return rc ? lhw_fail(LHW_ERR_HIP, "term statistics: parameter upload failed") : LHW_OK;
 }
 
 extern "C" int lhw_env_enable_term_stats(LhwEnv* e, int enable) {
@@ -422,7 +429,9 @@ extern "C" int lhw_env_phase_cycles(LhwEnv* e, int enable, int64_t* out16) {
   if (!e || !e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "phase profiling exists for the wave-per-env stepper only");
   HIPCHK(hipSetDevice(e->device));
   static_assert(sizeof(long long) == sizeof(int64_t), "");
-  if (humanoid_profile(e->hum, enable, (long long*)out16)) return lhw_fail(LHW_ERR_HIP, "profile buffer");
+  const int rc = humanoid_profile(e->hum, enable, (long long*)out16);
+  if (rc == -2) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_phase_cycles: the term statistics are on and their kernels carry no clocks: lhw_env_enable_term_stats(env, 0) first");
+  if (rc) return lhw_fail(LHW_ERR_HIP, "profile buffer");
   return LHW_OK;
 }
 
@@ -431,7 +440,9 @@ extern "C" int lhw_env_phase_cycles(LhwEnv* e, int enable, int64_t* out16) {
 extern "C" int lhw_env_debug_wave_cycles(LhwEnv* e, int64_t* out) {
   if (!e || !e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "wave cycles exist for the humanoid steppers only");
   HIPCHK(hipSetDevice(e->device));
-  if (humanoid_wave_cycles(e->hum, (long long*)out)) return lhw_fail(LHW_ERR_HIP, "wave cycle buffer");
+  const int rc = humanoid_wave_cycles(e->hum, (long long*)out);
+  if (rc == -2) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_debug_wave_cycles: the term statistics are on and their kernels carry no clocks: lhw_env_enable_term_stats(env, 0) first");
+  if (rc) return lhw_fail(LHW_ERR_HIP, "wave cycle buffer");
   return LHW_OK;
 }
 

@@ -4,12 +4,14 @@
 
 #include "lhw_humanoid_dev.h"
 
-// Two kernel families from one text: humanoid_kernel, and humanoid_stats_kernel, which also keeps the per-term episode statistics
-// (control_step<.., STATS>) and is launched instead (MODE 0, 1) while lhw_env_enable_term_stats is in force.  Generated by a macro and not
-// through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
-#define DEFINE_HUMANOID_KERNEL(NAME, STATS) \
+// Three kernel families from one text: humanoid_kernel; humanoid_stats_kernel, which also keeps the per-term episode statistics
+// (control_step<.., STATS>) and is launched instead (MODE 0, 1) while lhw_env_enable_term_stats is in force; and humanoid_diag_kernel, which
+// also runs the phase clock and the wave clock (control_step<.., DIAG>) and is launched instead (MODE 0) while one of them is armed.  Generated
+// by a macro and not through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the
+// features.  The clocks and the statistics exclude each other (include/lhw.h), so there is no family with both.
+#define DEFINE_HUMANOID_KERNEL(NAME, STATS, DIAG) \
 template <int MODE, int TASK, int W>  /* MODE: 0 step, 1 reset(mask), 2 set_state, 3 get_state; TASK: TASK_WALK / TASK_STAND / TASK_STEP / TASK_H1WALK; W: lanes per env */         \
-__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, const float* __restrict__ act, \
+__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* __restrict__ bp, HLaunch lz, HState st, const float* __restrict__ act,                          \
                                                       float* __restrict__ obs, float* __restrict__ term_obs,                                                                        \
                                                       float* __restrict__ rew, unsigned char* __restrict__ done_out,                                                                \
                                                       float* __restrict__ rew_terms, const unsigned char* __restrict__ mask,                                                        \
@@ -19,8 +21,8 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
   __shared__ L SG[G];                                                                                                                                                               \
   LHW_LDS_POISON(SG);                                                                                                                                                               \
   const int lane = threadIdx.x & (W - 1);   /* lane within the env's group */                                                                                                       \
-  HParamsRef p = *(const HParams LHW_GLOBAL_AS*)pp;                                                                                                                                 \
-  HModelRef m = *(const HModel LHW_GLOBAL_AS*)mp;   /* (a register copy of the whole record was measured: +3.5 %, its ~100 scalars crowd the SGPR file) */                          \
+  HParamsRef p = LHW_BLOCK_PARAMS(bp);                                                                                                                                              \
+  HModelRef m = LHW_BLOCK_MODEL(bp);                /* (a register copy of the whole record was measured: +3.5 %, its ~100 scalars crowd the SGPR file) */                          \
   if constexpr (MODE == 0 && W == 64) {                                                                                                                                             \
     /* One call site for both uses of the one-env-per-wave step kernel.  As the re-run behind the two-envs-per-wave kernel */                                                       \
     /* (only_flagged) it is launched with FEW workgroups, each scanning the flags of `chunk` <= 64 consecutive envs and stepping */                                                 \
@@ -37,18 +39,19 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
     while (todo) {                                                                                                                                                                  \
       const int i = __ffsll(todo) - 1;                                                                                                                                              \
       todo &= todo - 1;                                                                                                                                                             \
-      control_step<MODE, TASK, W, STATS>(m, p, lz, st, SG, SG[0], lz.env_first + e0 + i, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                               \
+      control_step<MODE, TASK, W, STATS, DIAG>(m, p, lz, st, SG, SG[0], lz.env_first + e0 + i, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                               \
     }                                                                                                                                                                               \
   } else {                                                                                                                                                                          \
     const int eidx = blockIdx.x * G + group_id<W>();                                                                                                                                \
     if (eidx >= lz.env_count) return;                                                                                                                                               \
     const int env = eidx + lz.env_first;                                                                                                                                            \
     if (MODE == 1 && mask && !mask[env]) return;                                                                                                                                    \
-    control_step<MODE, TASK, W, STATS>(m, p, lz, st, SG, SG[group_id<W>()], env, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                                       \
+    control_step<MODE, TASK, W, STATS, DIAG>(m, p, lz, st, SG, SG[group_id<W>()], env, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                                       \
   }                                                                                                                                                                                 \
 }
-DEFINE_HUMANOID_KERNEL(humanoid_kernel, false)
-DEFINE_HUMANOID_KERNEL(humanoid_stats_kernel, true)
+DEFINE_HUMANOID_KERNEL(humanoid_kernel, false, false)
+DEFINE_HUMANOID_KERNEL(humanoid_stats_kernel, true, false)
+DEFINE_HUMANOID_KERNEL(humanoid_diag_kernel, false, true)
 
 // ------------------------------------------------------------------------------------------------ host side
 static void h_quat2mat(double* R, const double* q) {
@@ -63,10 +66,10 @@ template <typename T>
 static DevTab<T> to_dev(HumanoidEnv* h, const T* src, size_t n) { return DevTab<T>{h->mem.put(src, n)}; }
 
 static bool humanoid_upload_params(HumanoidEnv* h) {
-  if (!h->p_dev) h->p_dev = h->mem.get<HParams>(1, LhwDevMem::RAW);
-  if (!h->m_dev) h->m_dev = h->mem.get<HModel>(1, LhwDevMem::RAW);
-  return h->p_dev && h->m_dev && hipMemcpy(h->p_dev, &h->p, sizeof(HParams), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(h->m_dev, &h->m, sizeof(HModel), hipMemcpyHostToDevice) == hipSuccess;
+  // (two copies into the one block: the host keeps m and p apart, and the padding between them is never read)
+  if (!h->b_dev) h->b_dev = h->mem.get<HDevBlock>(1, LhwDevMem::RAW);
+  return h->b_dev && hipMemcpy(&h->b_dev->p, &h->p, sizeof(HParams), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(&h->b_dev->m, &h->m, sizeof(HModel), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // The steps of humanoid_create, in the order they run, and what one step hands to the next.
@@ -578,7 +581,7 @@ int HumanoidCreate::reset_template(HumanoidEnv* h) {
     // reset the template record (index N) once with the ordinary reset kernel; auto-resets copy its state from then on
     if (!humanoid_upload_params(h)) return lhw_fail(LHW_ERR_HIP, "humanoid_create: parameter upload failed");
     const HLaunch lz{(int)N, 1, 0, 0, 0};
-    hipLaunchKernelGGL((humanoid_kernel<1, TASK_WALK, 64>), dim3(1), dim3(64), 0, 0, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, h->st, (const float*)nullptr, (float*)nullptr,
+    hipLaunchKernelGGL((humanoid_kernel<1, TASK_WALK, 64>), dim3(1), dim3(64), 0, 0, (const HDevBlock*)h->b_dev, lz, h->st, (const float*)nullptr, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, (double*)nullptr,
                        (double*)nullptr);
     if (hipDeviceSynchronize() != hipSuccess) return lhw_fail(LHW_ERR_HIP, "humanoid_create: reset template launch failed");
@@ -615,9 +618,9 @@ void humanoid_destroy(HumanoidEnv* h) { delete h; }   // (its LhwDevMem frees th
 #define LAUNCH_OTHER_TASKS(KERNEL, MODE, WIDTH, ...)
 #else
 #define LAUNCH_OTHER_TASKS(KERNEL, MODE, WIDTH, ...)                                                                \
-    else if (pp_.task == TASK_STEP) hipLaunchKernelGGL((KERNEL<MODE, TASK_STEP, 64>), grid_, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz_, h->st, __VA_ARGS__); \
-    else if (pp_.task == TASK_H1WALK) hipLaunchKernelGGL((KERNEL<MODE, TASK_H1WALK, WIDTH>), grid_, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz_, h->st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<MODE, TASK_STAND, WIDTH>), grid_, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz_, h->st, __VA_ARGS__);
+    else if (pp_.task == TASK_STEP) hipLaunchKernelGGL((KERNEL<MODE, TASK_STEP, 64>), grid_, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz_, h->st, __VA_ARGS__); \
+    else if (pp_.task == TASK_H1WALK) hipLaunchKernelGGL((KERNEL<MODE, TASK_H1WALK, WIDTH>), grid_, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz_, h->st, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<MODE, TASK_STAND, WIDTH>), grid_, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz_, h->st, __VA_ARGS__);
 #endif
 #define LAUNCH_RANGE_K(KERNEL, MODE, WIDTH, FLAGGED, FIRST, COUNT, ...)                                                   \
   do {                                                                                                             \
@@ -626,12 +629,14 @@ void humanoid_destroy(HumanoidEnv* h) { delete h; }   // (its LhwDevMem frees th
     /* the re-run launch scans the flags with few workgroups (at most 64 envs each): see humanoid_kernel */           \
     const int full_ = (lz_.env_count + (64 / WIDTH) - 1) / (64 / WIDTH);                                            \
     const dim3 grid_((FLAGGED) ? std::min(full_, std::max(256, (lz_.env_count + 63) / 64)) : full_);                \
-    if (pp_.task == TASK_WALK) hipLaunchKernelGGL((KERNEL<MODE, TASK_WALK, WIDTH>), grid_, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz_, h->st, __VA_ARGS__); \
+    if (pp_.task == TASK_WALK) hipLaunchKernelGGL((KERNEL<MODE, TASK_WALK, WIDTH>), grid_, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz_, h->st, __VA_ARGS__); \
     LAUNCH_OTHER_TASKS(KERNEL, MODE, WIDTH, __VA_ARGS__)                                                            \
   } while (0)
 // (MODE 0 / 1 while the per-term episode statistics are armed: the kernels that keep them)
+// (MODE 0 while the phase clock or the wave clock is armed: the kernels that run them; the statistics are off then, humanoid_set_term_stats)
 #define LAUNCH_RANGE(MODE, WIDTH, FLAGGED, FIRST, COUNT, ...)                                                       \
   do {                                                                                                             \
+    if ((MODE) == 0 && humanoid_diag_armed(h)) { LAUNCH_RANGE_K(humanoid_diag_kernel, 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__); break; } \
     if ((MODE) > 1 || !h->p.tstat) { LAUNCH_RANGE_K(humanoid_kernel, MODE, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__); break; } \
     LAUNCH_RANGE_K(humanoid_stats_kernel, (MODE) <= 1 ? (MODE) : 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__);    \
   } while (0)
@@ -675,6 +680,7 @@ void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, 
 double* humanoid_ep_stats(HumanoidEnv* h) { return h->st.ep_stats; }
 double* humanoid_term_stats(HumanoidEnv* h) { return h->p.tstat; }
 int humanoid_set_term_stats(HumanoidEnv* h, double* block) {
+  if (block && humanoid_diag_armed(h)) return -2;   // (the kernels that keep the statistics carry no clocks)
   h->p.tstat = block;
   return humanoid_upload_params(h) ? 0 : -1;   // (the kernels read the task parameters from device memory)
 }
@@ -688,6 +694,7 @@ int humanoid_set_task_shaping(HumanoidEnv* h, const double* weights, int n_weigh
   for (int k = 0; limits && k < LHW_TERM_LIMIT_COUNT; k++) h->p.term_lim[k] = limits[k];
   return humanoid_upload_params(h) ? 0 : -1;
 }
+bool humanoid_diag_armed(const HumanoidEnv* h) { return h->st.prof || h->st.wave_cyc; }
 int humanoid_occupancy() {
   int nb = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, humanoid_kernel<0, TASK_WALK, 32>, 64, 0) != hipSuccess) return -1;
@@ -696,6 +703,7 @@ int humanoid_occupancy() {
 // diagnostic: per-env duration of the last control-step launch (load balance across wavefronts)
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out) {
   const size_t N = h->p.n_envs;
+  if (!h->st.wave_cyc && h->p.tstat) return -2;
   if (!h->st.wave_cyc) return (h->st.wave_cyc = h->mem.get_lazy<long long>(N + 1)) ? 0 : -1;
   if (!out) return 0;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -720,6 +728,7 @@ int humanoid_task_inputs(HumanoidEnv* h, bool step_record, int enable, double* o
   return 0;
 }
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16) {
+  if (enable && !h->st.prof && h->p.tstat) return -2;
   if (enable && !h->st.prof && !(h->st.prof = h->mem.get_lazy<long long>(16))) return -1;
   if (out16 && h->st.prof) {
     (void)hipDeviceSynchronize();

@@ -277,15 +277,26 @@ struct HParams {
                                         // site below lo (stepping: hi is +inf, it has none).  Uniform across the batch: scalar loads of p.  Added
                                         // behind tstat by the same rule
 };
+// What the stepper kernels read of an env's configuration, in ONE device allocation behind ONE kernel-argument pointer: the model record, and
+// the task parameters at a fixed, aligned offset behind it (the kernels form both references from the block's address; two argument pointers
+// were two SGPR pairs that the register allocator of the walking rollout kernel kept in spill lanes: profiles/r18_sgpr_working_set_ab.txt).
+struct HDevBlock {
+  HModel m;
+  alignas(256) HParams p;
+};
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const HModel LHW_GLOBAL_AS& HModelRef;
 typedef const HParams LHW_GLOBAL_AS& HParamsRef;
+#define LHW_BLOCK_MODEL(bp) (((const HDevBlock LHW_GLOBAL_AS*)(bp))->m)
+#define LHW_BLOCK_PARAMS(bp) (((const HDevBlock LHW_GLOBAL_AS*)(bp))->p)
 #else
 typedef const HModel& HModelRef;
 typedef const HParams& HParamsRef;
+#define LHW_BLOCK_MODEL(bp) ((bp)->m)
+#define LHW_BLOCK_PARAMS(bp) ((bp)->p)
 #endif
 
-// what changes from launch to launch (everything else of the task configuration sits in device memory: HumanoidEnv::p_dev)
+// what changes from launch to launch (everything else of the task configuration sits in device memory: HumanoidEnv::b_dev)
 struct HLaunch {
   int env_first, env_count;             // sub-range of envs this launch advances (lhw_env_step_range); blockIdx.x is relative to it
   int only_flagged;                     // 1: advance only the envs whose st.slow flag is set (re-run of fast-path overflows), clearing it
@@ -322,7 +333,20 @@ static __device__ long long g_fine_t;
 #define FINE_BEGIN(ph)
 #define FINE_MARK(ph, i)
 #endif
-#define PROF_BEGIN() long long prof_t = (st_prof && lane == 0) ? (long long)clock64() : 0   // lane = lane within the group
+// The two diagnostic clocks -- the phase clock of env 0 (HState::prof, lhw_env_phase_cycles) and the per-env wave clock (HState::wave_cyc,
+// lhw_env_debug_wave_cycles) -- exist in the DIAG = true instantiations of the kernels only, which the host launches while one of them is
+// armed.  A template parameter like STATS, and for a stronger reason: compiled into the product kernels, the clocks' values held 8 VGPRs and a
+// block of SGPR spill lanes across the whole kernel for a profiler nobody had armed (profiles/r18_sgpr_working_set_ab.txt).  With DIAG = false
+// the objects below are empty: no pointer, no time stamp, no shader-clock read.
+template <bool DIAG> struct PhaseClock {};
+template <> struct PhaseClock<true> {
+  long long* slots;   // HState::prof for env 0, NULL for the other envs and while the phase clock is not armed
+  long long t;        // shader clock at the last mark (lane 0 of the group)
+};
+template <bool DIAG> struct WaveClock {};
+template <> struct WaveClock<true> { long long t; };   // shader clock at the start of the control step / of the rollout's chunk
+// (all three inside function templates with a DIAG parameter and a PhaseClock<DIAG> pc; lane = lane within the group)
+#define PROF_BEGIN() do { if constexpr (DIAG) pc.t = (pc.slots && lane == 0) ? (long long)clock64() : 0; } while (0)
 #ifdef LHW_ASM_MARKS   // (analysis builds: phase boundaries as comments in the ISA listing)
 #define ASM_MARK(slot) asm volatile("; LHW_PHASE " #slot)
 #else
@@ -331,12 +355,15 @@ static __device__ long long g_fine_t;
 #define PROF_MARK(slot)                                                  \
   do {                                                                   \
     ASM_MARK(slot);                                                      \
-    if (st_prof && lane == 0) {                                          \
-      long long now_ = (long long)clock64();                             \
-      st_prof[slot] += now_ - prof_t;                                    \
-      prof_t = now_;                                                     \
+    if constexpr (DIAG) {                                                \
+      if (pc.slots && lane == 0) {                                       \
+        long long now_ = (long long)clock64();                           \
+        pc.slots[slot] += now_ - pc.t;                                   \
+        pc.t = now_;                                                     \
+      }                                                                  \
     }                                                                    \
   } while (0)
+#define PROF_COUNT(slot) do { if constexpr (DIAG) { if (pc.slots && lane == 0) pc.slots[slot] += 1; } } while (0)   // pass counters of env 0
 
 // Many contacts in the stepping task (one env per wave).  Every walk mode but FORWARD leaves the 20 terrain boxes coplanar with the
 // floor (tasks/stepping_task.py:320-334), so a foot rests on the floor AND on every box under it: 16 (STANDING) to ~110 (LATERAL)
@@ -391,11 +418,10 @@ static __device__ long long g_fine_t;
 struct HumanoidEnv {
   HModel m;
   HParams p;
-  HModel* m_dev;    // device copy of m (same reason)
-  HParams* p_dev;   // device copy the kernels read (passed by pointer: its fields need not live in SGPRs across the sub-steps)
+  HDevBlock* b_dev; // device copy of m and p the kernels read (passed by pointer: its fields need not live in SGPRs across the sub-steps)
   int iteration;
   HState st;
-  LhwDevMem mem;    // every device block of the env (p_dev, m_dev, the tables of p, the records of st, ro_queue)
+  LhwDevMem mem;    // every device block of the env (b_dev, the tables of p, the records of st, ro_queue)
   int device;
   bool fast;   // the model fits the two-envs-per-wave kernels (W = 32)
   unsigned* ro_queue = nullptr;   // job counter + per-group progress words of the resident rollout's queue mode (lhw_humanoid_rollout.hip)
@@ -2727,8 +2753,8 @@ __device__ __noinline__ void newton_big(HModelRef m, HParamsRef p, L& S, const i
 // Everything of the sub-step behind the joint-space inertia: constraint rows, smooth acceleration, Newton, Euler.
 // Dofs sit in the half-env-per-DPP-row layout of the chain solver: a root dof is held by two lanes, `prim` marks the one that
 // counts in sums over dofs and writes the dof's results.  `cross`: some contact couples the two chains (group-uniform).
-template <class L>
-__device__ __forceinline__ void solve_tail(HModelRef m, HParamsRef p, L& S, const int lane, const int flags, long long* st_prof,
+template <bool DIAG, class L>
+__device__ __forceinline__ void solve_tail(HModelRef m, HParamsRef p, L& S, const int lane, const int flags, PhaseClock<DIAG> pc,
                                            const int dof, const bool prim, const bool cross, const double (&Mrow)[NR], const double mdiag,
                                            const double marm, const double qapp, const double bias, gws_d bd, gws_i bi) {
   constexpr int W = L::W_;
@@ -2963,7 +2989,7 @@ __device__ __forceinline__ void solve_tail(HModelRef m, HParamsRef p, L& S, cons
     // (the products of the start point were formed for the warm-start comparison: round 4, same box -0.5 %)
     if (warm_have) { ja_run = warm_pick_s ? warm_js : warm_jw; Ma_run = warm_pick_s ? mprod(as) : warm_Ma; have_prod = true; }
     for (int iter = 0; iter <= m.iterations; iter++) {
-      if (st_prof && lane == 0) st_prof[6] += 1;    // diagnostic: Newton passes (cost evaluations) of env 0
+      PROF_COUNT(6);    // diagnostic: Newton passes (cost evaluations) of env 0
       // J qacc and M qacc: computed for the first iterate, then advanced with the step (J search and M search exist for the line
       // search anyway) -- mj_solNewton's own bookkeeping (engine_solver.c: Jaref += alpha jv, Ma += alpha Mv).  Round 4, same box:
       // control step -1.5 % (round 3 measured +1 %: two more values live across the line search then cost spills)
@@ -3115,7 +3141,7 @@ __device__ __forceinline__ void solve_tail(HModelRef m, HParamsRef p, L& S, cons
           const double d0 = fabs(d1);
           double lo = 0, hi = -1;
           for (int it = 0; it < 40; it++) {
-            if (st_prof && lane == 0) st_prof[14] += 1;   // diagnostic: line-search passes of env 0
+            PROF_COUNT(14);   // diagnostic: line-search passes of env 0
             double a = alpha - qdiv(d1, d2);
             if (hi >= 0 && (a <= lo || a >= hi)) a = 0.5 * (lo + hi);
             deriv_rows(a, &r1, &r2);
@@ -3186,8 +3212,8 @@ __device__ __forceinline__ void solve_tail(HModelRef m, HParamsRef p, L& S, cons
 // Jacobians are +-unit vectors -- are three scalars slots of their dof's lane (0 frictionloss, 1 lower limit, 2 upper limit):
 // J x is the lane's own element, J^T f lands on the lane's own dof, J^T D J on its own diagonal entry.  Only the summation
 // order differs from the row order of the reference; every row is there.
-template <bool BOXBOX, class L>
-__device__ __forceinline__ void substep(HModelRef m, HParamsRef p, L* SG0, int flags, long long* st_prof, gtab_d ter, gws_d bd, gws_i bi) {
+template <bool BOXBOX, bool DIAG, class L>
+__device__ __forceinline__ void substep(HModelRef m, HParamsRef p, L* SG0, int flags, PhaseClock<DIAG> pc, gtab_d ter, gws_d bd, gws_i bi) {
   constexpr int W = L::W_;
 #if defined(__HIP_DEVICE_COMPILE__) && defined(LHW_SUBSTEP_PRIO)
   // (Resident rollout kernels only -- lhw_humanoid_rollout.hip defines LHW_SUBSTEP_PRIO.  In the launch-per-step pipeline the
@@ -3213,8 +3239,7 @@ __device__ __forceinline__ void substep(HModelRef m, HParamsRef p, L* SG0, int f
     if ((hw ^ ph) & 1u) __builtin_amdgcn_s_setprio(LHW_PRIO_LEVEL); else __builtin_amdgcn_s_setprio(0);
   }
 #endif
-  long long prof_t;
-  { FRESH_GROUP(W, SG0); prof_t = (st_prof && lane == 0) ? (long long)clock64() : 0; fwd_kinematics<BOXBOX>(m, S, lane); PROF_MARK(0); }
+  { FRESH_GROUP(W, SG0); PROF_BEGIN(); fwd_kinematics<BOXBOX>(m, S, lane); PROF_MARK(0); }
   { FRESH_GROUP(W, SG0); fwd_collision<BOXBOX>(m, p, S, lane, ter, bd, bi); PROF_MARK(3); }   // stage A temporaries (geom frames) die with fwd_com
   FRESH_GROUP(W, SG0);
   // The chain solver needs the [root | chain A | chain B] block structure of M (checked at create).  A contact between bodies
@@ -3235,7 +3260,7 @@ __device__ __forceinline__ void substep(HModelRef m, HParamsRef p, L* SG0, int f
   double Mrow[NR], mdiag, marm, bias, qapp;
   chain_dynamics(m, p, S, lane, dof, prim, Mrow, mdiag, marm, bias, qapp);
   PROF_MARK(5);
-  solve_tail(m, p, S, lane, flags, st_prof, dof, prim, cross, Mrow, mdiag, marm, qapp, bias, bd, bi);
+  solve_tail<DIAG>(m, p, S, lane, flags, pc, dof, prim, cross, Mrow, mdiag, marm, qapp, bias, bd, bi);
 }
 // ------------------------------------------------------------------------------------------------ task layer
 __device__ __forceinline__ void sample_ref(HParamsRef p, unsigned genv, unsigned stream, unsigned counter, unsigned slot0,
@@ -3378,16 +3403,17 @@ struct LayoutOf {
                ((TASK == TASK_STEP || W == 64) ? NG : 16), (W == 64 ? NB : ((TASK == TASK_STAND || TASK == TASK_H1WALK) ? 15 : 18)), TASK == TASK_STEP> type;
 };
 
-template <int MODE, int TASK, int W>
+template <int MODE, int TASK, int W, bool DIAG>
 __device__ __forceinline__ bool store_record(HModelRef m, const HLaunch& lz, const HState& st, typename LayoutOf<TASK, W>::type* SG0, const int env,
-                                             const long long t_launch);
+                                             const WaveClock<DIAG> wc);
 
 // One control step (MODE 0), reset (1), set_state (2) or get_state (3) of env `env` by the group of W lanes that calls it
 // (`lane` = lane within the group, S = the group's LDS working set).  Returns true iff the env exceeded the contact capacity
 // of the two-envs-per-wave layout before anything of this control step was written: the caller repeats the step with W = 64.
 // STATS: the instantiation that also keeps the per-term episode statistics (HParams::tstat).  A template parameter and not a run-time
 // branch: the kernels launched while the statistics are off are, instruction for instruction, the kernels without the feature.
-template <int MODE, int TASK, int W, bool STATS = false>
+// DIAG: the instantiation that also runs the phase clock and the wave clock (PhaseClock / WaveClock above).
+template <int MODE, int TASK, int W, bool STATS = false, bool DIAG = false>
 __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, typename LayoutOf<TASK, W>::type* SG0,
                                              typename LayoutOf<TASK, W>::type& S, const int env,
                                              const int lane, const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ term_obs,
@@ -3403,10 +3429,13 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
   const int OBS = TASK == TASK_WALK ? 37 : (TASK == TASK_STEP ? 39 : (TASK == TASK_H1WALK ? 43 : 35));
   int* irec = st.irec + (size_t)env * REC_I;
   const unsigned genv = p.env_id_base + env;
-  long long* sprof = (env == 0) ? st.prof : nullptr;
-  long long* st_prof = sprof;
+  PhaseClock<DIAG> pc;
+  WaveClock<DIAG> wc;
+  if constexpr (DIAG) {
+    pc.slots = (env == 0) ? st.prof : nullptr;
+    wc.t = (MODE == 0 && st.wave_cyc) ? (long long)clock64() : 0;
+  }
   PROF_BEGIN();
-  const long long t_launch = (MODE == 0 && st.wave_cyc) ? (long long)clock64() : 0;
   if (MODE == 3) {
     if (lane < m.nq) xq[(size_t)env * m.nq + lane] = rec[R_QPOS + lane];
     if (lane < NV) xv[(size_t)env * NV + lane] = rec[R_QVEL + lane];
@@ -4013,7 +4042,7 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
     // (Every phase of the sub-step takes its lane index from fresh_wave_lane(): besides keeping the addresses built from it out of
     // scratch, the opaque value keeps the ~100 model-table loads of a sub-step -- indexed by the lane, invariant across the 25
     // sub-steps -- inside the loop.  Hoisted, they would be parked in scratch and reloaded from there, FETCH_SIZE 708 MB per launch.)
-    substep<TASK == TASK_STEP>(m, p, SG0, flags, sprof, (gtab_d)ter,
+    substep<TASK == TASK_STEP, DIAG>(m, p, SG0, flags, pc, (gtab_d)ter,
                                (TASK == TASK_STEP && W == 64 && st.bigd) ? (gws_d)(st.bigd + (size_t)env * BW_DOUBLES) : (gws_d) nullptr,
                                (TASK == TASK_STEP && W == 64 && st.bigd) ? (gws_i)(st.bigi + (size_t)env * BW_INTS) : (gws_i) nullptr);
     if (stage == ST_LAST) break;
@@ -4027,13 +4056,13 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
   PROF_MARK(10);
   // ---- store the record
   SYNC();
-  return store_record<MODE, TASK, W>(m, lz, st, SG0, env, t_launch);
+  return store_record<MODE, TASK, W, DIAG>(m, lz, st, SG0, env, wc);
 }
 
 // The persistent record goes back to HBM (lane-strided); everything it needs is re-derived from the env index and a fresh lane.
-template <int MODE, int TASK, int W>
+template <int MODE, int TASK, int W, bool DIAG>
 __device__ __forceinline__ bool store_record(HModelRef m, const HLaunch& lz, const HState& st, typename LayoutOf<TASK, W>::type* SG0, const int env,
-                                             const long long t_launch) {
+                                             const WaveClock<DIAG> wc) {
   using L = typename LayoutOf<TASK, W>::type;
   FRESH_GROUP(W, SG0);
   double* rec = st.rec + (size_t)env * REC_D;
@@ -4050,7 +4079,7 @@ __device__ __forceinline__ bool store_record(HModelRef m, const HLaunch& lz, con
     irec[dst] = S.ci[lane];
   }
   if (lane == 0 && MODE == 0 && lz.only_flagged) { st.slow[env] = 0; atomicAdd(&st.ep_stats[5], 1.0); }
-  if (MODE == 0 && st.wave_cyc && lane == 0) st.wave_cyc[env] = (long long)clock64() - t_launch;
+  if constexpr (DIAG) { if (MODE == 0 && st.wave_cyc && lane == 0) st.wave_cyc[env] = (long long)clock64() - wc.t; }
   return false;
 }
 

@@ -530,7 +530,7 @@ __device__ __forceinline__ void lstm_policy_step(const LhwRolloutLstmPolicy& q, 
 }
 
 // Control steps [t0, t1) of env group `grp` of the range (the G envs one wave advances together).
-template <int TASK, int W, bool STATS, int PK>
+template <int TASK, int W, bool STATS, bool DIAG, int PK>
 __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro, unsigned char* SGraw, int grp,
                                               int t0, int t1) {
   using L = typename LayoutOf<TASK, W>::type;
@@ -542,14 +542,18 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
   const int env0 = lz.env_first + eidx0;
   const int OBS = humanoid_base_obs_dim(TASK);
   const size_t N = (size_t)ro.n_total;
-  // (diagnostic, lhw_env_debug_wave_cycles: shader-clock cycles the group's control steps took, summed over the rollout's chunks;
-  //  control_step leaves the last step's own figure in the same word, so the running sum is picked up before the chunk's first step)
-  long long cyc_before = 0;
-  if (st.wave_cyc && t0 > 0) {
-    const int wl = fresh_wave_lane();
-    if ((wl & (W - 1)) == 0 && (W == 32 ? (wl >> 5) : 0) < nlive) cyc_before = st.wave_cyc[env0 + (W == 32 ? (wl >> 5) : 0)];
+  // (diagnostic, lhw_env_debug_wave_cycles, DIAG instantiations only: shader-clock cycles the group's control steps took, summed over the
+  //  rollout's chunks; control_step leaves the last step's own figure in the same word, so the running sum is picked up before the chunk's
+  //  first step)
+  WaveClock<DIAG> wc, wc_before;
+  if constexpr (DIAG) {
+    wc_before.t = 0;
+    if (st.wave_cyc && t0 > 0) {
+      const int wl = fresh_wave_lane();
+      if ((wl & (W - 1)) == 0 && (W == 32 ? (wl >> 5) : 0) < nlive) wc_before.t = st.wave_cyc[env0 + (W == 32 ? (wl >> 5) : 0)];
+    }
+    wc.t = st.wave_cyc ? (long long)clock64() : 0;
   }
-  const long long t_begin = st.wave_cyc ? (long long)clock64() : 0;
   for (int t = t0; t < t1; t++) {
     GROUP_SYNC(64);
     // what this wave wrote in the previous control step (the observation rows it now reads; after a W = 64 re-run, by other
@@ -601,7 +605,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     HLaunch lzt = lz;
     lzt.tin_off = (long long)t * ro.tin_step;   // (the batched sim facade of EVERY control step, for reward-only task plug-ins: lhw_env_rollout_task_inputs)
     if (g < nlive)
-      ovf = control_step<0, TASK, W, STATS>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+      ovf = control_step<0, TASK, W, STATS, DIAG>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
 #ifndef LHW_RO_NO_RERUN   // (analysis builds: without the in-wave re-run, to see what its code costs the hot path -- nothing measurable)
     if constexpr (W == 32) {
       GROUP_SYNC(64);
@@ -614,7 +618,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
           if ((ob >> (32 * gg)) & 1ull) {
             SYNC();
             // (as a call -- it is rare -- the kernel spills 12 fewer VGPRs and 200 fewer SGPRs and is 9 % SLOWER: profiles/r05_calls_and_scratch.txt)
-            control_step<0, TASK, 64, STATS>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+            control_step<0, TASK, 64, STATS, DIAG>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
           }
       }
     }
@@ -628,10 +632,12 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
       //  history: the one at the top of the loop, and the one behind the chunk in the job loop)
     }
   }
-  if (st.wave_cyc) {
-    const int wl = fresh_wave_lane();
-    const int g = W == 32 ? (wl >> 5) : 0;
-    if ((wl & (W - 1)) == 0 && g < nlive) st.wave_cyc[env0 + g] = cyc_before + ((long long)clock64() - t_begin);
+  if constexpr (DIAG) {
+    if (st.wave_cyc) {
+      const int wl = fresh_wave_lane();
+      const int g = W == 32 ? (wl >> 5) : 0;
+      if ((wl & (W - 1)) == 0 && g < nlive) st.wave_cyc[env0 + g] = wc_before.t + ((long long)clock64() - wc.t);
+    }
   }
 }
 
@@ -646,9 +652,9 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 // Kernel families from one text (each once more for the LSTM actor, policy kind POLICY_LSTM, and for the observation history, POLICY_HIST): humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
 // statistics (control_step<.., STATS>) and is launched instead while lhw_env_enable_term_stats is in force.  Generated by a macro and not
 // through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
-#define DEFINE_ROLLOUT_KERNEL(NAME, STATS, PK) \
+#define DEFINE_ROLLOUT_KERNEL(NAME, STATS, DIAG, PK) \
 template <int TASK, int W, bool QUEUE>                                                                                                                              \
-__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __restrict__ mp, const HParams* __restrict__ pp, HLaunch lz, HState st, typename RolloutOf<PK>::type ro) { \
+__global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* __restrict__ bp, HLaunch lz, HState st, typename RolloutOf<PK>::type ro) {                          \
   using L = typename LayoutOf<TASK, W>::type;                                                                                                                       \
   using L1 = typename LayoutOf<TASK, 64>::type;                                                                                                                     \
   constexpr int G = 64 / W;                                                                                                                                         \
@@ -657,12 +663,12 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
   static_assert(L::USIZE_ * 2 - 48 >= PolicyLdsOf<PK, G>::FLOATS, "the policy step's activations must fit the stage region in front of the observation staging");         \
   __shared__ __attribute__((aligned(16))) unsigned char SGraw[LDS_BYTES];                                                                                           \
   LHW_LDS_POISON(SGraw);                                                                                                                                            \
-  HParamsRef p = *(const HParams LHW_GLOBAL_AS*)pp;                                                                                                                 \
-  HModelRef m = *(const HModel LHW_GLOBAL_AS*)mp;                                                                                                                   \
+  HParamsRef p = LHW_BLOCK_PARAMS(bp);                                                                                                                              \
+  HModelRef m = LHW_BLOCK_MODEL(bp);                                                                                                                                \
   const int n_groups = (lz.env_count + G - 1) / G;                                                                                                                  \
   if constexpr (!QUEUE) {                                                                                                                                           \
     if ((int)blockIdx.x >= n_groups) return;                                                                                                                        \
-    rollout_steps<TASK, W, STATS, PK>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
+    rollout_steps<TASK, W, STATS, DIAG, PK>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
   } else {                                                                                                                                                          \
     const int n_chunks = (ro.T + ro.chunk - 1) / ro.chunk;                                                                                                          \
     for (;;) {                                                                                                                                                      \
@@ -674,31 +680,39 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HModel* __r
       const int t0 = c * ro.chunk, t1 = min(ro.T, t0 + ro.chunk);                                                                                                   \
       /* the group's previous chunk was popped n_groups - 1 jobs ago by a wave that is running: it ends without waiting for anyone */                               \
       while (lhw_load_agent(ro.queue + 1 + grp) < (unsigned)c) __builtin_amdgcn_s_sleep(32);                                                                        \
-      rollout_steps<TASK, W, STATS, PK>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
+      rollout_steps<TASK, W, STATS, DIAG, PK>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
       __threadfence();   /* the group's records, observations and flags of this chunk, before the chunk counts as done */                                           \
       if (fresh_wave_lane() == 0) lhw_store_agent(ro.queue + 1 + grp, (unsigned)(c + 1));                                                                           \
     }                                                                                                                                                               \
   }                                                                                                                                                                 \
 }
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false, POLICY_MLP)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, POLICY_MLP)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false, false, POLICY_MLP)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, false, POLICY_MLP)
+// ... and with the diagnostic clocks (control_step<.., DIAG>, rollout_steps' wave clock), launched instead while one of them is armed.  The
+// plain feed-forward family only: with a clock armed, a rollout of any other family is declined (humanoid_rollout, include/lhw.h)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_diag_kernel, false, true, POLICY_MLP)
 // the same two families with the LSTM actor's in-wave step (lhw_env_rollout_lstm)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, POLICY_LSTM)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, POLICY_LSTM)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, false, POLICY_LSTM)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, false, POLICY_LSTM)
 // ... and with the feed-forward actor on an observation history (lhw_env_rollout_history, history_len > 1): rows of up to PXW columns
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, POLICY_HIST)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, POLICY_HIST)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, false, POLICY_HIST)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, false, POLICY_HIST)
 
 // ------------------------------------------------------------------------------------------------ host side
-// A policy kind's two kernel families, plain and with the term statistics: the one place that names them.  The launch tables below are
-// built from it, so a kernel is instantiated where a table names it and nowhere else.
-template <int PK> using RolloutFn = void (*)(const HModel*, const HParams*, HLaunch, HState, typename RolloutOf<PK>::type);
-template <int PK, bool STATS, int TASK, int W, bool QUEUE>
+// A policy kind's kernel families -- plain, with the term statistics, with the diagnostic clocks (the feed-forward kind only: the other kinds'
+// cells stay empty) -- : the one place that names them.  The launch tables below are built from it, so a kernel is instantiated where a table
+// names it and nowhere else.  FAMILY: a table's first index.
+enum { FAMILY_PLAIN = 0, FAMILY_STATS = 1, FAMILY_DIAG = 2 };
+template <int PK> using RolloutFn = void (*)(const HDevBlock*, HLaunch, HState, typename RolloutOf<PK>::type);
+template <int PK, int FAMILY, int TASK, int W, bool QUEUE>
 constexpr RolloutFn<PK> rollout_kernel() {
+  constexpr bool STATS = FAMILY == FAMILY_STATS;
 #if defined(LHW_ONLY_WALK) && !defined(LHW_ROLLOUT_STEP_TU)   // (development builds: this unit compiles the jvrc_walk kernels only, the other tasks' cells stay empty)
   if constexpr (TASK != TASK_WALK) return nullptr; else
 #endif
-  if constexpr (PK == POLICY_LSTM) {
+  if constexpr (FAMILY == FAMILY_DIAG) {
+    if constexpr (PK == POLICY_MLP) return humanoid_rollout_diag_kernel<TASK, W, QUEUE>; else return nullptr;
+  } else if constexpr (PK == POLICY_LSTM) {
     if constexpr (STATS) return humanoid_rollout_lstm_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_lstm_kernel<TASK, W, QUEUE>;
   } else if constexpr (PK == POLICY_HIST) {
     if constexpr (STATS) return humanoid_rollout_hist_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_hist_kernel<TASK, W, QUEUE>;
@@ -712,34 +726,37 @@ constexpr RolloutFn<PK> rollout_kernel() {
 // (the two-envs-per-wave kernels are built with iterative-maxocc instead: _lib.EXTRA_FLAGS, profiles/r06_stepper_compiler_flags.txt) -- and the two
 // halves compile in parallel.
 template <int PK>
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st,
+void humanoid_rollout_launch_step(int family, bool queued, dim3 grid, hipStream_t s, const HDevBlock* b_dev, HLaunch lz, HState st,
                                   const typename RolloutOf<PK>::type& ro);
 #ifdef LHW_ROLLOUT_STEP_TU
 template <int PK>
-void humanoid_rollout_launch_step(bool stats, bool queued, dim3 grid, hipStream_t s, const HModel* m_dev, const HParams* p_dev, HLaunch lz, HState st,
+void humanoid_rollout_launch_step(int family, bool queued, dim3 grid, hipStream_t s, const HDevBlock* b_dev, HLaunch lz, HState st,
                                   const typename RolloutOf<PK>::type& ro) {
-  // [stats][not queued].  The plain family is named first, and the kinds are instantiated below in the order MLP, LSTM, HIST: the compiler
+  // [family][not queued].  The plain family is named first, and the kinds are instantiated below in the order MLP, LSTM, HIST: the compiler
   // emits kernels in the order it meets them, and theirs is then the order without the feature
-  static constexpr RolloutFn<PK> table[2][2] = {{rollout_kernel<PK, false, TASK_STEP, 64, true>(), rollout_kernel<PK, false, TASK_STEP, 64, false>()},
-                                                {rollout_kernel<PK, true, TASK_STEP, 64, true>(), rollout_kernel<PK, true, TASK_STEP, 64, false>()}};
-  hipLaunchKernelGGL(table[stats][!queued], grid, dim3(64), 0, s, m_dev, p_dev, lz, st, ro);
+  static constexpr RolloutFn<PK> table[3][2] = {{rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, false>()},
+                                                {rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, false>()},
+                                                {rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, false>()}};
+  const RolloutFn<PK> k = table[family][!queued];
+  if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, b_dev, lz, st, ro);   // (an empty cell: humanoid_rollout has declined the request)
 }
 #define ROLLOUT_STEP_KIND(PK) \
-  template void humanoid_rollout_launch_step<PK>(bool, bool, dim3, hipStream_t, const HModel*, const HParams*, HLaunch, HState, const typename RolloutOf<PK>::type&);
+  template void humanoid_rollout_launch_step<PK>(int, bool, dim3, hipStream_t, const HDevBlock*, HLaunch, HState, const typename RolloutOf<PK>::type&);
 ROLLOUT_STEP_KIND(POLICY_MLP) ROLLOUT_STEP_KIND(POLICY_LSTM) ROLLOUT_STEP_KIND(POLICY_HIST)
 #else
 int humanoid_last_rollout_queued(const HumanoidEnv* h) { return h->last_rollout_queued; }
 
 // the two-envs-per-wave launches of one policy kind
 template <int PK>
-static void rollout_launch_fast(HumanoidEnv* h, bool stats, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro) {
-  // [stats][task: walk, h1_walk, stand].  The plain family is named first: the compiler emits kernels in the order it meets them, and
+static void rollout_launch_fast(HumanoidEnv* h, int family, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro) {
+  // [family][task: walk, h1_walk, stand].  The plain family is named first: the compiler emits kernels in the order it meets them, and
   // theirs is then the order without the feature
-  static constexpr RolloutFn<PK> table[2][3] = {
-      {rollout_kernel<PK, false, TASK_WALK, 32, false>(), rollout_kernel<PK, false, TASK_H1WALK, 32, false>(), rollout_kernel<PK, false, TASK_STAND, 32, false>()},
-      {rollout_kernel<PK, true, TASK_WALK, 32, false>(), rollout_kernel<PK, true, TASK_H1WALK, 32, false>(), rollout_kernel<PK, true, TASK_STAND, 32, false>()}};
-  const RolloutFn<PK> k = table[stats][h->p.task == TASK_WALK ? 0 : (h->p.task == TASK_H1WALK ? 1 : 2)];
-  if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+  static constexpr RolloutFn<PK> table[3][3] = {
+      {rollout_kernel<PK, FAMILY_PLAIN, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_STAND, 32, false>()},
+      {rollout_kernel<PK, FAMILY_STATS, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_STATS, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_STATS, TASK_STAND, 32, false>()},
+      {rollout_kernel<PK, FAMILY_DIAG, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STAND, 32, false>()}};
+  const RolloutFn<PK> k = table[family][h->p.task == TASK_WALK ? 0 : (h->p.task == TASK_H1WALK ? 1 : 2)];
+  if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz, st, ro);
 }
 
 // everything of a resident rollout but the policy view (ro.pol, filled by the caller) and the checks (humanoid_rollout); -4 HIP error
@@ -788,10 +805,11 @@ static int rollout_launch(HumanoidEnv* h, typename RolloutOf<PK>::type& ro, cons
   }
   const dim3 grid(grid_n);
   h->last_rollout_queued = ro.queue != nullptr;
-  const bool stats = h->p.tstat != nullptr;   // per-term episode statistics armed: the kernels that keep them
-  if (h->fast) rollout_launch_fast<PK>(h, stats, grid, s, lz, st, ro);
+  // per-term episode statistics armed: the kernels that keep them; a diagnostic clock armed: the kernels that run it (never both: humanoid_rollout)
+  const int family = humanoid_diag_armed(h) ? FAMILY_DIAG : (h->p.tstat != nullptr ? FAMILY_STATS : FAMILY_PLAIN);
+  if (h->fast) rollout_launch_fast<PK>(h, family, grid, s, lz, st, ro);
 #ifndef LHW_ONLY_WALK
-  else humanoid_rollout_launch_step<PK>(stats, ro.queue != nullptr, grid, s, (const HModel*)h->m_dev, (const HParams*)h->p_dev, lz, st, ro);
+  else humanoid_rollout_launch_step<PK>(family, ro.queue != nullptr, grid, s, (const HDevBlock*)h->b_dev, lz, st, ro);
 #endif
   return 0;
 }
@@ -819,6 +837,8 @@ int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s) {
   } else if (!policy_fits(rq.mlp, h, obs_dim, rq.kind == POLICY_HIST ? PXW : PXK)) {
     return -2;
   }
+  // the diagnostic clocks exist in the plain feed-forward family only: no rollout that would silently record nothing
+  if (humanoid_diag_armed(h) && (rq.kind != POLICY_MLP || h->p.tstat)) return -5;
   if (!h->fast && h->p.task != TASK_STEP) return -3;   // a walking / standing model that does not fit the two-envs-per-wave layout (or LHW_ONE_ENV_PER_WAVE): launch-per-step only
   if (rq.kind == POLICY_MLP) {
     HRollout ro;

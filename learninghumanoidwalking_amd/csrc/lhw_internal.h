@@ -118,7 +118,8 @@ struct HumanoidRollout {
   const uint8_t* reset0 = nullptr;              // POLICY_LSTM
   int history_len = 1;                          // > 1: POLICY_HIST
 };
-int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s);   // -1 bad range, -2 / -3 unsupported, -4 HIP error
+// -1 bad range, -2 / -3 unsupported, -4 HIP error, -5 a diagnostic clock is armed and the rollout's kernel family has no clocks
+int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s);
 // width of a task's base observation (the kernels' TASK_* ids are the ABI's LHW_TASK_* values: lhw_humanoid.hip)
 constexpr int humanoid_base_obs_dim(int task) {
   return task == LHW_TASK_JVRC_WALK ? 37 : (task == LHW_TASK_JVRC_STEP ? 39 : (task == LHW_TASK_H1_WALK ? 43 : 35));
@@ -127,13 +128,17 @@ void humanoid_get_state(HumanoidEnv* h, double* qpos, double* qvel, hipStream_t 
 void humanoid_set_state(HumanoidEnv* h, const double* qpos, const double* qvel, hipStream_t s);
 double* humanoid_ep_stats(HumanoidEnv* h);
 double* humanoid_term_stats(HumanoidEnv* h);                   // the term-statistics block the kernels write (NULL = off)
-int humanoid_set_term_stats(HumanoidEnv* h, double* block);    // hands it to the kernels (NULL stops them); -1 HIP error
+int humanoid_set_term_stats(HumanoidEnv* h, double* block);    // hands it to the kernels (NULL stops them); -1 HIP error, -2 a diagnostic clock is armed
 // task shaping (lhw_env_set_task_shaping): weights [LHW_MAX_REWARD_TERMS] / limits [LHW_TERM_LIMIT_COUNT] of the host mirror; the setter
 // takes validated values (either half may be NULL), uploads the parameters and returns -1 on a HIP error
 void humanoid_get_task_shaping(const HumanoidEnv* h, double* weights, double* limits);
 int humanoid_set_task_shaping(HumanoidEnv* h, const double* weights, int n_weights, const double* limits);
 void humanoid_set_iteration(HumanoidEnv* h, int64_t it);
 int humanoid_occupancy();
+// The diagnostic clocks (phase clock: humanoid_profile, wave clock: humanoid_wave_cycles).  Once one is armed, control steps run the kernels
+// that carry the clocks (humanoid_diag_kernel, humanoid_rollout_diag_kernel); the term statistics have kernels of their own, without clocks,
+// so the two exclude each other: arming returns -2 while the statistics are on, -1 on a HIP error
+bool humanoid_diag_armed(const HumanoidEnv* h);
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
 // step_record: the stepping task's second record (LhwStepTaskInput) instead of LhwTaskInput; -1 HIP error, -2 not enabled
