@@ -399,6 +399,7 @@ def empty(*shape, dtype, device):
     return t
 
 
-def check(rc: int):
+def check(rc: int, L=None):
+    """raise LhwError with the error text of the library that returned `rc` (None: the GPU library)"""
     if rc != 0:
-        raise LhwError(rc, lib().lhw_last_error().decode(errors="replace"))
+        raise LhwError(rc, (lib() if L is None else L).lhw_last_error().decode(errors="replace"))

@@ -31,7 +31,8 @@ def _ptr(t):
 
 
 def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    """The current stream of a GPU device; None for a CPU one (a host build of the library, which takes a null stream)."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
 
 
 def history_update(prev_full: torch.Tensor, base_obs: torch.Tensor, term_base: torch.Tensor, done: torch.Tensor, base: int):
@@ -54,11 +55,15 @@ class BatchedEnv:
     ``max_traj_len > 0``.
     """
 
-    def __init__(self, model: Model, task: int, n_envs: int, *, device: int | torch.device = 0, history_len: int = 1, **config):
-        """`config`: the keywords of _lib.env_config (frame_skip, kp, kd, seed, max_traj_len, env_id_base, action_smoothing, ...)."""
-        if not torch.cuda.is_available():
+    def __init__(self, model: Model, task: int, n_envs: int, *, device: int | torch.device = 0, history_len: int = 1, library=None, **config):
+        """`config`: the keywords of _lib.env_config (frame_skip, kp, kd, seed, max_traj_len, env_id_base, action_smoothing, ...).
+        `library`: a ctypes handle of another build of the C ABI that _lib.declare was applied to (None: _lib.lib(), the GPU library);
+        only with one may `device` be a CPU device -- the buffers are then CPU tensors and the calls get a null stream."""
+        if library is None and not torch.cuda.is_available():
             raise _lib.LhwError(-5, "no GPU visible: BatchedEnv has no CPU fallback")
-        self.device = torch.device("cuda", device) if isinstance(device, int) else device
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if library is None and self.device.type != "cuda":
+            raise _lib.LhwError(-5, f"device {self.device}: BatchedEnv has no CPU fallback")
         self.model = model
         self.n_envs = int(n_envs)
         self.task = task
@@ -66,10 +71,9 @@ class BatchedEnv:
         cfg, _keep = _lib.env_config(task, self.n_envs, device=self.device.index or 0, **config)    # (_keep: until lhw_env_create has copied them)
         self.env_id_base = cfg.env_id_base      # global index of env 0: every RNG key of the kernels uses env_id_base + n
         self._h = ctypes.c_void_p()
-        L = _lib.lib()
-        _lib.check(L.lhw_env_create(self._ib.ctypes.data, self._ib.size, self._db.ctypes.data, self._db.size,
+        self._L = L = _lib.lib() if library is None else library
+        self._check(L.lhw_env_create(self._ib.ctypes.data, self._ib.size, self._db.ctypes.data, self._db.size,
                                     ctypes.byref(cfg), ctypes.byref(self._h)))
-        self._L = L
         # obs_history_len > 1 (base_humanoid_env.py:177-197): obs_dim is the full length.  The resident rollout shifts the history rows
         # inside the stepper's wavefronts (lhw_env_rollout_history); the launch-per-step calls (step / step_range / reset) get the base
         # observation from the kernels and shift the rows by a few torch ops per step (history_update) -- the same values
@@ -92,6 +96,14 @@ class BatchedEnv:
             self._tbase = torch.zeros(N, self.base_obs_dim, dtype=torch.float32, device=dev)
             self._full = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=dev)         # current full observation
 
+    def _check(self, rc: int):
+        _lib.check(rc, self._L)     # (the error text of this env's own library)
+
+    def _here(self, *tensors) -> bool:
+        """every tensor is on this env's device (the index compared only where both sides carry one: torch.device("cuda") has none)"""
+        d = self.device
+        return all(t.device.type == d.type and (t.device.index is None or d.index is None or t.device.index == d.index) for t in tensors)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._L.lhw_env_destroy(self._h)
@@ -107,12 +119,12 @@ class BatchedEnv:
         """Reset the envs whose mask byte is non-zero (None: all).  The first observation of the reset envs goes to `obs_out`
         ([N, obs_dim], rows of the other envs untouched) or, by default, to self.obs."""
         if mask is not None:
-            assert mask.dtype == torch.uint8 and mask.is_cuda and mask.numel() == self.n_envs
+            assert mask.dtype == torch.uint8 and self._here(mask) and mask.numel() == self.n_envs
         if obs_out is None or self.history_len > 1:     # (a history env always resets into its own buffer)
             obs_out = self.obs
         else:
-            assert obs_out.is_cuda and obs_out.dtype == torch.float32 and obs_out.is_contiguous() and obs_out.shape == self.obs.shape
-        _lib.check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(self._kernel_out(obs_out)[0]), _stream_ptr(self.device)))
+            assert self._here(obs_out) and obs_out.dtype == torch.float32 and obs_out.is_contiguous() and obs_out.shape == self.obs.shape
+        self._check(self._L.lhw_env_reset(self._h, _ptr(mask), _ptr(self._kernel_out(obs_out)[0]), _stream_ptr(self.device)))
         if self.history_len > 1:
             sel = slice(None) if mask is None else mask.bool()
             self._full[sel] = 0
@@ -137,13 +149,13 @@ class BatchedEnv:
     def step(self, act: torch.Tensor, obs_out: torch.Tensor | None = None, term_obs_out: torch.Tensor | None = None,
              rew_out: torch.Tensor | None = None, done_out: torch.Tensor | None = None):
         """act [N, act_dim] float32 on device.  Returns (obs, rew, done, term_obs) device tensors."""
-        assert act.is_cuda and act.dtype == torch.float32 and act.is_contiguous() and act.numel() == self.n_envs * self.act_dim
+        assert self._here(act) and act.dtype == torch.float32 and act.is_contiguous() and act.numel() == self.n_envs * self.act_dim
         obs = self.obs if obs_out is None else obs_out
         tob = self.term_obs if term_obs_out is None else term_obs_out
         rew = self.rew if rew_out is None else rew_out
         done = self.done if done_out is None else done_out
         kobs, ktob = self._kernel_out(obs, tob)
-        _lib.check(self._L.lhw_env_step(self._h, _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done), _ptr(self.rew_terms),
+        self._check(self._L.lhw_env_step(self._h, _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done), _ptr(self.rew_terms),
                                         _stream_ptr(self.device)))
         self._history(0, self.n_envs, obs, tob, done)
         return obs, rew, done, tob
@@ -152,9 +164,9 @@ class BatchedEnv:
                    done: torch.Tensor):
         """Advance envs [first, first + count) only, on the current stream.  All tensors are the FULL-batch buffers ([N, ...]);
         independent groups issued on different streams overlap on the GPU (no batch-wide barrier per control step)."""
-        assert act.is_cuda and act.dtype == torch.float32 and act.is_contiguous() and act.numel() == self.n_envs * self.act_dim
+        assert self._here(act) and act.dtype == torch.float32 and act.is_contiguous() and act.numel() == self.n_envs * self.act_dim
         kobs, ktob = self._kernel_out(obs, term_obs)
-        _lib.check(self._L.lhw_env_step_range(self._h, int(first), int(count), _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done),
+        self._check(self._L.lhw_env_step_range(self._h, int(first), int(count), _ptr(act), _ptr(kobs), _ptr(ktob), _ptr(rew), _ptr(done),
                                               _ptr(self.rew_terms), _stream_ptr(self.device)))
         self._history(int(first), int(first) + int(count), obs, term_obs, done)
 
@@ -201,19 +213,19 @@ class BatchedEnv:
         for x in flags:
             assert x.shape == (N,) and x.dtype == torch.uint8
         for x in bufs + tuple(flags):
-            assert x.is_cuda and x.is_contiguous()
+            assert self._here(x) and x.is_contiguous()
         if step_task_inputs is not None:
             assert task_inputs is not None, "the stepping record is exported together with the LhwTaskInput one"
             assert step_task_inputs.shape == (T, N, _lib.STEP_TASK_INPUT_DIM) and step_task_inputs.dtype == torch.float64
-            assert step_task_inputs.is_cuda and step_task_inputs.is_contiguous()
+            assert self._here(step_task_inputs) and step_task_inputs.is_contiguous()
         if task_inputs is not None:
-            assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and task_inputs.is_cuda and task_inputs.is_contiguous()
+            assert task_inputs.shape == (T, N, _lib.TASK_INPUT_DIM) and task_inputs.dtype == torch.float64 and self._here(task_inputs) and task_inputs.is_contiguous()
         tail = tuple(flags) + (task_inputs, step_task_inputs)[:records]
         rc = fn(self._h, ctypes.byref(policy), int(first), int(N - first if count is None else count), int(T), *head, *(_ptr(x) for x in bufs),
                 _ptr(self.rew_terms), *(_ptr(x) for x in tail), _stream_ptr(self.device))
         if rc == -4:
             return False
-        _lib.check(rc)
+        self._check(rc)
         return True
 
     def rollout_lstm(self, policy, T: int, obs: torch.Tensor, act: torch.Tensor, logp: torch.Tensor, term_obs: torch.Tensor, rew: torch.Tensor,
@@ -235,19 +247,19 @@ class BatchedEnv:
     def get_state(self):
         qpos = np.zeros((self.n_envs, self.nq))
         qvel = np.zeros((self.n_envs, self.nv))
-        _lib.check(self._L.lhw_env_get_state(self._h, qpos.ctypes.data, qvel.ctypes.data))
+        self._check(self._L.lhw_env_get_state(self._h, qpos.ctypes.data, qvel.ctypes.data))
         return qpos, qvel
 
     def set_state(self, qpos, qvel):
         qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(self.n_envs, self.nq)
         qvel = np.ascontiguousarray(qvel, dtype=np.float64).reshape(self.n_envs, self.nv)
-        _lib.check(self._L.lhw_env_set_state(self._h, qpos.ctypes.data, qvel.ctypes.data))
+        self._check(self._L.lhw_env_set_state(self._h, qpos.ctypes.data, qvel.ctypes.data))
 
     def task_shaping(self):
         """({term name: weight} in the order of rew_terms, (lo, hi)): the reward-term weights and termination bounds this env's kernels
         apply, read back from the library (lhw_env_get_task_shaping; humanoid tasks only)."""
         w, lim = np.zeros(self.n_terms), np.zeros(2)
-        _lib.check(self._L.lhw_env_get_task_shaping(self._h, w.ctypes.data, lim.ctypes.data))
+        self._check(self._L.lhw_env_get_task_shaping(self._h, w.ctypes.data, lim.ctypes.data))
         return dict(zip(REWARD_TERMS[self.task], w.tolist())), (float(lim[0]), float(lim[1]))
 
     def set_task_shaping(self, reward_weights=None, termination=None):
@@ -261,26 +273,26 @@ class BatchedEnv:
             w = _lib.shaping_weights(self.task, reward_weights, self.task_shaping()[0].values())
         if termination is not None:
             lim = np.array([float(x) for x in termination], dtype=np.float64)
-        _lib.check(self._L.lhw_env_set_task_shaping(self._h, w.ctypes.data if w is not None else None, 0 if w is None else w.size,
+        self._check(self._L.lhw_env_set_task_shaping(self._h, w.ctypes.data if w is not None else None, 0 if w is None else w.size,
                                                     lim.ctypes.data if lim is not None else None, 0 if lim is None else lim.size))
 
     def pop_episode_stats(self):
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
-        _lib.check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))
+        self._check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))
         return r.value, l.value, c.value
 
     def enable_term_stats(self, enable: bool = True):
         """Arm / disarm the per-term episode statistics (lhw_env_enable_term_stats): from the next control step on the kernels keep,
         per env, the running episode's sum of every reward term -- the `info` dictionary of the reference's env.step
         (robots/robot_base.py:88-96) -- and add it to global sums where the episode ends.  Arming zeroes all sums."""
-        _lib.check(self._L.lhw_env_enable_term_stats(self._h, int(bool(enable))))
+        self._check(self._L.lhw_env_enable_term_stats(self._h, int(bool(enable))))
 
     def pop_term_sums(self):
         """(term sums [n_terms] float64 over the episodes finished since the last call, terminated, truncated): the raw counters
         (what data-parallel ranks add up); running episodes keep their partial sums."""
         s = np.zeros(self.n_terms)
         ep, te, tr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self._L.lhw_env_pop_term_stats(self._h, s.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr)))
+        self._check(self._L.lhw_env_pop_term_stats(self._h, s.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr)))
         return s, te.value, tr.value
 
     def pop_term_stats(self) -> dict:
@@ -290,13 +302,13 @@ class BatchedEnv:
     def phase_cycles(self, enable=True):
         """Per-phase shader-clock cycles of env 0 since the last call (diagnostic, wave-per-env stepper only)."""
         out = np.zeros(16, dtype=np.int64)
-        _lib.check(self._L.lhw_env_phase_cycles(self._h, int(enable), out.ctypes.data))
+        self._check(self._L.lhw_env_phase_cycles(self._h, int(enable), out.ctypes.data))
         return out
 
     def pop_fault_stats(self):
         """(contact-overflow steps, diverged-env steps) since the last call."""
         a, b = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self._L.lhw_env_pop_fault_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        self._check(self._L.lhw_env_pop_fault_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def get_actuator_state(self):
@@ -304,41 +316,41 @@ class BatchedEnv:
         (reference robot_interface.py:163-185)."""
         nu = self.act_dim
         out = [np.zeros((self.n_envs, nu)) for _ in range(3)]
-        _lib.check(self._L.lhw_env_get_actuator_state(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+        self._check(self._L.lhw_env_get_actuator_state(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
         return tuple(out)
 
     def enable_task_inputs(self, enable: bool = True):
         """Arm / disarm the batched sim facade (include/lhw.h: LhwTaskInput): from the next control step on the kernel exports,
         per env, what the reference's tasks read through RobotInterface and what RobotBase.step passes to calc_reward."""
-        _lib.check(self._L.lhw_env_enable_task_inputs(self._h, int(bool(enable))))
+        self._check(self._L.lhw_env_enable_task_inputs(self._h, int(bool(enable))))
 
     def get_task_inputs(self) -> dict:
         """Named float64 arrays of the last control step's task inputs (host copy, synchronous)."""
         rec = np.zeros((self.n_envs, _lib.TASK_INPUT_DIM))
-        _lib.check(self._L.lhw_env_get_task_inputs(self._h, rec.ctypes.data))
+        self._check(self._L.lhw_env_get_task_inputs(self._h, rec.ctypes.data))
         return _lib.split_task_inputs(rec, self.nq, self.nv, self.act_dim)
 
     def enable_step_task_inputs(self, enable: bool = True):
         """Arm / disarm the stepping task's second record (include/lhw.h: LhwStepTaskInput; jvrc_step only): foot force sites,
         footstep targets, the target state machine and the root quaternion of every control step from the next one on."""
-        _lib.check(self._L.lhw_env_enable_step_task_inputs(self._h, int(bool(enable))))
+        self._check(self._L.lhw_env_enable_step_task_inputs(self._h, int(bool(enable))))
 
     def get_step_task_inputs(self) -> dict:
         """Named float64 arrays of the last control step's stepping record (host copy, synchronous)."""
         rec = np.zeros((self.n_envs, _lib.STEP_TASK_INPUT_DIM))
-        _lib.check(self._L.lhw_env_get_step_task_inputs(self._h, rec.ctypes.data))
+        self._check(self._L.lhw_env_get_step_task_inputs(self._h, rec.ctypes.data))
         return _lib.split_step_task_inputs(rec)
 
     def wave_cycles(self):
         """Per-env shader-clock cycles of the last control-step launch (diagnostic; the first call only arms the recording)."""
         out = np.zeros(self.n_envs, dtype=np.int64)
-        _lib.check(self._L.lhw_env_debug_wave_cycles(self._h, out.ctypes.data))
+        self._check(self._L.lhw_env_debug_wave_cycles(self._h, out.ctypes.data))
         return out
 
     def pop_rerun_count(self):
         """Control steps since the last call that needed the one-env-per-wave re-run (more than 8 contacts)."""
         a = ctypes.c_int64()
-        _lib.check(self._L.lhw_env_pop_rerun_count(self._h, ctypes.byref(a)))
+        self._check(self._L.lhw_env_pop_rerun_count(self._h, ctypes.byref(a)))
         return a.value
 
     def debug_step_record(self):
@@ -346,8 +358,8 @@ class BatchedEnv:
         seq = np.zeros((self.n_envs, 20, 6))
         fz = np.zeros(self.n_envs)
         ist = np.zeros((self.n_envs, 5), np.int32)
-        _lib.check(self._L.lhw_env_debug_step_record(self._h, seq.ctypes.data, fz.ctypes.data, ist.ctypes.data))
+        self._check(self._L.lhw_env_debug_step_record(self._h, seq.ctypes.data, fz.ctypes.data, ist.ctypes.data))
         return seq, fz, ist
 
     def set_iteration(self, it: int):
-        _lib.check(self._L.lhw_env_set_iteration(self._h, int(it)))
+        self._check(self._L.lhw_env_set_iteration(self._h, int(it)))

@@ -78,18 +78,22 @@ class WalkingTask:
 
 
 # The class make_batched instantiates.  None: batched_env.BatchedEnv, looked up at call time so that importing a spec needs no torch.
-# A module attribute because callers substitute it (an emulated backend, a recorder of the constructor arguments).
+# A module attribute because callers substitute it: a recorder of the constructor arguments.  (Another build of the library -- a host
+# emulation of the kernels -- needs no substitute: it is handed to make_batched as `library`.)
 BatchedEnv = None
 
 
 class BatchedFactory:
     """Mixin of every spec (cartpole included): the GPU env of ``env_args()``."""
 
-    def make_batched(self, n_envs, seed=0, device=0, max_traj_len=0, env_id_base=0):
+    def make_batched(self, n_envs, seed=0, device=0, max_traj_len=0, env_id_base=0, library=None):
+        """`library`: BatchedEnv's keyword of that name, passed on only when given."""
         cls = BatchedEnv
         if cls is None:
             from ..batched_env import BatchedEnv as cls
         model, task, kw = self.env_args()
+        if library is not None:
+            kw = dict(kw, library=library)
         env = cls(model, task, n_envs, seed=seed, device=device, max_traj_len=max_traj_len, env_id_base=env_id_base, **kw)
         shaping = self.task_shaping()
         if shaping is not None:      # (only then: a substituted backend without the method serves every config that does not shape the task)

@@ -91,7 +91,7 @@ def device_task_inputs(env) -> TaskInputs:
     if view is None:
         env.enable_task_inputs(True)
         p = ctypes.c_void_p()
-        _lib.check(env._L.lhw_env_task_inputs_device(env._h, ctypes.byref(p)))
+        env._check(env._L.lhw_env_task_inputs_device(env._h, ctypes.byref(p)))
         if not p.value:
             raise _lib.LhwError(-4, "this env exports no task inputs (humanoid tasks only)")
         rec = torch.as_tensor(_DevArray(p.value, (env.n_envs, _lib.TASK_INPUT_DIM)), device=env.device)
@@ -99,7 +99,7 @@ def device_task_inputs(env) -> TaskInputs:
         if env.task == TASK_JVRC_STEP:
             env.enable_step_task_inputs(True)
             q = ctypes.c_void_p()
-            _lib.check(env._L.lhw_env_step_task_inputs_device(env._h, ctypes.byref(q)))
+            env._check(env._L.lhw_env_step_task_inputs_device(env._h, ctypes.byref(q)))
             srec = torch.as_tensor(_DevArray(q.value, (env.n_envs, _lib.STEP_TASK_INPUT_DIM)), device=env.device)
         view = env._task_inputs_view = TaskInputs(rec, env.nq, env.nv, env.act_dim, srec)
     return view

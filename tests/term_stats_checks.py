@@ -11,12 +11,12 @@ ORDER_RTOL = 1e-9         # checks 4 / 5: the same float64 numbers added in anot
 
 
 def enable(env, on=True):
-    rc = env._L.lhw_env_enable_term_stats(env._h, int(on))
-    assert rc == 0, env._L.lhw_last_error()
+    env.enable_term_stats(on)
 
 
 def pop(env):
-    """(term sums [n_terms], episodes, terminated, truncated)"""
+    """(term sums [n_terms], episodes, terminated, truncated): the raw call, for the library's own `episodes` counter -- BatchedEnv.pop_term_sums
+    returns the two kinds of ending only, and check_counts holds the three numbers against each other"""
     s = np.zeros(env.n_terms)
     ep, te, tr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     rc = env._L.lhw_env_pop_term_stats(env._h, s.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr))

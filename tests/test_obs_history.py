@@ -57,3 +57,46 @@ def test_spec_dimensions_and_normalisation_follow_the_history_length(tmp_path):
     assert (s1.base_obs_dim, s1.history_len, s1.obs_dim, len(s1.obs_mean)) == (37, 1, 37, 37) and s1.mirror_tables() is not None
     st = JvrcStepSpec(yaml_path=str(y))
     assert (st.base_obs_dim, st.obs_dim, len(st.obs_mean), len(st.obs_std)) == (39, 117, 117, 117)
+
+
+def _emulated(spec, N, **kw):
+    from tests import emu
+    return spec.make_batched(N, device=torch.device("cpu"), library=emu.lib(), **kw)
+
+
+def test_batched_env_history_on_the_emulator(tmp_path):
+    """BatchedEnv's own history bookkeeping on the SIMT emulator: the deque check of tests/test_obs_history_gpu.py through reset / step /
+    step_range (N = 5: groups of 3 + 2, every env reset twice), then a resident history rollout (lhw_env_rollout_history) against a twin
+    that takes the same control steps launch per step -- { lhw_debug_policy_step on the full rows ; BatchedEnv.step } -- and one more
+    launch-per-step control step on both: the rollout must leave the env's own copy of the current full observation at obs[T]."""
+    import ctypes
+    from tests import emu
+    from tests.obs_history_checks import check_history_is_the_deque, spec_h3
+    from tests.test_rollout_resident import NumpyActor
+    check_history_is_the_deque(_emulated, tmp_path, N=5, T=20, max_traj_len=8, groups=(3, 2))
+
+    s3, _ = spec_h3(tmp_path)
+    N, T, D, A = 5, 6, 111, 12      # (the step behind the rollout is the third of an episode: it has a history to continue)
+    stepped, resident = (_emulated(s3, N, seed=3, max_traj_len=4) for _ in range(2))      # truncation + auto-reset inside the rollout
+    pol = NumpyActor(D, A, seed=5, scale=2.0)
+    new = lambda: dict(obs=torch.zeros(T + 1, N, D), act=torch.zeros(T, N, A), logp=torch.zeros(T, N), tob=torch.zeros(T, N, D),
+                       rew=torch.zeros(T, N), done=torch.zeros(T, N, dtype=torch.uint8))
+    a, b = new(), new()
+    a["obs"][0], b["obs"][0] = stepped.reset(), resident.reset()
+    assert torch.equal(a["obs"][0], b["obs"][0])
+    L, y = emu.lib(), torch.zeros(N, pol.view.act_pad)
+    for t in range(T):
+        rc = L.lhw_debug_policy_step(ctypes.byref(pol.view), a["obs"][t].data_ptr(), N, 0, pol.view.counter + t, y.data_ptr(),
+                                     a["act"][t].data_ptr(), a["logp"][t].data_ptr(), None)
+        assert rc == 0, L.lhw_last_error()
+        obs, rew, done, tob = stepped.step(a["act"][t])
+        a["obs"][t + 1], a["rew"][t], a["done"][t], a["tob"][t] = obs, rew, done, tob
+    assert resident.rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"])
+    for k in ("obs", "act", "logp", "rew", "done"):
+        assert torch.equal(a[k], b[k]), k
+    ended = a["done"] != 0
+    assert (a["done"] & 2).any() and torch.equal(a["tob"][ended], b["tob"][ended])
+    act = torch.zeros(N, A)
+    for x, y in zip(stepped.step(act), resident.step(act)):
+        assert torch.equal(x, y)
+    assert (resident.obs[:, 37:] != 0).any()      # (the step had a history to continue)

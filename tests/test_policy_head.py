@@ -375,10 +375,10 @@ def test_emulated_resident_lstm_rollout(case):
 @pytest.mark.parametrize("H", [3, 8])      # rows of 111 -> 112 columns, and of 296: past the 256 columns the in-wave step holds at a time
 def test_emulated_resident_history_rollout(case, H):
     """lhw_env_rollout_history (policy_step_wide).  Largest error / bound: action 0.950 / 0.760, log-density 0.025 / 0.072."""
-    from tests.test_rollout_history import _first_full, _resident
-    spec = _spec()
-    env = _env(spec)
-    obs = [_first_full(env.reset(), H)]
+    from tests.test_rollout_history import _first_full, _history_env, _resident
+    env = _history_env(_spec(), H, N_ENVS, seed=3, max_traj_len=TRAJ, env_id_base=ENV_BASE)
+    obs = [env.reset().copy()]
+    np.testing.assert_array_equal(obs[0], _first_full(obs[0][:, :37], H))
 
     def launch(pol, T, first, count):
         b = _resident(env, pol, T, obs[0], H, first=first, count=count)

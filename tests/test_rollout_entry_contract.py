@@ -96,7 +96,7 @@ def _call(entry, H, env, over, rew_terms=True):
         if k.startswith("pol."):
             setattr(view, k[4:], v(getattr(view, k[4:])) if callable(v) else v)
     b = _buffers(T, N, Hb * D, A)
-    b["obs"][0, :, :env.obs.shape[1]] = env.obs
+    b["obs"][0, :, :env.obs.shape[1]] = env.obs.numpy()
     reset0 = np.ones(N, np.uint8)
     tin = np.zeros((T, N, product.TASK_INPUT_DIM))
     stin = np.zeros((T, N, product.STEP_TASK_INPUT_DIM))
@@ -104,7 +104,7 @@ def _call(entry, H, env, over, rew_terms=True):
     a = dict(first=0, count=N, T=T)
     a.update({k: v for k, v in over.items() if k in a})
     head = [env._h, None if ("pol" in over) else ctypes.byref(view), a["first"], a["count"], a["T"]]
-    bufs = [ptr(k, b[k]) for k in BUFFERS] + [env.rew_terms.ctypes.data if rew_terms else None]
+    bufs = [ptr(k, b[k]) for k in BUFFERS] + [env.rew_terms.data_ptr() if rew_terms else None]
     want_tin = entry in ("task_inputs", "step_task_inputs") or over.get("tin") is True
     want_stin = entry == "step_task_inputs" or over.get("stin") is True
     ptin = ptr("tin", tin) if want_tin else None

@@ -3,6 +3,7 @@ configs: envs/common/base_humanoid_env.py:53,177-197,274) on the SIMT emulator, 
 H x base wide rows ; env.step ; the history rule in numpy }: every buffer BITWISE the same -- observations, actions, log-densities,
 rewards, done flags, the terminal rows where an episode ended -- and the env state and episode statistics afterwards.
 CPU twin of tests/test_rollout_history_gpu.py."""
+import copy
 import ctypes
 
 import numpy as np
@@ -11,14 +12,25 @@ import pytest
 from tests import emu
 from tests.test_rollout_resident import NumpyActor, _buffers, _fallen_states
 
-UNSUPPORTED = -4
-
-
 def _first_full(base_obs, H):
     """the full observation after a reset: the base observation in front of an emptied, zero-filled history"""
     full = np.zeros((base_obs.shape[0], H * base_obs.shape[1]), np.float32)
     full[:, :base_obs.shape[1]] = base_obs
     return full
+
+
+def _history_env(spec, H, N, **kw):
+    """the emulated BatchedEnv of `spec` with history_len = H (make_batched takes the length from the spec)"""
+    spec = copy.copy(spec)
+    spec.history_len = H
+    env = emu.make_emulated(spec, N, **kw)
+    assert env.history_len == H and env.obs_dim == H * env.base_obs_dim
+    return env
+
+
+def _pair(spec, H, N, **kw):
+    """(a plain env for the launch-per-step reference, its twin with the history for the resident rollout)"""
+    return [emu.make_emulated(spec, N, **kw), _history_env(spec, H, N, **kw)]
 
 
 def _reference(env, pol, T, obs0, H):
@@ -41,16 +53,21 @@ def _reference(env, pol, T, obs0, H):
     return b
 
 
-def _resident(env, pol, T, obs0, H, first=0, count=None, expect=0):
-    L = emu.lib()
-    N, B, A = env.n_envs, env.obs_dim, env.act_dim
-    b = _buffers(T, N, H * B, A)
+def _resident(env, pol, T, obs0, H, first=0, count=None, launched=True):
+    """BatchedEnv.rollout of an env built with history_len = H (lhw_env_rollout_history); `launched`: False where the library declines"""
+    assert env.history_len == H
+    b = _buffers(T, env.n_envs, env.obs_dim, env.act_dim)
     b["obs"][0] = obs0
-    rc = L.lhw_env_rollout_history(env._h, ctypes.byref(pol.view), int(first), int(N - first if count is None else count), int(T), int(H),
-                                   b["obs"].ctypes.data, b["act"].ctypes.data, b["logp"].ctypes.data, b["tob"].ctypes.data, b["rew"].ctypes.data,
-                                   b["done"].ctypes.data, env.rew_terms.ctypes.data, None, None, None)
-    assert rc == expect, (rc, L.lhw_last_error())
+    ok = env.rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], first=first, count=count)
+    assert ok == launched, emu.lib().lhw_last_error()
     return b
+
+
+def _first_obs(envs, H):
+    """reset (plain env, history env): the hand-built first full observation of the former, which the latter's reset must return"""
+    want, got = _first_full(envs[0].reset(), H), envs[1].reset().copy()
+    np.testing.assert_array_equal(want, got)
+    return [want, got]
 
 
 def _same(a, b, rows=slice(None)):
@@ -69,10 +86,9 @@ def test_history_rollout_is_bitwise_the_launch_per_step_loop_jvrc_walk():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     N, T, H = 5, 7, 3                             # odd: the last wavefront holds one env
-    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=4) for _ in range(2)]     # truncation + auto-reset inside the rollout
+    envs = _pair(spec, H, N, seed=3, max_traj_len=4)     # truncation + auto-reset inside the rollout
     pol = NumpyActor(H * 37, 12, seed=5, scale=2.0)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
-    np.testing.assert_array_equal(obs0[0], obs0[1])
+    obs0 = _first_obs(envs, H)
     a = _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H)
     _same(a, b)
@@ -95,13 +111,13 @@ def test_history_shift_follows_the_in_wave_rerun_of_an_overflowing_env():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     N, T, H = 4, 4, 2
-    envs = [emu.make_emulated(spec, N, seed=11, max_traj_len=50) for _ in range(2)]
+    envs = _pair(spec, H, N, seed=11, max_traj_len=50)
     pol = NumpyActor(H * 37, 12, seed=8)
     q, v = _fallen_states(spec, N, seed=21)
     for e in envs:
         e.reset()
         e.set_state(q, v)
-    obs0 = _first_full(envs[0].obs, H)      # (the observation still describes the reset pose: the same stale input for both paths)
+    obs0 = _first_full(envs[0].obs.numpy(), H)      # (the observation still describes the reset pose: the same stale input for both paths)
     a = _reference(envs[0], pol, T, obs0, H)
     b = _resident(envs[1], pol, T, obs0, H)
     _same(a, b)
@@ -115,9 +131,9 @@ def test_history_rollout_of_a_sub_range_leaves_the_other_envs_alone():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     N, T, H = 5, 3, 2
-    envs = [emu.make_emulated(spec, N, seed=4, max_traj_len=2) for _ in range(2)]
+    envs = _pair(spec, H, N, seed=4, max_traj_len=2)
     pol = NumpyActor(H * 37, 12, seed=6, deterministic=True)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs, H)
     a = _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H, first=1, count=3)      # envs 1..3: an odd range that starts inside a wavefront pair
     _same(a, b, rows=slice(1, 4))
@@ -135,31 +151,34 @@ def test_history_rollout_h1_keeps_the_observation_noise_counter():
     from learninghumanoidwalking_amd.envs.h1 import H1Spec
     spec = H1Spec()
     N, T, H = 3, 5, 2
-    envs = [emu.make_emulated(spec, N, seed=2, max_traj_len=3) for _ in range(2)]
+    envs = _pair(spec, H, N, seed=2, max_traj_len=3)
     pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=9)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs, H)
     a = _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H)
     _same(a, b)
     assert (a["done"] != 0).any()
     _same_state(*envs)
     # one more launch-per-step control step on both: the next observation (and its noise draw) is the same
+    # (the history env continues from the rollout's last observation: its older entries, emptied where this step ends an episode)
     act = np.zeros((N, spec.act_dim), np.float32)
-    np.testing.assert_array_equal(envs[0].step(act)[0], envs[1].step(act)[0])
+    base, _, done, _ = envs[0].step(act)
+    tail = np.where(done[:, None] != 0, np.float32(0), a["obs"][T][:, :(H - 1) * spec.obs_dim])
+    np.testing.assert_array_equal(np.concatenate([base, tail], axis=1), envs[1].step(act)[0])
 
 
 def test_history_rollout_through_the_job_queue(monkeypatch):
     from learninghumanoidwalking_amd.envs.jvrc_step import JvrcStepSpec
     spec = JvrcStepSpec()
     N, T, H = 3, 7, 2
-    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=4) for _ in range(2)]
+    envs = _pair(spec, H, N, seed=3, max_traj_len=4)
     pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs, H)
     a = _reference(envs[0], pol, T, obs0[0], H)
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "3")      # a chunk that does not divide T
     monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")      # one resident wave drains every (group, chunk) job
     b = _resident(envs[1], pol, T, obs0[1], H)
-    assert emu.lib().lhw_env_last_rollout_queued(envs[1]._h) == 1
+    assert envs[1].last_rollout_queued()
     _same(a, b)
     assert (a["done"] & 2).any()
     _same_state(*envs)
@@ -175,26 +194,23 @@ def test_history_rollout_other_kernels(name, stats, monkeypatch):
     queued = name.endswith("_queued")
     spec = _spec(name[:-7] if queued else name)
     N, T, H = 3, 2, 2
-    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=2) for _ in range(2)]
+    envs = [_history_env(spec, H, N, seed=3, max_traj_len=2) for _ in range(2)] if stats else _pair(spec, H, N, seed=3, max_traj_len=2)
     pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
-    L = emu.lib()
+    obs0 = [e.reset().copy() for e in envs] if stats else _first_obs(envs, H)
     if stats:
-        assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
+        envs[1].enable_term_stats()
     if queued:      # every (group, control step) a job of one resident wave
         monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
         monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
     a = _resident(envs[0], pol, T, obs0[0], H) if stats else _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H)
     _same(a, b)
-    assert L.lhw_env_last_rollout_queued(envs[1]._h) == int(queued)
+    assert envs[1].last_rollout_queued() == queued
     assert (a["done"] != 0).any()
     _same_state(*envs)
     if stats:
-        terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
-        ep = ctypes.c_int64()
-        assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), None, None) == 0
-        assert ep.value == int((a["done"] != 0).sum())
+        from tests import term_stats_checks as C
+        assert C.pop(envs[1])[1] == int((a["done"] != 0).sum())
 
 
 def test_history_entry_point_bounds_and_history_one():
@@ -212,24 +228,30 @@ def test_history_entry_point_bounds_and_history_one():
     obs0 = [e.reset().copy() for e in envs]
     a = _buffers(T, N, 37, 12)
     a["obs"][0] = obs0[0]
-    envs[0].rollout(pol.view, T, a["obs"], a["act"], a["logp"], a["tob"], a["rew"], a["done"])
-    b = _resident(envs[1], pol, T, obs0[1], 1)
+    assert envs[0].rollout(pol.view, T, a["obs"], a["act"], a["logp"], a["tob"], a["rew"], a["done"])
+    # (the entry point itself with history_len = 1: BatchedEnv.rollout takes lhw_env_rollout for such an env)
+    L, env = emu.lib(), envs[1]
+    b = _buffers(T, N, 37, 12)
+    b["obs"][0] = obs0[1]
+    rc = L.lhw_env_rollout_history(env._h, ctypes.byref(pol.view), 0, N, T, 1, *(ctypes.c_void_p(b[k].ctypes.data) for k in ("obs", "act", "logp", "tob", "rew", "done")),
+                                   ctypes.c_void_p(env.rew_terms.data_ptr()), None, None, None)
+    assert rc == 0, (rc, L.lhw_last_error())
     for k in a:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
     _same_state(*envs)
     # the policy's width must be history_len x the env's, and within the capacity of the in-wave step
-    env = envs[1]
     cap = product.ROLLOUT_HISTORY_MAX_OBS_PAD
     H = cap // 37                                 # the longest history whose padded row fits: 6 x 37 = 222 -> 224
     assert (H + 1) * 37 > cap
-    _resident(env, NumpyActor((H + 1) * 37, 12, seed=1), 1, _first_full(env.obs, H + 1), H + 1, expect=UNSUPPORTED)
-    _resident(env, NumpyActor(3 * 37, 12, seed=1), 1, _first_full(env.obs, 2), 2, expect=UNSUPPORTED)      # a policy of another width
+    for h, width in ((H + 1, H + 1), (2, 3)):      # past the capacity; a policy of another width
+        env = _history_env(spec, h, N, seed=6, max_traj_len=0)
+        _resident(env, NumpyActor(width * 37, 12, seed=1), 1, env.reset().copy(), h, launched=False)      # (LHW_ERR_UNSUPPORTED)
     # ... at the capacity, and with fp16 operands, the in-wave step is still the reference launch bit for bit
     for half in (0, 1):
-        twins = [emu.make_emulated(spec, N, seed=7, max_traj_len=0) for _ in range(2)]
+        twins = _pair(spec, H, N, seed=7, max_traj_len=0)
         wide = NumpyActor(H * 37, 12, seed=13, scale=1.5)
         wide.view.fp16_operands = half
-        full = [_first_full(e.reset(), H) for e in twins]
+        full = _first_obs(twins, H)
         rs = np.random.default_rng(3)
         full[0][:, 37:] = full[1][:, 37:] = rs.normal(size=(N, (H - 1) * 37)).astype(np.float32)      # a filled history
         _same(_reference(twins[0], wide, 2, full[0], H), _resident(twins[1], wide, 2, full[1], H))

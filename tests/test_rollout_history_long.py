@@ -9,15 +9,14 @@ eight columns (520), and the capacity (1000 of 1024).  CPU twin of tests/test_ro
 import numpy as np
 import pytest
 
-from tests import emu
-from tests.test_rollout_history import UNSUPPORTED, _first_full, _reference, _resident, _same, _same_state
+from tests.test_rollout_history import _first_full, _first_obs, _history_env, _pair, _reference, _resident, _same, _same_state
 from tests.test_rollout_resident import NumpyActor, _fallen_states
 
 N = 3
 
 
-def _twins(spec, seed, max_traj_len):
-    return [emu.make_emulated(spec, N, seed=seed, max_traj_len=max_traj_len) for _ in range(2)]
+def _twins(spec, H, seed, max_traj_len):
+    return _pair(spec, H, N, seed=seed, max_traj_len=max_traj_len)
 
 
 def test_second_chunk_of_four_columns_with_a_truncation_inside():
@@ -26,10 +25,10 @@ def test_second_chunk_of_four_columns_with_a_truncation_inside():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     T, H = 5, 7
-    envs = _twins(spec, 3, 3)
+    envs = _twins(spec, H, 3, 3)
     pol = NumpyActor(H * 37, 12, seed=5, scale=2.0)
     assert pol.view.obs_pad == 260
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs, H)
     a = _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H)
     _same(a, b)
@@ -48,19 +47,18 @@ def test_two_full_chunks_one_wave_per_group_and_through_the_job_queue(monkeypatc
     from learninghumanoidwalking_amd.envs.jvrc_step import JvrcStepSpec
     spec = JvrcStepSpec()
     T, H = 3, 13
-    envs = [emu.make_emulated(spec, N, seed=3, max_traj_len=2) for _ in range(3)]
+    envs = _twins(spec, H, 3, 2) + [_history_env(spec, H, N, seed=3, max_traj_len=2)]
     pol = NumpyActor(H * spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
     assert pol.view.obs_pad == 508
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs[:2], H) + [envs[2].reset().copy()]
     a = _reference(envs[0], pol, T, obs0[0], H)
-    L = emu.lib()
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "0")      # one wave per group whatever the batch
     b = _resident(envs[1], pol, T, obs0[1], H)
-    assert L.lhw_env_last_rollout_queued(envs[1]._h) == 0
+    assert not envs[1].last_rollout_queued()
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "2")      # a chunk of control steps that does not divide T
     monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")      # one resident wave drains every (group, chunk) job
     c = _resident(envs[2], pol, T, obs0[2], H)
-    assert L.lhw_env_last_rollout_queued(envs[2]._h) == 1
+    assert envs[2].last_rollout_queued()
     _same(a, b)
     _same(a, c)
     assert (a["done"] != 0).any()
@@ -74,11 +72,11 @@ def test_three_chunks_the_last_eight_columns_wide(half):
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     T, H = 2, 14
-    envs = _twins(spec, 7, 0)
+    envs = _twins(spec, H, 7, 0)
     pol = NumpyActor(H * 37, 12, seed=13, scale=1.5)
     assert pol.view.obs_pad == 520
     pol.view.fp16_operands = half
-    full = [_first_full(e.reset(), H) for e in envs]
+    full = _first_obs(envs, H)
     full[0][:, 37:] = full[1][:, 37:] = np.random.default_rng(3).normal(size=(N, (H - 1) * 37)).astype(np.float32)
     _same(_reference(envs[0], pol, T, full[0], H), _resident(envs[1], pol, T, full[1], H))
     _same_state(*envs)
@@ -90,14 +88,14 @@ def test_in_wave_rerun_of_an_overflowing_env_with_a_long_row():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     T, H = 3, 7
-    envs = _twins(spec, 11, 50)
+    envs = _twins(spec, H, 11, 50)
     pol = NumpyActor(H * 37, 12, seed=8)
     q, v = _fallen_states(spec, 4, seed=21)
     q, v = q[[0, 1, 3]], v[[0, 1, 3]]      # (the fallen poses: one in the full wavefront, one in the half-filled one)
     for e in envs:
         e.reset()
         e.set_state(q, v)
-    obs0 = _first_full(envs[0].obs, H)      # (the observation still describes the reset pose: the same stale input for both paths)
+    obs0 = _first_full(envs[0].obs.numpy(), H)      # (the observation still describes the reset pose: the same stale input for both paths)
     a = _reference(envs[0], pol, T, obs0, H)
     b = _resident(envs[1], pol, T, obs0, H)
     _same(a, b)
@@ -111,9 +109,9 @@ def test_sub_range_with_a_long_row_leaves_env_0_alone():
     from learninghumanoidwalking_amd.envs.jvrc_walk import JvrcWalkSpec
     spec = JvrcWalkSpec()
     T, H = 2, 7
-    envs = _twins(spec, 4, 50)
+    envs = _twins(spec, H, 4, 50)
     pol = NumpyActor(H * 37, 12, seed=6, deterministic=True)
-    obs0 = [_first_full(e.reset(), H) for e in envs]
+    obs0 = _first_obs(envs, H)
     before = [x.copy() for x in envs[1].get_state()]
     a = _reference(envs[0], pol, T, obs0[0], H)
     b = _resident(envs[1], pol, T, obs0[1], H, first=1, count=2)      # envs 1, 2: the range starts inside a wavefront pair
@@ -137,16 +135,18 @@ def test_capacity():
     spec = JvrcWalkSpec()
     assert product.ROLLOUT_HISTORY_MAX_OBS_PAD == 1024
     H = 27
-    envs = _twins(spec, 6, 0)
+    envs = _twins(spec, H, 6, 0)
     pol = NumpyActor(H * 37, 12, seed=1, scale=1.5)
     assert pol.view.obs_pad == 1000
-    full = [_first_full(e.reset(), H) for e in envs]
+    full = _first_obs(envs, H)
     full[0][:, 37:] = full[1][:, 37:] = np.random.default_rng(4).normal(size=(N, (H - 1) * 37)).astype(np.float32)
     _same(_reference(envs[0], pol, 1, full[0], H), _resident(envs[1], pol, 1, full[1], H))
     _same_state(*envs)
-    env = envs[1]
-    b = _resident(env, NumpyActor((H + 1) * 37, 12, seed=1), 1, _first_full(env.obs, H + 1), H + 1, expect=UNSUPPORTED)
+    env = _history_env(spec, H + 1, N, seed=6, max_traj_len=0)
+    first, before = env.reset().copy(), env.get_state()
+    b = _resident(env, NumpyActor((H + 1) * 37, 12, seed=1), 1, first, H + 1, launched=False)      # (LHW_ERR_UNSUPPORTED)
     for k in ("act", "logp", "tob", "rew", "done"):
         assert not b[k].any(), k
     assert not b["obs"][1:].any()
-    _same_state(*envs)
+    for x, y in zip(before, env.get_state()):
+        np.testing.assert_array_equal(x, y)

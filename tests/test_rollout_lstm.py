@@ -76,15 +76,10 @@ def _per_step(env, pol, T, obs0, reset0):
 
 
 def _resident(env, pol, T, obs0, reset0, first=0, count=None):
-    L = emu.lib()
-    N, D, A = env.n_envs, env.obs_dim, env.act_dim
-    b = _buffers(T, N, D, A)
+    b = _buffers(T, env.n_envs, env.obs_dim, env.act_dim)
     b["obs"][0] = obs0
-    reset0 = np.ascontiguousarray(reset0, np.uint8)
-    rc = L.lhw_env_rollout_lstm(env._h, ctypes.byref(pol.view), int(first), int(N - first if count is None else count), T, b["obs"].ctypes.data,
-                                b["act"].ctypes.data, b["logp"].ctypes.data, b["tob"].ctypes.data, b["rew"].ctypes.data, b["done"].ctypes.data,
-                                env.rew_terms.ctypes.data, reset0.ctypes.data, None, None, None)
-    assert rc == 0, L.lhw_last_error()
+    assert env.rollout_lstm(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], np.ascontiguousarray(reset0, np.uint8),
+                            first=first, count=count)
     return b
 
 
@@ -148,7 +143,7 @@ def test_lstm_resident_rollout_repeats_overflowing_envs_inside_the_wave():
     for e in envs:
         e.reset()
         e.set_state(q, v)
-    obs0 = envs[0].obs.copy()
+    obs0 = envs[0].obs.numpy().copy()
     reset0 = np.ones(N, np.uint8)
     a = _per_step(envs[0], pols[0], T, obs0, reset0)
     b = _resident(envs[1], pols[1], T, obs0, reset0)
@@ -208,7 +203,7 @@ def test_lstm_resident_rollout_through_the_job_queue_is_bitwise_the_same(monkeyp
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "3")
     monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
     c = _resident(envs[2], pols[2], T, obs0[2], reset0)
-    assert emu.lib().lhw_env_last_rollout_queued(envs[2]._h) == 1 and emu.lib().lhw_env_last_rollout_queued(envs[1]._h) == 0
+    assert envs[2].last_rollout_queued() and not envs[1].last_rollout_queued()
     _same(a, b)
     _same(a, c)
     assert a["done"][:-1].any()
@@ -228,19 +223,16 @@ def test_lstm_resident_rollout_with_armed_term_statistics_gives_the_same_bits(na
         monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
         monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
     envs, pols = _pair(spec, N, 6, 4, max_traj_len=traj)
-    L = emu.lib()
-    assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
+    envs[1].enable_term_stats()
     obs0 = [e.reset().copy() for e in envs]
     reset0 = np.ones(N, np.uint8)
     a = _resident(envs[0], pols[0], T, obs0[0], reset0)
     b = _resident(envs[1], pols[1], T, obs0[1], reset0)
     _same(a, b)
     _same_state(pols[0], pols[1])
-    assert all(L.lhw_env_last_rollout_queued(e._h) == int(queued) for e in envs)
-    terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
-    ep, te, tr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), ctypes.byref(te), ctypes.byref(tr)) == 0
-    assert ep.value == int((a["done"] != 0).sum()) > 0
+    assert all(e.last_rollout_queued() == queued for e in envs)
+    from tests import term_stats_checks as C
+    assert C.pop(envs[1])[1] == int((a["done"] != 0).sum()) > 0
 
 
 def test_lstm_rollout_refuses_what_the_lane_mapping_does_not_cover():
@@ -253,7 +245,7 @@ def test_lstm_rollout_refuses_what_the_lane_mapping_does_not_cover():
     b["obs"][0] = obs0
     r0 = np.zeros(2, np.uint8)
     args = lambda: (env._h, ctypes.byref(pol.view), 0, 2, 1, b["obs"].ctypes.data, b["act"].ctypes.data, b["logp"].ctypes.data, b["tob"].ctypes.data,
-                    b["rew"].ctypes.data, b["done"].ctypes.data, env.rew_terms.ctypes.data, r0.ctypes.data, None, None, None)
+                    b["rew"].ctypes.data, b["done"].ctypes.data, env.rew_terms.data_ptr(), r0.ctypes.data, None, None, None)
     pol.view.hidden = 32
     assert L.lhw_env_rollout_lstm(*args()) == -4      # LHW_ERR_UNSUPPORTED
     pol.view.hidden = 256

@@ -61,7 +61,7 @@ def _resident(env, pol, T, obs0, first=0, count=None):
     N, D, A = env.n_envs, env.obs_dim, env.act_dim
     b = _buffers(T, N, D, A)
     b["obs"][0] = obs0
-    env.rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], first=first, count=count)
+    assert env.rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], first=first, count=count)
     return b
 
 
@@ -120,7 +120,7 @@ def test_resident_rollout_repeats_overflowing_envs_inside_the_wave():
     for e in envs:
         e.reset()
         e.set_state(q, v)
-    obs0 = envs[0].obs.copy()      # (the observation still describes the reset pose: the same stale input for both paths)
+    obs0 = envs[0].obs.numpy().copy()      # (the observation still describes the reset pose: the same stale input for both paths)
     a = _per_step(envs[0], pol, T, obs0)
     b = _resident(envs[1], pol, T, obs0)
     _same(a, b)
@@ -179,18 +179,15 @@ def test_resident_rollout_with_armed_term_statistics_gives_the_same_bits(name, m
         monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "1")
         monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
     envs = [emu.make_emulated(spec, N, seed=2, max_traj_len=2) for _ in range(2)]
-    L = emu.lib()
-    assert L.lhw_env_enable_term_stats(envs[1]._h, 1) == 0
+    envs[1].enable_term_stats()
     pol = NumpyActor(spec.obs_dim, spec.act_dim, seed=9)
     a, b = (_resident(e, pol, T, e.reset().copy()) for e in envs)
     _same(a, b)
-    assert all(L.lhw_env_last_rollout_queued(e._h) == int(queued) for e in envs)
+    assert all(e.last_rollout_queued() == queued for e in envs)
     for x, y in zip(envs[0].get_state(), envs[1].get_state()):
         np.testing.assert_array_equal(x, y)
-    terms = np.zeros(L.lhw_env_num_reward_terms(envs[1]._h))
-    ep = ctypes.c_int64()
-    assert L.lhw_env_pop_term_stats(envs[1]._h, terms.ctypes.data, ctypes.byref(ep), None, None) == 0
-    assert ep.value == int((a["done"] != 0).sum()) > 0
+    from tests import term_stats_checks as C
+    assert C.pop(envs[1])[1] == int((a["done"] != 0).sum()) > 0
 
 
 def test_resident_rollout_through_the_job_queue_is_bitwise_the_same(monkeypatch):
@@ -284,25 +281,23 @@ def test_resident_rollout_exports_the_task_inputs_of_every_control_step():
     envs[0].enable_task_inputs(True)
     a = _buffers(T, N, 37, 12)
     a["obs"][0] = obs0
-    want = np.zeros((T, N, product.TASK_INPUT_DIM))
+    want = []
     y = np.zeros((N, pol.view.act_pad), np.float32)
     for t in range(T):
         assert L.lhw_debug_policy_step(ctypes.byref(pol.view), a["obs"][t].ctypes.data, N, 0, pol.view.counter + t, y.ctypes.data,
                                        a["act"][t].ctypes.data, a["logp"][t].ctypes.data, None) == 0
         obs, rew, done, tob = envs[0].step(a["act"][t])
         a["obs"][t + 1], a["rew"][t], a["done"][t], a["tob"][t] = obs, rew, done, tob
-        rec = np.zeros((N, product.TASK_INPUT_DIM))
-        envs[0]._check(L.lhw_env_get_task_inputs(envs[0]._h, rec.ctypes.data))
-        want[t] = rec
+        want.append(envs[0].get_task_inputs())
     # one launch, every record
     b = _buffers(T, N, 37, 12)
     b["obs"][0] = obs0
     got = np.full((T, N, product.TASK_INPUT_DIM), np.nan)
-    envs[1].rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], task_inputs=got)
+    assert envs[1].rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], task_inputs=got)
     _same(a, b)
-    used = np.zeros(product.TASK_INPUT_DIM, bool)
-    for name, (o, n) in product.TASK_INPUT_FIELDS.items():
-        n = dict(qpos=19, qvel=18, qacc=18).get(name, n)
-        used[o:o + n] = True
-    np.testing.assert_array_equal(got[:, :, used], want[:, :, used])
+    for t in range(T):      # every named field of the record (what lies between the fields is padding)
+        rec = product.split_task_inputs(got[t], 19, 18, 12)
+        assert set(rec) == set(want[t]) == set(product.TASK_INPUT_FIELDS)
+        for name in rec:
+            np.testing.assert_array_equal(rec[name], want[t][name], err_msg=f"{name} at step {t}")
     assert (a["done"] & 2).any() and envs[0].pop_rerun_count() == envs[1].pop_rerun_count() > 0

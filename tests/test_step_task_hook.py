@@ -63,11 +63,8 @@ def test_vector_stepping_task_matches_the_reference_stepping_task():
     assert 0 < done.sum() < len(done) and (ti.reached != 0).any()
 
 
-def _enable_step_record(env):
-    assert env._L.lhw_env_enable_step_task_inputs(env._h, 1) == 0, env._L.lhw_last_error()
-
-
 def _step_record(env):
+    """the raw [N][32] record: column 31 is reserved, and BatchedEnv.get_step_task_inputs returns the named fields only"""
     rec = np.zeros((env.n_envs, 32))
     assert env._L.lhw_env_get_step_task_inputs(env._h, rec.ctypes.data) == 0, env._L.lhw_last_error()
     return rec
@@ -75,9 +72,8 @@ def _step_record(env):
 
 def _task_record(env):
     from learninghumanoidwalking_amd import _lib
-    rec = np.zeros((env.n_envs, _lib.TASK_INPUT_DIM))
-    assert env._L.lhw_env_get_task_inputs(env._h, rec.ctypes.data) == 0
-    return rec
+    from tests.task_shaping_checks import record_rows
+    return record_rows(env.get_task_inputs(), _lib.TASK_INPUT_FIELDS, _lib.TASK_INPUT_DIM)
 
 
 def test_emulated_step_record_matches_the_oracle_and_the_fused_terms():
@@ -100,7 +96,7 @@ def test_emulated_step_record_matches_the_oracle_and_the_fused_terms():
         o.reset()
     assert {o.mode for o in orc} == {0, 1, 2, 3, 4}
     env.enable_task_inputs(True)
-    _enable_step_record(env)
+    env.enable_step_task_inputs()
     task = VectorSteppingTask(spec, "cpu")
     tape = (np.random.default_rng(3).normal(size=(T, N, 12)) * 0.1).astype(np.float32)
     advanced = 0
@@ -151,7 +147,7 @@ def test_emulated_resident_step_record_equals_the_per_step_record(monkeypatch):
     obs0 = [e.reset().copy() for e in envs]
     L = emu.lib()
     envs[0].enable_task_inputs(True)
-    _enable_step_record(envs[0])
+    envs[0].enable_step_task_inputs()
     a = _buffers(T, N, spec.obs_dim, spec.act_dim)
     a["obs"][0] = obs0[0]
     want = np.zeros((T, N, _lib.STEP_TASK_INPUT_DIM))
@@ -171,18 +167,16 @@ def test_emulated_resident_step_record_equals_the_per_step_record(monkeypatch):
         b["obs"][0] = o0
         tin = np.full((T, N, _lib.TASK_INPUT_DIM), np.nan)
         stin = np.full((T, N, _lib.STEP_TASK_INPUT_DIM), np.nan)
-        args = (env._h, ctypes.byref(pol.view), 0, N, T, b["obs"].ctypes.data, b["act"].ctypes.data, b["logp"].ctypes.data,
-                b["tob"].ctypes.data, b["rew"].ctypes.data, b["done"].ctypes.data, env.rew_terms.ctypes.data)
-        assert L.lhw_env_rollout_step_task_inputs(*args, tin.ctypes.data, stin.ctypes.data, None) == 0, L.lhw_last_error()
+        assert env.rollout(pol.view, T, b["obs"], b["act"], b["logp"], b["tob"], b["rew"], b["done"], task_inputs=tin, step_task_inputs=stin)
         return b, tin, stin
 
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "0")
     b, tin, stin = resident(envs[1], obs0[1])
-    assert L.lhw_env_last_rollout_queued(envs[1]._h) == 0
+    assert not envs[1].last_rollout_queued()
     monkeypatch.setenv("LHW_ROLLOUT_CHUNK", "3")
     monkeypatch.setenv("LHW_ROLLOUT_SLOTS", "1")
     c, tin_q, stin_q = resident(envs[2], obs0[2])
-    assert L.lhw_env_last_rollout_queued(envs[2]._h) == 1
+    assert envs[2].last_rollout_queued()
     used = np.zeros(_lib.TASK_INPUT_DIM, bool)
     for o, n in _lib.TASK_INPUT_FIELDS.values():
         used[o:o + n] = True

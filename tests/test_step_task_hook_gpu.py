@@ -129,18 +129,17 @@ def test_resident_step_record_equals_the_per_step_record(monkeypatch, queued):
     e = envs[1]
     e.enable_task_inputs(True)
     e.enable_step_task_inputs(True)
-    used = np.zeros(_lib.TASK_INPUT_DIM, bool)
-    for o, n in _lib.TASK_INPUT_FIELDS.values():
-        used[o:o + n] = True
+    assert (e.nq, e.nv, e.act_dim) == (19, 18, 12)      # the widths of LhwTaskInput's vectors: the named fields are every used column
     for t in range(T):
         o, r, d, _ = e.step(act[t])
         assert torch.equal(o, obs[t + 1]) and torch.equal(r, rew[t]) and torch.equal(d, done[t])
         srec = np.concatenate([v.reshape(N, -1) for v in e.get_step_task_inputs().values()], axis=1)
         np.testing.assert_array_equal(srec, stin[t, :, :31].cpu().numpy(), err_msg=f"t={t}")
         assert not stin[t, :, 31].any()
-        rec = np.zeros((N, _lib.TASK_INPUT_DIM))
-        _lib.check(e._L.lhw_env_get_task_inputs(e._h, rec.ctypes.data))
-        np.testing.assert_array_equal(rec[:, used], tin[t].cpu().numpy()[:, used], err_msg=f"t={t}")
+        rec, want = e.get_task_inputs(), _lib.split_task_inputs(tin[t].cpu().numpy(), e.nq, e.nv, e.act_dim)
+        assert set(rec) == set(_lib.TASK_INPUT_FIELDS)
+        for name in rec:
+            np.testing.assert_array_equal(rec[name], want[name], err_msg=f"{name} t={t}")
     assert ((done & 2) != 0).any()
 
 

@@ -23,18 +23,16 @@ def _spec(name):
 
 def _run(name, resident, armed):
     spec = _spec(name)
-    L = emu.lib()
     env = emu.make_emulated(spec, N, seed=3, max_traj_len=4)      # truncation + auto-reset inside the rollout
     phase, wave = np.zeros(16, np.int64), np.zeros(N, np.int64)
     if armed:
-        assert L.lhw_env_phase_cycles(env._h, 1, phase.ctypes.data) == 0
-        assert L.lhw_env_debug_wave_cycles(env._h, wave.ctypes.data) == 0      # (the first call arms)
+        env.phase_cycles()
+        env.wave_cycles()      # (the first call arms)
     pol = NumpyActor(spec.obs_dim, spec.act_dim, seed=5, scale=2.0)
     obs0 = env.reset().copy()
     b = (_resident if resident else _per_step)(env, pol, T, obs0)
     if armed:
-        assert L.lhw_env_phase_cycles(env._h, 1, phase.ctypes.data) == 0
-        assert L.lhw_env_debug_wave_cycles(env._h, wave.ctypes.data) == 0
+        phase, wave = env.phase_cycles(), env.wave_cycles()
     state = env.get_state()
     env.close()
     return b, state, phase, wave

@@ -4,6 +4,8 @@ terms OUTSIDE the kernel from that export -- with the restatement of the referen
 (oracle/env_jvrc_walk.py, tests/test_specs.py, tests/golden/rewards.npz) -- must give the kernel's fused `rew_terms`.  This is the
 slow-path BaseTask hook of INTEGRATION.md, exercised.  Runs on the SIMT emulator here; tests/test_task_inputs_gpu.py is the GPU twin."""
 import numpy as np
+import torch
+
 
 def reward_functions():
     """-> (module-like object with the reference's tasks/rewards.py function names, False): the oracle's restatement, which
@@ -66,12 +68,9 @@ def check_env(env, spec, steps, rs):
     worst = 0.0
     for t in range(steps):
         act = (rs.normal(size=(env.n_envs, 12)) * 0.3).astype(np.float32)
-        if hasattr(env.rew_terms, "cpu"):      # the product env takes device tensors
-            import torch
-            act = torch.from_numpy(act).cuda()
-        env.step(act)
+        env.step(torch.from_numpy(act).to(env.device))
         ti = env.get_task_inputs()
-        terms = np.array(env.rew_terms.cpu() if hasattr(env.rew_terms, "cpu") else env.rew_terms, dtype=np.float64)
+        terms = env.rew_terms.cpu().numpy().astype(np.float64)
         for i in range(env.n_envs):
             mine = walking_terms(rw, ti, i, spec, lut, mass)
             np.testing.assert_allclose(terms[i], mine, rtol=0, atol=1e-6, err_msg=f"t={t} env={i} (reference rewards.py: {is_ref})")

@@ -7,9 +7,12 @@ CPU twin of tests/test_task_shaping_gpu.py."""
 import numpy as np
 import pytest
 
+import torch
+
+from tests import emu
 from tests import task_shaping_checks as C
 
-BACKEND = C.EmuBackend()
+BACKEND = C.Backend(C.EmuRunner, device=torch.device("cpu"), library=emu.lib)
 
 
 def test_fresh_env_reports_the_reference_values():

@@ -14,7 +14,7 @@ from tests import task_shaping_checks as C
 
 pytestmark = pytest.mark.gpu
 
-BACKEND = C.GpuBackend()
+BACKEND = C.Backend(C.GpuRunner, device=0)
 
 
 def test_fresh_env_reports_the_reference_values():

@@ -6,7 +6,9 @@ launch per step.  What the statistics stand for: the per-term `info` dictionary 
 import ctypes
 
 import numpy as np
+import pytest
 
+from learninghumanoidwalking_amd._lib import LhwError
 from tests import emu
 from tests import term_stats_checks as C
 from tests.test_rollout_resident import NumpyActor, _buffers, _fallen_states, _resident, _same
@@ -39,7 +41,7 @@ def _per_step_with_terms(env, pol, T, obs0):
                                         b["act"][t].ctypes.data, b["logp"][t].ctypes.data, None) == 0
         obs, rew, done, tob = env.step(b["act"][t])
         b["obs"][t + 1], b["rew"][t], b["done"][t], b["tob"][t] = obs, rew, done, tob
-        terms[t] = env.rew_terms
+        terms[t] = env.rew_terms.numpy()
     return b, terms
 
 
@@ -106,6 +108,8 @@ def test_term_stats_are_off_by_default_and_reset_with_the_env():
     s = np.zeros(env.n_terms)
     assert env._L.lhw_env_pop_term_stats(env._h, s.ctypes.data, None, None, None) != 0
     assert b"lhw_env_enable_term_stats" in env._L.lhw_last_error()
+    with pytest.raises(LhwError, match="lhw_env_enable_term_stats"):      # (the env raises with the text of its own, emulated, library)
+        env.pop_term_sums()
     C.enable(env)
     act = np.zeros((N, 12), np.float32)
     env.step(act)
@@ -134,7 +138,7 @@ def test_term_stats_emulated_cartpole():
         out, want = env.step(tape[t]), ref.step(tape[t])
         for x, y in zip(out, want):
             np.testing.assert_array_equal(x, y)
-        terms[t], done[t] = env.rew_terms, env.done
+        terms[t], done[t] = env.rew_terms.numpy(), env.done.numpy()
     got, eps = C.pop(env), env.pop_episode_stats()
     C.check_counts(got, done, eps[2])
     host_sum, host_abs, _ = C.host_term_sums(terms, done)
