@@ -366,6 +366,35 @@ int lhw_env_pop_term_stats(LhwEnv* env, double* term_sum, int64_t* episodes, int
 #define LHW_TERM_LIMIT_COUNT 2   /* [0] lower bound, [1] upper bound (stepping task: must be +inf, it has none) */
 int lhw_env_set_task_shaping(LhwEnv* env, const double* term_weights, int32_t n_weights, const double* term_limits, int32_t n_limits);
 int lhw_env_get_task_shaping(const LhwEnv* env, double* term_weights /*[lhw_env_num_reward_terms]*/, double* term_limits /*[2]*/);
+/* Actuator randomisation: the two sim-to-real settings of the reference's PD law (robots/robot_base.py:5-62; every humanoid env inherits
+ * them), for the whole batch and, like the task shaping, from the next control step on.  Off on a fresh env: {0, 0, 10, 5.0, 40.0}.
+ *  - pdrand_k in [0, 1): > 0, every control step draws its own gains per env and actuator u, kp_u ~ U((1 - k) kp[u], (1 + k) kp[u]) and
+ *    kd_u likewise, and its frame_skip sub-steps run on them (robot_base.py:43-47).
+ *  - sim_bemf != 0: every control step redraws, with probability 1 / bemf_interval (>= 1; the reference: 10), the env's back-EMF damping
+ *    tau_d[u] ~ U(bemf_lo, bemf_hi) (0 <= bemf_lo <= bemf_hi, finite; the reference: 5, 40), and every sub-step applies
+ *    tau = kp_u (q* - q) - kd_u w - tau_d[u] w (robot_base.py:53-60).  tau_d is per-env state: 0 at lhw_env_create, kept across
+ *    lhw_env_reset and auto-resets (the reference's RobotBase outlives reset()), zeroed for every env by the call that turns sim_bemf off,
+ *    kept by every other call.
+ * Draws: lhw_rng.h on the STEP stream under the env's control-step counter (the one this step's task draws use), slots 128 + u (kp),
+ * 144 + u (kd), 160 (back-EMF trigger), 161 + u (tau_d).  A reset runs no PD law and draws nothing.  With both off, every output is bit
+ * for bit what it is without the feature: the kernels that carry it are a family of their own, launched only while one of the two is on.
+ * That family exists for the launch-per-step calls (lhw_env_step / lhw_env_step_range) and the resident rollout of a feed-forward policy
+ * without an observation history (lhw_env_rollout and its *_task_inputs forms), with and without the per-term statistics, on all four
+ * humanoid tasks.  While it is on, lhw_env_rollout_lstm and lhw_env_rollout_history (history_len > 1) are declined with
+ * LHW_ERR_UNSUPPORTED before anything is launched -- the caller steps the env launch by launch, as for any declined rollout -- and the
+ * diagnostic clocks cannot be armed (see there).  HOST pointers; the setter synchronises the device (as lhw_env_set_state).  LHW_ERR_ARG,
+ * with a message that names the field and nothing changed, for a value outside the ranges above; LHW_ERR_UNSUPPORTED for cartpole (its
+ * robot class is not RobotBase). */
+typedef struct {
+  double pdrand_k;
+  int32_t sim_bemf;
+  int32_t bemf_interval;
+  double bemf_lo, bemf_hi;
+} LhwActuatorRand;
+int lhw_env_set_actuator_randomization(LhwEnv* env, const LhwActuatorRand* settings);
+int lhw_env_get_actuator_randomization(LhwEnv* env, LhwActuatorRand* out);
+/* Parity hook: every env's back-EMF damping tau_d, HOST pointer [N][lhw_env_act_dim] float64, synchronous. */
+int lhw_env_get_bemf_damping(LhwEnv* env, double* tau_d_host);
 /* Fault counters since the last call (host pointers, synchronous, resets them): control steps in which contacts were
  * dropped because more than the compiled-in cap were active (16 per env; the stepping task, whose feet rest on the floor AND on
  * the terrain boxes under them, merges identical contacts and holds 192 found / 64 distinct ones per sub-step), and control steps in which an env's state became
@@ -513,7 +542,9 @@ int lhw_debug_lstm_values(const LhwLstmValuesArgs* args, int32_t fused, void* st
  *    launched -- the code with which a resident rollout is declined for any other reason; the caller steps the env launch by launch
  *    (BatchedEnv.rollout returns False), and those steps record.
  *  - The clocks and the per-term episode statistics exclude each other: arming a clock while lhw_env_enable_term_stats is in force, and
- *    lhw_env_enable_term_stats(env, 1) on an env with an armed clock, fail with LHW_ERR_UNSUPPORTED and change nothing. */
+ *    lhw_env_enable_term_stats(env, 1) on an env with an armed clock, fail with LHW_ERR_UNSUPPORTED and change nothing.
+ *  - Likewise the clocks and the actuator randomisation: arming a clock while pdrand_k > 0 or sim_bemf is set, and a
+ *    lhw_env_set_actuator_randomization that sets either on an env with an armed clock, fail with LHW_ERR_UNSUPPORTED and change nothing. */
 /* Diagnostic (load balance): the first call arms the recording; later calls return, per env, the shader-clock cycles its
  * wavefront group spent in the most recent control-step launch (after a resident rollout: in all control steps of the rollout).
  * HOST pointer [N] int64, synchronous; humanoid tasks only. */

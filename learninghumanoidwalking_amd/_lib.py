@@ -107,6 +107,16 @@ def env_config(task, n_envs, *, frame_skip, kp, kd, seed=0, device=0, max_traj_l
     return cfg, keep
 
 
+class LhwActuatorRand(ctypes.Structure):      # include/lhw.h: lhw_env_set_actuator_randomization / lhw_env_get_actuator_randomization
+    _fields_ = [("pdrand_k", ctypes.c_double), ("sim_bemf", ctypes.c_int32), ("bemf_interval", ctypes.c_int32),
+                ("bemf_lo", ctypes.c_double), ("bemf_hi", ctypes.c_double)]
+
+
+# The actuator randomisation an env starts with (lhw_env_get_actuator_randomization on a fresh env; robots/robot_base.py:5, 53-54), in the
+# keywords of BatchedEnv.set_actuator_randomization -- which are also the sub-keys of `actuator_randomization:` in an env's YAML
+DEFAULT_ACTUATOR_RANDOMIZATION = dict(pdrand_k=0.0, sim_bemf=False, bemf_range=(5.0, 40.0), bemf_interval=10)
+
+
 class LhwPpoConfig(ctypes.Structure):      # include/lhw.h: hyper-parameters and shapes of a PPO / LSTM handle
     _fields_ = [
         ("device", ctypes.c_int32), ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
@@ -297,6 +307,9 @@ def declare(L):
     sig("lhw_env_pop_term_stats", [vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_set_task_shaping", [vp, vp, i32, vp, i32])
     sig("lhw_env_get_task_shaping", [vp, vp, vp])
+    sig("lhw_env_set_actuator_randomization", [vp, ctypes.POINTER(LhwActuatorRand)])
+    sig("lhw_env_get_actuator_randomization", [vp, ctypes.POINTER(LhwActuatorRand)])
+    sig("lhw_env_get_bemf_damping", [vp, vp])
     sig("lhw_env_set_iteration", [vp, i64])
     sig("lhw_env_pop_fault_stats", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_pop_rerun_count", [vp, ctypes.POINTER(i64)])

@@ -276,6 +276,31 @@ class BatchedEnv:
         self._check(self._L.lhw_env_set_task_shaping(self._h, w.ctypes.data if w is not None else None, 0 if w is None else w.size,
                                                     lim.ctypes.data if lim is not None else None, 0 if lim is None else lim.size))
 
+    @property
+    def actuator_randomization(self) -> dict:
+        """dict(pdrand_k, sim_bemf, bemf_range, bemf_interval): the actuator randomisation this env's kernels apply, read back from the
+        library (lhw_env_get_actuator_randomization; humanoid tasks only) in the keywords of set_actuator_randomization."""
+        a = _lib.LhwActuatorRand()
+        self._check(self._L.lhw_env_get_actuator_randomization(self._h, ctypes.byref(a)))
+        return dict(pdrand_k=a.pdrand_k, sim_bemf=bool(a.sim_bemf), bemf_range=(a.bemf_lo, a.bemf_hi), bemf_interval=int(a.bemf_interval))
+
+    def set_actuator_randomization(self, pdrand_k=0.0, sim_bemf=False, bemf_range=(5.0, 40.0), bemf_interval=10):
+        """The two sim-to-real settings of the reference's PD law (robots/robot_base.py:5-62), for the whole batch from the next control
+        step on (lhw_env_set_actuator_randomization: synchronises the device).  `pdrand_k` in [0, 1): every control step draws its gains
+        per env and actuator from U((1 - k) kp, (1 + k) kp), kd likewise.  `sim_bemf`: with probability 1 / `bemf_interval` a control
+        step redraws the env's back-EMF damping tau_d ~ U(*bemf_range), which every sub-step applies to the joint velocity; tau_d
+        survives resets and is zeroed by the call that turns sim_bemf off.  Every argument not given takes the reference's value (off).
+        While either is on, an LSTM policy or an observation history samples launch per step (their resident rollouts are declined)."""
+        lo, hi = (float(x) for x in bemf_range)
+        a = _lib.LhwActuatorRand(float(pdrand_k), int(bool(sim_bemf)), int(bemf_interval), lo, hi)
+        self._check(self._L.lhw_env_set_actuator_randomization(self._h, ctypes.byref(a)))
+
+    def bemf_damping(self):
+        """[N, act_dim] float64: every env's back-EMF damping tau_d (host copy, synchronous; lhw_env_get_bemf_damping)"""
+        out = np.zeros((self.n_envs, self.act_dim))
+        self._check(self._L.lhw_env_get_bemf_damping(self._h, out.ctypes.data))
+        return out
+
     def pop_episode_stats(self):
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
         self._check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))

@@ -232,6 +232,9 @@ static int env_rollout(const char* name, LhwEnv* e, const HumanoidRollout& rq, v
   if (rc == -5)
     return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: a diagnostic clock of this env is armed (lhw_env_phase_cycles / lhw_env_debug_wave_cycles) and only the plain feed-forward "
                                          "rollout kernels carry the clocks: step this env launch by launch (lhw_env_step)", name);
+  if (rc == -6)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: the actuator randomisation of this env is armed (lhw_env_set_actuator_randomization) and only the feed-forward "
+                                         "rollout kernels without a history carry it: step this env launch by launch (lhw_env_step)", name);
   if (rc && rq.kind == POLICY_MLP)
     return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: needs a float32 actor obs %d -> 256 -> 256 -> act %d (<= 12) and a model that fits the task's resident kernel", name,
                     e->obs_dim, e->act_dim);
@@ -367,6 +370,38 @@ static int pop_stats(LhwEnv* e, int first, int count, double* out) {
   return LHW_OK;
 }
 
+extern "C" int lhw_env_get_actuator_randomization(LhwEnv* e, LhwActuatorRand* out) {
+  if (!e || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (!e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_get_actuator_randomization: the actuator randomisation exists for the humanoid tasks only");
+  humanoid_get_actuator_rand(e->hum, out);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_set_actuator_randomization(LhwEnv* e, const LhwActuatorRand* a) {
+  if (!e || !a) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (!e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_set_actuator_randomization: the actuator randomisation exists for the humanoid tasks only");
+  const char* fn = "lhw_env_set_actuator_randomization";
+  if (!std::isfinite(a->pdrand_k) || a->pdrand_k < 0 || a->pdrand_k >= 1) return lhw_fail(LHW_ERR_ARG, "%s: pdrand_k = %g, must lie in [0, 1)", fn, a->pdrand_k);
+  if (a->bemf_interval < 1) return lhw_fail(LHW_ERR_ARG, "%s: bemf_interval = %d, must be >= 1", fn, (int)a->bemf_interval);
+  if (!std::isfinite(a->bemf_lo) || a->bemf_lo < 0) return lhw_fail(LHW_ERR_ARG, "%s: bemf_lo = %g, must be finite and >= 0", fn, a->bemf_lo);
+  if (!std::isfinite(a->bemf_hi) || a->bemf_lo > a->bemf_hi) return lhw_fail(LHW_ERR_ARG, "%s: bemf_hi = %g, must be finite and >= bemf_lo = %g", fn, a->bemf_hi, a->bemf_lo);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  const int rc = humanoid_set_actuator_rand(e->hum, a);
+  if (rc == -2)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: a diagnostic clock of this env is armed (lhw_env_phase_cycles / lhw_env_debug_wave_cycles) and the kernels that "
+                                         "carry the actuator randomisation carry no clocks", fn);
+  return rc ? lhw_fail(LHW_ERR_HIP, "%s: parameter upload failed", fn) : LHW_OK;
+}
+
+extern "C" int lhw_env_get_bemf_damping(LhwEnv* e, double* tau_d_host) {
+  if (!e || !tau_d_host) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (!e->hum) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_get_bemf_damping: the actuator randomisation exists for the humanoid tasks only");
+  HIPCHK(hipSetDevice(e->device));
+  if (humanoid_bemf_damping(e->hum, tau_d_host)) return lhw_fail(LHW_ERR_HIP, "lhw_env_get_bemf_damping: copy failed");
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len_sum, int64_t* count) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
   double h[3];
@@ -431,6 +466,7 @@ extern "C" int lhw_env_phase_cycles(LhwEnv* e, int enable, int64_t* out16) {
   static_assert(sizeof(long long) == sizeof(int64_t), "");
   const int rc = humanoid_profile(e->hum, enable, (long long*)out16);
   if (rc == -2) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_phase_cycles: the term statistics are on and their kernels carry no clocks: lhw_env_enable_term_stats(env, 0) first");
+  if (rc == -3) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_phase_cycles: the actuator randomisation is armed and its kernels carry no clocks: switch it off first (lhw_env_set_actuator_randomization)");
   if (rc) return lhw_fail(LHW_ERR_HIP, "profile buffer");
   return LHW_OK;
 }
@@ -442,6 +478,7 @@ extern "C" int lhw_env_debug_wave_cycles(LhwEnv* e, int64_t* out) {
   HIPCHK(hipSetDevice(e->device));
   const int rc = humanoid_wave_cycles(e->hum, (long long*)out);
   if (rc == -2) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_debug_wave_cycles: the term statistics are on and their kernels carry no clocks: lhw_env_enable_term_stats(env, 0) first");
+  if (rc == -3) return lhw_fail(LHW_ERR_UNSUPPORTED, "lhw_env_debug_wave_cycles: the actuator randomisation is armed and its kernels carry no clocks: switch it off first (lhw_env_set_actuator_randomization)");
   if (rc) return lhw_fail(LHW_ERR_HIP, "wave cycle buffer");
   return LHW_OK;
 }

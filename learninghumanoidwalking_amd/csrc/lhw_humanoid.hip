@@ -9,7 +9,7 @@
 // also runs the phase clock and the wave clock (control_step<.., DIAG>) and is launched instead (MODE 0) while one of them is armed.  Generated
 // by a macro and not through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the
 // features.  The clocks and the statistics exclude each other (include/lhw.h), so there is no family with both.
-#define DEFINE_HUMANOID_KERNEL(NAME, STATS, DIAG) \
+#define DEFINE_HUMANOID_KERNEL(NAME, STATS, DIAG, ACT) \
 template <int MODE, int TASK, int W>  /* MODE: 0 step, 1 reset(mask), 2 set_state, 3 get_state; TASK: TASK_WALK / TASK_STAND / TASK_STEP / TASK_H1WALK; W: lanes per env */         \
 __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* __restrict__ bp, HLaunch lz, HState st, const float* __restrict__ act,                          \
                                                       float* __restrict__ obs, float* __restrict__ term_obs,                                                                        \
@@ -39,19 +39,23 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* 
     while (todo) {                                                                                                                                                                  \
       const int i = __ffsll(todo) - 1;                                                                                                                                              \
       todo &= todo - 1;                                                                                                                                                             \
-      control_step<MODE, TASK, W, STATS, DIAG>(m, p, lz, st, SG, SG[0], lz.env_first + e0 + i, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                               \
+      control_step<MODE, TASK, W, STATS, DIAG, ACT>(m, p, lz, st, SG, SG[0], lz.env_first + e0 + i, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                          \
     }                                                                                                                                                                               \
   } else {                                                                                                                                                                          \
     const int eidx = blockIdx.x * G + group_id<W>();                                                                                                                                \
     if (eidx >= lz.env_count) return;                                                                                                                                               \
     const int env = eidx + lz.env_first;                                                                                                                                            \
     if (MODE == 1 && mask && !mask[env]) return;                                                                                                                                    \
-    control_step<MODE, TASK, W, STATS, DIAG>(m, p, lz, st, SG, SG[group_id<W>()], env, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                                       \
+    control_step<MODE, TASK, W, STATS, DIAG, ACT>(m, p, lz, st, SG, SG[group_id<W>()], env, lane, act, obs, term_obs, rew, done_out, rew_terms, xq, xv);                                  \
   }                                                                                                                                                                                 \
 }
-DEFINE_HUMANOID_KERNEL(humanoid_kernel, false, false)
-DEFINE_HUMANOID_KERNEL(humanoid_stats_kernel, true, false)
-DEFINE_HUMANOID_KERNEL(humanoid_diag_kernel, false, true)
+DEFINE_HUMANOID_KERNEL(humanoid_kernel, false, false, false)
+DEFINE_HUMANOID_KERNEL(humanoid_stats_kernel, true, false, false)
+DEFINE_HUMANOID_KERNEL(humanoid_diag_kernel, false, true, false)
+// ... and two more while the actuator randomisation is armed (control_step<.., ACT>; MODE 0 only: a reset runs no PD law and draws nothing),
+// without and with the term statistics.  The clocks have no such kernel: arming one of the two refuses the other (include/lhw.h).
+DEFINE_HUMANOID_KERNEL(humanoid_act_kernel, false, false, true)
+DEFINE_HUMANOID_KERNEL(humanoid_act_stats_kernel, true, false, true)
 
 // ------------------------------------------------------------------------------------------------ host side
 static void h_quat2mat(double* R, const double* q) {
@@ -487,6 +491,7 @@ bool HumanoidCreate::task_params(HumanoidEnv* h) {
     p.term_lim[0] = p.task == TASK_STAND ? 0.9 : 0.6;
     p.term_lim[1] = p.task == TASK_STEP ? (double)INFINITY : 1.4;
   }
+  p.pdrand_k = 0; p.sim_bemf = 0; p.bemf_interval = 10; p.bemf_lo = 5.0; p.bemf_hi = 40.0;   // robot_base.py:5, 53-54: off, 1 in 10, U(5, 40)
   if (stepping) {
     p.box_geom0 = cfg->task_iparams[LHW_TI_STEP_BOX_GEOM0]; p.nbox = cfg->task_iparams[LHW_TI_STEP_NBOX];
     p.floor_geom = cfg->task_iparams[LHW_TI_STEP_FLOOR_GEOM]; p.delay_frames = cfg->task_iparams[LHW_TI_STEP_DELAY_FRAMES];
@@ -570,6 +575,7 @@ bool HumanoidCreate::alloc_state(HumanoidEnv* h) {
   h->st.rec = h->mem.get<double>(REC_D * (N + 1));
   h->st.irec = h->mem.get<int>(REC_I * (N + 1));
   h->st.ep_stats = h->mem.get<double>(8);
+  h->p.tau_d = h->mem.get<double>((size_t)NU * N);   // back-EMF damping of every env: 0 until a control step with sim_bemf draws it
   return !h->mem.failed();
 }
 
@@ -634,9 +640,15 @@ void humanoid_destroy(HumanoidEnv* h) { delete h; }   // (its LhwDevMem frees th
   } while (0)
 // (MODE 0 / 1 while the per-term episode statistics are armed: the kernels that keep them)
 // (MODE 0 while the phase clock or the wave clock is armed: the kernels that run them; the statistics are off then, humanoid_set_term_stats)
+// (MODE 0 while the actuator randomisation is armed: the kernels that carry it, with or without the statistics; no clock is armed then)
 #define LAUNCH_RANGE(MODE, WIDTH, FLAGGED, FIRST, COUNT, ...)                                                       \
   do {                                                                                                             \
     if ((MODE) == 0 && humanoid_diag_armed(h)) { LAUNCH_RANGE_K(humanoid_diag_kernel, 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__); break; } \
+    if ((MODE) == 0 && humanoid_act_armed(h)) {                                                                     \
+      if (h->p.tstat) LAUNCH_RANGE_K(humanoid_act_stats_kernel, 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__);      \
+      else LAUNCH_RANGE_K(humanoid_act_kernel, 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__);                       \
+      break;                                                                                                       \
+    }                                                                                                              \
     if ((MODE) > 1 || !h->p.tstat) { LAUNCH_RANGE_K(humanoid_kernel, MODE, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__); break; } \
     LAUNCH_RANGE_K(humanoid_stats_kernel, (MODE) <= 1 ? (MODE) : 0, WIDTH, FLAGGED, FIRST, COUNT, __VA_ARGS__);    \
   } while (0)
@@ -695,6 +707,31 @@ int humanoid_set_task_shaping(HumanoidEnv* h, const double* weights, int n_weigh
   return humanoid_upload_params(h) ? 0 : -1;
 }
 bool humanoid_diag_armed(const HumanoidEnv* h) { return h->st.prof || h->st.wave_cyc; }
+bool humanoid_act_armed(const HumanoidEnv* h) { return h->p.pdrand_k > 0 || h->p.sim_bemf != 0; }
+void humanoid_get_actuator_rand(const HumanoidEnv* h, LhwActuatorRand* out) {
+  out->pdrand_k = h->p.pdrand_k; out->sim_bemf = h->p.sim_bemf; out->bemf_interval = h->p.bemf_interval;
+  out->bemf_lo = h->p.bemf_lo; out->bemf_hi = h->p.bemf_hi;
+}
+// (checked by the caller; the device is idle)
+int humanoid_set_actuator_rand(HumanoidEnv* h, const LhwActuatorRand* a) {
+  const bool arm = a->pdrand_k > 0 || a->sim_bemf != 0;
+  if (arm && humanoid_diag_armed(h)) return -2;   // (the kernels that carry the randomisation carry no clocks)
+  const bool bemf_off = h->p.sim_bemf != 0 && a->sim_bemf == 0;
+  h->p.pdrand_k = a->pdrand_k; h->p.sim_bemf = a->sim_bemf != 0; h->p.bemf_interval = a->bemf_interval;
+  h->p.bemf_lo = a->bemf_lo; h->p.bemf_hi = a->bemf_hi;
+  if (bemf_off && hipMemset(h->p.tau_d, 0, sizeof(double) * (size_t)NU * h->p.n_envs) != hipSuccess) return -1;
+  return humanoid_upload_params(h) ? 0 : -1;
+}
+int humanoid_bemf_damping(HumanoidEnv* h, double* out) {
+  const size_t N = h->p.n_envs;
+  const int nu = h->m.nu;
+  std::vector<double> rows(N * NU);
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(rows.data(), h->p.tau_d, rows.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  for (size_t n = 0; n < N; n++)
+    for (int u = 0; u < nu; u++) out[n * nu + u] = rows[n * NU + u];
+  return 0;
+}
 int humanoid_occupancy() {
   int nb = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, humanoid_kernel<0, TASK_WALK, 32>, 64, 0) != hipSuccess) return -1;
@@ -704,6 +741,7 @@ int humanoid_occupancy() {
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out) {
   const size_t N = h->p.n_envs;
   if (!h->st.wave_cyc && h->p.tstat) return -2;
+  if (!h->st.wave_cyc && humanoid_act_armed(h)) return -3;
   if (!h->st.wave_cyc) return (h->st.wave_cyc = h->mem.get_lazy<long long>(N + 1)) ? 0 : -1;
   if (!out) return 0;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -729,6 +767,7 @@ int humanoid_task_inputs(HumanoidEnv* h, bool step_record, int enable, double* o
 }
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16) {
   if (enable && !h->st.prof && h->p.tstat) return -2;
+  if (enable && !h->st.prof && humanoid_act_armed(h)) return -3;
   if (enable && !h->st.prof && !(h->st.prof = h->mem.get_lazy<long long>(16))) return -1;
   if (out16 && h->st.prof) {
     (void)hipDeviceSynchronize();

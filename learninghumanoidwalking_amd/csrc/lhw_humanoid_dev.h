@@ -276,6 +276,13 @@ struct HParams {
   double term_lim[2];                   // ... and the termination bounds: root z outside [lo, hi] (walking, standing), root z above the lower foot
                                         // site below lo (stepping: hi is +inf, it has none).  Uniform across the batch: scalar loads of p.  Added
                                         // behind tstat by the same rule
+  // Actuator randomisation (lhw_env_set_actuator_randomization; robots/robot_base.py:43-60).  Read by the ACT instantiations of the kernels
+  // only, which are launched while pdrand_k > 0 or sim_bemf is set (humanoid_act_armed); added behind term_lim by the same rule
+  double pdrand_k;                      // > 0: every control step runs on gains drawn from U((1 - k) kp, (1 + k) kp), kd likewise, per actuator
+  double bemf_lo, bemf_hi;              // range of the back-EMF damping draw
+  int sim_bemf, bemf_interval;          // sim_bemf: with probability 1 / bemf_interval a control step redraws the env's tau_d
+  double* tau_d;                        // [N][NU] back-EMF damping of every env, a side array like tstat: zero at create, never touched by a
+                                        // reset (the reference's RobotBase outlives reset()), zeroed by the setter that turns sim_bemf off
 };
 // What the stepper kernels read of an env's configuration, in ONE device allocation behind ONE kernel-argument pointer: the model record, and
 // the task parameters at a fixed, aligned offset behind it (the kernels form both references from the block's address; two argument pointers
@@ -3413,7 +3420,11 @@ __device__ __forceinline__ bool store_record(HModelRef m, const HLaunch& lz, con
 // STATS: the instantiation that also keeps the per-term episode statistics (HParams::tstat).  A template parameter and not a run-time
 // branch: the kernels launched while the statistics are off are, instruction for instruction, the kernels without the feature.
 // DIAG: the instantiation that also runs the phase clock and the wave clock (PhaseClock / WaveClock above).
-template <int MODE, int TASK, int W, bool STATS = false, bool DIAG = false>
+// ACT: the instantiation that also randomises the actuator model (HParams::pdrand_k / sim_bemf), launched while one of the two is armed.  A
+// family of its own for STATS' reason.  Nothing of it lives in a register or in LDS across a sub-step (the layouts are sized to the byte, the
+// walking rollout kernel has nine VGPRs to spare): the gains of a control step are pure functions of (seed, env, control-step counter,
+// actuator), so every sub-step draws them again from the counter in the env's LDS context, and tau_d is read from its HBM row.
+template <int MODE, int TASK, int W, bool STATS = false, bool DIAG = false, bool ACT = false>
 __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, typename LayoutOf<TASK, W>::type* SG0,
                                              typename LayoutOf<TASK, W>::type& S, const int env,
                                              const int lane, const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ term_obs,
@@ -3492,6 +3503,13 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
   if (MODE == 0 && lane < m.nu) {
     a_in = (double)act[(size_t)env * m.nu + lane];
     target = p.action_smoothing * a_in + (1 - p.action_smoothing) * rec[R_PREVPRED + lane] + p.action_offset[lane];
+    if constexpr (ACT) {
+      // back-EMF damping (robot_base.py:53-54): redrawn once per control step with probability 1 / bemf_interval, under the counter this
+      // step's task draws use; slot 160 the trigger, 161 + u the values.  (A W = 64 re-run of this control step draws the same values.)
+      const unsigned cnt = (unsigned)S.ci[CI_STEPCNT];
+      if (p.sim_bemf && lhw_rng_randint(p.seed, genv, LHW_STREAM_STEP, cnt, 160, p.bemf_interval) == 0)
+        p.tau_d[(size_t)env * NU + lane] = lhw_rng_uniform(p.seed, genv, LHW_STREAM_STEP, cnt, 161 + lane, p.bemf_lo, p.bemf_hi);
+    }
   }
   for (;;) {
     FRESH_GROUP(W, SG0);   // (shadows the parameters inside the stage loop: nothing lane-derived is carried across a sub-step)
@@ -3500,7 +3518,19 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
       if (kstep < p.frame_skip) {
         if (lane < m.nu) {
           // step_pd on the transmission fields of the previous forward pass (note S); ctrl = tau / gear
-          const double tau = p.kp[lane] * (target - S.sq[lane]) + p.kd[lane] * (0.0 - S.sv[lane]);
+          double tau;
+          if constexpr (ACT) {
+            // robot_base.py:43-47, 57-60: gains drawn per control step (slots 128 + u, 144 + u), back-EMF damping on the joint velocity
+            double kp = p.kp[lane], kd = p.kd[lane];
+            if (p.pdrand_k > 0) {
+              const unsigned cnt = (unsigned)S.ci[CI_STEPCNT];   // (unchanged until the control stage's epilogue)
+              kp = lhw_rng_uniform(p.seed, genv, LHW_STREAM_STEP, cnt, 128 + lane, (1 - p.pdrand_k) * kp, (1 + p.pdrand_k) * kp);
+              kd = lhw_rng_uniform(p.seed, genv, LHW_STREAM_STEP, cnt, 144 + lane, (1 - p.pdrand_k) * kd, (1 + p.pdrand_k) * kd);
+            }
+            tau = kp * (target - S.sq[lane]) + kd * (0.0 - S.sv[lane]) - p.tau_d[(size_t)S.env_id * NU + lane] * S.sv[lane];
+          } else {
+            tau = p.kp[lane] * (target - S.sq[lane]) + p.kd[lane] * (0.0 - S.sv[lane]);
+          }
           S.ctrl[lane] = qdiv(tau, m.act_d[ADS * (lane) + AD_GEAR]);
         }
         SYNC();

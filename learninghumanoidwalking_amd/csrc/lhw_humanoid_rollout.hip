@@ -530,7 +530,7 @@ __device__ __forceinline__ void lstm_policy_step(const LhwRolloutLstmPolicy& q, 
 }
 
 // Control steps [t0, t1) of env group `grp` of the range (the G envs one wave advances together).
-template <int TASK, int W, bool STATS, bool DIAG, int PK>
+template <int TASK, int W, bool STATS, bool DIAG, int PK, bool ACT = false>
 __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro, unsigned char* SGraw, int grp,
                                               int t0, int t1) {
   using L = typename LayoutOf<TASK, W>::type;
@@ -605,7 +605,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
     HLaunch lzt = lz;
     lzt.tin_off = (long long)t * ro.tin_step;   // (the batched sim facade of EVERY control step, for reward-only task plug-ins: lhw_env_rollout_task_inputs)
     if (g < nlive)
-      ovf = control_step<0, TASK, W, STATS, DIAG>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+      ovf = control_step<0, TASK, W, STATS, DIAG, ACT>(m, p, lzt, st, SG, SG[g], env0 + g, lane, act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
 #ifndef LHW_RO_NO_RERUN   // (analysis builds: without the in-wave re-run, to see what its code costs the hot path -- nothing measurable)
     if constexpr (W == 32) {
       GROUP_SYNC(64);
@@ -618,7 +618,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
           if ((ob >> (32 * gg)) & 1ull) {
             SYNC();
             // (as a call -- it is rare -- the kernel spills 12 fewer VGPRs and 200 fewer SGPRs and is 9 % SLOWER: profiles/r05_calls_and_scratch.txt)
-            control_step<0, TASK, 64, STATS, DIAG>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
+            control_step<0, TASK, 64, STATS, DIAG, ACT>(m, p, lz1, st, S1, S1[0], env0 + gg, fresh_wave_lane(), act_t, obs_n, tob_t, rew_t, done_t, ro.rew_terms, nullptr, nullptr);
           }
       }
     }
@@ -652,7 +652,7 @@ __device__ __forceinline__ void rollout_steps(HModelRef m, HParamsRef p, const H
 // Kernel families from one text (each once more for the LSTM actor, policy kind POLICY_LSTM, and for the observation history, POLICY_HIST): humanoid_rollout_kernel, and humanoid_rollout_stats_kernel, which also keeps the per-term episode
 // statistics (control_step<.., STATS>) and is launched instead while lhw_env_enable_term_stats is in force.  Generated by a macro and not
 // through a shared device function, so that the plain family stays, instruction for instruction, the kernels without the feature.
-#define DEFINE_ROLLOUT_KERNEL(NAME, STATS, DIAG, PK) \
+#define DEFINE_ROLLOUT_KERNEL(NAME, STATS, DIAG, PK, ACT) \
 template <int TASK, int W, bool QUEUE>                                                                                                                              \
 __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* __restrict__ bp, HLaunch lz, HState st, typename RolloutOf<PK>::type ro) {                          \
   using L = typename LayoutOf<TASK, W>::type;                                                                                                                       \
@@ -668,7 +668,7 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* 
   const int n_groups = (lz.env_count + G - 1) / G;                                                                                                                  \
   if constexpr (!QUEUE) {                                                                                                                                           \
     if ((int)blockIdx.x >= n_groups) return;                                                                                                                        \
-    rollout_steps<TASK, W, STATS, DIAG, PK>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                               \
+    rollout_steps<TASK, W, STATS, DIAG, PK, ACT>(m, p, lz, st, ro, SGraw, (int)blockIdx.x, 0, ro.T);                                                                          \
   } else {                                                                                                                                                          \
     const int n_chunks = (ro.T + ro.chunk - 1) / ro.chunk;                                                                                                          \
     for (;;) {                                                                                                                                                      \
@@ -680,29 +680,34 @@ __global__ void __launch_bounds__(64, LHW_WAVES_PER_SIMD) NAME(const HDevBlock* 
       const int t0 = c * ro.chunk, t1 = min(ro.T, t0 + ro.chunk);                                                                                                   \
       /* the group's previous chunk was popped n_groups - 1 jobs ago by a wave that is running: it ends without waiting for anyone */                               \
       while (lhw_load_agent(ro.queue + 1 + grp) < (unsigned)c) __builtin_amdgcn_s_sleep(32);                                                                        \
-      rollout_steps<TASK, W, STATS, DIAG, PK>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                          \
+      rollout_steps<TASK, W, STATS, DIAG, PK, ACT>(m, p, lz, st, ro, SGraw, grp, t0, t1);                                                                                     \
       __threadfence();   /* the group's records, observations and flags of this chunk, before the chunk counts as done */                                           \
       if (fresh_wave_lane() == 0) lhw_store_agent(ro.queue + 1 + grp, (unsigned)(c + 1));                                                                           \
     }                                                                                                                                                               \
   }                                                                                                                                                                 \
 }
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false, false, POLICY_MLP)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, false, POLICY_MLP)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_kernel, false, false, POLICY_MLP, false)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_stats_kernel, true, false, POLICY_MLP, false)
 // ... and with the diagnostic clocks (control_step<.., DIAG>, rollout_steps' wave clock), launched instead while one of them is armed.  The
 // plain feed-forward family only: with a clock armed, a rollout of any other family is declined (humanoid_rollout, include/lhw.h)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_diag_kernel, false, true, POLICY_MLP)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_diag_kernel, false, true, POLICY_MLP, false)
 // the same two families with the LSTM actor's in-wave step (lhw_env_rollout_lstm)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, false, POLICY_LSTM)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, false, POLICY_LSTM)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_kernel, false, false, POLICY_LSTM, false)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_lstm_stats_kernel, true, false, POLICY_LSTM, false)
 // ... and with the feed-forward actor on an observation history (lhw_env_rollout_history, history_len > 1): rows of up to PXW columns
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, false, POLICY_HIST)
-DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, false, POLICY_HIST)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_kernel, false, false, POLICY_HIST, false)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_hist_stats_kernel, true, false, POLICY_HIST, false)
+// ... and, behind all of them, the feed-forward family with the actuator randomisation (control_step<.., ACT>), without and with the term
+// statistics, launched instead while lhw_env_set_actuator_randomization has armed it.  The other policy kinds and the clocks have no such
+// kernels: their rollouts are declined while it is armed (humanoid_rollout, include/lhw.h)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_act_kernel, false, false, POLICY_MLP, true)
+DEFINE_ROLLOUT_KERNEL(humanoid_rollout_act_stats_kernel, true, false, POLICY_MLP, true)
 
 // ------------------------------------------------------------------------------------------------ host side
-// A policy kind's kernel families -- plain, with the term statistics, with the diagnostic clocks (the feed-forward kind only: the other kinds'
-// cells stay empty) -- : the one place that names them.  The launch tables below are built from it, so a kernel is instantiated where a table
+// A policy kind's kernel families -- plain, with the term statistics, with the diagnostic clocks, with the actuator randomisation without and
+// with the statistics (the last three of the feed-forward kind only: the other kinds' cells stay empty) -- : the one place that names them.  The launch tables below are built from it, so a kernel is instantiated where a table
 // names it and nowhere else.  FAMILY: a table's first index.
-enum { FAMILY_PLAIN = 0, FAMILY_STATS = 1, FAMILY_DIAG = 2 };
+enum { FAMILY_PLAIN = 0, FAMILY_STATS = 1, FAMILY_DIAG = 2, FAMILY_ACT = 3, FAMILY_ACT_STATS = 4, FAMILY_COUNT = 5 };
 template <int PK> using RolloutFn = void (*)(const HDevBlock*, HLaunch, HState, typename RolloutOf<PK>::type);
 template <int PK, int FAMILY, int TASK, int W, bool QUEUE>
 constexpr RolloutFn<PK> rollout_kernel() {
@@ -712,6 +717,10 @@ constexpr RolloutFn<PK> rollout_kernel() {
 #endif
   if constexpr (FAMILY == FAMILY_DIAG) {
     if constexpr (PK == POLICY_MLP) return humanoid_rollout_diag_kernel<TASK, W, QUEUE>; else return nullptr;
+  } else if constexpr (FAMILY == FAMILY_ACT) {
+    if constexpr (PK == POLICY_MLP) return humanoid_rollout_act_kernel<TASK, W, QUEUE>; else return nullptr;
+  } else if constexpr (FAMILY == FAMILY_ACT_STATS) {
+    if constexpr (PK == POLICY_MLP) return humanoid_rollout_act_stats_kernel<TASK, W, QUEUE>; else return nullptr;
   } else if constexpr (PK == POLICY_LSTM) {
     if constexpr (STATS) return humanoid_rollout_lstm_stats_kernel<TASK, W, QUEUE>; else return humanoid_rollout_lstm_kernel<TASK, W, QUEUE>;
   } else if constexpr (PK == POLICY_HIST) {
@@ -734,9 +743,11 @@ void humanoid_rollout_launch_step(int family, bool queued, dim3 grid, hipStream_
                                   const typename RolloutOf<PK>::type& ro) {
   // [family][not queued].  The plain family is named first, and the kinds are instantiated below in the order MLP, LSTM, HIST: the compiler
   // emits kernels in the order it meets them, and theirs is then the order without the feature
-  static constexpr RolloutFn<PK> table[3][2] = {{rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, false>()},
-                                                {rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, false>()},
-                                                {rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, false>()}};
+  static constexpr RolloutFn<PK> table[FAMILY_COUNT][2] = {{rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_STEP, 64, false>()},
+                                                           {rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_STATS, TASK_STEP, 64, false>()},
+                                                           {rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STEP, 64, false>()},
+                                                           {rollout_kernel<PK, FAMILY_ACT, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_ACT, TASK_STEP, 64, false>()},
+                                                           {rollout_kernel<PK, FAMILY_ACT_STATS, TASK_STEP, 64, true>(), rollout_kernel<PK, FAMILY_ACT_STATS, TASK_STEP, 64, false>()}};
   const RolloutFn<PK> k = table[family][!queued];
   if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, b_dev, lz, st, ro);   // (an empty cell: humanoid_rollout has declined the request)
 }
@@ -751,10 +762,12 @@ template <int PK>
 static void rollout_launch_fast(HumanoidEnv* h, int family, dim3 grid, hipStream_t s, const HLaunch& lz, const HState& st, const typename RolloutOf<PK>::type& ro) {
   // [family][task: walk, h1_walk, stand].  The plain family is named first: the compiler emits kernels in the order it meets them, and
   // theirs is then the order without the feature
-  static constexpr RolloutFn<PK> table[3][3] = {
+  static constexpr RolloutFn<PK> table[FAMILY_COUNT][3] = {
       {rollout_kernel<PK, FAMILY_PLAIN, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_PLAIN, TASK_STAND, 32, false>()},
       {rollout_kernel<PK, FAMILY_STATS, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_STATS, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_STATS, TASK_STAND, 32, false>()},
-      {rollout_kernel<PK, FAMILY_DIAG, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STAND, 32, false>()}};
+      {rollout_kernel<PK, FAMILY_DIAG, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_DIAG, TASK_STAND, 32, false>()},
+      {rollout_kernel<PK, FAMILY_ACT, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_ACT, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_ACT, TASK_STAND, 32, false>()},
+      {rollout_kernel<PK, FAMILY_ACT_STATS, TASK_WALK, 32, false>(), rollout_kernel<PK, FAMILY_ACT_STATS, TASK_H1WALK, 32, false>(), rollout_kernel<PK, FAMILY_ACT_STATS, TASK_STAND, 32, false>()}};
   const RolloutFn<PK> k = table[family][h->p.task == TASK_WALK ? 0 : (h->p.task == TASK_H1WALK ? 1 : 2)];
   if (k) hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const HDevBlock*)h->b_dev, lz, st, ro);
 }
@@ -806,7 +819,10 @@ static int rollout_launch(HumanoidEnv* h, typename RolloutOf<PK>::type& ro, cons
   const dim3 grid(grid_n);
   h->last_rollout_queued = ro.queue != nullptr;
   // per-term episode statistics armed: the kernels that keep them; a diagnostic clock armed: the kernels that run it (never both: humanoid_rollout)
-  const int family = humanoid_diag_armed(h) ? FAMILY_DIAG : (h->p.tstat != nullptr ? FAMILY_STATS : FAMILY_PLAIN);
+  // ... the actuator randomisation armed (no clock is armed then: humanoid_set_actuator_rand): the kernels that carry it, with or without the statistics
+  const int family = humanoid_diag_armed(h) ? FAMILY_DIAG
+                     : humanoid_act_armed(h) ? (h->p.tstat != nullptr ? FAMILY_ACT_STATS : FAMILY_ACT)
+                                             : (h->p.tstat != nullptr ? FAMILY_STATS : FAMILY_PLAIN);
   if (h->fast) rollout_launch_fast<PK>(h, family, grid, s, lz, st, ro);
 #ifndef LHW_ONLY_WALK
   else humanoid_rollout_launch_step<PK>(family, ro.queue != nullptr, grid, s, (const HDevBlock*)h->b_dev, lz, st, ro);
@@ -839,6 +855,8 @@ int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s) {
   }
   // the diagnostic clocks exist in the plain feed-forward family only: no rollout that would silently record nothing
   if (humanoid_diag_armed(h) && (rq.kind != POLICY_MLP || h->p.tstat)) return -5;
+  // ... and the actuator randomisation in the feed-forward family without a history only: no rollout that would silently run the plain PD law
+  if (humanoid_act_armed(h) && rq.kind != POLICY_MLP) return -6;
   if (!h->fast && h->p.task != TASK_STEP) return -3;   // a walking / standing model that does not fit the two-envs-per-wave layout (or LHW_ONE_ENV_PER_WAVE): launch-per-step only
   if (rq.kind == POLICY_MLP) {
     HRollout ro;

@@ -118,7 +118,8 @@ struct HumanoidRollout {
   const uint8_t* reset0 = nullptr;              // POLICY_LSTM
   int history_len = 1;                          // > 1: POLICY_HIST
 };
-// -1 bad range, -2 / -3 unsupported, -4 HIP error, -5 a diagnostic clock is armed and the rollout's kernel family has no clocks
+// -1 bad range, -2 / -3 unsupported, -4 HIP error, -5 a diagnostic clock is armed and the rollout's kernel family has no clocks,
+// -6 the actuator randomisation is armed and the rollout's policy kind has no kernels that carry it
 int humanoid_rollout(HumanoidEnv* h, const HumanoidRollout& rq, hipStream_t s);
 // width of a task's base observation (the kernels' TASK_* ids are the ABI's LHW_TASK_* values: lhw_humanoid.hip)
 constexpr int humanoid_base_obs_dim(int task) {
@@ -137,8 +138,16 @@ void humanoid_set_iteration(HumanoidEnv* h, int64_t it);
 int humanoid_occupancy();
 // The diagnostic clocks (phase clock: humanoid_profile, wave clock: humanoid_wave_cycles).  Once one is armed, control steps run the kernels
 // that carry the clocks (humanoid_diag_kernel, humanoid_rollout_diag_kernel); the term statistics have kernels of their own, without clocks,
-// so the two exclude each other: arming returns -2 while the statistics are on, -1 on a HIP error
+// so the two exclude each other: arming returns -2 while the statistics are on, -3 while the actuator randomisation is armed, -1 on a HIP error
 bool humanoid_diag_armed(const HumanoidEnv* h);
+// Actuator randomisation (lhw_env_set_actuator_randomization).  While pdrand_k > 0 or sim_bemf is set, control steps run the kernels that carry
+// it (humanoid_act_kernel / humanoid_act_stats_kernel, humanoid_rollout_act_kernel / humanoid_rollout_act_stats_kernel); the clocks' kernels and
+// the LSTM / history rollout kernels do not, so arming refuses while a clock is armed (-2) and those rollouts are declined while it is armed.
+// The setter takes validated values, zeroes every env's tau_d when it turns sim_bemf off, uploads the parameters; -1 on a HIP error
+bool humanoid_act_armed(const HumanoidEnv* h);
+void humanoid_get_actuator_rand(const HumanoidEnv* h, LhwActuatorRand* out);
+int humanoid_set_actuator_rand(HumanoidEnv* h, const LhwActuatorRand* a);
+int humanoid_bemf_damping(HumanoidEnv* h, double* out /* [N][nu] host */);
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
 // step_record: the stepping task's second record (LhwStepTaskInput) instead of LhwTaskInput; -1 HIP error, -2 not enabled

@@ -98,10 +98,16 @@ class BatchedFactory:
         shaping = self.task_shaping()
         if shaping is not None:      # (only then: a substituted backend without the method serves every config that does not shape the task)
             env.set_task_shaping(reward_weights=shaping[0], termination=shaping[1])
+        actuator = self.actuator_randomization()
+        if actuator is not None:     # (likewise)
+            env.set_actuator_randomization(**actuator)
         return env
 
     def task_shaping(self):
         return None     # (the humanoid specs read it from the YAML)
+
+    def actuator_randomization(self):
+        return None     # (likewise)
 
 
 @dataclass
@@ -139,6 +145,9 @@ class HumanoidSpec(BatchedFactory):
         # task shaping, no reference counterpart in the YAML (there: literals of tasks/*_task.py): `reward_weights: {term: weight}` (partial,
         # by the names of REWARD_TERMS) and `termination: {min_height:, max_height:}`; checked here, applied by make_batched
         self._shaping = self._read_task_shaping(c)
+        # actuator randomisation (robots/robot_base.py:5-62: pdrand_k, sim_bemf -- constructor arguments there, which no shipped env passes):
+        # `actuator_randomization: {pdrand_k:, sim_bemf:, bemf_range: [lo, hi], bemf_interval:}`; checked here, applied by make_batched
+        self._actuator = self._read_actuator_randomization(c)
         self._model = None
         self._configure(c)
         # jvrc_walk.py:62-63, h1_env.py:54-55: np.tile over the history
@@ -197,6 +206,32 @@ class HumanoidSpec(BatchedFactory):
         (term weights [n_terms] float64 in REWARD_TERMS order -- the YAML's over the reference's --, (lo, hi)): what make_batched hands to
         BatchedEnv.set_task_shaping.  Not part of env_args(): the weights are a run-time setting of the env, not of its creation."""
         return self._shaping
+
+    def _read_actuator_randomization(self, c):
+        from .._lib import DEFAULT_ACTUATOR_RANDOMIZATION
+        ar = c.get("actuator_randomization")
+        if ar is None:
+            return None
+        ar = dict(ar)
+        if ar.pop("sim_motor_dyn", False):
+            raise NotImplementedError(f"actuator_randomization.sim_motor_dyn in {self.yaml_path}: the learned motor model's per-joint networks are "
+                                      "not part of the reference tree; pdrand_k and sim_bemf are implemented")
+        unknown = set(ar) - set(DEFAULT_ACTUATOR_RANDOMIZATION)
+        if unknown:
+            raise KeyError(f"unknown actuator_randomization keys {sorted(unknown)} in {self.yaml_path}: {', '.join(DEFAULT_ACTUATOR_RANDOMIZATION)}")
+        out = dict(DEFAULT_ACTUATOR_RANDOMIZATION, **ar)
+        lo, hi = (float(x) for x in out["bemf_range"])
+        out.update(pdrand_k=float(out["pdrand_k"]), sim_bemf=bool(out["sim_bemf"]), bemf_range=(lo, hi), bemf_interval=int(out["bemf_interval"]))
+        if not 0 <= out["pdrand_k"] < 1:      # (NaN fails it too)
+            raise ValueError(f"actuator_randomization.pdrand_k of {self.yaml_path} must lie in [0, 1): {out['pdrand_k']}")
+        if not (0 <= lo <= hi < float("inf")) or out["bemf_interval"] < 1:
+            raise ValueError(f"actuator_randomization of {self.yaml_path}: bemf_range must be 0 <= lo <= hi (finite), bemf_interval >= 1")
+        return out
+
+    def actuator_randomization(self):
+        """None for a YAML without `actuator_randomization:` (every shipped config), else the keywords make_batched hands to
+        BatchedEnv.set_actuator_randomization -- the YAML's over the reference's defaults.  Not part of env_args(): a run-time setting."""
+        return self._actuator
 
     def clock_lut(self):
         return None     # (a task with a gait clock mixes in WalkingTask)
