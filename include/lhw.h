@@ -759,6 +759,39 @@ int lhw_rnn_debug_grad_sqnorms(LhwRnn* rnn, float* out2_host);
 int lhw_rnn_normalize(LhwRnn* rnn, const float* obs, int64_t R, const float* obs_mean, const float* obs_std, float* xn,
                       float* xm, void* stream);
 
+/* Headless eval frames: the rendering half of the reference's eval (rl/utils/eval.py:38-67: a 640 x 480 tracking camera on the robot,
+ * mujoco.Renderer.update_scene / render once per control step, the frames written as a video) as a ray caster for the analytic
+ * primitives the model loader accepts (mjtGeom values of lhw_model_fields.h's geom_type: plane 0, sphere 2, capsule 3, ellipsoid 4,
+ * cylinder 5, box 6; geom_size as MuJoCo's: sphere r; capsule / cylinder r, half length along local z; ellipsoid semi-axes; box half
+ * extents; a plane is infinite).  No GL, no CPU MuJoCo, no pixel parity with MuJoCo's renderer: the camera model and the shading are
+ * the ones stated here.  Pixel (x, y) of a W x H image, y growing downwards, looks along
+ *   d = normalize(forward + tan(fovy / 2) * ((2 (x + 0.5) / W - 1) * W / H * right - (2 (y + 0.5) / H - 1) * up)). */
+typedef struct {
+  int32_t width, height;        /* pixels, any value >= 1 (edge tiles are clipped) */
+  float   fovy_deg;             /* vertical field of view; default 45 */
+  float   light_dir[3];         /* unit vector towards the light, world frame */
+  float   ambient, diffuse;     /* colour = rgb * (ambient + diffuse * max(0, n.l) * lit) */
+  float   background[3];
+  float   checker_size;         /* > 0: planes get a checkerboard of this cell size (second colour = 0.8 * rgb); 0: none */
+  int32_t shadows;              /* != 0: one shadow ray towards light_dir, origin = hit + 1e-3 m * n */
+  int32_t cull;                 /* != 0 (default): per-tile geom culling; 0: every tile tests every geom (test hook, same bits) */
+} LhwRenderSettings;
+#define LHW_RENDER_MAX_GEOMS 64
+/* F frames of G geoms in one launch, one wavefront per 8 x 8 pixel tile of one frame.  All pointers are device buffers; the call keeps
+ * no state and works on any stream.  geom_pos is RELATIVE TO THE FRAME'S CAMERA POSITION (the host subtracts in float64 before it casts:
+ * a robot 50 m from the origin renders like one at the origin); geom_mat is the geom's world rotation, row-major (columns = local axes).
+ * cam[f] = the rows right, up, forward of the camera frame (9), the camera's world x, y reduced modulo 2 * checker_size in float64 (2:
+ * the checkerboard is anchored to the world), one pad.  A geom with rgba alpha 0 is not drawn and casts no shadow.  Outputs: rgb 8-bit
+ * (channel = floor(255 * min(1, c) + 0.5)); hit = geom_id * 8 + surface part (box face 0..5 = -x +x -y +y -z +z; capsule 0 body, 1 the
+ * cap at -z, 2 at +z; cylinder 0 body, 1 the disc at -z, 2 at +z; 0 otherwise), -1 for background; depth = the ray parameter t of the
+ * unit direction d, +inf for background.  Planes are two-sided (the normal is flipped towards the viewer); only hits with t > 0 count.
+ * G > LHW_RENDER_MAX_GEOMS: LHW_ERR_UNSUPPORTED; a non-positive image size, field of view or drawn geom size, an unknown geom type:
+ * LHW_ERR_ARG -- with nothing written (the type and size tables are read back once: the call synchronises `stream` before it launches). */
+int lhw_render_frames(const LhwRenderSettings* s, int32_t G, const int32_t* geom_type_dev /*[G]*/, const float* geom_size_dev /*[G][3]*/,
+                      const float* geom_rgba_dev /*[G][4], alpha 0 = not drawn*/, int32_t F, const float* geom_pos_dev /*[F][G][3]*/,
+                      const float* geom_mat_dev /*[F][G][9]*/, const float* cam_dev /*[F][12]*/, uint8_t* rgb_dev /*[F][H][W][3]*/,
+                      int32_t* hit_dev /*[F][H][W], nullable*/, float* depth_dev /*[F][H][W], nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

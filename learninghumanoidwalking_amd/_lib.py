@@ -159,6 +159,14 @@ class LhwRolloutLstmPolicy(ctypes.Structure):      # include/lhw.h: the frozen L
         ("seed", ctypes.c_uint64), ("counter", ctypes.c_uint32)]
 
 
+class LhwRenderSettings(ctypes.Structure):      # include/lhw.h: lhw_render_frames
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fovy_deg", ctypes.c_float), ("light_dir", ctypes.c_float * 3),
+                ("ambient", ctypes.c_float), ("diffuse", ctypes.c_float), ("background", ctypes.c_float * 3), ("checker_size", ctypes.c_float),
+                ("shadows", ctypes.c_int32), ("cull", ctypes.c_int32)]
+
+
+RENDER_MAX_GEOMS = 64      # include/lhw.h LHW_RENDER_MAX_GEOMS
+
 # include/lhw.h: enum LhwTaskInput (offsets into one env's record, length)
 TASK_INPUT_DIM = 176
 TASK_INPUT_FIELDS = dict(grf_r=(0, 1), grf_l=(1, 1), contact_z=(2, 1), foot_contact=(3, 1), self_collision=(4, 1), phase=(5, 1), mode=(6, 1),
@@ -383,6 +391,7 @@ def declare(L):
     sig("lhw_rnn_rollout_policy", [vp, vp, vp, vp, u64, u32, ctypes.c_int, ctypes.POINTER(LhwRolloutLstmPolicy), vp])
     sig("lhw_env_rollout_lstm", [vp, ctypes.POINTER(LhwRolloutLstmPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_debug_lstm_policy_step", [ctypes.POINTER(LhwRolloutLstmPolicy), vp, i32, vp, u32, u32, vp, vp, vp, vp])
+    sig("lhw_render_frames", [ctypes.POINTER(LhwRenderSettings), i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     return L
 
 

@@ -20,7 +20,8 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from .model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_ELLIPSOID, GEOM_PLANE, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, Model)
+from .model import (GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_ELLIPSOID, GEOM_PLANE, GEOM_SPHERE, JNT_FREE, JNT_HINGE, JNT_SLIDE, Model,
+                    default_geom_rgba)
 
 
 class MjcfError(ValueError):
@@ -320,7 +321,8 @@ class _Compiler:
                  solmix=float(a.get("solmix", 1.0)), solref=_floats(a.get("solref", "0.02 1"), 2),
                  solimp=self._solimp(a.get("solimp")), margin=float(a.get("margin", 0.0)),
                  gap=float(a.get("gap", 0.0)), density=float(a.get("density", 1000.0)),
-                 mass=float(a["mass"]) if "mass" in a else None, group=int(a.get("group", 0)))
+                 mass=float(a["mass"]) if "mass" in a else None, group=int(a.get("group", 0)),
+                 rgba=_floats(a["rgba"], 4) if "rgba" in a else None)      # (the geom's own or its default class's; None: model.default_geom_rgba)
         if g["condim"] not in (1, 3):
             raise MjcfError("only condim 1 and 3 are supported")
         self.geoms.append(g)
@@ -559,6 +561,7 @@ class _Compiler:
         a["geom_solimp"] = np.array([g["solimp"] for g in G], dtype=float).reshape(ng, 5)
         a["geom_margin"] = np.array([g["margin"] for g in G], dtype=float)
         a["geom_gap"] = np.array([g["gap"] for g in G], dtype=float)
+        m.geom_rgba = np.array([g["rgba"] if g["rgba"] is not None else default_geom_rgba(g["type"], g["body"]) for g in G], dtype=float).reshape(ng, 4)
 
         # sites
         ns = m.nsite

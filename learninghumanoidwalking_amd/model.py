@@ -115,6 +115,18 @@ FIELDS = [
 I_FIELDS = [f for f in FIELDS if f[1] == "i"]
 D_FIELDS = [f for f in FIELDS if f[1] == "d"]
 
+# Colours of geoms whose MJCF names none (render.py): eight hues indexed by body id, so that neighbouring links -- and the left and the
+# right leg of the stand-in robots -- differ; a plane (the floor) is 0.5 grey
+GEOM_PALETTE = ((0.90, 0.45, 0.35), (0.35, 0.60, 0.90), (0.45, 0.80, 0.45), (0.95, 0.80, 0.30), (0.70, 0.50, 0.85), (0.35, 0.80, 0.80),
+                (0.90, 0.55, 0.75), (0.65, 0.65, 0.60))
+
+
+def default_geom_rgba(geom_type: int, body_id: int) -> tuple:
+    if int(geom_type) == GEOM_PLANE:
+        return (0.5, 0.5, 0.5, 1.0)
+    return GEOM_PALETTE[int(body_id) % len(GEOM_PALETTE)] + (1.0,)
+
+
 # mjtDisableBit subset
 DSBL_ACTUATION = 1 << 10  # informational: actuation is disabled per call, not in the model
 DSBL_REFSAFE = 1 << 11
@@ -153,6 +165,7 @@ class Model:
     actuator_names: list = field(default_factory=list)
     site_names: list = field(default_factory=list)
     fused_into: dict = field(default_factory=dict)   # fuse_static: absorbed body name -> absorbing body name
+    geom_rgba: object = None   # [ngeom][4] float64 colours for render.py (mjcf.py: the geom's rgba or default_geom_rgba); not packed: the stepper never reads it
 
     def __getattr__(self, name):
         arrays = self.__dict__.get("arrays", {})
@@ -181,6 +194,7 @@ class Model:
         m.arrays = {k: v.copy() for k, v in self.arrays.items()}
         for k in ("body_names", "jnt_names", "geom_names", "actuator_names", "site_names"):
             setattr(m, k, list(getattr(self, k)))
+        m.geom_rgba = None if self.geom_rgba is None else np.array(self.geom_rgba, dtype=np.float64)
         return m
 
     # -- fusestatic -----------------------------------------------------------------

@@ -5,6 +5,7 @@ on-device rollout + PPO of this repository.
     python run_experiment.py train --env jvrc_walk --gpus 8 ...        (re-executes itself as 8 ranks under torch.distributed.run)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_experiment.py train --env jvrc_walk ...
     python run_experiment.py eval --path RUN_DIR|ACTOR.pt [--num-envs 64] [--ep-len 10] [--seed S] [--out-dir DIR] [--trace-envs 16]
+    python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1]
     python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
 Differences from the reference, by design: no Ray (`--num-procs` is the number of on-device envs per GPU unless
@@ -17,7 +18,9 @@ counts trajectories in the reference; `--imitate` needs an env description with 
 `--num-envs` deterministic episodes of `--ep-len` seconds in parallel on the device, prints one JSON object -- checkpoint, env, seed,
 episodes, terminated, truncated, mean return, mean length, mean episode sum per reward term -- and writes it to eval_summary.json in
 `--out-dir` (default: the run directory).  With `--out-dir`, a feed-forward policy also leaves trajectory.npz there: qpos [T][K][nq],
-qvel, action, reward, done of the first `--trace-envs` envs, enough to replay the motion in a MuJoCo viewer elsewhere.
+qvel, action, reward, done of the first `--trace-envs` envs, enough to replay the motion in a MuJoCo viewer elsewhere.  `--render-envs K`
+also draws the first K of them, one PNG per control step under DIR/frames/env<k>/ -- the tracking camera of the reference's eval
+(rl/utils/eval.py:38-67) through the HIP ray caster of render.py, no GL and no MuJoCo -- and adds "frames" to the summary.
 """
 import argparse
 import json
@@ -123,7 +126,43 @@ def build_eval_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out-dir", type=Path, default=None, help="where eval_summary.json (and trajectory.npz) go; default: the run directory, summary only")
     p.add_argument("--trace-envs", type=int, default=16, help="envs whose trajectory is written with --out-dir")
+    p.add_argument("--render-envs", type=int, default=0, help="with --out-dir: PNG frames of the first K traced envs, frames/env<k>/<step>.png (0: none, no renderer is created)")
+    p.add_argument("--render-size", type=_size, default=(640, 480), metavar="WxH", help="frame size in pixels (the reference's eval: 640x480)")
+    p.add_argument("--render-every", type=int, default=1, metavar="N", help="a frame every N control steps")
     return p
+
+
+def _size(text):
+    try:
+        w, h = (int(x) for x in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not WxH") from None
+    if w < 1 or h < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: both sizes must be at least 1")
+    return w, h
+
+
+def write_frames(out_dir, env, env_name, qpos, size, every):
+    """PNG frames of the traced motion qpos [T][K][nq], the tracking camera of the reference's eval (rl/utils/eval.py:38-67) on every env:
+    <out_dir>/frames/env<k:03d>/<t:05d>.png for every `every`-th control step t.  Returns the summary's "frames" entry."""
+    from learninghumanoidwalking_amd.render import Renderer, write_png
+    hidden, entry = (), dict(dir="frames", count=0, size=list(size), every=every)
+    if env_name == "jvrc_step":
+        # the terrain boxes are placed per env and per episode and the record does not hold their poses: not drawn in this version
+        hidden = [g for g, n in enumerate(env.model.geom_names) if n.startswith("box")]
+        entry["note"] = "the stepping terrain's boxes are not drawn: the trajectory record does not hold their poses"
+    r = Renderer(env.model, size[0], size[1], device=env.device, hidden_geoms=hidden)
+    steps = list(range(0, qpos.shape[0], every))
+    for k in range(qpos.shape[1]):
+        d = Path(out_dir, "frames", f"env{k:03d}")
+        d.mkdir(parents=True, exist_ok=True)
+        for i in range(0, len(steps), r.frames_per_chunk):
+            part = steps[i:i + r.frames_per_chunk]
+            rgb = r.render(qpos[part, k]).cpu().numpy()
+            for t, img in zip(part, rgb):
+                write_png(d / f"{t:05d}.png", img)
+            entry["count"] += len(part)
+    return entry
 
 
 def get_latest_actor(run_dir: Path) -> Path:
@@ -168,6 +207,10 @@ def resolve_checkpoint(path, logdir):
 
 def run_eval(argv):
     ea = build_eval_parser().parse_args(argv)
+    if ea.render_envs > 0 and ea.out_dir is None:
+        raise SystemExit("eval: --render-envs needs --out-dir (the frames go to <out-dir>/frames)")
+    if ea.render_envs < 0 or ea.render_every < 1:
+        raise SystemExit("eval: --render-envs must be >= 0 and --render-every >= 1")
     actor, critic, pkl = resolve_checkpoint(ea.path, ea.logdir)
     import torch
     if not torch.cuda.is_available():
@@ -208,6 +251,8 @@ def run_eval(argv):
     if ea.out_dir is not None:
         if algo.rollout.tin_all is None:
             summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
+            if ea.render_envs > 0:
+                summary["frames"] = summary["trajectory"]
         else:
             ro, K = algo.rollout, max(1, min(ea.trace_envs, ea.num_envs))
             rec = ro.tin_all[:, :K].cpu().numpy()
@@ -217,6 +262,8 @@ def run_eval(argv):
                      action=rec[:, :, a0:a0 + env.act_dim], reward=ro.rew[:, :K].cpu().numpy(), done=ro.done[:, :K].cpu().numpy(),
                      control_dt=np.float64(env_fn().control_dt))
             summary["trajectory"] = "trajectory.npz"
+            if ea.render_envs > 0:
+                summary["frames"] = write_frames(out_dir, env, args.env, rec[:, :min(ea.render_envs, K), q0:q0 + env.nq], ea.render_size, ea.render_every)
     text = json.dumps(summary, indent=1)
     with open(Path(out_dir, "eval_summary.json"), "w") as f:
         f.write(text + "\n")
