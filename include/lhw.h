@@ -558,6 +558,17 @@ int lhw_env_set_iteration(LhwEnv* env, int64_t iteration);
 int lhw_env_phase_cycles(LhwEnv* env, int enable, int64_t* out16);
 /* Diagnostic: resident workgroups per CU the HIP runtime reports for the wave-per-env step kernel. */
 int lhw_debug_stepper_occupancy(void);
+/* Test hook: the cross-lane (DPP) fetches of the humanoid steppers in their two forms -- the reference form, which passes the identity of a
+ * lane without a source as the `old` operand, and the form the kernels run, which takes a zero identity word from bound_ctrl (csrc/
+ * lhw_humanoid_dev.h: dpp_d_ref / dpp_d, rbc_ref / rbc, gscan_lanes).  ONE wavefront; lane l takes part iff bit l of lane_mask is set, reads
+ * in[l] (DEVICE pointer, [64] doubles) and stores what it fetched, as bits, to out_ref / out_shipped [LHW_DPP_FORMS][64] (device): rows 0-3
+ * row_shr 1 2 4 8 and rows 4-7 row_shl 1 2 4 8 with identity 0.0, row 8 row_shr:1 with identity 1.0, row 9 with +inf, rows 10-13
+ * row_newbcast of row positions 0 2 5 15, rows 14 / 15 the inclusive int scan of ((low ^ high word) & 0xffff) with one env / two envs per
+ * wave, its masked row_bcast steps included.  Entries of lanes outside the mask are left as the caller filled them.  The two outputs are
+ * equal bit for bit, except that a row_newbcast whose source lane is outside the mask returns the lane's own value in the reference form and
+ * 0 in the other (no kernel reads either). */
+#define LHW_DPP_FORMS 16
+int lhw_debug_dpp_forms(uint64_t lane_mask, const double* in, uint64_t* out_ref, uint64_t* out_shipped, void* stream);
 
 /* ------------------------------------------------------------------ PPO (actor/critic MLP, GAE, update) */
 typedef struct LhwPpo LhwPpo;

@@ -737,6 +737,50 @@ int humanoid_occupancy() {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, humanoid_kernel<0, TASK_WALK, 32>, 64, 0) != hipSuccess) return -1;
   return nb;
 }
+// Test hook lhw_debug_dpp_forms: the cross-lane fetches of lhw_humanoid_dev.h, each in its reference form (REF: the identity as the `old`
+// operand) and in the form the kernels run, on ONE wavefront whose lanes outside `mask` have left before the first fetch.  Row f of `out`
+// receives the bits lane l fetched as out[64 f + l]; a lane outside the mask stores nothing.
+template <bool REF, int CTRL, long long IDENT>
+__device__ __forceinline__ unsigned long long dpp_form_d(double v) {
+  if constexpr (REF) return (unsigned long long)__double_as_longlong(dpp_d_ref<CTRL, 0xf, IDENT>(v));
+  else return (unsigned long long)__double_as_longlong(dpp_d<CTRL, 0xf, IDENT>(v));
+}
+template <bool REF, int SRC>
+__device__ __forceinline__ unsigned long long dpp_form_rbc(double v) {
+  if constexpr (REF) return (unsigned long long)__double_as_longlong(rbc_ref<SRC>(v));
+  else return (unsigned long long)__double_as_longlong(rbc<SRC>(v));
+}
+template <bool REF>
+__device__ __forceinline__ void dpp_forms_eval(double v, unsigned long long* __restrict__ out) {
+  out[64 * 0] = dpp_form_d<REF, 0x111, DPP_ZERO>(v); out[64 * 1] = dpp_form_d<REF, 0x112, DPP_ZERO>(v);      // row_shr 1 2 4 8: the sum scans
+  out[64 * 2] = dpp_form_d<REF, 0x114, DPP_ZERO>(v); out[64 * 3] = dpp_form_d<REF, 0x118, DPP_ZERO>(v);
+  out[64 * 4] = dpp_form_d<REF, 0x101, DPP_ZERO>(v); out[64 * 5] = dpp_form_d<REF, 0x102, DPP_ZERO>(v);      // row_shl 1 2 4 8: row_suffix
+  out[64 * 6] = dpp_form_d<REF, 0x104, DPP_ZERO>(v); out[64 * 7] = dpp_form_d<REF, 0x108, DPP_ZERO>(v);
+  out[64 * 8] = dpp_form_d<REF, 0x111, DPP_ONE>(v);                                                          // the affine scan's diagonal
+  out[64 * 9] = dpp_form_d<REF, 0x111, DPP_INF>(v);                                                          // gmin
+  out[64 * 10] = dpp_form_rbc<REF, 0>(v); out[64 * 11] = dpp_form_rbc<REF, 2>(v);
+  out[64 * 12] = dpp_form_rbc<REF, 5>(v); out[64 * 13] = dpp_form_rbc<REF, 15>(v);
+  const int iv = (__double2loint(v) ^ __double2hiint(v)) & 0xffff;                                           // gscan, one env / two envs per wave
+  out[64 * 14] = (unsigned long long)(unsigned)gscan_lanes<64, REF>(iv);
+  out[64 * 15] = (unsigned long long)(unsigned)gscan_lanes<32, REF>(iv);
+}
+static_assert(LHW_DPP_FORMS == 16, "dpp_forms_eval: rows of include/lhw.h");
+__global__ void __launch_bounds__(64) dpp_forms_kernel(unsigned long long mask, const double* __restrict__ in, unsigned long long* __restrict__ ref,
+                                                       unsigned long long* __restrict__ shipped) {
+  const int lane = (int)threadIdx.x;
+  if ((mask >> lane) & 1ull) {
+    const double v = in[lane];
+    dpp_forms_eval<true>(v, ref + lane);
+    dpp_forms_eval<false>(v, shipped + lane);
+  }
+}
+extern "C" int lhw_debug_dpp_forms(uint64_t lane_mask, const double* in, uint64_t* out_ref, uint64_t* out_shipped, void* stream) {
+  if (!in || !out_ref || !out_shipped) return lhw_fail(LHW_ERR_ARG, "lhw_debug_dpp_forms: bad argument");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
+  hipLaunchKernelGGL(dpp_forms_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)lane_mask, in, (unsigned long long*)out_ref,
+                     (unsigned long long*)out_shipped);
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "dpp_forms_kernel launch failed");
+}
 // diagnostic: per-env duration of the last control-step launch (load balance across wavefronts)
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out) {
   const size_t N = h->p.n_envs;

@@ -622,12 +622,39 @@ template <class L> __device__ __forceinline__ double prm_ipos(HModelRef m, const
 // rows: an inclusive scan whose last lane holds the total) instead of ds_bpermute shuffles: ~20 VALU ops and no LDS round
 // trips per reduction.  gfx950 is GFX9-family, so row_bcast is available.  With W = 32 the row_bcast:15 step (rows 1 and 3
 // only) completes the scan of both halves at once and the total sits in lane 31 / 63; nothing crosses the half boundary.
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int dpp_i(int v, int ident) { return __builtin_amdgcn_update_dpp(ident, v, CTRL, ROWMASK, 0xf, false); }
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_d(double v, double ident) {
-  int lo = dpp_i<CTRL, ROWMASK>(__double2loint(v), __double2loint(ident));
-  int hi = dpp_i<CTRL, ROWMASK>(__double2hiint(v), __double2hiint(ident));
+// A lane whose DPP source does not exist (row_shr past the start of the row ...) or is switched off receives the operation's identity,
+// IDENT -- a template parameter, the bit pattern for a double (DPP_ZERO / DPP_ONE / DPP_INF), so that the form of the fetch is settled
+// at compile time.  dpp_i_ref / dpp_d_ref are the reference form: IDENT travels as the `old` operand of the DPP move.  That operand is
+// tied to the destination register, which the move overwrites, so the compiler materialises IDENT in a fresh register in front of EVERY
+// fetch: one `v_mov_b32 vN, 0` per 32-bit word of a sum scan (profiles/r22_dpp_bound_ctrl_ab.txt has the counts).  dpp_i / dpp_d are the
+// form the kernels run: a word whose identity is 0 is fetched with old = 0 and bound_ctrl, under which the hardware itself hands 0 to a
+// lane without a source and no register is set up (both words of 0.0, the low words of 1.0 and of +inf, gscan's 0).  A word with another
+// identity (the high words of 1.0 and of +inf) keeps the reference form, and so does every fetch with a partial row mask (gscan's
+// row_bcast steps): the rows outside the mask are not written at all and must keep `old`, which bound_ctrl does not give them.  The
+// moved bits are the same in both forms (tests/test_dpp_forms_gpu.py, lhw_debug_dpp_forms); LHW_DPP_BOUND_CTRL=0 builds the reference
+// form everywhere (A/B, scripts/build_variant.sh).  The builtin stays, so the compiler's hazard recogniser keeps placing the wait
+// states between a VALU write and a DPP read of the same register.
+#ifndef LHW_DPP_BOUND_CTRL
+#define LHW_DPP_BOUND_CTRL 1
+#endif
+constexpr long long DPP_ZERO = 0ll, DPP_ONE = 0x3ff0000000000000ll, DPP_INF = 0x7ff0000000000000ll;   // 0.0, 1.0, +inf
+template <int CTRL, int ROWMASK, int IDENT>
+__device__ __forceinline__ int dpp_i_ref(int v) { return __builtin_amdgcn_update_dpp(IDENT, v, CTRL, ROWMASK, 0xf, false); }
+template <int CTRL, int ROWMASK, int IDENT>
+__device__ __forceinline__ int dpp_i(int v) {
+  if constexpr (LHW_DPP_BOUND_CTRL && IDENT == 0 && ROWMASK == 0xf) return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+  else return dpp_i_ref<CTRL, ROWMASK, IDENT>(v);
+}
+template <int CTRL, int ROWMASK, long long IDENT>
+__device__ __forceinline__ double dpp_d_ref(double v) {
+  int lo = dpp_i_ref<CTRL, ROWMASK, (int)(unsigned)(IDENT & 0xffffffffll)>(__double2loint(v));
+  int hi = dpp_i_ref<CTRL, ROWMASK, (int)(unsigned)((unsigned long long)IDENT >> 32)>(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+template <int CTRL, int ROWMASK, long long IDENT>
+__device__ __forceinline__ double dpp_d(double v) {
+  int lo = dpp_i<CTRL, ROWMASK, (int)(unsigned)(IDENT & 0xffffffffll)>(__double2loint(v));
+  int hi = dpp_i<CTRL, ROWMASK, (int)(unsigned)((unsigned long long)IDENT >> 32)>(__double2hiint(v));
   return __hiloint2double(hi, lo);
 }
 // index of this lane's group inside the wavefront (0 for W = 64)
@@ -671,11 +698,27 @@ __device__ __forceinline__ int gbcast_i(int v, int src) {
     return group_id<W>() ? b : a;
   }
 }
-// value held by lane SRC of the caller's 16-lane row: one v_mov_b64_dpp (row_newbcast, gfx90a+)
+// value held by lane SRC of the caller's 16-lane row: one v_mov_b64_dpp (row_newbcast, gfx90a+).  rbc_ref, the reference form, passes the
+// source as `old` too; where the source is still live behind the fetch (dg in chain_col; cv, ca, fs, ci in chain_dynamics) the compiler
+// then copies it first, because `old` is tied to the destination.  row_newbcast has a source lane inside the row for every lane, so `old`
+// is never read for want of one: rbc passes old = 0 with bound_ctrl and the copy goes.  The two forms differ in one case only, a source
+// lane that EXEC has switched off: the reference form leaves the reader its own value, bound_ctrl gives it 0.  Neither is the value of
+// the lane asked for, and no reader uses it: the chain phases run these fetches with the whole group active -- a lane without a dof
+// computes along and its results are dropped by the selects on `isdof` / the row position -- so a lane that has left can only be the
+// source of lanes that have left as well (every stored output of the three bench envs is byte for byte the same in the two forms,
+// profiles/r22_dpp_bound_ctrl_ab.txt).
 template <int SRC>
-__device__ __forceinline__ double rbc(double v) {
+__device__ __forceinline__ double rbc_ref(double v) {
   const long long lv = __double_as_longlong(v);
   return __longlong_as_double(__builtin_amdgcn_update_dpp(lv, lv, 0x150 + SRC, 0xf, 0xf, false));
+}
+template <int SRC>
+__device__ __forceinline__ double rbc(double v) {
+#if LHW_DPP_BOUND_CTRL
+  return __longlong_as_double(__builtin_amdgcn_update_dpp(0ll, __double_as_longlong(v), 0x150 + SRC, 0xf, 0xf, true));
+#else
+  return rbc_ref<SRC>(v);
+#endif
 }
 // ---- v_fmac_f64 with a DPP source (round 6).  gfx90a+ encode v_fmac_f64 as VOP2, and a VOP2 instruction can take its first source
 // through DPP; for 64-bit operands the one control available is row_newbcast -- exactly the chain layout's "value held by the lane of
@@ -808,7 +851,7 @@ __device__ __forceinline__ void x32_pair(double v, double& lower, double& upper)
 // group are combined with lane-swap instructions -- no v_readlane / SGPR round trip, ~18 VALU instructions for W = 32.
 template <int W>
 __device__ __forceinline__ double gsum(double v) {
-  v += dpp_d<0x111, 0xf>(v, 0.0); v += dpp_d<0x112, 0xf>(v, 0.0); v += dpp_d<0x114, 0xf>(v, 0.0); v += dpp_d<0x118, 0xf>(v, 0.0);
+  v += dpp_d<0x111, 0xf, DPP_ZERO>(v); v += dpp_d<0x112, 0xf, DPP_ZERO>(v); v += dpp_d<0x114, 0xf, DPP_ZERO>(v); v += dpp_d<0x118, 0xf, DPP_ZERO>(v);
   v = xhalf_sum(rbc<15>(v));
   if constexpr (W == 64) { double l, u; x32_pair(v, l, u); v = l + u; }
   return v;
@@ -821,7 +864,7 @@ __device__ __forceinline__ void gsum2(double a, double b, double& sa, double& sb
   const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
   // first result: [a(even row), b(even row)] per row pair, second: [a(odd row), b(odd row)]
   double v = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-  v += dpp_d<0x111, 0xf>(v, 0.0); v += dpp_d<0x112, 0xf>(v, 0.0); v += dpp_d<0x114, 0xf>(v, 0.0); v += dpp_d<0x118, 0xf>(v, 0.0);
+  v += dpp_d<0x111, 0xf, DPP_ZERO>(v); v += dpp_d<0x112, 0xf, DPP_ZERO>(v); v += dpp_d<0x114, 0xf, DPP_ZERO>(v); v += dpp_d<0x118, 0xf, DPP_ZERO>(v);
   xhalf_pair(rbc<15>(v), sa, sb);
   if constexpr (W == 64) {
     double l, u;
@@ -831,21 +874,27 @@ __device__ __forceinline__ void gsum2(double a, double b, double& sa, double& sb
 }
 template <int W>
 __device__ __forceinline__ double gmin(double v) {
-  const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  v = fmin(v, dpp_d<0x111, 0xf>(v, inf)); v = fmin(v, dpp_d<0x112, 0xf>(v, inf)); v = fmin(v, dpp_d<0x114, 0xf>(v, inf));
-  v = fmin(v, dpp_d<0x118, 0xf>(v, inf));
+  v = fmin(v, dpp_d<0x111, 0xf, DPP_INF>(v)); v = fmin(v, dpp_d<0x112, 0xf, DPP_INF>(v)); v = fmin(v, dpp_d<0x114, 0xf, DPP_INF>(v));
+  v = fmin(v, dpp_d<0x118, 0xf, DPP_INF>(v));
   double e, o;
   xhalf_pair(rbc<15>(v), e, o);
   v = fmin(e, o);
   if constexpr (W == 64) { double l, u; x32_pair(v, l, u); v = fmin(l, u); }
   return v;
 }
-// inclusive prefix sum across the group; *total receives the group total
+// inclusive prefix sum across the group; *total receives the group total.  gscan_lanes: the scan itself (REF: with every fetch in the
+// reference form, for lhw_debug_dpp_forms); its row_bcast steps write the rows of their mask only and keep the reference form either way
+template <int W, bool REF>
+__device__ __forceinline__ int gscan_lanes(int v) {
+  if constexpr (REF) { v += dpp_i_ref<0x111, 0xf, 0>(v); v += dpp_i_ref<0x112, 0xf, 0>(v); v += dpp_i_ref<0x114, 0xf, 0>(v); v += dpp_i_ref<0x118, 0xf, 0>(v); }
+  else { v += dpp_i<0x111, 0xf, 0>(v); v += dpp_i<0x112, 0xf, 0>(v); v += dpp_i<0x114, 0xf, 0>(v); v += dpp_i<0x118, 0xf, 0>(v); }
+  v += dpp_i<0x142, 0xa, 0>(v);
+  if constexpr (W == 64) v += dpp_i<0x143, 0xc, 0>(v);
+  return v;
+}
 template <int W>
 __device__ __forceinline__ int gscan(int v, int* total) {
-  v += dpp_i<0x111, 0xf>(v, 0); v += dpp_i<0x112, 0xf>(v, 0); v += dpp_i<0x114, 0xf>(v, 0); v += dpp_i<0x118, 0xf>(v, 0);
-  v += dpp_i<0x142, 0xa>(v, 0);
-  if constexpr (W == 64) v += dpp_i<0x143, 0xc>(v, 0);
+  v = gscan_lanes<W, false>(v);
   *total = gbcast_i<W>(v, W - 1);
   return v;
 }
@@ -1047,15 +1096,17 @@ __device__ __forceinline__ double chain_solve(double (&R)[NR], double dg, double
 // Hillis-Steele scan of map compositions along the row (row_shr 1, 2, 4 [, 8]; identity where a lane has no source) gives every
 // world frame in log2 depth: three rounds of 24 DPP moves + a 3x3 product instead of seven dependent tree levels with an LDS
 // hand-off each.  Bodies without a joint (welded upper body ...) are then one product with the frame of the body they move with.
+// value of the lane the row control names; 0.0 / 1.0 where the row has none (the off-diagonal / diagonal entries of the identity map)
 template <int CTRL>
-__device__ __forceinline__ double dpp_row_id(double v, double ident) { return dpp_d<CTRL, 0xf>(v, ident); }
+__device__ __forceinline__ double dpp_row(double v) { return dpp_d<CTRL, 0xf, DPP_ZERO>(v); }
+template <int CTRL>
+__device__ __forceinline__ double dpp_row_one(double v) { return dpp_d<CTRL, 0xf, DPP_ONE>(v); }
 template <int CTRL>
 __device__ __forceinline__ void affine_scan_round(double (&R)[9], double (&pw)[3]) {
-  double Ra[9], pa[3];
-#pragma unroll
-  for (int k = 0; k < 9; k++) Ra[k] = dpp_row_id<CTRL>(R[k], (k % 4 == 0) ? 1.0 : 0.0);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pa[k] = dpp_row_id<CTRL>(pw[k], 0.0);
+  // (written out: which identity an entry takes is a compile-time property of its fetch)
+  const double Ra[9] = {dpp_row_one<CTRL>(R[0]), dpp_row<CTRL>(R[1]), dpp_row<CTRL>(R[2]), dpp_row<CTRL>(R[3]), dpp_row_one<CTRL>(R[4]), dpp_row<CTRL>(R[5]),
+                        dpp_row<CTRL>(R[6]), dpp_row<CTRL>(R[7]), dpp_row_one<CTRL>(R[8])};
+  const double pa[3] = {dpp_row<CTRL>(pw[0]), dpp_row<CTRL>(pw[1]), dpp_row<CTRL>(pw[2])};
   double Rn[9], t[3];
   mat_mul(Rn, Ra, R);
   mat_vec(t, Ra, pw);
@@ -1247,8 +1298,6 @@ __device__ __forceinline__ void fwd_com(HModelRef m, HParamsRef p, L& S, int lan
 // share the bodies that move with the root (pelvis, welded upper body), so the suffix sum at position 0, added over the two
 // rows, is the total of the whole tree = the root's subtree.  M[p][e] = cdof_e . (crb_p cdof_p) for e an ancestor dof of p comes
 // from row broadcasts of cdof; the mirror half of the (symmetric) row is fetched through a 12 x 12 transposition buffer in LDS.
-template <int CTRL>
-__device__ __forceinline__ double dpp_row(double v) { return dpp_d<CTRL, 0xf>(v, 0.0); }
 template <int N>
 __device__ __forceinline__ void row_prefix(double (&v)[N]) {   // inclusive prefix sums along the 16-lane row
 #pragma unroll
