@@ -803,6 +803,41 @@ int lhw_render_frames(const LhwRenderSettings* s, int32_t G, const int32_t* geom
                       const float* geom_mat_dev /*[F][G][9]*/, const float* cam_dev /*[F][12]*/, uint8_t* rgb_dev /*[F][H][W][3]*/,
                       int32_t* hit_dev /*[F][H][W], nullable*/, float* depth_dev /*[F][H][W], nullable*/, void* stream);
 
+/* lhw_render_frames with per-frame geoms, more of them, translucency and a cone: the task markers and the stepping terrain of the
+ * reference's eval (envs/jvrc/jvrc_step.py:78-198 draw_markers, tasks/stepping_task.py:320-334).  Camera model, ray, shading formula, the
+ * 8 x 8 tile per wavefront, camera-relative float32 positions, cam[f], hit parts and byte rounding are those stated above; what is added:
+ *
+ * Static and dynamic geoms.  A frame draws the G static geoms -- type / size / rgba shared by all F frames, poses per frame, as above --
+ * and M dynamic geoms whose type [F][M], size [F][M][3], rgba [F][M][4], pos [F][M][3] (relative to the frame's camera) and mat [F][M][9]
+ * are all per frame.  Alpha 0 = absent in this frame.  Geom ids in the outputs: static g -> g, dynamic m -> G + m.  G or M may be 0 and
+ * their pointers then NULL.  G + M <= LHW_RENDER_SCENE_MAX_GEOMS, else LHW_ERR_UNSUPPORTED (nothing written); the wave walks them in
+ * passes of 64 in id order.  cull = 0 gives the same bits as cull = 1.
+ *
+ * Alpha.  alpha == 0: not drawn.  0 < alpha < 1: translucent.  Any other value (1 in particular): opaque.  Along a pixel's ray let t_o be
+ * the nearest opaque surface (+inf: none); hit / depth / the shadow ray are those of that surface, as above.  Every translucent geom
+ * contributes at most ONE layer: its nearest surface point with t > 0, if t < t_o (strictly).  Layer colour = rgb * (ambient + diffuse *
+ * max(0, n.l)), planes with the checker rule, n the outward normal of that point (planes: towards the viewer); a layer takes no shadow
+ * test, and translucent geoms cast no shadow (shadow rays see every OPAQUE drawn geom, of every pass).  The nearest LHW_RENDER_MAX_LAYERS
+ * layers, ordered by t (equal t: the lower geom id in front), are composited front to back over the opaque colour or the background C_o
+ * in float32:  C = sum_k a_k c_k prod_{j<k} (1 - a_j) + prod_k (1 - a_k) * C_o;  farther layers are dropped.  Outputs, both nullable:
+ * layers = the number of composited layers (0..8), layer_hit = id * 8 + part of the front-most layer, -1 where there is none.
+ *
+ * Cone, type LHW_RENDER_CONE (render-only, not an mjtGeom value): size (r, hl); axis = local z, the base disc of radius r at z = -hl, the
+ * apex at z = +hl.  Part 0 = the lateral surface, part 1 = the base (normal -z).  Lateral normal proportional to (x, y, rho * r / (2 hl)),
+ * rho = sqrt(x^2 + y^2); at the apex (0, 0, 1).  Bounding radius for the culling sqrt(r^2 + hl^2).
+ *
+ * Errors as above, with nothing written: an unknown type or a non-positive needed size (cone: r and hl) of a geom with alpha != 0 -- static,
+ * or dynamic in any frame -- is LHW_ERR_ARG.  The static and the dynamic type / size / rgba tables are read back once before the launch. */
+#define LHW_RENDER_SCENE_MAX_GEOMS 256
+#define LHW_RENDER_MAX_LAYERS 8
+#define LHW_RENDER_CONE 32
+int lhw_render_scene(const LhwRenderSettings* s, int32_t G, const int32_t* geom_type_dev /*[G]*/, const float* geom_size_dev /*[G][3]*/,
+                     const float* geom_rgba_dev /*[G][4]*/, int32_t M, const int32_t* dyn_type_dev /*[F][M]*/, const float* dyn_size_dev /*[F][M][3]*/,
+                     const float* dyn_rgba_dev /*[F][M][4]*/, int32_t F, const float* geom_pos_dev /*[F][G][3]*/, const float* geom_mat_dev /*[F][G][9]*/,
+                     const float* dyn_pos_dev /*[F][M][3]*/, const float* dyn_mat_dev /*[F][M][9]*/, const float* cam_dev /*[F][12]*/,
+                     uint8_t* rgb_dev /*[F][H][W][3]*/, int32_t* hit_dev /*[F][H][W], nullable*/, float* depth_dev /*[F][H][W], nullable*/,
+                     int32_t* layers_dev /*[F][H][W], nullable*/, int32_t* layer_hit_dev /*[F][H][W], nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,7 @@ class LhwRenderSettings(ctypes.Structure):      # include/lhw.h: lhw_render_fram
 
 
 RENDER_MAX_GEOMS = 64      # include/lhw.h LHW_RENDER_MAX_GEOMS
+RENDER_SCENE_MAX_GEOMS, RENDER_MAX_LAYERS, RENDER_CONE = 256, 8, 32      # include/lhw.h LHW_RENDER_SCENE_MAX_GEOMS / _MAX_LAYERS / _CONE
 
 # include/lhw.h: enum LhwTaskInput (offsets into one env's record, length)
 TASK_INPUT_DIM = 176
@@ -393,6 +394,7 @@ def declare(L):
     sig("lhw_env_rollout_lstm", [vp, ctypes.POINTER(LhwRolloutLstmPolicy), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_debug_lstm_policy_step", [ctypes.POINTER(LhwRolloutLstmPolicy), vp, i32, vp, u32, u32, vp, vp, vp, vp])
     sig("lhw_render_frames", [ctypes.POINTER(LhwRenderSettings), i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_render_scene", [ctypes.POINTER(LhwRenderSettings), i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     return L
 
 

@@ -160,6 +160,10 @@ class Rollout(_RolloutStorage):
         super().__init__(env, kernels, T, seed)
         self.task, self.max_traj_len = task, int(max_traj_len if max_traj_len is not None else T)
         self.record_task_inputs = False      # True: a resident rollout also keeps the task-input record of every control step (tin_all)
+        # True, on the stepping env without a plugged-in task: the rollout runs launch per step (bitwise the resident one), keeps both
+        # task-input records of every control step and the stepping terrain that was in force during it (terrain_seq / _nseq / _floor_z)
+        self.record_terrain = False
+        self.terrain_seq = self.terrain_nseq = self.terrain_floor_z = None
         # (reward_only is honoured only where the task's done() is this env's fused termination: task_hook.reward_only_on)
         # ... against the bounds the env is configured with (a stand-in env without task_shaping: the reference's)
         shaping = getattr(env, "task_shaping", None) if task is not None else None
@@ -197,7 +201,12 @@ class Rollout(_RolloutStorage):
     def tin_all(self):
         """[T][N][TASK_INPUT_DIM] float64 record of the last resident rollout (None unless one exported it: record_task_inputs or a
         reward-only task)"""
-        return self._tin_all if getattr(self, "last_mode", None) == "resident" else None
+        return self._tin_all if getattr(self, "last_mode", None) in ("resident", "recorded") else None
+
+    @property
+    def stin_all(self):
+        """[T][N][STEP_TASK_INPUT_DIM] float64 stepping record of the last rollout that exported it (stepping env only), else None"""
+        return self._stin_all if getattr(self, "last_mode", None) in ("resident", "recorded") else None
 
     def collect(self, deterministic=False):
         self._start()
@@ -217,7 +226,10 @@ class Rollout(_RolloutStorage):
         """Fills obs / act / logp / tob_all / rew / done and sets last_mode: which path collected the rollout (tests, bench line)."""
         T = self.T
         hooked = self.task is not None and not self.reward_only
-        if not hooked and self._collect_resident(deterministic, task_inputs=self.reward_only or self.record_task_inputs):
+        if self.record_terrain and self.task is None and self.env.task == TASK_JVRC_STEP:
+            self.last_mode = "recorded"
+            self._collect_recorded(deterministic)
+        elif not hooked and self._collect_resident(deterministic, task_inputs=self.reward_only or self.record_task_inputs):
             self.last_mode = "resident"
             if self.reward_only:
                 self._evaluate_recorded_rewards()
@@ -271,6 +283,36 @@ class Rollout(_RolloutStorage):
             return self._declined(mode, "the library has no resident rollout kernel for this env / policy")
         self.counter += T
         return True
+
+    def _collect_recorded(self, deterministic):
+        """The stepping env, launch per step, with a record of everything a frame of it needs: after every control step the two device
+        task-input records go to tin_all[t] / stin_all[t], and the host reads the env's footstep sequence (BatchedEnv.debug_step_record:
+        a small copy per step at eval batch sizes).  The terrain of step t is the sequence that was IN FORCE DURING control step t: the one
+        read after the initial reset for t = 0 and after step t - 1 otherwise -- the one read after step t belongs, at a step that ends
+        an episode, to the next episode already."""
+        from .task_hook import device_task_inputs
+        env, T, N = self.env, self.T, self.N
+        ti = device_task_inputs(env)      # (arms both exports before the first control step)
+        if self._tin_all is None:
+            self._tin_all = _lib.empty(T, N, _lib.TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+            self._stin_all = _lib.empty(T, N, _lib.STEP_TASK_INPUT_DIM, dtype=torch.float64, device=self.obs.device)
+        self.terrain_seq, self.terrain_nseq, self.terrain_floor_z = np.zeros((T, N, 20, 4)), np.zeros((T, N), dtype=np.int32), np.zeros((T, N))
+        torch.cuda.current_stream(self.obs.device).synchronize()
+        in_force = [env.debug_step_record()]
+
+        def after_step(t):
+            self._tin_all[t].copy_(ti.rec)
+            self._stin_all[t].copy_(ti.srec)
+            seq, floor_z, istate = in_force[0]
+            self.terrain_seq[t], self.terrain_nseq[t], self.terrain_floor_z[t] = seq[:, :, :4], istate[:, 4], floor_z
+            torch.cuda.current_stream(self.obs.device).synchronize()
+            in_force[0] = env.debug_step_record()
+
+        groups, self.groups = self.groups, 1      # (one group on the current stream: the hook reads the whole batch)
+        try:
+            self._collect_steps(deterministic, self.rew, self.done, after_step)
+        finally:
+            self.groups = groups
 
     def _collect_steps(self, deterministic, rew, done, after_step=None):
         """Launch per control step: the actor, then the env step writing its reward and flags to rew[t] / done[t], then

@@ -1,5 +1,5 @@
-"""Headless frames of a recorded motion: the host side of lhw_render_frames (include/lhw.h), the HIP ray caster for the analytic
-primitives the model loader accepts.
+"""Headless frames of a recorded motion: the host side of lhw_render_frames and lhw_render_scene (include/lhw.h), the HIP ray caster
+for the analytic primitives the model loader accepts; markers.py builds the per-frame geoms (task markers, stepping terrain) of the second.
 
 The reference's eval renders a 640 x 480 tracking camera once per control step through MuJoCo's GL renderer and writes a video
 (rl/utils/eval.py:38-86).  Here the geoms of every frame are posed on the host in float64 (kinematics.geom_poses), expressed relative
@@ -160,15 +160,68 @@ class Renderer:
                       None if hit is None else hit[f0:f1], None if depth is None else depth[f0:f1])
         return (rgb, hit, depth) if aux or out is not None else rgb
 
-    def render(self, qpos, camera: TrackingCamera | None = None, aux=False):
-        """Frames of the poses qpos [F][nq] (or [nq]) seen by `camera` (default: TrackingCamera()): uint8 tensor [F][H][W][3]."""
+    def upload_dynamic(self, dynamic, cam_pos):
+        """The per-frame device tables of lhw_render_scene's dynamic geoms -- (type [F][M] int32, size [F][M][3], rgba [F][M][4], pos
+        [F][M][3] relative to the camera, mat [F][M][9]), float32 -- from `dynamic`: a markers.Markers, or a dict of numpy arrays type
+        [F][M], size, rgba, pos (world, float64), mat.  The subtraction is done here, in float64."""
+        cam_pos = np.asarray(cam_pos, dtype=np.float64).reshape(-1, 3)
+        F = cam_pos.shape[0]
+        d = dynamic.arrays(F) if hasattr(dynamic, "arrays") else dynamic
+        t = np.asarray(d.get("type", np.zeros((F, 0))), dtype=np.int32).reshape(F, -1)
+        M = t.shape[1]
+        f64 = lambda k, n: np.asarray(d[k], dtype=np.float64).reshape(F, M, n) if M else np.zeros((F, 0, n))
+        rel = f64("pos", 3) - cam_pos[:, None, :]
+        up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(self.device)
+        return up(t, np.int32), up(f64("size", 3), np.float32), up(f64("rgba", 4), np.float32), up(rel, np.float32), up(f64("mat", 9), np.float32)
+
+    def draw_scene(self, frames, dyn, rgb, hit=None, depth=None, layers=None, layer_hit=None):
+        """One lhw_render_scene call on the current stream: `frames` from upload(), `dyn` from upload_dynamic(), outputs as draw()'s plus
+        layers / layer_hit [F][H][W] int32"""
+        if getattr(self._L, "lhw_render_scene", None) is None:
+            raise _lib.LhwError(-4, "this build of the library does not export lhw_render_scene")
+        d_pos, d_mat, d_cam = frames
+        d_type, d_size, d_rgba, d_dpos, d_dmat = dyn
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
+        _lib.check(self._L.lhw_render_scene(ctypes.byref(self.settings), self.n_geoms, _ptr(self._type), _ptr(self._size), _ptr(self._rgba),
+                                            d_type.shape[1], _ptr(d_type), _ptr(d_size), _ptr(d_rgba), d_cam.shape[0], _ptr(d_pos), _ptr(d_mat),
+                                            _ptr(d_dpos), _ptr(d_dmat), _ptr(d_cam), _ptr(rgb), _ptr(hit), _ptr(depth), _ptr(layers), _ptr(layer_hit),
+                                            stream), self._L)
+
+    def render_scene(self, pos, mat, cam_pos, cam_rows, dynamic=None, aux=False, out=None):
+        """render_geoms plus per-frame geoms.  `dynamic` None: exactly render_geoms (lhw_render_frames, the bytes its callers get today).
+        Otherwise -- a markers.Markers or the dict upload_dynamic takes, an empty one included -- the frames go through lhw_render_scene:
+        the dynamic geoms get the ids G + m, alpha in (0, 1) is translucent, and aux=True returns (rgb, hit, depth, layers, layer_hit).
+        `out`: the five tensors (the last four may be None) to draw into, one launch."""
+        if dynamic is None:
+            return self.render_geoms(pos, mat, cam_pos, cam_rows, aux=aux, out=out)
+        pos, mat, cam_pos, cam_rows = (np.asarray(x, dtype=np.float64) for x in (pos, mat, cam_pos, cam_rows))
+        F, H, W = cam_pos.reshape(-1, 3).shape[0], self.height, self.width
+        pos, mat = pos.reshape(F, self.n_geoms, 3), mat.reshape(F, self.n_geoms, 9)
+        if out is not None:
+            bufs, chunk = list(out), max(F, 1)
+        else:
+            i32 = lambda: _lib.empty(F, H, W, dtype=torch.int32, device=self.device) if aux else None
+            bufs = [_lib.empty(F, H, W, 3, dtype=torch.uint8, device=self.device), i32(),
+                    _lib.empty(F, H, W, dtype=torch.float32, device=self.device) if aux else None, i32(), i32()]
+            chunk = self.frames_per_chunk
+        d = dynamic.arrays(F) if hasattr(dynamic, "arrays") else dynamic
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            cp = cam_pos.reshape(F, 3)[f0:f1]
+            self.draw_scene(self.upload(pos[f0:f1], mat[f0:f1], cp, cam_rows.reshape(F, 9)[f0:f1]),
+                            self.upload_dynamic({k: np.asarray(v)[f0:f1] for k, v in d.items()}, cp), *(None if b is None else b[f0:f1] for b in bufs))
+        return tuple(bufs) if aux or out is not None else bufs[0]
+
+    def render(self, qpos, camera: TrackingCamera | None = None, aux=False, markers=None):
+        """Frames of the poses qpos [F][nq] (or [nq]) seen by `camera` (default: TrackingCamera()): uint8 tensor [F][H][W][3].  `markers`: a
+        markers.Markers (or upload_dynamic's dict) of per-frame geoms drawn with the model's, through lhw_render_scene (render_scene)."""
         if self.model is None:
             raise ValueError("a renderer of loose geoms has no kinematics: use render_geoms")
         camera = TrackingCamera() if camera is None else camera
         q = np.atleast_2d(np.asarray(qpos, dtype=np.float64))
         pos, mat = geom_poses(self.model, q)
         cam_pos, cam_rows = camera.poses(body_poses(self.model, q)[0])
-        return self.render_geoms(pos, mat, cam_pos, cam_rows, aux=aux)
+        return self.render_scene(pos, mat, cam_pos, cam_rows, dynamic=markers, aux=aux)
 
 
 def write_png(path, array) -> None:

@@ -5,7 +5,7 @@ on-device rollout + PPO of this repository.
     python run_experiment.py train --env jvrc_walk --gpus 8 ...        (re-executes itself as 8 ranks under torch.distributed.run)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_experiment.py train --env jvrc_walk ...
     python run_experiment.py eval --path RUN_DIR|ACTOR.pt [--num-envs 64] [--ep-len 10] [--seed S] [--out-dir DIR] [--trace-envs 16]
-    python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1]
+    python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1] [--render-markers]
     python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
 Differences from the reference, by design: no Ray (`--num-procs` is the number of on-device envs per GPU unless
@@ -18,9 +18,12 @@ counts trajectories in the reference; `--imitate` needs an env description with 
 `--num-envs` deterministic episodes of `--ep-len` seconds in parallel on the device, prints one JSON object -- checkpoint, env, seed,
 episodes, terminated, truncated, mean return, mean length, mean episode sum per reward term -- and writes it to eval_summary.json in
 `--out-dir` (default: the run directory).  With `--out-dir`, a feed-forward policy also leaves trajectory.npz there: qpos [T][K][nq],
-qvel, action, reward, done of the first `--trace-envs` envs, enough to replay the motion in a MuJoCo viewer elsewhere.  `--render-envs K`
-also draws the first K of them, one PNG per control step under DIR/frames/env<k>/ -- the tracking camera of the reference's eval
-(rl/utils/eval.py:38-67) through the HIP ray caster of render.py, no GL and no MuJoCo -- and adds "frames" to the summary.
+qvel, action, reward, done and the task-input record task_inputs [T][K][176] of the first `--trace-envs` envs -- on jvrc_step also
+step_task_inputs [T][K][32] and the terrain in force during every control step, terrain_seq [T][K][20][4] (x y z theta of every footstep /
+box), terrain_nseq, terrain_floor_z -- enough to replay the motion in a MuJoCo viewer elsewhere.  `--render-envs K` also draws the first K
+of them, one PNG per control step under DIR/frames/env<k>/ -- the tracking camera of the reference's eval (rl/utils/eval.py:38-67) through
+the HIP ray caster of render.py, no GL and no MuJoCo; jvrc_step with its terrain boxes -- and adds "frames" to the summary.
+`--render-markers` draws the task's markers into them (the reference's draw_markers: velocity arrows, footstep targets, foot frames).
 """
 import argparse
 import json
@@ -129,6 +132,7 @@ def build_eval_parser():
     p.add_argument("--render-envs", type=int, default=0, help="with --out-dir: PNG frames of the first K traced envs, frames/env<k>/<step>.png (0: none, no renderer is created)")
     p.add_argument("--render-size", type=_size, default=(640, 480), metavar="WxH", help="frame size in pixels (the reference's eval: 640x480)")
     p.add_argument("--render-every", type=int, default=1, metavar="N", help="a frame every N control steps")
+    p.add_argument("--render-markers", action="store_true", help="draw the task's markers into the frames: velocity arrows (walking tasks), footstep targets and foot frames (jvrc_step)")
     return p
 
 
@@ -142,15 +146,28 @@ def _size(text):
     return w, h
 
 
-def write_frames(out_dir, env, env_name, qpos, size, every):
-    """PNG frames of the traced motion qpos [T][K][nq], the tracking camera of the reference's eval (rl/utils/eval.py:38-67) on every env:
-    <out_dir>/frames/env<k:03d>/<t:05d>.png for every `every`-th control step t.  Returns the summary's "frames" entry."""
+def write_frames(out_dir, env, spec, record, size, every, markers=False):
+    """PNG frames of the traced motion, the tracking camera of the reference's eval (rl/utils/eval.py:38-67) on every env:
+    <out_dir>/frames/env<k:03d>/<t:05d>.png for every `every`-th control step t.  `record`: the arrays of trajectory.npz -- qpos [T][K][nq],
+    task_inputs [T][K][176] and, on jvrc_step, step_task_inputs and terrain_seq / _nseq / _floor_z, from which the terrain of every frame is
+    drawn (markers.step_terrain in place of the model's own boxes and floor).  `markers`: also the task's markers (markers.walk_markers /
+    step_markers; a task without a command -- h1 standing -- has none).  Returns the summary's "frames" entry."""
+    import numpy as np
+    from learninghumanoidwalking_amd import markers as M
     from learninghumanoidwalking_amd.render import Renderer, write_png
     hidden, entry = (), dict(dir="frames", count=0, size=list(size), every=every)
-    if env_name == "jvrc_step":
-        # the terrain boxes are placed per env and per episode and the record does not hold their poses: not drawn in this version
-        hidden = [g for g, n in enumerate(env.model.geom_names) if n.startswith("box")]
-        entry["note"] = "the stepping terrain's boxes are not drawn: the trajectory record does not hold their poses"
+    qpos = record["qpos"]
+    stepping = "terrain_seq" in record
+    if stepping:
+        box0, floor = spec.terrain_ids()
+        hidden = list(range(box0, box0 + M.NBOX)) + [floor]
+        box_h = np.asarray(env.model.arrays["geom_size"]).reshape(-1, 3)[box0:box0 + M.NBOX, 2]
+    elif getattr(spec, "name", "") == "jvrc_step":      # (an LSTM policy's rollout keeps no terrain record: the boxes stay hidden)
+        hidden = list(range(spec.terrain_ids()[0], spec.terrain_ids()[0] + M.NBOX))
+        entry["note"] = "the stepping terrain's boxes are not drawn: a recurrent policy's rollout does not record their poses"
+    walking = markers and getattr(spec, "name", "") in ("jvrc_walk", "h1_walk")
+    if markers:
+        entry["markers"] = True
     r = Renderer(env.model, size[0], size[1], device=env.device, hidden_geoms=hidden)
     steps = list(range(0, qpos.shape[0], every))
     for k in range(qpos.shape[1]):
@@ -158,7 +175,15 @@ def write_frames(out_dir, env, env_name, qpos, size, every):
         d.mkdir(parents=True, exist_ok=True)
         for i in range(0, len(steps), r.frames_per_chunk):
             part = steps[i:i + r.frames_per_chunk]
-            rgb = r.render(qpos[part, k]).cpu().numpy()
+            dyn = None
+            if stepping:
+                seq, nseq = record["terrain_seq"][part, k], record["terrain_nseq"][part, k]
+                dyn = M.step_terrain(seq, nseq, record["terrain_floor_z"][part, k], box_h, env.model.geom_rgba[floor] if env.model.geom_rgba is not None else (0.5, 0.5, 0.5, 1.0))
+                if markers:
+                    dyn.merge(M.step_markers(record["task_inputs"][part, k], record["step_task_inputs"][part, k], seq, nseq, env.model, qpos[part, k], spec.body_ids()[2:4]))
+            elif walking:
+                dyn = M.walk_markers(record["task_inputs"][part, k])
+            rgb = r.render(qpos[part, k], markers=dyn).cpu().numpy()
             for t, img in zip(part, rgb):
                 write_png(d / f"{t:05d}.png", img)
             entry["count"] += len(part)
@@ -240,6 +265,8 @@ def run_eval(argv):
     algo = PPO(env_fn, args, seed=ea.seed, term_stats=True)
     if ea.out_dir is not None:
         algo.rollout.record_task_inputs = True      # (kept by the resident rollout; asking for it selects that path for an LSTM actor too)
+        if args.env == "jvrc_step" and hasattr(algo.rollout, "record_terrain"):
+            algo.rollout.record_terrain = True      # launch per step, bitwise the resident rollout: the terrain of every control step is read on the way
     algo.sample_parallel_with_workers(deterministic=True)      # Rollout.collect(deterministic=True), as PPO.evaluate
     ls = algo._ep_stats[1]
     ts = algo.term_stats
@@ -256,14 +283,23 @@ def run_eval(argv):
         else:
             ro, K = algo.rollout, max(1, min(ea.trace_envs, ea.num_envs))
             rec = ro.tin_all[:, :K].cpu().numpy()
+            pad = np.ones(rec.shape[-1], dtype=bool)      # (the record's pad columns are written by nobody: zero in the file)
+            for o, n in _lib.TASK_INPUT_FIELDS.values():
+                pad[o:o + n] = False
+            rec[:, :, pad] = 0.0
             q0, v0, a0 = (_lib.TASK_INPUT_FIELDS[k][0] for k in ("qpos", "qvel", "action"))
             env = algo.env
-            np.savez(Path(out_dir, "trajectory.npz"), qpos=rec[:, :, q0:q0 + env.nq], qvel=rec[:, :, v0:v0 + env.nv],
-                     action=rec[:, :, a0:a0 + env.act_dim], reward=ro.rew[:, :K].cpu().numpy(), done=ro.done[:, :K].cpu().numpy(),
-                     control_dt=np.float64(env_fn().control_dt))
+            record = dict(qpos=rec[:, :, q0:q0 + env.nq], qvel=rec[:, :, v0:v0 + env.nv], action=rec[:, :, a0:a0 + env.act_dim],
+                          reward=ro.rew[:, :K].cpu().numpy(), done=ro.done[:, :K].cpu().numpy(), control_dt=np.float64(env_fn().control_dt), task_inputs=rec)
+            if getattr(ro, "last_mode", None) == "recorded":      # jvrc_step: what a replay of the episode needs beyond the robot's state
+                record.update(step_task_inputs=ro.stin_all[:, :K].cpu().numpy(), terrain_seq=ro.terrain_seq[:, :K], terrain_nseq=ro.terrain_nseq[:, :K],
+                              terrain_floor_z=ro.terrain_floor_z[:, :K])
+            np.savez(Path(out_dir, "trajectory.npz"), **record)
             summary["trajectory"] = "trajectory.npz"
             if ea.render_envs > 0:
-                summary["frames"] = write_frames(out_dir, env, args.env, rec[:, :min(ea.render_envs, K), q0:q0 + env.nq], ea.render_size, ea.render_every)
+                R = min(ea.render_envs, K)
+                summary["frames"] = write_frames(out_dir, env, algo.spec, {k: (v[:, :R] if np.ndim(v) >= 2 else v) for k, v in record.items()}, ea.render_size,
+                                                 ea.render_every, markers=ea.render_markers)
     text = json.dumps(summary, indent=1)
     with open(Path(out_dir, "eval_summary.json"), "w") as f:
         f.write(text + "\n")
