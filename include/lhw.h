@@ -395,6 +395,43 @@ int lhw_env_set_actuator_randomization(LhwEnv* env, const LhwActuatorRand* setti
 int lhw_env_get_actuator_randomization(LhwEnv* env, LhwActuatorRand* out);
 /* Parity hook: every env's back-EMF damping tau_d, HOST pointer [N][lhw_env_act_dim] float64, synchronous. */
 int lhw_env_get_bemf_damping(LhwEnv* env, double* tau_d_host);
+/* Task commands: which command an env of a fused walking or stepping task follows -- its mode and the speeds of that mode -- is decided
+ * inside the control step by the reference's samplers, whose numbers are literals of tasks/walking_task.py:149-170, 194-205 and
+ * tasks/stepping_task.py:261-334.  LhwTaskCommands holds them, batch-wide, from the next control step on, in every way a control step is
+ * executed; a fresh env reports the reference's values, and with those every output is bit for bit what it is without the setter.
+ * Walking tasks (jvrc_walk, h1_walk) read:
+ *  - mode_cdf: the reset draw u in [0, 1) gives STANDING if u < [0], INPLACE if u < [1], else FORWARD (the reference: 0.6, 0.8).
+ *    CUMULATIVE thresholds, stored and compared as given: get -> set changes no bit.
+ *  - inplace_yaw, forward_vx, forward_vy: (lo, hi) of the uniform draws of the yaw rate (INPLACE: -0.5, 0.5), the forward speed (FORWARD:
+ *    0, 0.4) and the lateral speed (FORWARD: 0, 0).  The draws keep their RNG slots; the lateral speed takes the third slot of the mode_ref
+ *    draw, which FORWARD mode leaves free.  A range with lo == hi yields lo without a draw.  STANDING's three +-1 draws are not a setting.
+ *  - switch_stand_every / switch_walk_every: every control step switches STANDING <-> INPLACE with odds 1 / n while both feet are in
+ *    stance (100), and INPLACE <-> FORWARD with odds 1 / n (200).  0: that switch never fires and draws nothing.
+ * The stepping task (jvrc_step) reads:
+ *  - step_mode_cdf: u < [0] CURVED, < [1] STANDING, < [2] BACKWARD, < [3] LATERAL, else FORWARD (0.15, 0.2, 0.4, 0.7).
+ *  - step_height_*: the stair height of FORWARD mode, clamp((iteration - start) / span, 0, 1) * max (3000, 8000, 0.1), with the
+ *    iteration of lhw_env_set_iteration.  Its step length, gap and lateral width stay literals.
+ * Each task reads its own group; the other group is validated and stored, and nobody reads it.
+ * Pinned commands: per env, a mode (0 STANDING, 1 INPLACE, 2 FORWARD) and its mode_ref {yaw rate, forward speed, lateral speed} that the
+ * kernels use for that env INSTEAD of drawing: at every task reset -- auto-resets inside a resident rollout included; the phase is still
+ * drawn -- and at every task step, where a pinned env evaluates neither switch and takes mode and mode_ref from its pin before the reward
+ * and the observation are formed, so a pin changed between two launches acts from the next control step on.  Mode -1 frees an env; free
+ * envs, and every env before the first pin call, behave exactly as without the feature, also beside a pinned env in one wavefront.
+ * lhw_env_pin_commands sets envs [first, first + count); lhw_env_get_pinned_commands reports the whole batch (-1 and zeros for a free env).
+ * HOST pointers; all four calls synchronise the device (as lhw_env_set_task_shaping).  LHW_ERR_ARG, with a message that names the field and
+ * nothing changed, for a non-finite value, a range with lo > hi, a cdf that does not ascend within [0, 1], a negative *_every,
+ * step_height_span <= 0, a mode outside {-1, 0, 1, 2} or a pin range outside the batch.  LHW_ERR_UNSUPPORTED for cartpole and the h1
+ * standing task (every call: they have no command), and for lhw_env_pin_commands on jvrc_step (its command is a footstep plan). */
+typedef struct {
+  double mode_cdf[2], inplace_yaw[2], forward_vx[2], forward_vy[2];
+  int32_t switch_stand_every, switch_walk_every;
+  double step_mode_cdf[4], step_height_start, step_height_span, step_height_max;
+} LhwTaskCommands;
+int lhw_env_set_task_commands(LhwEnv* env, const LhwTaskCommands* settings);
+int lhw_env_get_task_commands(const LhwEnv* env, LhwTaskCommands* out);
+int lhw_env_pin_commands(LhwEnv* env, int32_t first, int32_t count, const int32_t* mode_host /*[count], -1 frees*/,
+                         const double* ref_host /*[count][3]*/);
+int lhw_env_get_pinned_commands(LhwEnv* env, int32_t* mode_host /*[N]*/, double* ref_host /*[N][3]*/);
 /* Fault counters since the last call (host pointers, synchronous, resets them): control steps in which contacts were
  * dropped because more than the compiled-in cap were active (16 per env; the stepping task, whose feet rest on the floor AND on
  * the terrain boxes under them, merges identical contacts and holds 192 found / 64 distinct ones per sub-step), and control steps in which an env's state became

@@ -117,6 +117,55 @@ class LhwActuatorRand(ctypes.Structure):      # include/lhw.h: lhw_env_set_actua
 DEFAULT_ACTUATOR_RANDOMIZATION = dict(pdrand_k=0.0, sim_bemf=False, bemf_range=(5.0, 40.0), bemf_interval=10)
 
 
+class LhwTaskCommands(ctypes.Structure):      # include/lhw.h: lhw_env_set_task_commands / lhw_env_get_task_commands
+    _fields_ = [("mode_cdf", ctypes.c_double * 2), ("inplace_yaw", ctypes.c_double * 2), ("forward_vx", ctypes.c_double * 2),
+                ("forward_vy", ctypes.c_double * 2), ("switch_stand_every", ctypes.c_int32), ("switch_walk_every", ctypes.c_int32),
+                ("step_mode_cdf", ctypes.c_double * 4), ("step_height_start", ctypes.c_double), ("step_height_span", ctypes.c_double),
+                ("step_height_max", ctypes.c_double)]
+
+
+# The task commands an env starts with (lhw_env_get_task_commands on a fresh env: the literals of the reference's tasks/walking_task.py:149-170,
+# 194-205 and tasks/stepping_task.py:261-334), by the struct's field names -- the keywords of BatchedEnv.set_task_commands.  The cdfs are
+# CUMULATIVE thresholds of the reset draw: STANDING | INPLACE | FORWARD, and CURVED | STANDING | BACKWARD | LATERAL | FORWARD
+DEFAULT_TASK_COMMANDS = dict(mode_cdf=(0.6, 0.8), inplace_yaw=(-0.5, 0.5), forward_vx=(0.0, 0.4), forward_vy=(0.0, 0.0), switch_stand_every=100,
+                             switch_walk_every=200, step_mode_cdf=(0.15, 0.2, 0.4, 0.7), step_height_start=3000.0, step_height_span=8000.0,
+                             step_height_max=0.1)
+COMMAND_MODES = ("standing", "inplace", "forward")      # a walking task's mode index (LHW_TIN_MODE, lhw_env_pin_commands) by name
+STEP_COMMAND_MODES = ("curved", "standing", "backward", "lateral", "forward")      # the stepping task's, in the order of step_mode_cdf
+
+
+def task_commands_struct(fields: dict) -> "LhwTaskCommands":
+    """LhwTaskCommands from a full dict by field name (sequences for the array fields)"""
+    c = LhwTaskCommands()
+    for name, ctype in LhwTaskCommands._fields_:
+        v = fields[name]
+        if isinstance(getattr(c, name), ctypes.Array):
+            v = [float(x) for x in v]
+            if len(v) != len(getattr(c, name)):
+                raise ValueError(f"task commands: {name} takes {len(getattr(c, name))} values, got {len(v)}")
+            setattr(c, name, ctype(*v))
+        elif ctype is ctypes.c_int32:
+            if int(v) != v:
+                raise ValueError(f"task commands: {name} must be an integer, got {v!r}")
+            setattr(c, name, int(v))
+        else:
+            setattr(c, name, float(v))
+    return c
+
+
+def task_commands_dict(c: "LhwTaskCommands") -> dict:
+    """the struct as a dict by field name (tuples for the array fields)"""
+    return {name: (tuple(getattr(c, name)) if isinstance(getattr(c, name), ctypes.Array) else getattr(c, name)) for name, _ in LhwTaskCommands._fields_}
+
+
+def cdf_from_probs(probs, names, what="mode_probs"):
+    """cumulative thresholds (all but the last, which is 1) of probabilities by `names`; they must sum to 1 within 1e-9"""
+    p = [float(probs[k]) for k in names]
+    if not all(np.isfinite(p)) or min(p) < 0 or abs(sum(p) - 1.0) > 1e-9:
+        raise ValueError(f"{what} {dict(zip(names, p))} must be non-negative and sum to 1")
+    return tuple(min(1.0, float(x)) for x in np.cumsum(p)[:-1])
+
+
 class LhwPpoConfig(ctypes.Structure):      # include/lhw.h: hyper-parameters and shapes of a PPO / LSTM handle
     _fields_ = [
         ("device", ctypes.c_int32), ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
@@ -319,6 +368,10 @@ def declare(L):
     sig("lhw_env_set_actuator_randomization", [vp, ctypes.POINTER(LhwActuatorRand)])
     sig("lhw_env_get_actuator_randomization", [vp, ctypes.POINTER(LhwActuatorRand)])
     sig("lhw_env_get_bemf_damping", [vp, vp])
+    sig("lhw_env_set_task_commands", [vp, ctypes.POINTER(LhwTaskCommands)])
+    sig("lhw_env_get_task_commands", [vp, ctypes.POINTER(LhwTaskCommands)])
+    sig("lhw_env_pin_commands", [vp, i32, i32, vp, vp])
+    sig("lhw_env_get_pinned_commands", [vp, vp, vp])
     sig("lhw_env_set_iteration", [vp, i64])
     sig("lhw_env_pop_fault_stats", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_pop_rerun_count", [vp, ctypes.POINTER(i64)])

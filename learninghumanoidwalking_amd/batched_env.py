@@ -301,6 +301,59 @@ class BatchedEnv:
         self._check(self._L.lhw_env_get_bemf_damping(self._h, out.ctypes.data))
         return out
 
+    def get_task_commands(self) -> dict:
+        """The settings of the fused task's command sampler this env's kernels apply, read back from the library
+        (lhw_env_get_task_commands; jvrc_walk, h1_walk, jvrc_step), by the field names of LhwTaskCommands: _lib.DEFAULT_TASK_COMMANDS on a
+        fresh env."""
+        c = _lib.LhwTaskCommands()
+        self._check(self._L.lhw_env_get_task_commands(self._h, ctypes.byref(c)))
+        return _lib.task_commands_dict(c)
+
+    def set_task_commands(self, **fields):
+        """Settings of the fused task's command sampler, for the whole batch from the next control step on (lhw_env_set_task_commands:
+        synchronises the device).  Keywords are the fields of LhwTaskCommands -- mode_cdf (cumulative: standing | inplace | forward),
+        inplace_yaw / forward_vx / forward_vy (lo, hi), switch_stand_every / switch_walk_every (0: never) for the walking tasks;
+        step_mode_cdf (curved | standing | backward | lateral | forward), step_height_start / _span / _max for jvrc_step -- and those not
+        given keep their current value.  An unknown keyword raises KeyError."""
+        unknown = sorted(set(fields) - set(_lib.DEFAULT_TASK_COMMANDS))
+        if unknown:
+            raise KeyError(f"unknown task command settings {unknown}: {', '.join(_lib.DEFAULT_TASK_COMMANDS)}")
+        c = _lib.task_commands_struct(dict(self.get_task_commands(), **fields))
+        self._check(self._L.lhw_env_set_task_commands(self._h, ctypes.byref(c)))
+
+    def _env_range(self, envs):
+        """(first, count) of `envs`: None (all), an int, or a range / sequence of consecutive env indices"""
+        if envs is None:
+            return 0, self.n_envs
+        idx = [int(envs)] if np.ndim(envs) == 0 else [int(k) for k in envs]
+        if idx and idx != list(range(idx[0], idx[0] + len(idx))):
+            raise ValueError(f"envs must be consecutive indices, got {idx}")
+        return (idx[0], len(idx)) if idx else (0, 0)
+
+    def pin_commands(self, mode, ref, envs=None):
+        """Pin the command of `envs` (None: all; an index or consecutive indices) on a walking task: `mode` ("standing" / "inplace" /
+        "forward" or 0 / 1 / 2, one for all or one per env; -1 frees) and `ref` = mode_ref {yaw rate, forward speed, lateral speed} ([3] for
+        all or [count][3]).  The kernels then use them for those envs instead of drawing, across auto-resets, from the next control step
+        on (lhw_env_pin_commands: synchronises the device).  Pin before the reset whose observation a rollout starts from."""
+        first, count = self._env_range(envs)
+        code = lambda m: _lib.COMMAND_MODES.index(m) if isinstance(m, str) else int(m)      # noqa: E731
+        modes = np.array([code(m) for m in mode] if np.ndim(mode) else [code(mode)] * count, dtype=np.int32)
+        refs = np.ascontiguousarray(np.broadcast_to(np.asarray(ref, dtype=np.float64), (count, 3)))
+        if modes.shape != (count,):
+            raise ValueError(f"{modes.size} modes for {count} envs")
+        self._check(self._L.lhw_env_pin_commands(self._h, first, count, modes.ctypes.data, refs.ctypes.data))
+
+    def unpin_commands(self, envs=None):
+        """Free `envs` (None: all): their commands are drawn again, from the next reset or switch on."""
+        first, count = self._env_range(envs)
+        self.pin_commands(-1, np.zeros(3), envs=range(first, first + count))
+
+    def pinned_commands(self):
+        """(mode [N] int32, -1 for a free env; ref [N][3] float64) of the whole batch (lhw_env_get_pinned_commands)"""
+        mode, ref = np.zeros(self.n_envs, np.int32), np.zeros((self.n_envs, 3))
+        self._check(self._L.lhw_env_get_pinned_commands(self._h, mode.ctypes.data, ref.ctypes.data))
+        return mode, ref
+
     def pop_episode_stats(self):
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
         self._check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))

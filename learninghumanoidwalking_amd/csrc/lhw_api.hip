@@ -402,6 +402,76 @@ extern "C" int lhw_env_get_bemf_damping(LhwEnv* e, double* tau_d_host) {
   return LHW_OK;
 }
 
+// which tasks have a command: the walking tasks and the stepping task (the latter no pin)
+static int commands_supported(const LhwEnv* e, const char* fn, bool pin) {
+  if (!e->hum || e->task == LHW_TASK_H1_STAND)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: this task has no command (task commands exist for jvrc_walk, h1_walk and jvrc_step)", fn);
+  if (pin && e->task == LHW_TASK_JVRC_STEP)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: the stepping task's command is a footstep plan; only the walking tasks' commands can be pinned", fn);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_get_task_commands(const LhwEnv* e, LhwTaskCommands* out) {
+  if (!e || !out) return lhw_fail(LHW_ERR_ARG, "null argument");
+  if (const int rc = commands_supported(e, "lhw_env_get_task_commands", false)) return rc;
+  humanoid_get_task_commands(e->hum, out);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_set_task_commands(LhwEnv* e, const LhwTaskCommands* c) {
+  if (!e || !c) return lhw_fail(LHW_ERR_ARG, "null argument");
+  const char* fn = "lhw_env_set_task_commands";
+  if (const int rc = commands_supported(e, fn, false)) return rc;
+  const struct { const char* name; const double* v; } ranges[3] = {{"inplace_yaw", c->inplace_yaw}, {"forward_vx", c->forward_vx}, {"forward_vy", c->forward_vy}};
+  for (const auto& r : ranges) {
+    if (!std::isfinite(r.v[0]) || !std::isfinite(r.v[1])) return lhw_fail(LHW_ERR_ARG, "%s: %s = (%g, %g) is not finite", fn, r.name, r.v[0], r.v[1]);
+    if (r.v[0] > r.v[1]) return lhw_fail(LHW_ERR_ARG, "%s: %s = (%g, %g), lo must not exceed hi", fn, r.name, r.v[0], r.v[1]);
+  }
+  const struct { const char* name; const double* v; int n; } cdfs[2] = {{"mode_cdf", c->mode_cdf, 2}, {"step_mode_cdf", c->step_mode_cdf, 4}};
+  for (const auto& d : cdfs)
+    for (int k = 0; k < d.n; k++) {
+      const double lo = k ? d.v[k - 1] : 0.0;
+      if (!(d.v[k] >= lo && d.v[k] <= 1.0))   // (NaN fails it too)
+        return lhw_fail(LHW_ERR_ARG, "%s: %s[%d] = %g, the cumulative thresholds must ascend within [0, 1]", fn, d.name, k, d.v[k]);
+    }
+  if (c->switch_stand_every < 0) return lhw_fail(LHW_ERR_ARG, "%s: switch_stand_every = %d, must be >= 0 (0: never)", fn, (int)c->switch_stand_every);
+  if (c->switch_walk_every < 0) return lhw_fail(LHW_ERR_ARG, "%s: switch_walk_every = %d, must be >= 0 (0: never)", fn, (int)c->switch_walk_every);
+  if (!std::isfinite(c->step_height_start)) return lhw_fail(LHW_ERR_ARG, "%s: step_height_start = %g is not finite", fn, c->step_height_start);
+  if (!std::isfinite(c->step_height_span) || c->step_height_span <= 0) return lhw_fail(LHW_ERR_ARG, "%s: step_height_span = %g, must be finite and > 0", fn, c->step_height_span);
+  if (!std::isfinite(c->step_height_max)) return lhw_fail(LHW_ERR_ARG, "%s: step_height_max = %g is not finite", fn, c->step_height_max);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (humanoid_set_task_commands(e->hum, c)) return lhw_fail(LHW_ERR_HIP, "%s: parameter upload failed", fn);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_pin_commands(LhwEnv* e, int32_t first, int32_t count, const int32_t* mode_host, const double* ref_host) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  const char* fn = "lhw_env_pin_commands";
+  if (const int rc = commands_supported(e, fn, true)) return rc;
+  if (first < 0 || count < 0 || (int64_t)first + count > e->n_envs)
+    return lhw_fail(LHW_ERR_ARG, "%s: envs [first = %d, first + count = %lld) lie outside the batch of %d", fn, (int)first, (long long)first + count, e->n_envs);
+  if (count > 0 && (!mode_host || !ref_host)) return lhw_fail(LHW_ERR_ARG, "%s: null mode / ref array", fn);
+  for (int i = 0; i < count; i++) {
+    if (mode_host[i] < -1 || mode_host[i] > 2) return lhw_fail(LHW_ERR_ARG, "%s: mode[%d] = %d, must be -1 (free), 0 STANDING, 1 INPLACE or 2 FORWARD", fn, i, (int)mode_host[i]);
+    for (int k = 0; mode_host[i] >= 0 && k < 3; k++)
+      if (!std::isfinite(ref_host[3 * i + k])) return lhw_fail(LHW_ERR_ARG, "%s: ref[%d][%d] = %g is not finite", fn, i, k, ref_host[3 * i + k]);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (humanoid_pin_commands(e->hum, first, count, mode_host, ref_host)) return lhw_fail(LHW_ERR_HIP, "%s: upload failed", fn);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_get_pinned_commands(LhwEnv* e, int32_t* mode_host, double* ref_host) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  if (const int rc = commands_supported(e, "lhw_env_get_pinned_commands", true)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  humanoid_get_pinned_commands(e->hum, mode_host, ref_host);
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len_sum, int64_t* count) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
   double h[3];

@@ -467,6 +467,17 @@ int HumanoidCreate::pack_model(HModel& m) {
   return LHW_OK;
 }
 
+// the ABI's task commands <-> the fields the kernels read (each task reads its own group; the other is stored and nobody reads it)
+static void humanoid_store_task_commands(HParams& p, const LhwTaskCommands* c) {
+  for (int k = 0; k < 2; k++) {
+    p.cmd_mode_cdf[k] = c->mode_cdf[k]; p.cmd_inplace_yaw[k] = c->inplace_yaw[k];
+    p.cmd_forward_vx[k] = c->forward_vx[k]; p.cmd_forward_vy[k] = c->forward_vy[k];
+  }
+  p.cmd_switch_stand_every = c->switch_stand_every; p.cmd_switch_walk_every = c->switch_walk_every;
+  for (int k = 0; k < 4; k++) p.step_mode_cdf[k] = c->step_mode_cdf[k];
+  p.step_height_start = c->step_height_start; p.step_height_span = c->step_height_span; p.step_height_max = c->step_height_max;
+}
+
 bool HumanoidCreate::task_params(HumanoidEnv* h) {
   HModel& m = h->m;
   const int nb = m.nbody;
@@ -492,6 +503,11 @@ bool HumanoidCreate::task_params(HumanoidEnv* h) {
     p.term_lim[1] = p.task == TASK_STEP ? (double)INFINITY : 1.4;
   }
   p.pdrand_k = 0; p.sim_bemf = 0; p.bemf_interval = 10; p.bemf_lo = 5.0; p.bemf_hi = 40.0;   // robot_base.py:5, 53-54: off, 1 in 10, U(5, 40)
+  {   // task commands as the reference's samplers have them (walking_task.py:149-170, 194-205; stepping_task.py:261-334) until
+      // lhw_env_set_task_commands says otherwise; no pin (cmd_pin stays NULL)
+    LhwTaskCommands c = {{0.6, 0.8}, {-0.5, 0.5}, {0.0, 0.4}, {0.0, 0.0}, 100, 200, {0.15, 0.2, 0.4, 0.7}, 3000.0, 8000.0, 0.1};
+    humanoid_store_task_commands(p, &c);
+  }
   if (stepping) {
     p.box_geom0 = cfg->task_iparams[LHW_TI_STEP_BOX_GEOM0]; p.nbox = cfg->task_iparams[LHW_TI_STEP_NBOX];
     p.floor_geom = cfg->task_iparams[LHW_TI_STEP_FLOOR_GEOM]; p.delay_frames = cfg->task_iparams[LHW_TI_STEP_DELAY_FRAMES];
@@ -731,6 +747,48 @@ int humanoid_bemf_damping(HumanoidEnv* h, double* out) {
   for (size_t n = 0; n < N; n++)
     for (int u = 0; u < nu; u++) out[n * nu + u] = rows[n * NU + u];
   return 0;
+}
+void humanoid_get_task_commands(const HumanoidEnv* h, LhwTaskCommands* out) {
+  const HParams& p = h->p;
+  for (int k = 0; k < 2; k++) {
+    out->mode_cdf[k] = p.cmd_mode_cdf[k]; out->inplace_yaw[k] = p.cmd_inplace_yaw[k];
+    out->forward_vx[k] = p.cmd_forward_vx[k]; out->forward_vy[k] = p.cmd_forward_vy[k];
+  }
+  out->switch_stand_every = p.cmd_switch_stand_every; out->switch_walk_every = p.cmd_switch_walk_every;
+  for (int k = 0; k < 4; k++) out->step_mode_cdf[k] = p.step_mode_cdf[k];
+  out->step_height_start = p.step_height_start; out->step_height_span = p.step_height_span; out->step_height_max = p.step_height_max;
+}
+// (checked by the caller; the device is idle)
+int humanoid_set_task_commands(HumanoidEnv* h, const LhwTaskCommands* c) {
+  humanoid_store_task_commands(h->p, c);
+  return humanoid_upload_params(h) ? 0 : -1;
+}
+// rows [first, first + count) of the pin array <- (mode, ref); the array is created, all rows free, by the first call.  (checked by the
+// caller; the device is idle)
+int humanoid_pin_commands(HumanoidEnv* h, int first, int count, const int32_t* mode, const double* ref) {
+  const size_t N = h->p.n_envs;
+  std::vector<double> rows = h->pin_host;
+  if (rows.empty()) { rows.assign(N * 4, 0.0); for (size_t n = 0; n < N; n++) rows[4 * n] = -1.0; }
+  for (int i = 0; i < count; i++) {
+    double* r = &rows[4 * (size_t)(first + i)];
+    r[0] = (double)mode[i];
+    for (int k = 0; k < 3; k++) r[1 + k] = mode[i] < 0 ? 0.0 : ref[3 * i + k];
+  }
+  double* dev = h->p.cmd_pin;
+  if (!dev && !(dev = h->mem.get_lazy<double>(N * 4, LhwDevMem::RAW))) return -1;
+  if (hipMemcpy(dev, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return -1;
+  h->pin_host.swap(rows);
+  if (h->p.cmd_pin == dev) return 0;
+  h->p.cmd_pin = dev;
+  return humanoid_upload_params(h) ? 0 : -1;
+}
+void humanoid_get_pinned_commands(const HumanoidEnv* h, int32_t* mode, double* ref) {
+  const size_t N = h->p.n_envs;
+  for (size_t n = 0; n < N; n++) {
+    const bool have = !h->pin_host.empty();
+    if (mode) mode[n] = have ? (int32_t)h->pin_host[4 * n] : -1;
+    for (int k = 0; ref && k < 3; k++) ref[3 * n + k] = have ? h->pin_host[4 * n + 1 + k] : 0.0;
+  }
 }
 int humanoid_occupancy() {
   int nb = -1;

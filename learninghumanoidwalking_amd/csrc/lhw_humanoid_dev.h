@@ -283,6 +283,20 @@ struct HParams {
   int sim_bemf, bemf_interval;          // sim_bemf: with probability 1 / bemf_interval a control step redraws the env's tau_d
   double* tau_d;                        // [N][NU] back-EMF damping of every env, a side array like tstat: zero at create, never touched by a
                                         // reset (the reference's RobotBase outlives reset()), zeroed by the setter that turns sim_bemf off
+  // Task commands (lhw_env_set_task_commands; tasks/walking_task.py:149-170, 194-205, tasks/stepping_task.py:261-334): what the reference
+  // keeps as literals of its command sampler.  Uniform across the batch: scalar loads of p, each inside the branch that needs it (a reset,
+  // a firing switch).  Added behind tau_d by the same rule
+  double cmd_mode_cdf[2];               // walking tasks, reset draw u: u < [0] STANDING, u < [1] INPLACE, else FORWARD (cumulative: 0.6, 0.8)
+  double cmd_inplace_yaw[2];            // INPLACE: ref[0] ~ U(lo, hi) (-0.5, 0.5); a range with lo == hi yields lo without a draw
+  double cmd_forward_vx[2];             // FORWARD: ref[1] ~ U(lo, hi) (0, 0.4)
+  double cmd_forward_vy[2];             // FORWARD: ref[2] ~ U(lo, hi) from the slot behind ref[1]'s (0, 0: the literal 0)
+  int cmd_switch_stand_every;           // STANDING <-> INPLACE with odds 1 / n per control step in double stance (100); 0: never, no draw
+  int cmd_switch_walk_every;            // INPLACE <-> FORWARD with odds 1 / n per control step (200); 0: never, no draw
+  double step_mode_cdf[4];              // stepping task, reset draw u: u < [0] CURVED, < [1] STANDING, < [2] BACKWARD, < [3] LATERAL, else FORWARD
+  double step_height_start, step_height_span, step_height_max;   // stair height clamp((iteration - start) / span, 0, 1) * max (3000, 8000, 0.1)
+  double* cmd_pin;                      // [N][4] pinned commands {mode or -1, mode_ref[3]} (lhw_env_pin_commands), a side array like tstat /
+                                        // tau_d: NULL until the first pin call; walking tasks only.  An env whose row holds a mode takes
+                                        // mode and mode_ref from it at every task reset and task step instead of drawing
 };
 // What the stepper kernels read of an env's configuration, in ONE device allocation behind ONE kernel-argument pointer: the model record, and
 // the task parameters at a fixed, aligned offset behind it (the kernels form both references from the block's address; two argument pointers
@@ -432,6 +446,7 @@ struct HumanoidEnv {
   int device;
   bool fast;   // the model fits the two-envs-per-wave kernels (W = 32)
   unsigned* ro_queue = nullptr;   // job counter + per-group progress words of the resident rollout's queue mode (lhw_humanoid_rollout.hip)
+  std::vector<double> pin_host;   // host mirror of p.cmd_pin ([N][4]; empty until the first lhw_env_pin_commands)
   int last_rollout_queued = 0;    // the most recent resident rollout drained the job queue (humanoid_rollout_kernel<.., QUEUE = true>)
   float *hist_base = nullptr, *hist_tbase = nullptr;   // [n_envs][obs_dim] each: the base observation / terminal observation rows control_step writes
                                                        // in a rollout with an observation history (lhw_env_rollout_history), one block in `mem`
@@ -3319,15 +3334,32 @@ __device__ __forceinline__ void substep(HModelRef m, HParamsRef p, L* SG0, int f
   solve_tail<DIAG>(m, p, S, lane, flags, pc, dof, prim, cross, Mrow, mdiag, marm, qapp, bias, bd, bi);
 }
 // ------------------------------------------------------------------------------------------------ task layer
+// one command value from its configured range (HParams::cmd_*): a range with lo == hi is that value, without a draw
+__device__ __forceinline__ double cmd_draw(HParamsRef p, unsigned genv, unsigned stream, unsigned counter, unsigned slot, double lo, double hi) {
+  return lo == hi ? lo : lhw_rng_uniform(p.seed, genv, stream, counter, slot, lo, hi);
+}
 __device__ __forceinline__ void sample_ref(HParamsRef p, unsigned genv, unsigned stream, unsigned counter, unsigned slot0,
                                            int mode, double* ref) {
   if (mode == MODE_STANDING) {
     for (int k = 0; k < 3; k++) ref[k] = lhw_rng_uniform(p.seed, genv, stream, counter, slot0 + k, -1.0, 1.0);
   } else if (mode == MODE_INPLACE) {
-    ref[0] = lhw_rng_uniform(p.seed, genv, stream, counter, slot0, -0.5, 0.5); ref[1] = 0; ref[2] = 0;
-  } else {
-    ref[0] = 0; ref[1] = lhw_rng_uniform(p.seed, genv, stream, counter, slot0, 0.0, 0.4); ref[2] = 0;
+    ref[0] = cmd_draw(p, genv, stream, counter, slot0, p.cmd_inplace_yaw[0], p.cmd_inplace_yaw[1]); ref[1] = 0; ref[2] = 0;
+  } else {   // (slot0 + 2 is free in FORWARD mode: the lateral speed draws from it once its range is one)
+    ref[0] = 0; ref[1] = cmd_draw(p, genv, stream, counter, slot0, p.cmd_forward_vx[0], p.cmd_forward_vx[1]);
+    ref[2] = cmd_draw(p, genv, stream, counter, slot0 + 2, p.cmd_forward_vy[0], p.cmd_forward_vy[1]);
   }
+}
+// A pinned command (HParams::cmd_pin, lhw_env_pin_commands): true iff env's row holds a mode, which then replaces mode / mode_ref.  The row
+// is addressed from an opaque copy of the env index, as the term statistics' rows are: nothing of it is live in the sub-steps.
+// (`pin`: p.cmd_pin, read by the caller beside its other task parameters: one wait covers those scalar loads)
+__device__ __forceinline__ bool load_pinned_command(const double* pin, int env, int& mode, double* mode_ref) {
+  if (!pin) return false;
+  const double* row = pin + (size_t)opaque_int(env) * 4;
+  const int pm = (int)row[0];
+  if (pm < 0) return false;
+  mode = pm;
+  for (int k = 0; k < 3; k++) mode_ref[k] = row[1 + k];
+  return true;
 }
 
 // transforms3d quat2euler 'sxyz' roll/pitch (tasks/observations.py:22)
@@ -3646,19 +3678,25 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
         }
         if (WALKT) {
         // ---- WalkingTask.step (walking_task.py:149-170)
+        const double* const pin = p.cmd_pin;                                              // (lhw_env_pin_commands; NULL: nobody is pinned)
+        const int n_stand = p.cmd_switch_stand_every, n_walk = p.cmd_switch_walk_every;   // (0: that switch never fires, no draw)
         phase += 1;
         if (phase >= p.period) phase = 0;
         {
-          const bool dbl = p.clock_lut[0 * p.period + phase] == 1.0 && p.clock_lut[2 * p.period + phase] == 1.0;
-          if (lhw_rng_randint(p.seed, genv, LHW_STREAM_STEP, step_count, WS + 0, 100) == 0 && dbl) {
-            if (mode == MODE_INPLACE) mode = MODE_STANDING;
-            else if (mode == MODE_STANDING) mode = MODE_INPLACE;
-            sample_ref(p, genv, LHW_STREAM_STEP, step_count, WS + 1, mode, mode_ref);
-          }
-          if (lhw_rng_randint(p.seed, genv, LHW_STREAM_STEP, step_count, WS + 4, 200) == 0 && mode != MODE_STANDING) {
-            if (mode == MODE_FORWARD) mode = MODE_INPLACE;
-            else if (mode == MODE_INPLACE) mode = MODE_FORWARD;
-            sample_ref(p, genv, LHW_STREAM_STEP, step_count, WS + 5, mode, mode_ref);
+          // a pinned env (lhw_env_pin_commands) follows its pin row -- as it reads now: a pin changed between two launches acts from this
+          // control step on -- and evaluates neither switch; the draws are keyed, so skipping them moves no other draw
+          if (!load_pinned_command(pin, env, mode, mode_ref)) {
+            const bool dbl = p.clock_lut[0 * p.period + phase] == 1.0 && p.clock_lut[2 * p.period + phase] == 1.0;
+            if (n_stand > 0 && lhw_rng_randint(p.seed, genv, LHW_STREAM_STEP, step_count, WS + 0, n_stand) == 0 && dbl) {
+              if (mode == MODE_INPLACE) mode = MODE_STANDING;
+              else if (mode == MODE_STANDING) mode = MODE_INPLACE;
+              sample_ref(p, genv, LHW_STREAM_STEP, step_count, WS + 1, mode, mode_ref);
+            }
+            if (n_walk > 0 && lhw_rng_randint(p.seed, genv, LHW_STREAM_STEP, step_count, WS + 4, n_walk) == 0 && mode != MODE_STANDING) {
+              if (mode == MODE_FORWARD) mode = MODE_INPLACE;
+              else if (mode == MODE_INPLACE) mode = MODE_FORWARD;
+              sample_ref(p, genv, LHW_STREAM_STEP, step_count, WS + 5, mode, mode_ref);
+            }
           }
           if (!H1R) step_count++;   // h1_walk: the counter advances after the post-observation randomisation draws below
         }
@@ -3971,9 +4009,11 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
         double prevpred = 0;
         if (WALKT) {
           // WalkingTask.reset (walking_task.py:194-205): slot 0 mode, 1..3 mode_ref, 4 phase (+100 for h1_walk)
+          const double* const pin = p.cmd_pin;
           const double u = lhw_rng_u01(p.seed, genv, LHW_STREAM_RESET, reset_count, WS + 0);
-          mode = u < 0.6 ? MODE_STANDING : (u < 0.8 ? MODE_INPLACE : MODE_FORWARD);
+          mode = u < p.cmd_mode_cdf[0] ? MODE_STANDING : (u < p.cmd_mode_cdf[1] ? MODE_INPLACE : MODE_FORWARD);
           sample_ref(p, genv, LHW_STREAM_RESET, reset_count, WS + 1, mode, mode_ref);
+          load_pinned_command(pin, env, mode, mode_ref);   // a pinned env keeps its command across the reset; the phase is still drawn
           phase = lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, WS + 4, p.period);
         }
         if (TASK == TASK_STEP) {
@@ -3984,7 +4024,8 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
           reached = 0; frames = 0;
           phase = lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 0, 2) == 0 ? 0 : p.period / 2;
           const double u = lhw_rng_u01(p.seed, genv, LHW_STREAM_RESET, reset_count, 1);
-          mode = u < 0.15 ? WALK_CURVED : (u < 0.2 ? WALK_STANDING : (u < 0.4 ? WALK_BACKWARD : (u < 0.7 ? WALK_LATERAL : WALK_FORWARD)));
+          mode = u < p.step_mode_cdf[0] ? WALK_CURVED : (u < p.step_mode_cdf[1] ? WALK_STANDING : (u < p.step_mode_cdf[2] ? WALK_BACKWARD
+                 : (u < p.step_mode_cdf[3] ? WALK_LATERAL : WALK_FORWARD)));
           const int k = lane;
           double sx = 0, sy = 0, sz = 0, sth = 0;
           if (mode == WALK_CURVED) {
@@ -4004,7 +4045,7 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
             const double size = mode == WALK_BACKWARD ? -0.1 : 0.3, gap = 0.15;
             double height = 0;
             if (mode == WALK_FORWARD) {
-              const double hh = fmin(1.0, fmax(0.0, ((double)lz.iteration - 3000.0) / 8000.0)) * 0.1;
+              const double hh = fmin(1.0, fmax(0.0, ((double)lz.iteration - p.step_height_start) / p.step_height_span)) * p.step_height_max;
               height = lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, 2) == 0 ? -hh : hh;
             }
             const double uf = lhw_rng_uniform(p.seed, genv, LHW_STREAM_RESET, reset_count, 3, 0.095, 0.105);

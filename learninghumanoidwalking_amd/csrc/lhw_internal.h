@@ -148,6 +148,13 @@ bool humanoid_act_armed(const HumanoidEnv* h);
 void humanoid_get_actuator_rand(const HumanoidEnv* h, LhwActuatorRand* out);
 int humanoid_set_actuator_rand(HumanoidEnv* h, const LhwActuatorRand* a);
 int humanoid_bemf_damping(HumanoidEnv* h, double* out /* [N][nu] host */);
+// Task commands (lhw_env_set_task_commands / lhw_env_pin_commands).  The setters take validated values and upload the parameters; -1 on a
+// HIP error.  The pin array -- device rows {mode or -1, mode_ref[3]} and a host mirror the getter answers from -- is created, every row
+// free, by the first pin call; freeing every env afterwards keeps it (the kernels find no mode in any row)
+void humanoid_get_task_commands(const HumanoidEnv* h, LhwTaskCommands* out);
+int humanoid_set_task_commands(HumanoidEnv* h, const LhwTaskCommands* c);
+int humanoid_pin_commands(HumanoidEnv* h, int first, int count, const int32_t* mode, const double* ref /* [count][3] */);
+void humanoid_get_pinned_commands(const HumanoidEnv* h, int32_t* mode /* [N] */, double* ref /* [N][3] */);
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
 // step_record: the stepping task's second record (LhwStepTaskInput) instead of LhwTaskInput; -1 HIP error, -2 not enabled

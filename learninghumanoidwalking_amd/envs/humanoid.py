@@ -101,12 +101,18 @@ class BatchedFactory:
         actuator = self.actuator_randomization()
         if actuator is not None:     # (likewise)
             env.set_actuator_randomization(**actuator)
+        commands = self.commands()
+        if commands is not None:     # (likewise)
+            env.set_task_commands(**commands)
         return env
 
     def task_shaping(self):
         return None     # (the humanoid specs read it from the YAML)
 
     def actuator_randomization(self):
+        return None     # (likewise)
+
+    def commands(self):
         return None     # (likewise)
 
 
@@ -148,6 +154,11 @@ class HumanoidSpec(BatchedFactory):
         # actuator randomisation (robots/robot_base.py:5-62: pdrand_k, sim_bemf -- constructor arguments there, which no shipped env passes):
         # `actuator_randomization: {pdrand_k:, sim_bemf:, bemf_range: [lo, hi], bemf_interval:}`; checked here, applied by make_batched
         self._actuator = self._read_actuator_randomization(c)
+        # task commands (tasks/walking_task.py:149-170, 194-205, tasks/stepping_task.py:261-334: literals of the command samplers there):
+        # `commands: {mode_probs: {standing:, inplace:, forward:}, inplace_yaw_range: [lo, hi], forward_speed_range:, lateral_speed_range:,
+        # switch_standing_every:, switch_walking_every:}`; on jvrc_step `commands: {mode_probs: {curved:, standing:, backward:, lateral:,
+        # forward:}, stair_height: {start_iteration:, span_iterations:, max:}}`; checked here, applied by make_batched
+        self._commands = self._read_commands(c)
         self._model = None
         self._configure(c)
         # jvrc_walk.py:62-63, h1_env.py:54-55: np.tile over the history
@@ -232,6 +243,65 @@ class HumanoidSpec(BatchedFactory):
         """None for a YAML without `actuator_randomization:` (every shipped config), else the keywords make_batched hands to
         BatchedEnv.set_actuator_randomization -- the YAML's over the reference's defaults.  Not part of env_args(): a run-time setting."""
         return self._actuator
+
+    def _read_commands(self, c):
+        from .._lib import COMMAND_MODES, STEP_COMMAND_MODES, TASK_H1_WALK, TASK_JVRC_STEP, TASK_JVRC_WALK, cdf_from_probs
+        cm = c.get("commands")
+        if cm is None:
+            return None
+        where = f"commands of {self.yaml_path}"
+        if self.task_code not in (TASK_JVRC_WALK, TASK_H1_WALK, TASK_JVRC_STEP):
+            raise ValueError(f"{where}: the task of {self.name} has no command")
+        cm, out = dict(cm), {}
+        stepping = self.task_code == TASK_JVRC_STEP
+        ranges = {} if stepping else dict(inplace_yaw_range="inplace_yaw", forward_speed_range="forward_vx", lateral_speed_range="forward_vy")
+        every = {} if stepping else dict(switch_standing_every="switch_stand_every", switch_walking_every="switch_walk_every")
+        known = ["mode_probs", *ranges, *every] + (["stair_height"] if stepping else [])
+        unknown = sorted(set(cm) - set(known))
+        if unknown:
+            raise KeyError(f"unknown keys {unknown} in {where}: {', '.join(known)}")
+        if "mode_probs" in cm:
+            names = STEP_COMMAND_MODES if stepping else COMMAND_MODES
+            probs = dict(cm["mode_probs"])
+            if set(probs) != set(names):
+                raise KeyError(f"mode_probs in {where} must give exactly {', '.join(names)}: got {sorted(probs)}")
+            try:
+                out["step_mode_cdf" if stepping else "mode_cdf"] = cdf_from_probs(probs, names, f"mode_probs in {where}")
+            except TypeError as e:
+                raise ValueError(f"mode_probs in {where}: {e}") from None
+        for key, field in ranges.items():
+            if key in cm:
+                try:
+                    lo, hi = (float(x) for x in cm[key])
+                except (TypeError, ValueError):
+                    raise ValueError(f"{key} in {where} must be [lo, hi]: {cm[key]!r}") from None
+                if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+                    raise ValueError(f"{key} in {where} must be finite with lo <= hi: {cm[key]!r}")
+                out[field] = (lo, hi)
+        for key, field in every.items():
+            if key in cm:
+                n = cm[key]
+                if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+                    raise ValueError(f"{key} in {where} must be an integer >= 0 (0: never): {n!r}")
+                out[field] = n
+        if "stair_height" in cm:
+            sh = dict(cm["stair_height"])
+            names = dict(start_iteration="step_height_start", span_iterations="step_height_span", max="step_height_max")
+            unknown = sorted(set(sh) - set(names))
+            if unknown:
+                raise KeyError(f"unknown stair_height keys {unknown} in {where}: {', '.join(names)}")
+            for key, field in names.items():
+                if key in sh:
+                    v = float(sh[key])
+                    if not np.isfinite(v) or (key == "span_iterations" and v <= 0):
+                        raise ValueError(f"stair_height.{key} in {where} must be finite{' and > 0' if key == 'span_iterations' else ''}: {sh[key]!r}")
+                    out[field] = v
+        return out
+
+    def commands(self):
+        """None for a YAML without `commands:` (every shipped config), else the keywords make_batched hands to BatchedEnv.set_task_commands:
+        the settings the YAML gives (the others keep the reference's values).  Not part of env_args(): a run-time setting."""
+        return self._commands
 
     def clock_lut(self):
         return None     # (a task with a gait clock mixes in WalkingTask)

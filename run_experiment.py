@@ -6,6 +6,7 @@ on-device rollout + PPO of this repository.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_experiment.py train --env jvrc_walk ...
     python run_experiment.py eval --path RUN_DIR|ACTOR.pt [--num-envs 64] [--ep-len 10] [--seed S] [--out-dir DIR] [--trace-envs 16]
     python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1] [--render-markers]
+    python run_experiment.py eval --path RUN_DIR --command forward:0.1..0.4 [--num-envs 4]     (walking tasks: pinned commands)
     python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
 Differences from the reference, by design: no Ray (`--num-procs` is the number of on-device envs per GPU unless
@@ -24,6 +25,9 @@ box), terrain_nseq, terrain_floor_z -- enough to replay the motion in a MuJoCo v
 of them, one PNG per control step under DIR/frames/env<k>/ -- the tracking camera of the reference's eval (rl/utils/eval.py:38-67) through
 the HIP ray caster of render.py, no GL and no MuJoCo; jvrc_step with its terrain boxes -- and adds "frames" to the summary.
 `--render-markers` draws the task's markers into them (the reference's draw_markers: velocity arrows, footstep targets, foot frames).
+`--command SPEC` (jvrc_walk, h1_walk) pins every env's command before the reset the episodes start from, instead of the task's draw --
+standing | inplace:YAW | forward:VX[,VY], a value A..B spread linearly over the envs -- and adds "command" and "per_env" (mode, mode_ref,
+return and length of each env's first episode) to the summary: one launch gives a return-against-commanded-speed curve.
 """
 import argparse
 import json
@@ -133,7 +137,58 @@ def build_eval_parser():
     p.add_argument("--render-size", type=_size, default=(640, 480), metavar="WxH", help="frame size in pixels (the reference's eval: 640x480)")
     p.add_argument("--render-every", type=int, default=1, metavar="N", help="a frame every N control steps")
     p.add_argument("--render-markers", action="store_true", help="draw the task's markers into the frames: velocity arrows (walking tasks), footstep targets and foot frames (jvrc_step)")
+    p.add_argument("--command", type=str, default=None, metavar="SPEC",
+                   help="walking tasks: pin every env's command instead of drawing it: standing | inplace:YAW | forward:VX[,VY]; a value A..B is spread linearly over the envs")
     return p
+
+
+COMMAND_ENVS = ("jvrc_walk", "h1_walk")      # the envs whose command can be pinned (BatchedEnv.pin_commands)
+
+
+def parse_command(text, K):
+    """`eval --command SPEC` for K envs -> (mode [K] int32, mode_ref [K][3] float64 = yaw rate, forward speed, lateral speed).
+    SPEC: standing | inplace:YAW | forward:VX[,VY]; a value may be A..B, spread linearly over the envs: env k gets A + k (B - A) / (K - 1),
+    and K = 1 gets A."""
+    import numpy as np
+
+    def spread(v):
+        try:
+            a, b = (float(x) for x in v.split("..")) if ".." in v else (float(v), float(v))
+        except ValueError:
+            raise SystemExit(f"eval: --command {text!r}: {v!r} is neither a number nor A..B") from None
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise SystemExit(f"eval: --command {text!r}: {v!r} is not finite")
+        return np.array([a + k * (b - a) / (K - 1) if K > 1 else a for k in range(K)], dtype=np.float64)
+
+    name, _, rest = text.partition(":")
+    vals = [v for v in rest.split(",")] if rest else []
+    want = {"standing": (0, 0), "inplace": (1, 1), "forward": (1, 2)}
+    if name not in want or not want[name][0] <= len(vals) <= want[name][1] or any(not v.strip() for v in vals):
+        raise SystemExit(f"eval: --command {text!r} is none of standing | inplace:YAW | forward:VX[,VY]")
+    mode = ("standing", "inplace", "forward").index(name)
+    ref = np.zeros((K, 3))
+    if name == "inplace":
+        ref[:, 0] = spread(vals[0].strip())
+    elif name == "forward":
+        ref[:, 1] = spread(vals[0].strip())
+        if len(vals) == 2:
+            ref[:, 2] = spread(vals[1].strip())
+    return np.full(K, mode, dtype=np.int32), ref
+
+
+def first_episodes(rew, done):
+    """(return [K] float64, length [K]) of every env's first episode from the rollout's rew [T][K] / done [T][K]: the rewards up to and
+    including the first step whose done flag is set (the whole rollout if none is), summed in float64 in time order."""
+    import numpy as np
+    rew, done = np.asarray(rew, dtype=np.float64), np.asarray(done)
+    T, K = rew.shape
+    ret, length = np.zeros(K), np.zeros(K, dtype=np.int64)
+    for k in range(K):
+        ended = np.flatnonzero(done[:, k] != 0)
+        length[k] = int(ended[0]) + 1 if ended.size else T
+        for t in range(length[k]):
+            ret[k] += rew[t, k]
+    return ret, length
 
 
 def _size(text):
@@ -248,6 +303,8 @@ def run_eval(argv):
         args = pickle.load(f)
     if args.env not in ENVIRONMENTS:
         raise SystemExit(f"eval: unknown env {args.env!r} in {pkl}")
+    if ea.command is not None and args.env not in COMMAND_ENVS:
+        raise SystemExit(f"eval: --command pins the command of a walking task ({', '.join(COMMAND_ENVS)}); the env of this run, {args.env}, has none to pin")
     Spec = ENVIRONMENTS[args.env]
     yaml = Path(actor.parent, "config.yaml")      # the run's own copy of --yaml (run_experiment.py train)
     env_fn = partial(Spec, yaml_path=str(yaml)) if (yaml.is_file() and args.env != "cartpole") else Spec
@@ -267,6 +324,11 @@ def run_eval(argv):
         algo.rollout.record_task_inputs = True      # (kept by the resident rollout; asking for it selects that path for an LSTM actor too)
         if args.env == "jvrc_step" and hasattr(algo.rollout, "record_terrain"):
             algo.rollout.record_terrain = True      # launch per step, bitwise the resident rollout: the terrain of every control step is read on the way
+    if ea.command is not None:
+        # every env is pinned BEFORE the reset whose observation the rollout starts from: that observation carries the command
+        mode, ref = parse_command(ea.command, ea.num_envs)
+        algo.env.pin_commands(mode, ref)
+        algo.rollout.started = False      # (the rollout resets the env before its first control step)
     algo.sample_parallel_with_workers(deterministic=True)      # Rollout.collect(deterministic=True), as PPO.evaluate
     ls = algo._ep_stats[1]
     ts = algo.term_stats
@@ -275,6 +337,12 @@ def run_eval(argv):
     summary = dict(checkpoint=str(actor), env=args.env, seed=ea.seed, num_envs=ea.num_envs, control_steps=T, episodes=ts["episodes"],
                    terminated=ts["terminated"], truncated=ts["truncated"], mean_return=sum(ts["terms"].values()) if ts["episodes"] else float("nan"),
                    mean_length=ls / ts["episodes"] if ts["episodes"] else float("nan"), terms=ts["terms"])
+    if ea.command is not None:
+        # one launch, a return-against-command curve: every env's command and the return / length of the episode it started with
+        ret, length = first_episodes(algo.rollout.rew.cpu().numpy(), algo.rollout.done.cpu().numpy())
+        summary["command"] = ea.command
+        summary["per_env"] = [dict(mode=int(mode[k]), mode_ref=[float(x) for x in ref[k]], episode_return=float(ret[k]), episode_length=int(length[k]))
+                              for k in range(ea.num_envs)]
     if ea.out_dir is not None:
         if algo.rollout.tin_all is None:
             summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
