@@ -606,6 +606,12 @@ int lhw_debug_stepper_occupancy(void);
  * 0 in the other (no kernel reads either). */
 #define LHW_DPP_FORMS 16
 int lhw_debug_dpp_forms(uint64_t lane_mask, const double* in, uint64_t* out_ref, uint64_t* out_shipped, void* stream);
+/* Test hook: the fp64 helpers the humanoid steppers use in place of IEEE `/` and sqrt() (csrc/lhw_humanoid_dev.h: the v_rcp_f64 / v_rsq_f64
+ * seed plus two Newton steps), one launch over n input pairs, 1 <= n <= 2^24.  DEVICE pointers, [n] doubles each: out_rcp[i] = rcp_f64(b[i]),
+ * out_qdiv[i] = qdiv(a[i], b[i]), out_rsqrt[i] = rsqrt_f64(b[i]), out_qsqrt[i] = qsqrt(b[i]).  Not IEEE at the ends: a zero or infinite
+ * b gives NaN from the first three, a negative or infinite b gives NaN from the roots, qsqrt(+-0) is +0. */
+int lhw_debug_fastmath(int64_t n, const double* a, const double* b, double* out_rcp, double* out_qdiv, double* out_rsqrt, double* out_qsqrt,
+                       void* stream);
 
 /* ------------------------------------------------------------------ PPO (actor/critic MLP, GAE, update) */
 typedef struct LhwPpo LhwPpo;

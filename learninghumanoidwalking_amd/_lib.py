@@ -399,6 +399,7 @@ def declare(L):
     sig("lhw_debug_wgrad_wide", [vp, vp, i32, i32, vp, vp, vp])
     sig("lhw_debug_wgrad_skinny", [i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp])
     sig("lhw_debug_dpp_forms", [u64, vp, vp, vp, vp])
+    sig("lhw_debug_fastmath", [i64, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_env_phase_cycles", [vp, ctypes.c_int, vp])
     sig("lhw_env_step_range", [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_ppo_create", [ctypes.POINTER(LhwPpoConfig), ctypes.POINTER(vp)])

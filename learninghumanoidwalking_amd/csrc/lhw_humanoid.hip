@@ -839,6 +839,27 @@ extern "C" int lhw_debug_dpp_forms(uint64_t lane_mask, const double* in, uint64_
                      (unsigned long long*)out_shipped);
   return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "dpp_forms_kernel launch failed");
 }
+// Test hook lhw_debug_fastmath: the fp64 reciprocal / division / square-root helpers of lhw_humanoid_dev.h as the steppers inline them, one
+// thread per input pair, in a kernel of its own (tests/fastmath_common.py holds the results against a wider reference)
+__global__ void __launch_bounds__(256) fastmath_kernel(long long n, const double* __restrict__ a, const double* __restrict__ b,
+                                                       double* __restrict__ rcp, double* __restrict__ quo, double* __restrict__ rsq,
+                                                       double* __restrict__ sq) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = a[i], d = b[i];
+  rcp[i] = rcp_f64(d);
+  quo[i] = qdiv(x, d);
+  rsq[i] = rsqrt_f64(d);
+  sq[i] = qsqrt(d);
+}
+extern "C" int lhw_debug_fastmath(int64_t n, const double* a, const double* b, double* out_rcp, double* out_qdiv, double* out_rsqrt,
+                                  double* out_qsqrt, void* stream) {
+  if (n <= 0 || n > (1ll << 24) || !a || !b || !out_rcp || !out_qdiv || !out_rsqrt || !out_qsqrt)
+    return lhw_fail(LHW_ERR_ARG, "lhw_debug_fastmath: bad argument");
+  hipLaunchKernelGGL(fastmath_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n, a, b, out_rcp, out_qdiv,
+                     out_rsqrt, out_qsqrt);
+  return hipGetLastError() == hipSuccess ? LHW_OK : lhw_fail(LHW_ERR_HIP, "fastmath_kernel launch failed");
+}
 // diagnostic: per-env duration of the last control-step launch (load balance across wavefronts)
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out) {
   const size_t N = h->p.n_envs;

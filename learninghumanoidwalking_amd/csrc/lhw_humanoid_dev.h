@@ -926,6 +926,10 @@ __device__ __forceinline__ bool gany(bool pred) {
 // exponent range -- so the seed instruction plus two Newton steps (error about one ulp, not correctly rounded) is enough: the float64
 // oracle keeps IEEE division and the parity tolerance (1e-12 per five-control-step segment) has four decades of room.
 // LHW_FASTDIV=0 compiles the IEEE forms back in (A/B, scripts/build_variant.sh).
+// Measured against a 64-bit-mantissa reference over 6888 inputs (lhw_debug_fastmath, tests/fastmath_common.py; ulps of the result's binade):
+// gfx950 rcp_f64 0.50, qdiv 1.32, rsqrt_f64 1.00, qsqrt 0.50; the emulator (seeds 1.0 / x and 1.0 / sqrt(x)) 0.50, 1.37, 1.00, 0.50.
+// The ends are not IEEE: a zero or infinite argument meets 0 * inf in the first fma, so rcp_f64 / qdiv / rsqrt_f64 return NaN where `/` gives
+// +-inf or 0, and qsqrt(inf) is NaN; the call sites keep their divisors and radicands away from both ends (table in DESIGN.md, section 2).
 #ifndef LHW_FASTDIV
 #define LHW_FASTDIV 1
 #endif
@@ -942,7 +946,7 @@ __device__ __forceinline__ double qdiv(double a, double b) {
   return a / b;
 #endif
 }
-// 1 / sqrt(x) for x > 0 (v_rsq_f64 + two Newton steps); x = 0 gives +inf like the instruction
+// 1 / sqrt(x) for x > 0 (v_rsq_f64 + two Newton steps); x = 0 gives NaN (the seed is +inf and the first step multiplies it by 0)
 __device__ __forceinline__ double rsqrt_f64(double x) {
   double y = __builtin_amdgcn_rsq(x);
   const double hx = 0.5 * x;

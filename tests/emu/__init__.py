@@ -26,7 +26,9 @@ from learninghumanoidwalking_amd.batched_env import BatchedEnv
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _CSRC = os.path.join(_ROOT, "learninghumanoidwalking_amd", "csrc")
-_BUILD = os.path.join(_HERE, "_build")
+# LHW_EMU_BUILD_DIR: a build directory of its own for an instrumented library (scripts/emu_coverage.py); LHW_EMU_DEFS / LHW_EMU_LDFLAGS:
+# extra words for every compile line / for the link line
+_BUILD = os.environ.get("LHW_EMU_BUILD_DIR") or os.path.join(_HERE, "_build")
 LIB_PATH = os.path.join(_BUILD, "liblhw_emu.so")
 SOURCES = ["lhw_humanoid.hip", "lhw_humanoid_rollout.hip", "lhw_humanoid_rollout_step.hip", "lhw_cartpole.hip", "lhw_api.hip", "lhw_mlp_strip.hip"]
 _LIB = None
@@ -50,7 +52,7 @@ def build(force: bool = False, opt: str = "-O1") -> str:
     for cmd, p in procs:
         if p.wait() != 0:
             raise RuntimeError("emulator build failed: " + " ".join(cmd))
-    subprocess.check_call(["g++", "-shared", "-o", LIB_PATH] + objs)
+    subprocess.check_call(["g++", "-shared", "-o", LIB_PATH] + objs + os.environ.get("LHW_EMU_LDFLAGS", "").split())
     return LIB_PATH
 
 

@@ -27,7 +27,7 @@ def build(force: bool = False, opt: str = "-O1") -> str:
                                                                         "-c", _SRC, "-o", obj])
     objs = [os.path.join(emu._BUILD, os.path.basename(s) + ".o") for s in emu.SOURCES + ["emu_runtime.cpp"]] + [obj]
     tmp = LIB_PATH + f".{os.getpid()}.tmp"
-    subprocess.check_call(["g++", "-shared", "-o", tmp] + objs)
+    subprocess.check_call(["g++", "-shared", "-o", tmp] + objs + os.environ.get("LHW_EMU_LDFLAGS", "").split())
     os.replace(tmp, LIB_PATH)
     return LIB_PATH
 
