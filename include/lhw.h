@@ -881,6 +881,70 @@ int lhw_render_scene(const LhwRenderSettings* s, int32_t G, const int32_t* geom_
                      uint8_t* rgb_dev /*[F][H][W][3]*/, int32_t* hit_dev /*[F][H][W], nullable*/, float* depth_dev /*[F][H][W], nullable*/,
                      int32_t* layers_dev /*[F][H][W], nullable*/, int32_t* layer_hit_dev /*[F][H][W], nullable*/, void* stream);
 
+/* Eval video: a baseline sequential JPEG encoder for the frames above (the reference's eval appends every frame to a video writer,
+ * rl/utils/eval.py:25-34, 63).  lhw_jpeg_encode produces, for each of F frames, the ENTROPY-CODED SEGMENT of a baseline JPEG -- every
+ * byte between the SOS header and EOI, restart markers included; the host writes the headers (learninghumanoidwalking_amd/video.py).
+ * All arithmetic is integer, and this comment is the specification: an independent program that follows it reproduces every byte.
+ * Integers are two's complement, >> is the arithmetic shift, / truncates.
+ *
+ * Settings.  width, height: 1..65535 (the range of a JPEG frame header).  qtable[0] (luminance) and qtable[1] (chrominance): 64 entries
+ * each, values 1..255, in NATURAL order (index 8 v + u for vertical frequency v, horizontal frequency u).
+ *
+ * Colour and sampling.  Three components Y, Cb, Cr, sampled 4:2:0: the MCU covers 16 x 16 pixels and holds six 8 x 8 blocks in the order
+ * Y(0,0) Y(8,0) Y(0,8) Y(8,8) Cb Cr (x, y offsets of the block in the MCU).  M = ceil(W / 16) MCUs per MCU row, R = ceil(H / 16) MCU rows.
+ * A sample at (x, y) outside the image is the pixel (min(x, W - 1), min(y, H - 1)): the last column and row are replicated.  Per pixel,
+ * from its bytes R, G, B (16-bit fixed point, the JFIF matrix):
+ *   Y  = ( 19595 R + 38470 G +  7471 B +   32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16          (8421375 = 128 * 65536 + 32767)
+ *   Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16
+ * all in 0..255.  A chroma sample (i, j) of an MCU is the mean of the Cb (Cr) of the four pixels (2 i + {0, 1}, 2 j + {0, 1}) of the MCU,
+ * rounded as (a + b + c + d + 2) >> 2.  Every sample is then level-shifted: s - 128.
+ *
+ * DCT.  The 8 x 8 forward DCT in the Loeffler-Ligtenberg-Moschytz factorisation with 13-bit constants, rows first, then columns; its
+ * output is 8 times the orthonormal 2-D DCT-II.  With D(x, n) = (x + (1 << (n - 1))) >> n, the constants
+ *   c1 = 2446 (0.298631336)  c2 = 3196 (0.390180644)  c3 = 4433 (0.541196100)  c4 = 6270 (0.765366865)  c5 = 7373 (0.899976223)
+ *   c6 = 9633 (1.175875602)  c7 = 12299 (1.501321110) c8 = 15137 (1.847759065) c9 = 16069 (1.961570560) c10 = 16819 (2.053119869)
+ *   c11 = 20995 (2.562915447) c12 = 25172 (3.072711026)                                    (round(8192 x) of the value in brackets)
+ * and the eight inputs d0..d7 of one row (pass 1) or column (pass 2), the outputs o0..o7 replace them:
+ *   t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4
+ *   e0 = t0 + t3, e3 = t0 - t3, e1 = t1 + t2, e2 = t1 - t2,  z = (e2 + e3) c3
+ *   pass 1: o0 = (e0 + e1) << 2, o4 = (e0 - e1) << 2, o2 = D(z + e3 c4, 11), o6 = D(z - e2 c8, 11)
+ *   pass 2: o0 = D(e0 + e1, 2),  o4 = D(e0 - e1, 2),  o2 = D(z + e3 c4, 15), o6 = D(z - e2 c8, 15)
+ *   z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) c6,  a3 = z5 - z3 c9, a4 = z5 - z4 c2
+ *   o7 = D(t4 c1 - z1 c5 + a3, n), o5 = D(t5 c10 - z2 c11 + a4, n), o3 = D(t6 c12 - z2 c11 + a3, n), o1 = D(t7 c7 - z1 c5 + a4, n)
+ *   with n = 11 in pass 1 and 15 in pass 2.
+ * Quantisation of the coefficient c at natural index i of a block of component table t, q = qtable[t][i]: sign-symmetric rounding
+ * division, k = (|c| + 4 q) / (8 q), the quantised value is k with the sign of c.
+ *
+ * Entropy coding.  Huffman coding with the four tables of ITU-T T.81 Annex K (K.3 / K.4 DC, K.5 / K.6 AC; luminance tables for Y,
+ * chrominance tables for Cb and Cr), coefficients in zig-zag order.  DC: the difference to the previous block OF THE SAME COMPONENT in
+ * the restart interval (0 for the first), category s = bit length of |diff|, the code of s, then the s low bits of diff (diff >= 0) or of
+ * diff - 1 (diff < 0).  AC: for every non-zero coefficient, ZRL (0xF0) for each full 16 zeros of the run in front of it, then the code of
+ * (run << 4) | s and the s bits as for DC; EOB (0x00) closes the block unless coefficient 63 is non-zero.  Bits fill bytes from the most
+ * significant bit.  The restart interval is one MCU row (DRI = M).  At the end of every MCU row the last byte is padded with 1-bits; after
+ * every MCU row r but the last follow the two bytes FF, D0 + (r mod 8), and the DC predictions restart at 0.  In the coded bytes (the
+ * padded ones included, the markers not) every byte FF is followed by a byte 00.
+ *
+ * Sizes.  A block codes to at most 22 + 63 * 26 = 1660 bits (DC: 11-bit code, 11 bits; each AC: 16-bit code, 10 bits), an MCU row to at
+ * most 2 * ceil(6 M * 1660 / 8) stuffed bytes and 2 marker bytes <= LHW_JPEG_MCU_BYTES * M + 4, so
+ *   lhw_jpeg_out_bytes     = F * R * (LHW_JPEG_MCU_BYTES * M + 4)          -- the capacity out_dev must have, whatever the content
+ *   lhw_jpeg_scratch_bytes = the same + 16 * (F * R + 1)                   -- per MCU row: its staged bytes, its size and its offset
+ * (both 0 for F = 0, -1 for bad settings or F < 0).  The call queues three kernels on `stream` -- one wavefront per (frame, MCU row)
+ * codes the row into scratch, one scans the row sizes, one packs the rows back to back -- keeps no state and returns without waiting:
+ * frame f is out_dev[frame_offset_dev[f] .. frame_offset_dev[f + 1]).  scratch_dev must be 8-byte aligned.
+ * Errors, with nothing written: NULL settings or buffers, a size outside 1..65535, F < 0, a table entry outside 1..255, more than
+ * 2^31 - 1 MCU rows in all: LHW_ERR_ARG; scratch_bytes or out_capacity below the sizes above: LHW_ERR_ARG, lhw_last_error() names the
+ * needed size. */
+typedef struct {
+  int32_t  width, height;
+  uint16_t qtable[2][64];
+} LhwJpegSettings;
+#define LHW_JPEG_MCU_BYTES 2496      /* 6 blocks * 2 * 208 bytes */
+int64_t lhw_jpeg_scratch_bytes(const LhwJpegSettings* s, int32_t F);
+int64_t lhw_jpeg_out_bytes(const LhwJpegSettings* s, int32_t F);
+int lhw_jpeg_encode(const LhwJpegSettings* s, int32_t F, const uint8_t* rgb_dev /*[F][H][W][3]*/, uint8_t* scratch_dev, int64_t scratch_bytes,
+                    uint8_t* out_dev, int64_t out_capacity, int64_t* frame_offset_dev /*[F + 1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,10 @@ class LhwRenderSettings(ctypes.Structure):      # include/lhw.h: lhw_render_fram
                 ("shadows", ctypes.c_int32), ("cull", ctypes.c_int32)]
 
 
+class LhwJpegSettings(ctypes.Structure):      # include/lhw.h: lhw_jpeg_encode
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("qtable", (ctypes.c_uint16 * 64) * 2)]
+
+
 RENDER_MAX_GEOMS = 64      # include/lhw.h LHW_RENDER_MAX_GEOMS
 RENDER_SCENE_MAX_GEOMS, RENDER_MAX_LAYERS, RENDER_CONE = 256, 8, 32      # include/lhw.h LHW_RENDER_SCENE_MAX_GEOMS / _MAX_LAYERS / _CONE
 
@@ -449,6 +453,9 @@ def declare(L):
     sig("lhw_debug_lstm_policy_step", [ctypes.POINTER(LhwRolloutLstmPolicy), vp, i32, vp, u32, u32, vp, vp, vp, vp])
     sig("lhw_render_frames", [ctypes.POINTER(LhwRenderSettings), i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp])
     sig("lhw_render_scene", [ctypes.POINTER(LhwRenderSettings), i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("lhw_jpeg_scratch_bytes", [ctypes.POINTER(LhwJpegSettings), i32], i64)
+    sig("lhw_jpeg_out_bytes", [ctypes.POINTER(LhwJpegSettings), i32], i64)
+    sig("lhw_jpeg_encode", [ctypes.POINTER(LhwJpegSettings), i32, vp, vp, i64, vp, i64, vp, vp])
     return L
 
 

@@ -6,6 +6,7 @@ on-device rollout + PPO of this repository.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_experiment.py train --env jvrc_walk ...
     python run_experiment.py eval --path RUN_DIR|ACTOR.pt [--num-envs 64] [--ep-len 10] [--seed S] [--out-dir DIR] [--trace-envs 16]
     python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1] [--render-markers]
+    python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 --render-format mjpeg [--render-quality 90]     (DIR/video/env000.avi)
     python run_experiment.py eval --path RUN_DIR --command forward:0.1..0.4 [--num-envs 4]     (walking tasks: pinned commands)
     python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
@@ -25,6 +26,9 @@ box), terrain_nseq, terrain_floor_z -- enough to replay the motion in a MuJoCo v
 of them, one PNG per control step under DIR/frames/env<k>/ -- the tracking camera of the reference's eval (rl/utils/eval.py:38-67) through
 the HIP ray caster of render.py, no GL and no MuJoCo; jvrc_step with its terrain boxes -- and adds "frames" to the summary.
 `--render-markers` draws the task's markers into them (the reference's draw_markers: velocity arrows, footstep targets, foot frames).
+`--render-format mjpeg` (or `both`) delivers the frames as the reference's eval does, as a video: DIR/video/env<k>.avi, Motion-JPEG in AVI
+at real-time speed, every frame coded on the device right behind the ray caster (video.py: lhw_jpeg_encode, `--render-quality`) so that
+only compressed bytes reach the host; the summary gains "video".
 `--command SPEC` (jvrc_walk, h1_walk) pins every env's command before the reset the episodes start from, instead of the task's draw --
 standing | inplace:YAW | forward:VX[,VY], a value A..B spread linearly over the envs -- and adds "command" and "per_env" (mode, mode_ref,
 return and length of each env's first episode) to the summary: one launch gives a return-against-commanded-speed curve.
@@ -136,6 +140,8 @@ def build_eval_parser():
     p.add_argument("--render-envs", type=int, default=0, help="with --out-dir: PNG frames of the first K traced envs, frames/env<k>/<step>.png (0: none, no renderer is created)")
     p.add_argument("--render-size", type=_size, default=(640, 480), metavar="WxH", help="frame size in pixels (the reference's eval: 640x480)")
     p.add_argument("--render-every", type=int, default=1, metavar="N", help="a frame every N control steps")
+    p.add_argument("--render-format", choices=("png", "mjpeg", "both"), default="png", help="png: frames/env<k>/<step>.png; mjpeg: video/env<k>.avi, Motion-JPEG coded on the device; both")
+    p.add_argument("--render-quality", type=int, default=90, metavar="Q", help="JPEG quality 1..100 of --render-format mjpeg")
     p.add_argument("--render-markers", action="store_true", help="draw the task's markers into the frames: velocity arrows (walking tasks), footstep targets and foot frames (jvrc_step)")
     p.add_argument("--command", type=str, default=None, metavar="SPEC",
                    help="walking tasks: pin every env's command instead of drawing it: standing | inplace:YAW | forward:VX[,VY]; a value A..B is spread linearly over the envs")
@@ -201,15 +207,18 @@ def _size(text):
     return w, h
 
 
-def write_frames(out_dir, env, spec, record, size, every, markers=False):
+def write_frames(out_dir, env, spec, record, size, every, markers=False, fmt="png", quality=90):
     """PNG frames of the traced motion, the tracking camera of the reference's eval (rl/utils/eval.py:38-67) on every env:
     <out_dir>/frames/env<k:03d>/<t:05d>.png for every `every`-th control step t.  `record`: the arrays of trajectory.npz -- qpos [T][K][nq],
     task_inputs [T][K][176] and, on jvrc_step, step_task_inputs and terrain_seq / _nseq / _floor_z, from which the terrain of every frame is
     drawn (markers.step_terrain in place of the model's own boxes and floor).  `markers`: also the task's markers (markers.walk_markers /
-    step_markers; a task without a command -- h1 standing -- has none).  Returns the summary's "frames" entry."""
+    step_markers; a task without a command -- h1 standing -- has none).  `fmt` "mjpeg" / "both": the same frames as <out_dir>/video/env<k:03d>.avi,
+    coded chunk by chunk on the device (video.JpegEncoder at `quality`) and played at 1 / (control_dt * every) frames a second; "mjpeg" writes
+    no PNG.  Returns the summary's ("frames", "video") entries, None for the one not written."""
     import numpy as np
     from learninghumanoidwalking_amd import markers as M
     from learninghumanoidwalking_amd.render import Renderer, write_png
+    png, avi = fmt in ("png", "both"), fmt in ("mjpeg", "both")
     hidden, entry = (), dict(dir="frames", count=0, size=list(size), every=every)
     qpos = record["qpos"]
     stepping = "terrain_seq" in record
@@ -225,9 +234,17 @@ def write_frames(out_dir, env, spec, record, size, every, markers=False):
         entry["markers"] = True
     r = Renderer(env.model, size[0], size[1], device=env.device, hidden_geoms=hidden)
     steps = list(range(0, qpos.shape[0], every))
+    video = None
+    if avi:
+        from learninghumanoidwalking_amd.video import JpegEncoder, MjpegWriter
+        enc = JpegEncoder(size[0], size[1], quality, device=env.device)
+        video = dict(dir="video", count=qpos.shape[1], frames=len(steps), size=list(size), every=every, fps=1.0 / (float(record["control_dt"]) * every), quality=quality)
+        Path(out_dir, "video").mkdir(parents=True, exist_ok=True)
     for k in range(qpos.shape[1]):
         d = Path(out_dir, "frames", f"env{k:03d}")
-        d.mkdir(parents=True, exist_ok=True)
+        if png:
+            d.mkdir(parents=True, exist_ok=True)
+        writer = MjpegWriter(Path(out_dir, "video", f"env{k:03d}.avi"), size[0], size[1], video["fps"]) if avi else None
         for i in range(0, len(steps), r.frames_per_chunk):
             part = steps[i:i + r.frames_per_chunk]
             dyn = None
@@ -238,11 +255,17 @@ def write_frames(out_dir, env, spec, record, size, every, markers=False):
                     dyn.merge(M.step_markers(record["task_inputs"][part, k], record["step_task_inputs"][part, k], seq, nseq, env.model, qpos[part, k], spec.body_ids()[2:4]))
             elif walking:
                 dyn = M.walk_markers(record["task_inputs"][part, k])
-            rgb = r.render(qpos[part, k], markers=dyn).cpu().numpy()
-            for t, img in zip(part, rgb):
-                write_png(d / f"{t:05d}.png", img)
-            entry["count"] += len(part)
-    return entry
+            rgb = r.render(qpos[part, k], markers=dyn)
+            if avi:      # (the chunk is coded where it was drawn: only the compressed bytes are copied)
+                for data in enc.encode(rgb):
+                    writer.add(data)
+            if png:
+                for t, img in zip(part, rgb.cpu().numpy()):
+                    write_png(d / f"{t:05d}.png", img)
+                entry["count"] += len(part)
+        if avi:
+            writer.close()
+    return (entry if png else None), video
 
 
 def get_latest_actor(run_dir: Path) -> Path:
@@ -291,6 +314,8 @@ def run_eval(argv):
         raise SystemExit("eval: --render-envs needs --out-dir (the frames go to <out-dir>/frames)")
     if ea.render_envs < 0 or ea.render_every < 1:
         raise SystemExit("eval: --render-envs must be >= 0 and --render-every >= 1")
+    if not 1 <= ea.render_quality <= 100:
+        raise SystemExit("eval: --render-quality must lie in 1..100")
     actor, critic, pkl = resolve_checkpoint(ea.path, ea.logdir)
     import torch
     if not torch.cuda.is_available():
@@ -347,7 +372,7 @@ def run_eval(argv):
         if algo.rollout.tin_all is None:
             summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
             if ea.render_envs > 0:
-                summary["frames"] = summary["trajectory"]
+                summary.update({k: summary["trajectory"] for k, fmts in (("frames", ("png", "both")), ("video", ("mjpeg", "both"))) if ea.render_format in fmts})
         else:
             ro, K = algo.rollout, max(1, min(ea.trace_envs, ea.num_envs))
             rec = ro.tin_all[:, :K].cpu().numpy()
@@ -366,8 +391,9 @@ def run_eval(argv):
             summary["trajectory"] = "trajectory.npz"
             if ea.render_envs > 0:
                 R = min(ea.render_envs, K)
-                summary["frames"] = write_frames(out_dir, env, algo.spec, {k: (v[:, :R] if np.ndim(v) >= 2 else v) for k, v in record.items()}, ea.render_size,
-                                                 ea.render_every, markers=ea.render_markers)
+                frames, video = write_frames(out_dir, env, algo.spec, {k: (v[:, :R] if np.ndim(v) >= 2 else v) for k, v in record.items()}, ea.render_size,
+                                             ea.render_every, markers=ea.render_markers, fmt=ea.render_format, quality=ea.render_quality)
+                summary.update({k: v for k, v in (("frames", frames), ("video", video)) if v is not None})
     text = json.dumps(summary, indent=1)
     with open(Path(out_dir, "eval_summary.json"), "w") as f:
         f.write(text + "\n")
