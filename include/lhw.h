@@ -421,7 +421,8 @@ int lhw_env_get_bemf_damping(LhwEnv* env, double* tau_d_host);
  * HOST pointers; all four calls synchronise the device (as lhw_env_set_task_shaping).  LHW_ERR_ARG, with a message that names the field and
  * nothing changed, for a non-finite value, a range with lo > hi, a cdf that does not ascend within [0, 1], a negative *_every,
  * step_height_span <= 0, a mode outside {-1, 0, 1, 2} or a pin range outside the batch.  LHW_ERR_UNSUPPORTED for cartpole and the h1
- * standing task (every call: they have no command), and for lhw_env_pin_commands on jvrc_step (its command is a footstep plan). */
+ * standing task (every call: they have no command), and for lhw_env_pin_commands on jvrc_step (its command is a footstep plan).  That
+ * plan has a pin of its own: lhw_env_pin_step_plans / lhw_env_get_pinned_step_plans, below. */
 typedef struct {
   double mode_cdf[2], inplace_yaw[2], forward_vx[2], forward_vy[2];
   int32_t switch_stand_every, switch_walk_every;
@@ -432,6 +433,33 @@ int lhw_env_get_task_commands(const LhwEnv* env, LhwTaskCommands* out);
 int lhw_env_pin_commands(LhwEnv* env, int32_t first, int32_t count, const int32_t* mode_host /*[count], -1 frees*/,
                          const double* ref_host /*[count][3]*/);
 int lhw_env_get_pinned_commands(LhwEnv* env, int32_t* mode_host /*[N]*/, double* ref_host /*[N][3]*/);
+/* Pinned footstep plans: the stepping task's command is a walk mode and the footstep plan that goes with it, both drawn at every task
+ * reset (tasks/stepping_task.py:278-311, 140-182).  An LhwStepPin replaces, for one env, the RESULT of the draws it names; every draw
+ * keeps its RNG slot and counter and the phase is still drawn, so pinning exactly what an env would have drawn changes no bit.
+ *  - mode: -1 frees the env (the other fields are then ignored and read back as zeros); else 0 CURVED, 1 STANDING, 2 BACKWARD,
+ *    3 LATERAL, 4 FORWARD, the order of step_mode_cdf.  Besides selecting the generator it keeps its other meanings: the floor sinks
+ *    under the stairs iff FORWARD, STANDING freezes the clocks and the goal update, LHW_TIN_MODE reports it.
+ *  - choice: -1 leaves the mode's own draw alone.  CURVED: the row of the plan table, in [0, number of plans).  LATERAL: 0 walks to the
+ *    side the draw 0 gives (sign -1), 1 to the other.  Every other mode: must be -1.
+ *  - height: FORWARD: the signed rise per step, instead of the stair schedule's value (step_height_*) AND of the sign draw; NaN leaves
+ *    both as they are.  Other modes do not read it.
+ *  - nseq: 0: the sequence is generated from the mode.  2..20: steps[0 .. nseq) is the plan -- x, y, z, theta of each step relative to
+ *    the feet mid-point and the root yaw at the reset, i.e. what generate_step_sequence returns -- and replaces the generated one.  The
+ *    transform into the world frame, the fill of the unused rows, the targets and the terrain boxes follow from it as from a generated
+ *    sequence.  steps beyond nseq are ignored and read back as zeros.
+ *  - reserved: 0.
+ * The pin acts at a task reset and nowhere else -- lhw_env_reset, every auto-reset of lhw_env_step / lhw_env_step_range, and the
+ * auto-resets inside every resident rollout (lhw_env_rollout*, feed-forward, history and LSTM policies, with and without the term
+ * statistics and the actuator randomisation) -- so it costs nothing per control step, and a pin changed between two launches acts from
+ * the env's next reset on.  Free envs, and every env before the first call, behave exactly as without the feature, also beside a pinned
+ * env.  lhw_env_pin_step_plans sets envs [first, first + count); lhw_env_get_pinned_step_plans reports the whole batch (mode -1 and zeros
+ * for a free env; get -> set changes no bit).  HOST pointers; both calls synchronise the device.  LHW_ERR_ARG, with a message that names
+ * the field and nothing changed, for a mode outside {-1 .. 4}, a choice outside its mode's range, nseq outside {0, 2 .. 20}, a
+ * non-finite value among steps[0 .. nseq), an infinite height, reserved != 0 or a range outside the batch (an empty range at the end of
+ * the batch lies inside it).  LHW_ERR_UNSUPPORTED for every env that is not jvrc_step. */
+typedef struct { int32_t mode, choice, nseq, reserved; double height; double steps[20][4]; } LhwStepPin;
+int lhw_env_pin_step_plans(LhwEnv* env, int32_t first, int32_t count, const LhwStepPin* pins_host /*[count]*/);
+int lhw_env_get_pinned_step_plans(LhwEnv* env, LhwStepPin* out_host /*[N]; mode -1 and zeros for a free env*/);
 /* Fault counters since the last call (host pointers, synchronous, resets them): control steps in which contacts were
  * dropped because more than the compiled-in cap were active (16 per env; the stepping task, whose feet rest on the floor AND on
  * the terrain boxes under them, merges identical contacts and holds 192 found / 64 distinct ones per sub-step), and control steps in which an env's state became

@@ -134,6 +134,20 @@ COMMAND_MODES = ("standing", "inplace", "forward")      # a walking task's mode 
 STEP_COMMAND_MODES = ("curved", "standing", "backward", "lateral", "forward")      # the stepping task's, in the order of step_mode_cdf
 
 
+STEP_MAX_SEQ = 20      # include/lhw.h LHW_STEP_MAX_SEQ: the longest footstep plan
+
+
+class LhwStepPin(ctypes.Structure):      # include/lhw.h: lhw_env_pin_step_plans / lhw_env_get_pinned_step_plans (one env's pinned footstep plan)
+    _fields_ = [("mode", ctypes.c_int32), ("choice", ctypes.c_int32), ("nseq", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("height", ctypes.c_double), ("steps", (ctypes.c_double * 4) * STEP_MAX_SEQ)]
+
+
+# the same record as a numpy dtype: an array of it is the [count] / [N] argument of the two calls
+STEP_PIN_DTYPE = np.dtype([("mode", np.int32), ("choice", np.int32), ("nseq", np.int32), ("reserved", np.int32), ("height", np.float64),
+                           ("steps", np.float64, (STEP_MAX_SEQ, 4))])
+assert STEP_PIN_DTYPE.itemsize == ctypes.sizeof(LhwStepPin)
+
+
 def task_commands_struct(fields: dict) -> "LhwTaskCommands":
     """LhwTaskCommands from a full dict by field name (sequences for the array fields)"""
     c = LhwTaskCommands()
@@ -376,6 +390,8 @@ def declare(L):
     sig("lhw_env_get_task_commands", [vp, ctypes.POINTER(LhwTaskCommands)])
     sig("lhw_env_pin_commands", [vp, i32, i32, vp, vp])
     sig("lhw_env_get_pinned_commands", [vp, vp, vp])
+    sig("lhw_env_pin_step_plans", [vp, i32, i32, vp])
+    sig("lhw_env_get_pinned_step_plans", [vp, vp])
     sig("lhw_env_set_iteration", [vp, i64])
     sig("lhw_env_pop_fault_stats", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)])
     sig("lhw_env_pop_rerun_count", [vp, ctypes.POINTER(i64)])

@@ -354,6 +354,57 @@ class BatchedEnv:
         self._check(self._L.lhw_env_get_pinned_commands(self._h, mode.ctypes.data, ref.ctypes.data))
         return mode, ref
 
+    def pin_step_plans(self, mode, *, height=None, choice=None, steps=None, envs=None):
+        """Pin the walk mode and footstep plan of `envs` (None: all; an index or consecutive indices) on jvrc_step, instead of the draws of
+        the task reset (lhw_env_pin_step_plans: synchronises the device; acts from each env's next reset on, across auto-resets).
+        `mode`: a name of _lib.STEP_COMMAND_MODES or its code, one for all or one per env; -1 frees.  `height` (forward): the signed rise
+        per step, instead of the stair schedule and the sign draw; None / NaN: both as drawn.  `choice`: the row of the plan table
+        (curved) or 0 / 1 for the side (lateral); None / -1: as drawn.  Both one for all or one per env.  `steps`: an explicit plan of
+        2..20 steps [n][4] = x, y, z, theta relative to the feet mid-point and the root yaw at the reset ([n][3] = x, y, theta: z = 0),
+        one for all or a list of one per env (None in it: that env's sequence is generated from its mode).  Pin before the reset whose
+        observation a rollout starts from."""
+        first, count = self._env_range(envs)
+        code = lambda m: _lib.STEP_COMMAND_MODES.index(m) if isinstance(m, str) else int(m)      # noqa: E731
+
+        def per_env(v, what, dtype, default):
+            if v is None:
+                return np.full(count, default, dtype=dtype)
+            a = np.array([default if x is None else x for x in v] if np.ndim(v) else [v] * count, dtype=dtype)
+            if a.shape != (count,):
+                raise ValueError(f"{a.size} values of {what} for {count} envs")
+            return a
+
+        pins = np.zeros(count, dtype=_lib.STEP_PIN_DTYPE)
+        pins["mode"] = per_env([code(m) for m in mode] if np.ndim(mode) else code(mode), "mode", np.int32, -1)
+        pins["choice"] = per_env(choice, "choice", np.int32, -1)
+        pins["height"] = per_env(height, "height", np.float64, np.nan)
+        if steps is not None:
+            one = not isinstance(steps, (list, tuple)) or (len(steps) > 0 and np.ndim(steps[0]) == 1)      # [n][3 | 4]: one plan for all
+            plans = [steps] * count if one else list(steps)
+            if len(plans) != count:
+                raise ValueError(f"{len(plans)} plans for {count} envs")
+            for i, plan in enumerate(plans):
+                if plan is None:
+                    continue
+                plan = np.asarray(plan, dtype=np.float64)
+                if plan.ndim != 2 or plan.shape[1] not in (3, 4) or not 2 <= plan.shape[0] <= _lib.STEP_MAX_SEQ:
+                    raise ValueError(f"a footstep plan is [n][3] (x, y, theta) or [n][4] (x, y, z, theta) with 2 <= n <= {_lib.STEP_MAX_SEQ}: got shape {plan.shape}")
+                pins["nseq"][i] = plan.shape[0]
+                pins["steps"][i, :plan.shape[0]] = plan if plan.shape[1] == 4 else np.insert(plan, 2, 0.0, axis=1)
+        self._check(self._L.lhw_env_pin_step_plans(self._h, first, count, pins.ctypes.data))
+
+    def unpin_step_plans(self, envs=None):
+        """Free `envs` (None: all): from their next reset on, mode and plan are drawn again."""
+        first, count = self._env_range(envs)
+        self.pin_step_plans(-1, envs=range(first, first + count))
+
+    def pinned_step_plans(self):
+        """The whole batch's pins as a numpy record array [N] of _lib.STEP_PIN_DTYPE -- mode (-1 for a free env, whose other fields are
+        zero), choice, nseq, reserved, height, steps [20][4] (lhw_env_get_pinned_step_plans)"""
+        out = np.zeros(self.n_envs, dtype=_lib.STEP_PIN_DTYPE)
+        self._check(self._L.lhw_env_get_pinned_step_plans(self._h, out.ctypes.data))
+        return out
+
     def pop_episode_stats(self):
         r, l, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
         self._check(self._L.lhw_env_pop_episode_stats(self._h, ctypes.byref(r), ctypes.byref(l), ctypes.byref(c)))

@@ -472,6 +472,56 @@ extern "C" int lhw_env_get_pinned_commands(LhwEnv* e, int32_t* mode_host, double
   return LHW_OK;
 }
 
+// the stepping task's pin (a walk mode and its footstep plan) exists for jvrc_step alone
+static int step_pins_supported(const LhwEnv* e, const char* fn) {
+  if (!e->hum || e->task != LHW_TASK_JVRC_STEP)
+    return lhw_fail(LHW_ERR_UNSUPPORTED, "%s: footstep plans are the command of the stepping task (jvrc_step); this env has none to pin", fn);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_pin_step_plans(LhwEnv* e, int32_t first, int32_t count, const LhwStepPin* pins) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  const char* fn = "lhw_env_pin_step_plans";
+  if (const int rc = step_pins_supported(e, fn)) return rc;
+  if (first < 0 || count < 0 || (int64_t)first + count > e->n_envs)
+    return lhw_fail(LHW_ERR_ARG, "%s: envs [first = %d, first + count = %lld) lie outside the batch of %d", fn, (int)first, (long long)first + count, e->n_envs);
+  if (count > 0 && !pins) return lhw_fail(LHW_ERR_ARG, "%s: null pins array", fn);
+  const int nplans = humanoid_step_nplans(e->hum);
+  for (int i = 0; i < count; i++) {
+    const LhwStepPin& s = pins[i];
+    if (s.reserved != 0) return lhw_fail(LHW_ERR_ARG, "%s: reserved[%d] = %d, must be 0", fn, i, (int)s.reserved);
+    if (s.mode < -1 || s.mode > 4)
+      return lhw_fail(LHW_ERR_ARG, "%s: mode[%d] = %d, must be -1 (free), 0 CURVED, 1 STANDING, 2 BACKWARD, 3 LATERAL or 4 FORWARD", fn, i, (int)s.mode);
+    if (s.mode < 0) continue;   // (a free env: nothing else of the row is read)
+    const int nchoice = s.mode == 0 ? nplans : (s.mode == 3 ? 2 : 0);
+    if (s.choice < -1 || s.choice >= nchoice) {
+      if (!nchoice) return lhw_fail(LHW_ERR_ARG, "%s: choice[%d] = %d, must be -1: mode %d has no choice to pin", fn, i, (int)s.choice, (int)s.mode);
+      return lhw_fail(LHW_ERR_ARG, "%s: choice[%d] = %d, must be -1 (drawn) or in [0, %d) for mode %d", fn, i, (int)s.choice, nchoice, (int)s.mode);
+    }
+    if (s.nseq != 0 && (s.nseq < 2 || s.nseq > LHW_STEP_MAX_SEQ))
+      return lhw_fail(LHW_ERR_ARG, "%s: nseq[%d] = %d, must be 0 (generated) or 2 .. %d steps", fn, i, (int)s.nseq, LHW_STEP_MAX_SEQ);
+    for (int k = 0; k < s.nseq; k++)
+      for (int a = 0; a < 4; a++)
+        if (!std::isfinite(s.steps[k][a])) return lhw_fail(LHW_ERR_ARG, "%s: steps[%d][%d][%d] = %g is not finite", fn, i, k, a, s.steps[k][a]);
+    if (std::isinf(s.height)) return lhw_fail(LHW_ERR_ARG, "%s: height[%d] = %g, must be finite, or NaN for the schedule's", fn, i, s.height);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (humanoid_pin_step_plans(e->hum, first, count, pins)) return lhw_fail(LHW_ERR_HIP, "%s: upload failed", fn);
+  return LHW_OK;
+}
+
+extern "C" int lhw_env_get_pinned_step_plans(LhwEnv* e, LhwStepPin* out_host) {
+  if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
+  const char* fn = "lhw_env_get_pinned_step_plans";
+  if (const int rc = step_pins_supported(e, fn)) return rc;
+  if (!out_host) return lhw_fail(LHW_ERR_ARG, "%s: null output array", fn);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  humanoid_get_pinned_step_plans(e->hum, out_host);
+  return LHW_OK;
+}
+
 extern "C" int lhw_env_pop_episode_stats(LhwEnv* e, double* ret_sum, double* len_sum, int64_t* count) {
   if (!e) return lhw_fail(LHW_ERR_ARG, "null env");
   double h[3];

@@ -790,6 +790,52 @@ void humanoid_get_pinned_commands(const HumanoidEnv* h, int32_t* mode, double* r
     for (int k = 0; ref && k < 3; k++) ref[3 * n + k] = have ? h->pin_host[4 * n + 1 + k] : 0.0;
   }
 }
+int humanoid_step_nplans(const HumanoidEnv* h) { return h->p.nplans; }
+// rows [first, first + count) of the stepping task's pin array <- pins; the array is created, all rows free, by the first call.  The
+// mirror keeps what the getter reports, the device row {mode, choice, nseq, height, steps[MAX_SEQ][4]} is formed from it.  (checked by
+// the caller; the device is idle)
+int humanoid_pin_step_plans(HumanoidEnv* h, int first, int count, const LhwStepPin* pins) {
+  const size_t N = h->p.n_envs;
+  std::vector<LhwStepPin> rows = h->step_pin_host;
+  if (rows.empty()) {
+    LhwStepPin free_row;
+    memset(&free_row, 0, sizeof(free_row));
+    free_row.mode = -1;
+    rows.assign(N, free_row);
+  }
+  for (int i = 0; i < count; i++) {
+    LhwStepPin& r = rows[(size_t)first + i];
+    memset(&r, 0, sizeof(r));
+    r.mode = -1;
+    if (pins[i].mode < 0) continue;
+    r.mode = pins[i].mode; r.choice = pins[i].choice; r.nseq = pins[i].nseq; r.height = pins[i].height;
+    for (int k = 0; k < r.nseq; k++)
+      for (int a = 0; a < 4; a++) r.steps[k][a] = pins[i].steps[k][a];
+  }
+  std::vector<double> dev_rows(N * STEP_PIN_D, 0.0);
+  for (size_t n = 0; n < N; n++) {
+    double* d = &dev_rows[n * STEP_PIN_D];
+    d[0] = (double)rows[n].mode; d[1] = (double)rows[n].choice; d[2] = (double)rows[n].nseq; d[3] = rows[n].height;
+    memcpy(d + 4, rows[n].steps, sizeof(rows[n].steps));
+  }
+  // the block is allocated once and remembered, so a call that failed behind the allocation does not allocate again; the pointer
+  // is published, and the mirror replaced, only once the rows are on the device: a failed call leaves the getter's answer as it was
+  if (!h->step_pin_dev && !(h->step_pin_dev = h->mem.get_lazy<double>(N * STEP_PIN_D, LhwDevMem::RAW))) return -1;
+  double* dev = h->step_pin_dev;
+  if (hipMemcpy(dev, dev_rows.data(), dev_rows.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return -1;
+  if (h->p.step_pin != dev) {
+    h->p.step_pin = dev;
+    if (!humanoid_upload_params(h)) { h->p.step_pin = nullptr; return -1; }
+  }
+  h->step_pin_host.swap(rows);
+  return 0;
+}
+void humanoid_get_pinned_step_plans(const HumanoidEnv* h, LhwStepPin* out) {
+  const size_t N = h->p.n_envs;
+  if (!h->step_pin_host.empty()) { memcpy(out, h->step_pin_host.data(), N * sizeof(LhwStepPin)); return; }
+  memset(out, 0, N * sizeof(LhwStepPin));
+  for (size_t n = 0; n < N; n++) out[n].mode = -1;
+}
 int humanoid_occupancy() {
   int nb = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, humanoid_kernel<0, TASK_WALK, 32>, 64, 0) != hipSuccess) return -1;

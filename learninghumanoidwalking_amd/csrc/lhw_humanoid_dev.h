@@ -297,7 +297,11 @@ struct HParams {
   double* cmd_pin;                      // [N][4] pinned commands {mode or -1, mode_ref[3]} (lhw_env_pin_commands), a side array like tstat /
                                         // tau_d: NULL until the first pin call; walking tasks only.  An env whose row holds a mode takes
                                         // mode and mode_ref from it at every task reset and task step instead of drawing
+  double* step_pin;                     // [N][STEP_PIN_D] pinned footstep plans (lhw_env_pin_step_plans), a side array like cmd_pin: NULL until
+                                        // the first pin call; the stepping task only.  A row is {mode or -1, choice, nseq, height,
+                                        // steps[MAX_SEQ][4] = x y z theta}; read at the task reset and nowhere else.  Added behind cmd_pin
 };
+#define STEP_PIN_D (4 + MAX_SEQ * 4)    // doubles per row of HParams::step_pin: the steps start 32 bytes into a row of 21 * 32 bytes
 // What the stepper kernels read of an env's configuration, in ONE device allocation behind ONE kernel-argument pointer: the model record, and
 // the task parameters at a fixed, aligned offset behind it (the kernels form both references from the block's address; two argument pointers
 // were two SGPR pairs that the register allocator of the walking rollout kernel kept in spill lanes: profiles/r18_sgpr_working_set_ab.txt).
@@ -447,6 +451,8 @@ struct HumanoidEnv {
   bool fast;   // the model fits the two-envs-per-wave kernels (W = 32)
   unsigned* ro_queue = nullptr;   // job counter + per-group progress words of the resident rollout's queue mode (lhw_humanoid_rollout.hip)
   std::vector<double> pin_host;   // host mirror of p.cmd_pin ([N][4]; empty until the first lhw_env_pin_commands)
+  double* step_pin_dev = nullptr;   // the device block behind p.step_pin, from its allocation on (p.step_pin: from its first successful upload on)
+  std::vector<LhwStepPin> step_pin_host;   // what lhw_env_get_pinned_step_plans answers: the rows of p.step_pin as the caller gave them ([N]; empty until the first lhw_env_pin_step_plans)
   int last_rollout_queued = 0;    // the most recent resident rollout drained the job queue (humanoid_rollout_kernel<.., QUEUE = true>)
   float *hist_base = nullptr, *hist_tbase = nullptr;   // [n_envs][obs_dim] each: the base observation / terminal observation rows control_step writes
                                                        // in a rollout with an observation history (lhw_env_rollout_history), one block in `mem`
@@ -4030,14 +4036,40 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
           const double u = lhw_rng_u01(p.seed, genv, LHW_STREAM_RESET, reset_count, 1);
           mode = u < p.step_mode_cdf[0] ? WALK_CURVED : (u < p.step_mode_cdf[1] ? WALK_STANDING : (u < p.step_mode_cdf[2] ? WALK_BACKWARD
                  : (u < p.step_mode_cdf[3] ? WALK_LATERAL : WALK_FORWARD)));
+          // A pinned footstep plan (HParams::step_pin, lhw_env_pin_step_plans): a row that holds a mode replaces the RESULT of the draws it
+          // names -- the mode, the mode's own choice, the stair height, or the whole generated sequence -- and every draw keeps its slot and
+          // counter, so pinning what was drawn changes nothing.  Pointer and row are read here, at the reset, the row addressed from an
+          // opaque copy of the env index as the statistics' rows are: nothing of it is live in the sub-steps.  Only the row's address
+          // is kept (NULL: a free env); each branch below reads the field it needs when it needs it -- a reset comes once per episode
+          // and can afford the reload, the kernels' register budget cannot afford the fields held across the draws.
+          // The pointer itself is read through an opaque offset: read as `p.step_pin`, a scalar load of the parameter block, the
+          // compiler joins it to the wide scalar load in the kernel's prologue and carries the pair across the whole kernel in spill
+          // lanes (two more SGPR spills in every stepping kernel, and in the rollout kernel one more VGPR to carry them: DESIGN.md
+          // section 8); behind the opaque value it is a load of the reset stage and of nothing else.
+          const double* const spin = *(double* const LHW_GLOBAL_AS*)((const char LHW_GLOBAL_AS*)&p + opaque_int((int)__builtin_offsetof(HParams, step_pin)));
+          const double* prow = nullptr;   // {mode, choice, nseq, height, steps[MAX_SEQ][4]}
+          if (spin) {
+            const double* row = spin + (size_t)opaque_int(env) * STEP_PIN_D;
+            const int pm = (int)row[0];
+            if (pm >= 0) { mode = pm; prow = row; }
+          }
           const int k = lane;
           double sx = 0, sy = 0, sz = 0, sth = 0;
-          if (mode == WALK_CURVED) {
-            const double* row = p.plans + (size_t)lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, p.nplans) * (1 + MAX_SEQ * 3);
+          if (prow && (int)prow[2]) {
+            // an explicit plan: lane k reads step k = (x, y, z, theta) relative to the feet mid-point and the root yaw, which is what
+            // generate_step_sequence hands to transform_sequence; everything below runs on it unchanged
+            nseq = (int)prow[2];
+            if (k < MAX_SEQ && k < nseq) { sx = prow[4 + 4 * k]; sy = prow[5 + 4 * k]; sz = prow[6 + 4 * k]; sth = prow[7 + 4 * k]; }
+          } else if (mode == WALK_CURVED) {
+            int choice = (int)lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, p.nplans);
+            if (prow && (int)prow[1] >= 0) choice = (int)prow[1];
+            const double* row = p.plans + (size_t)choice * (1 + MAX_SEQ * 3);
             nseq = (int)row[0];
             if (k < nseq) { sx = row[1 + 3 * k]; sy = row[2 + 3 * k]; sth = row[3 + 3 * k]; }
           } else if (mode == WALK_LATERAL) {
-            const double sgn = lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, 2) == 0 ? -1.0 : 1.0;
+            int choice = (int)lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, 2);
+            if (prow && (int)prow[1] >= 0) choice = (int)prow[1];
+            const double sgn = choice == 0 ? -1.0 : 1.0;
             nseq = 19;
             double y = 0;
             for (int i = 1; i <= k + 1 && i < 20; i++) {
@@ -4051,6 +4083,7 @@ __device__ __forceinline__ bool control_step(HModelRef m, HParamsRef p, const HL
             if (mode == WALK_FORWARD) {
               const double hh = fmin(1.0, fmax(0.0, ((double)lz.iteration - p.step_height_start) / p.step_height_span)) * p.step_height_max;
               height = lhw_rng_randint(p.seed, genv, LHW_STREAM_RESET, reset_count, 2, 2) == 0 ? -hh : hh;
+              if (prow && prow[3] == prow[3]) height = prow[3];   // (not NaN) a pinned rise per step stands for the schedule's value AND the sign draw
             }
             const double uf = lhw_rng_uniform(p.seed, genv, LHW_STREAM_RESET, reset_count, 3, 0.095, 0.105);
             const bool neg = (double)phase == 0.5 * (double)p.period;

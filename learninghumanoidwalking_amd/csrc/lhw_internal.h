@@ -155,6 +155,12 @@ void humanoid_get_task_commands(const HumanoidEnv* h, LhwTaskCommands* out);
 int humanoid_set_task_commands(HumanoidEnv* h, const LhwTaskCommands* c);
 int humanoid_pin_commands(HumanoidEnv* h, int first, int count, const int32_t* mode, const double* ref /* [count][3] */);
 void humanoid_get_pinned_commands(const HumanoidEnv* h, int32_t* mode /* [N] */, double* ref /* [N][3] */);
+// Pinned footstep plans of the stepping task (lhw_env_pin_step_plans): the same contract as the pin array above -- validated values in,
+// created with every row free by the first call, kept when every env is freed, -1 on a HIP error; the host mirror holds the rows as the
+// getter reports them (a free row: mode -1 and zeros; steps beyond nseq: zeros).  humanoid_step_nplans: rows of the env's plan table
+int humanoid_step_nplans(const HumanoidEnv* h);
+int humanoid_pin_step_plans(HumanoidEnv* h, int first, int count, const LhwStepPin* pins);
+void humanoid_get_pinned_step_plans(const HumanoidEnv* h, LhwStepPin* out /* [N] */);
 int humanoid_wave_cycles(HumanoidEnv* h, long long* out);
 int humanoid_profile(HumanoidEnv* h, int enable, long long* out16);
 // step_record: the stepping task's second record (LhwStepTaskInput) instead of LhwTaskInput; -1 HIP error, -2 not enabled

@@ -8,6 +8,7 @@ on-device rollout + PPO of this repository.
     python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 [--render-size 640x480] [--render-every 1] [--render-markers]
     python run_experiment.py eval --path RUN_DIR --out-dir DIR --render-envs 2 --render-format mjpeg [--render-quality 90]     (DIR/video/env000.avi)
     python run_experiment.py eval --path RUN_DIR --command forward:0.1..0.4 [--num-envs 4]     (walking tasks: pinned commands)
+    python run_experiment.py eval --path RUN_DIR --footsteps forward:0.0..0.1 [--num-envs 4]   (jvrc_step: pinned walk modes / footstep plans)
     python run_experiment.py eval --logdir DIR ...                     (latest run below DIR, its latest actor)
 
 Differences from the reference, by design: no Ray (`--num-procs` is the number of on-device envs per GPU unless
@@ -32,6 +33,11 @@ only compressed bytes reach the host; the summary gains "video".
 `--command SPEC` (jvrc_walk, h1_walk) pins every env's command before the reset the episodes start from, instead of the task's draw --
 standing | inplace:YAW | forward:VX[,VY], a value A..B spread linearly over the envs -- and adds "command" and "per_env" (mode, mode_ref,
 return and length of each env's first episode) to the summary: one launch gives a return-against-commanded-speed curve.
+`--footsteps SPEC` (jvrc_step) does the same for the stepping task, whose command is a walk mode and a footstep plan: forward[:H] (H the
+rise per step, A..B spread over the envs) | backward | standing | lateral[:left|right] | curved[:K] | plan:FILE[:K] (FILE in the format of
+the env's plans file, an optional fourth column z) -- and adds "footsteps", "per_env" (mode, height, nseq, return, length and
+targets_reached of each env's first episode) and the fault counters "contact_overflow" / "diverged" to the summary: one launch says how
+high a stair the policy climbs, or whether it follows the plan it is given.
 """
 import argparse
 import json
@@ -145,6 +151,8 @@ def build_eval_parser():
     p.add_argument("--render-markers", action="store_true", help="draw the task's markers into the frames: velocity arrows (walking tasks), footstep targets and foot frames (jvrc_step)")
     p.add_argument("--command", type=str, default=None, metavar="SPEC",
                    help="walking tasks: pin every env's command instead of drawing it: standing | inplace:YAW | forward:VX[,VY]; a value A..B is spread linearly over the envs")
+    p.add_argument("--footsteps", type=str, default=None, metavar="SPEC",
+                   help=f"jvrc_step: pin every env's walk mode and footstep plan instead of drawing them: {FOOTSTEP_FORMS}; H may be A..B, spread linearly over the envs")
     return p
 
 
@@ -180,6 +188,74 @@ def parse_command(text, K):
         if len(vals) == 2:
             ref[:, 2] = spread(vals[1].strip())
     return np.full(K, mode, dtype=np.int32), ref
+
+
+FOOTSTEP_FORMS = "forward[:H] | backward | standing | lateral[:left|right] | curved[:K] | plan:FILE[:K]"
+
+
+def parse_footsteps(text, K, nplans):
+    """`eval --footsteps SPEC` (jvrc_step) for K envs of an env whose plan table has `nplans` rows -> the per-env pin fields, the keywords
+    of BatchedEnv.pin_step_plans: dict(mode [K] int32, choice [K] int32 (-1: drawn), height [K] float64 (NaN: the stair schedule's),
+    steps: a list of K plans [n][4] = x, y, z, theta, or None where every env's sequence is generated).
+    SPEC: forward[:H] (H the signed rise per step; A..B is spread linearly over the envs as parse_command spreads) | backward | standing |
+    lateral[:left|right] | curved[:K] (a row of the env's plan table) | plan:FILE[:K] (FILE as load_plans reads it -- plans closed by
+    `---`, rows `x,y,theta` with an optional fourth column z -- of 2..20 steps each; without K env k walks plan k mod their number; a
+    plan with some z != 0 is walked in FORWARD mode, which sinks the floor under the stairs, else in CURVED mode)."""
+    import numpy as np
+    from learninghumanoidwalking_amd._lib import STEP_COMMAND_MODES, STEP_MAX_SEQ
+    from learninghumanoidwalking_amd.envs.jvrc_step import load_plans
+
+    def fail(why):
+        raise SystemExit(f"eval: --footsteps {text!r}: {why}") from None
+
+    def index(v, n, what):
+        if not v.isdigit() or int(v) >= n:
+            fail(f"{v!r} is not one of the {n} {what} (0..{n - 1})")
+        return int(v)
+
+    name, _, rest = text.partition(":")
+    if name not in STEP_COMMAND_MODES + ("plan",) or (":" in text and not rest) or (rest and name in ("backward", "standing")):
+        fail(f"is none of {FOOTSTEP_FORMS}")
+    out = dict(mode=np.full(K, STEP_COMMAND_MODES.index(name) if name != "plan" else 0, dtype=np.int32), choice=np.full(K, -1, dtype=np.int32),
+               height=np.full(K, np.nan), steps=None)
+    if name == "forward" and rest:
+        try:
+            a, b = (float(x) for x in rest.split("..")) if ".." in rest else (float(rest), float(rest))
+        except ValueError:
+            fail(f"{rest!r} is neither a number nor A..B")
+        if not (math.isfinite(a) and math.isfinite(b)):
+            fail(f"{rest!r} is not finite")
+        out["height"][:] = [a + k * (b - a) / (K - 1) if K > 1 else a for k in range(K)]
+    elif name == "lateral" and rest:
+        if rest not in ("left", "right"):
+            fail(f"{rest!r} is neither left nor right")
+        out["choice"][:] = 1 if rest == "left" else 0      # (the task's draw 0 gives sign -1: steps towards -y, the robot's right)
+    elif name == "curved" and rest:
+        out["choice"][:] = index(rest, nplans, "plans of the env's table")
+    elif name == "plan":
+        path, _, tail = rest.rpartition(":")
+        path, tail = (path, tail) if path and tail.isdigit() else (rest, "")
+        try:
+            plans = load_plans(path)
+        except OSError as e:
+            fail(f"cannot read {path!r} ({e.strerror})")
+        except ValueError as e:
+            if "could not convert" in str(e):
+                fail(f"{path!r} holds a row that is not numbers separated by commas")
+            fail(f"{path!r} holds a plan whose rows differ in their number of columns (every row of a plan has 3, x,y,theta, or 4, x,y,theta,z)")
+        if not plans:
+            fail(f"{path!r} holds no plan (every plan is closed by a line `---`)")
+        for i, p in enumerate(plans):
+            if p.ndim != 2 or p.shape[1] not in (3, 4) or not np.isfinite(p).all():
+                fail(f"plan {i} of {path!r} must have rows of 3 (x,y,theta) or 4 (x,y,theta,z) finite numbers")
+            if not 2 <= len(p) <= STEP_MAX_SEQ:
+                fail(f"plan {i} of {path!r} has {len(p)} steps (2..{STEP_MAX_SEQ} supported)")
+        # the file's columns x, y, theta [, z] -> the pin's x, y, z, theta
+        plans = [np.column_stack([p[:, 0], p[:, 1], p[:, 3] if p.shape[1] == 4 else np.zeros(len(p)), p[:, 2]]) for p in plans]
+        pick = [index(tail, len(plans), f"plans of {path!r}")] * K if tail else [k % len(plans) for k in range(K)]
+        out["steps"] = [plans[i] for i in pick]
+        out["mode"][:] = [STEP_COMMAND_MODES.index("forward" if plans[i][:, 2].any() else "curved") for i in pick]
+    return out
 
 
 def first_episodes(rew, done):
@@ -330,6 +406,8 @@ def run_eval(argv):
         raise SystemExit(f"eval: unknown env {args.env!r} in {pkl}")
     if ea.command is not None and args.env not in COMMAND_ENVS:
         raise SystemExit(f"eval: --command pins the command of a walking task ({', '.join(COMMAND_ENVS)}); the env of this run, {args.env}, has none to pin")
+    if ea.footsteps is not None and args.env != "jvrc_step":
+        raise SystemExit(f"eval: --footsteps pins the footstep plan of the stepping task (jvrc_step); the env of this run, {args.env}, has none to pin")
     Spec = ENVIRONMENTS[args.env]
     yaml = Path(actor.parent, "config.yaml")      # the run's own copy of --yaml (run_experiment.py train)
     env_fn = partial(Spec, yaml_path=str(yaml)) if (yaml.is_file() and args.env != "cartpole") else Spec
@@ -354,6 +432,13 @@ def run_eval(argv):
         mode, ref = parse_command(ea.command, ea.num_envs)
         algo.env.pin_commands(mode, ref)
         algo.rollout.started = False      # (the rollout resets the env before its first control step)
+    if ea.footsteps is not None:
+        # likewise: the reset the rollout starts from already lays out the pinned plan
+        pins = parse_footsteps(ea.footsteps, ea.num_envs, len(algo.spec.plans))
+        algo.env.pin_step_plans(pins["mode"], height=pins["height"], choice=pins["choice"], steps=pins["steps"])
+        algo.env.pop_fault_stats()
+        algo.rollout.record_task_inputs = True      # (the stepping record of every control step: targets_reached below)
+        algo.rollout.started = False
     algo.sample_parallel_with_workers(deterministic=True)      # Rollout.collect(deterministic=True), as PPO.evaluate
     ls = algo._ep_stats[1]
     ts = algo.term_stats
@@ -368,6 +453,20 @@ def run_eval(argv):
         summary["command"] = ea.command
         summary["per_env"] = [dict(mode=int(mode[k]), mode_ref=[float(x) for x in ref[k]], episode_return=float(ret[k]), episode_length=int(length[k]))
                               for k in range(ea.num_envs)]
+    if ea.footsteps is not None:
+        # per env, the plan it was given and how far it got: the targets it reached are the largest t1 its first episode's record shows
+        ret, length = first_episodes(algo.rollout.rew.cpu().numpy(), algo.rollout.done.cpu().numpy())
+        stin = getattr(algo.rollout, "stin_all", None)
+        t1 = None if stin is None else stin[:, :, _lib.STEP_TASK_INPUT_FIELDS["t1"][0]].cpu().numpy()
+        summary["footsteps"] = ea.footsteps
+        summary["per_env"] = [dict(mode=_lib.STEP_COMMAND_MODES[int(pins["mode"][k])], height=None if math.isnan(pins["height"][k]) else float(pins["height"][k]),
+                                   nseq=0 if pins["steps"] is None else len(pins["steps"][k]), **{"return": float(ret[k])}, length=int(length[k]),
+                                   targets_reached=None if t1 is None else int(t1[:length[k], k].max()))
+                              for k in range(ea.num_envs)]
+        # (a plan can stack more boxes under a foot than the contact merge holds: the control steps that dropped contacts, and the diverged ones)
+        summary["contact_overflow"], summary["diverged"] = algo.env.pop_fault_stats()
+        if t1 is None:
+            summary["targets_reached"] = f"not reported: the rollout ({getattr(algo.rollout, 'last_mode', None)}) kept no stepping record of its control steps"
     if ea.out_dir is not None:
         if algo.rollout.tin_all is None:
             summary["trajectory"] = f"not written: the rollout ran launch-per-step ({algo.rollout.last_mode}), which keeps no per-step record"
